@@ -21,15 +21,21 @@ to rank 0 in one RCCL gather (gr_raytracer_amd.distributed.gather_frame).  Stron
 scaling; the line carries each rank's kernel time, the max/mean imbalance and the
 gather time.  A 4096^2 frame takes minutes per GPU: run it with --steps 1 --warmup 0.
 
-Printed JSON carries the FP64 VALU roofline of the trace kernel (HIP events on the launch
-stream) and the CPU baseline: the oracle (reference algorithm restated in C++, stored
-trajectories + post-hoc window pass) timed on the host cores on a bounded sample.
+A plain run sets up, warms up, times the --steps frames and prints one JSON line: the
+headline figure and the FP64 VALU roofline of the trace kernel from the timed frames' own
+HIP events (on the launch stream).  --dump-outputs DIR also writes what the last timed
+frame delivered (DIR/xyza.npy, ray_class.npy, status.npy; the scene and camera are fixed,
+so two builds can be compared output for output).
 
-The metric's second half, "wall-clock for 1500x1500 Schwarzschild render", is the
-reference's own Elapsed time (main.rs:31, :175-176: CLI start -> image written): on one GPU
-the C2 line also runs the `grt` CLI (the reference's `render` command line, README.md:63)
-on the C2 scene at 1 spp and on the stock TOML (adaptive 4x4 supersampling, C5) and
-reports the process wall time and the CLI's phase times (render_wall).
+--full adds every measurement that takes runs of its own (each still has its own switch):
+frames rendered alone (frac_single_launch), the fused arithmetic mode, the CPU baseline
+(the oracle: reference algorithm restated in C++, stored trajectories + post-hoc window
+pass, timed on the host cores on a bounded sample), and the metric's second half,
+"wall-clock for 1500x1500 Schwarzschild render": the reference's own Elapsed time
+(main.rs:31, :175-176: CLI start -> image written).  For it, on one GPU the C2 line runs the
+`grt` CLI (the reference's `render` command line, README.md:63) on the C2 scene at 1 spp
+and on the stock TOML (adaptive 4x4 supersampling, C5) and reports the process wall time
+and the CLI's phase times (render_wall).
 """
 from __future__ import annotations
 
@@ -228,6 +234,34 @@ def roofline(workload: str, geometry: str, accepted: float, attempts: float, ker
     return out
 
 
+# -------------------------------------------------------------------- outputs ----
+DUMP_BUDGET_BYTES = 60 * 10**6  # --dump-outputs writes at most this much in all
+
+
+def dump_outputs(out_dir, arrays: dict) -> dict:
+    """Write each array as out_dir/<name>.npy in float32 (float64 stays float64).  When
+    the arrays together exceed DUMP_BUDGET_BYTES, every array keeps the same fraction of
+    its rows: a fixed sample (seeded, sorted; the same rows for arrays of equal length
+    and from run to run).  Returns {name: [rows written, rows in all]}."""
+    import numpy as np
+
+    out_dir = Path(out_dir)
+    out_dir.mkdir(parents=True, exist_ok=True)
+    conv = {k: np.ascontiguousarray(v, dtype=np.float64 if v.dtype == np.float64 else np.float32)
+            for k, v in arrays.items()}
+    total = sum(a.nbytes for a in conv.values())
+    keep = min(1.0, DUMP_BUDGET_BYTES / max(total, 1))
+    written = {}
+    for name, a in conv.items():
+        n = a.shape[0]
+        if keep < 1.0:
+            k = max(1, int(n * keep))
+            a = a[np.sort(np.random.default_rng(20240229).choice(n, size=k, replace=False))]
+        np.save(out_dir / f"{name}.npy", a)
+        written[name] = [int(a.shape[0]), int(n)]
+    return written
+
+
 # ------------------------------------------------------------------ workloads ----
 def reduce_over_ranks(elapsed: float, accepted: float, attempts: float, world: int, device="cpu"):
     """The weak-scaling line's job totals: the max over ranks of the timed region and the
@@ -393,6 +427,13 @@ def run_c2(args, rank, world, local_rank, dev):
         kernel_ms = max(ev[0][0].elapsed_time(e[1]) for e in ev[-F:]) / args.steps
     counters = [sum(v) for v in zip(*(s["stats"].cpu().tolist() for s in slots))]
     accepted, attempts = counters[0], counters[1]  # summed over K frames
+    dumped = None
+    if args.dump_outputs and rank == 0:  # the last timed frame, before anything else renders into its slot
+        last = slots[(args.steps - 1) % F]
+        arrays = {"xyza": last["xyza"], "ray_class": last["cls"], "status": last["status"]}
+        if last["gather"] is not None:  # what rank 0 received: every rank's frame
+            arrays.update({f"gathered_xyza_rank{r}": t for r, t in enumerate(last["gather"])})
+        dumped = dump_outputs(args.dump_outputs, {k: t.cpu().numpy() for k, t in arrays.items()})
     # One frame alone in flight (after the timed region, untimed): a single launch's own
     # duration, the basis of frac_single_launch beside the pipelined throughput fraction.
     single_ms = []
@@ -438,6 +479,8 @@ def run_c2(args, rank, world, local_rank, dev):
     # each timed frame's own span between its two events on its slot's stream (with frames in
     # flight a span includes the time the frame shares the CUs with its neighbours)
     line["roofline"]["frame_event_ms"] = [round(a.elapsed_time(b), 1) for a, b in ev]
+    if dumped is not None:
+        line["dumped_outputs"] = dumped
     line["roofline"]["kernel_ms_basis"] = (
         "mean launch duration (HIP events on the launch stream)" if F == 1 else
         f"pipelined throughput: device time per frame with {F} frames in flight, first frame's start event to "
@@ -553,7 +596,7 @@ def run_c4(args, rank, world, local_rank, dev):
 
     import gr_raytracer_amd as g
     from gr_raytracer_amd import _lib as L
-    from gr_raytracer_amd.distributed import pack_records, shard_row_count
+    from gr_raytracer_amd.distributed import pack_records, shard_row_count, unpack_records
 
     lib = L.lib()
     opts = c4_opts(g, args.size)
@@ -610,6 +653,10 @@ def run_c4(args, rank, world, local_rank, dev):
                              "traffic: the integrate kernel's PMC summary only), rank 0's shard"),
         "cpu_baseline": None,
     }
+    if args.dump_outputs:  # the gathered frame of the last timed step, as rank 0 holds it
+        names = ("xyza", "ray_class", "status")
+        line["dumped_outputs"] = dump_outputs(args.dump_outputs, {
+            k: t.cpu().numpy() for k, t in zip(names, unpack_records(res["frame"]))})
     if not args.no_cpu_baseline and world == 1:
         line["cpu_baseline"] = cpu_baseline(g, "c4")
     return line
@@ -625,22 +672,31 @@ def main() -> None:
     ap.add_argument("--workload", choices=("c2", "c4"), default="c2")
     ap.add_argument("--size", type=int, default=4096, help="c4: frame edge (4096 = configs[3])")
     ap.add_argument("--band-rows", type=int, default=16, help="c4: rows per cyclic band")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="also run what takes runs of its own: frames alone (--single-launches), the fused-mode "
+                    "loop, the grt CLI wall-clock runs and the CPU baseline; without it only the timed steps run")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the last timed step's outputs to DIR/<name>.npy (float32; a fixed seeded sample "
+                    "of the rows when they exceed 60 MB in all)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: skip the CPU baseline")
     ap.add_argument("--inflight", type=int, default=2,
                     help="c2: frames in flight (one stream and workspace each); 1 = one frame after another")
     ap.add_argument("--blocks-per-cu", type=int, default=0)
     ap.add_argument("--single-launches", type=int, default=2,
-                    help="c2: frames rendered alone after the timed region (frac_single_launch)")
-    ap.add_argument("--no-cli-wall", action="store_true", help="c2: skip the grt CLI wall-clock runs")
+                    help="c2, --full: frames rendered alone after the timed region (frac_single_launch)")
+    ap.add_argument("--no-cli-wall", action="store_true", help="c2, --full: skip the grt CLI wall-clock runs")
     ap.add_argument("--arith", choices=("exact", "fused"), default="exact",
                     help="grt_set_arithmetic for the timed loop (exact: the reference's roundings)")
     ap.add_argument("--no-fused-check", dest="fused_check", action="store_false",
-                    help="c2, one GPU: skip the extra fused-mode measurement")
+                    help="c2, one GPU, --full: skip the extra fused-mode measurement")
     ap.add_argument("--self-gather", action="store_true", help="c2, one GPU: run the multi-GPU gather path "
                     "in a process group of one (a check of the streams and RCCL gathers)")
     args = ap.parse_args()
     if args.steps is None:
         args.steps = 6 if args.workload == "c2" else 1
+    if not args.full:  # a plain run: set up, warm up, time the steps, print the line
+        args.single_launches, args.fused_check = 0, False
+        args.no_cli_wall = args.no_cpu_baseline = True
 
     import torch
     import torch.distributed as dist

@@ -233,6 +233,36 @@ def test_c2_frame_loop_gloo_world2():
     assert got[0]["gathered"] == [[6.0, 106.0], [5.0, 105.0]]
 
 
+def test_dump_outputs_whole_and_sampled(tmp_path, monkeypatch):
+    """bench.dump_outputs (--dump-outputs): float32 files of the whole arrays within the
+    budget; above it the same fixed sample of rows for arrays of equal length, identical
+    from run to run, and never more than the budget in all."""
+    import bench
+
+    rng = np.random.default_rng(5)
+    xyza = rng.random((1000, 4)).astype(np.float32)
+    cls = rng.integers(0, 4, 1000).astype(np.uint8)
+    f64 = rng.random(10)
+    w = bench.dump_outputs(tmp_path / "a", {"xyza": xyza, "ray_class": cls, "f64": f64})
+    assert w == {"xyza": [1000, 1000], "ray_class": [1000, 1000], "f64": [10, 10]}
+    got = np.load(tmp_path / "a" / "xyza.npy")
+    assert got.dtype == np.float32 and np.array_equal(got, xyza)
+    got = np.load(tmp_path / "a" / "ray_class.npy")
+    assert got.dtype == np.float32 and np.array_equal(got, cls.astype(np.float32))
+    assert np.load(tmp_path / "a" / "f64.npy").dtype == np.float64
+
+    monkeypatch.setattr(bench, "DUMP_BUDGET_BYTES", 8000)  # the arrays hold 16000 + 4000 bytes as float32
+    w = bench.dump_outputs(tmp_path / "b", {"xyza": xyza, "ray_class": cls})
+    bench.dump_outputs(tmp_path / "c", {"xyza": xyza, "ray_class": cls})
+    sx, sc = np.load(tmp_path / "b" / "xyza.npy"), np.load(tmp_path / "b" / "ray_class.npy")
+    assert w == {"xyza": [400, 1000], "ray_class": [400, 1000]}
+    assert sx.nbytes + sc.nbytes <= 8000
+    assert np.array_equal(sx, np.load(tmp_path / "c" / "xyza.npy"))
+    # the same rows of both arrays, in frame order
+    rows = np.flatnonzero((xyza[:, None, :] == sx[None, :, :]).all(axis=2).any(axis=1))
+    assert len(rows) == 400 and np.array_equal(xyza[rows], sx) and np.array_equal(cls[rows].astype(np.float32), sc)
+
+
 def test_parse_cli_phases():
     import bench
 

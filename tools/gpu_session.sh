@@ -8,10 +8,10 @@
 #   suite                  pytest -m gpu (the whole GPU parity suite)
 #   suite=EXPR             pytest -m gpu -k EXPR
 #   smoke                  __graft_entry__.smoke()
-#   bench                  bench.py (C2 headline line)
+#   bench                  bench.py --full (C2 headline line, fused line, CLI wall-clock, CPU baseline)
 #   benchprof              rocprofv3 --kernel-trace --stats of bench.py --steps 5, + tools/kernel_period.py
-#   bench_seq              bench.py --inflight 1 (one frame after another)
-#   bench_gather           bench.py --self-gather (the multi-GPU gather path in a group of one)
+#   bench_seq              bench.py --full --inflight 1 (one frame after another)
+#   bench_gather           bench.py --full --self-gather (the multi-GPU gather path in a group of one)
 #   bench_c4               bench.py --workload c4 (the whole C4 frame) under rocprofv3 --stats
 #   pmc=c2|c3|c4|c4full    PMC passes (tools/run_pmc.sh; c4full: FETCH / WRITE only)
 #   shards                 the eight C4 1/8 row-band shards (tools/c4_shard_time.py)
@@ -43,7 +43,7 @@ for step in "$@"; do
         || { tail -20 $OUT/smoke.log >&2; exit 1; }
       tail -2 $OUT/smoke.log >&2 ;;
     bench)
-      timeout -k 10 600 python3 bench.py > $OUT/bench.json 2> $OUT/bench.err || { tail -20 $OUT/bench.err >&2; exit 1; }
+      timeout -k 10 600 python3 bench.py --full > $OUT/bench.json 2> $OUT/bench.err || { tail -20 $OUT/bench.err >&2; exit 1; }
       cut -c1-400 $OUT/bench.json >&2 ;;
     benchprof)
       timeout -k 10 600 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/prof -o run -- \
@@ -52,11 +52,11 @@ for step in "$@"; do
       python3 tools/kernel_period.py $OUT/prof/run_kernel_trace.csv "integrate_kernel<1, false>" 5 \
         > $OUT/kernel_period.json && cut -c1-600 $OUT/kernel_period.json >&2 ;;
     bench_seq)
-      timeout -k 10 600 python3 bench.py --inflight 1 > $OUT/bench_seq.json 2> $OUT/bench_seq.err \
+      timeout -k 10 600 python3 bench.py --full --inflight 1 > $OUT/bench_seq.json 2> $OUT/bench_seq.err \
         || { tail -20 $OUT/bench_seq.err >&2; exit 1; }
       cut -c1-400 $OUT/bench_seq.json >&2 ;;
     bench_gather)
-      MASTER_PORT=29533 timeout -k 10 600 python3 bench.py --self-gather --no-cpu-baseline \
+      MASTER_PORT=29533 timeout -k 10 600 python3 bench.py --full --self-gather --no-cpu-baseline \
         > $OUT/bench_gather.json 2> $OUT/bench_gather.err || { tail -20 $OUT/bench_gather.err >&2; exit 1; }
       cut -c1-400 $OUT/bench_gather.json >&2 ;;
     bench_c4)
