@@ -120,6 +120,8 @@ class SubsampleFailures(C.Structure):
 
 
 GRT_MULTI_MAX_DEVICES = 16
+# grt_multi_transport, by the names the CLI's --transport takes
+MULTI_TRANSPORTS = {"rccl": 0, "peer": 1, "peer-staged": 2}
 
 
 class FrameOut(C.Structure):
@@ -130,7 +132,7 @@ class FrameOut(C.Structure):
 
 class MultiReport(C.Structure):
     _fields_ = [("n_devices", C.c_uint32), ("record_bytes", C.c_uint32), ("attempts", C.c_uint32),
-                ("_pad", C.c_uint32), ("wall_ms", _d), ("gather_ms", _d), ("allgather_ms", _d),
+                ("transport", C.c_uint32), ("wall_ms", _d), ("gather_ms", _d), ("allgather_ms", _d),
                 ("trace_ms", _d * GRT_MULTI_MAX_DEVICES), ("accepted_steps", C.c_uint64 * GRT_MULTI_MAX_DEVICES),
                 ("rows", C.c_uint64 * GRT_MULTI_MAX_DEVICES)]
 
@@ -255,6 +257,8 @@ def lib() -> C.CDLL:
         "grt_multi_release": (None, []),
         "grt_set_arithmetic": (C.c_int, [C.c_int]),
         "grt_get_arithmetic": (C.c_int, []),
+        "grt_set_multi_transport": (C.c_int, [C.c_int]),
+        "grt_get_multi_transport": (C.c_int, []),
     }
     # GRT_LIB_ALLOW_MISSING=1 (tools/time_variants.py only) binds an older experimental
     # build that lacks newer entry points; by default a missing symbol is an error.
@@ -302,7 +306,7 @@ EXPORTED_SYMBOLS = [
     "grt_ray_at", "grt_write_trajectory_csv", "grt_format_f64", "grt_adaptive_min_luminance", "grt_adaptive_min_luminance_device", "grt_supersample_shard",
     "grt_supersample_shard_device", "grt_adaptive_floor_device", "grt_render_section_ex",
     "grt_write_png_rgb", "grt_write_hdr_xyz", "grt_render_frame_multi", "grt_multi_release",
-    "grt_set_arithmetic", "grt_get_arithmetic",
+    "grt_set_arithmetic", "grt_get_arithmetic", "grt_set_multi_transport", "grt_get_multi_transport",
 ]
 
 

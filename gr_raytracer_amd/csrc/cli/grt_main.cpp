@@ -17,9 +17,11 @@
 // Extra (not in the reference): --device N selects the GPU, --resource-root DIR
 // resolves texture paths, --raw-out FILE dumps the f64 XYZA buffer; --gpus N (GPUs
 // 0..N-1) or --devices A,B,... renders the whole frame over several GPUs of this process
-// (grt_render_frame_multi: cyclic row bands of --band-rows rows, default 16, one RCCL
-// gather), --gpus 1 included; --arithmetic exact|fused selects grt_set_arithmetic (exact,
-// the reference's roundings, by default).
+// (grt_render_frame_multi: cyclic row bands of --band-rows rows, default 16, one
+// gather), --gpus 1 included; --transport rccl|peer|peer-staged selects how that frame's
+// blocks move (grt_set_multi_transport; rccl by default; under the peer transports
+// --devices may name a GPU several times, one rank per entry); --arithmetic exact|fused
+// selects grt_set_arithmetic (exact, the reference's roundings, by default).
 #include <algorithm>
 #include <charconv>
 #include <chrono>
@@ -53,6 +55,11 @@ static int usage(const char* msg) {
                "           [--min-redshift Z] [--max-redshift Z] [--width N] [--height N] [-f FILE]\n",
                msg);
   return 2;
+}
+
+// --transport's name of a grt_multi_transport.
+static const char* transport_name(uint32_t t) {
+  return t == GRT_TRANSPORT_PEER ? "peer" : t == GRT_TRANSPORT_PEER_STAGED ? "peer-staged" : "rccl";
 }
 
 // Debug form of the RaytracerError behind a grt_status (raytracer.rs:20-52).
@@ -293,6 +300,13 @@ int main(int argc, char** argv) {
     if (a == "--arithmetic") {
       if (v != "exact" && v != "fused") return bad();
       (void)grt_set_arithmetic(v == "fused" ? 1 : 0);
+      continue;
+    }
+    if (a == "--transport") {
+      const int mode = v == "rccl" ? GRT_TRANSPORT_RCCL : v == "peer" ? GRT_TRANSPORT_PEER
+                       : v == "peer-staged" ? GRT_TRANSPORT_PEER_STAGED : -1;
+      if (mode < 0) return bad();
+      (void)grt_set_multi_transport(mode);
       continue;
     }
     if (a == "--band-rows") {
@@ -591,8 +605,9 @@ int main(int argc, char** argv) {
                     (unsigned long long)mrep.rows[k], mrep.trace_ms[k]);
       per += b;
     }
-    std::fprintf(stderr, "[grt] %u GPU(s) [%s]; allgather %.2f ms, gather %.2f ms (%u B per pixel), %u trace(s)\n",
-                 mrep.n_devices, per.c_str(), mrep.allgather_ms, mrep.gather_ms, mrep.record_bytes, mrep.attempts);
+    std::fprintf(stderr, "[grt] %u GPU(s) [%s]; transport %s, allgather %.2f ms, gather %.2f ms (%u B per pixel), "
+                 "%u trace(s)\n", mrep.n_devices, per.c_str(), transport_name(mrep.transport), mrep.allgather_ms,
+                 mrep.gather_ms, mrep.record_bytes, mrep.attempts);
   }
   if (st.march_jobs)
     std::fprintf(stderr, "[grt] VolumetricDisc: %llu raymarches, %llu samples (%llu with noise, %llu emitting)\n",
@@ -635,8 +650,8 @@ int main(int argc, char** argv) {
   // where the wall time went: TOML + texture decode + LUTs; the descriptor copy; the render
   // call (device upload on first use, trace, supersampling, D2H); tone map; encode + write
   std::fprintf(stderr, "[grt] phases (ms): load %.1f, create %.1f, hip init %.1f, render %.1f, output %.1f, "
-               "write %.1f, since start %.1f\n", ph_load, ph_create, ph_init, ph_render, ph_output, ph_write,
-               ms_since(t_start));
+               "write %.1f, since start %.1f%s%s\n", ph_load, ph_create, ph_init, ph_render, ph_output, ph_write,
+               ms_since(t_start), multi ? "; transport " : "", multi ? transport_name(mrep.transport) : "");
   elapsed();
   // teardown after the reference's measured span (main.rs:175-176 logs before its drops;
   // the multi-GPU set-up is released by hip_init_join)

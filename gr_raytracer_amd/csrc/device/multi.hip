@@ -12,11 +12,22 @@
 // raytracer.rs:195-244, called from main.rs:80-116 via Raytracer::render_section
 // :460-497); every pixel here is identical to grt_render_pixels / grt_render_section of
 // the same frame on one device (tests/test_multi.py).
+//
+// Two further transports (grt_set_multi_transport) move the same blocks without RCCL: the
+// devices belong to one process, and after a trace's stream synchronise and the host
+// barrier every block is complete in its owner's memory.  GRT_TRANSPORT_PEER maps the
+// devices into each other (hipDeviceEnablePeerAccess) and gather_peer_kernel on the reading
+// device dereferences the owners' blocks in place; GRT_TRANSPORT_PEER_STAGED copies each
+// block into the reader's staging (hipMemcpyPeerAsync) and runs deinterleave_kernel as the
+// RCCL path does.  Neither loads RCCL, and under both a device list may name one GPU
+// several times: each entry is a rank with its own stream, events and arena, which runs
+// the whole N > 1 host path on one GPU (tests/test_multi_peer.py).
 #include <dlfcn.h>
 #include <hip/hip_runtime.h>
 #include <rccl/rccl.h>
 
 #include <algorithm>
+#include <atomic>
 #include <cerrno>
 #include <chrono>
 #include <condition_variable>
@@ -69,13 +80,26 @@ __host__ __device__ inline void frame_row_source(uint32_t band_rows, uint32_t n_
   *local = (band / n_shards) * band_rows + row % band_rows;
 }
 
+// Frame pixel p's field k: the shard that holds it, and its byte offset from the start of
+// what L.src is relative to (the gathered buffer, or the shard's own block).
+__host__ __device__ inline uint64_t gather_source_of(const GatherLayout& L, int k, uint64_t p, uint32_t* shard) {
+  const uint32_t row = (uint32_t)(p / L.cols), col = (uint32_t)(p % L.cols);
+  uint32_t lr;
+  frame_row_source(L.band_rows, L.n_shards, row, shard, &lr);
+  return L.src[*shard][k] + ((uint64_t)lr * L.cols + col) * L.elem[k];
+}
+
 // Byte offset in the gathered buffer of frame pixel p's field k.
 __host__ __device__ inline uint64_t gather_source(const GatherLayout& L, int k, uint64_t p) {
-  const uint32_t row = (uint32_t)(p / L.cols), col = (uint32_t)(p % L.cols);
-  uint32_t s, lr;
-  frame_row_source(L.band_rows, L.n_shards, row, &s, &lr);
-  return L.src[s][k] + ((uint64_t)lr * L.cols + col) * L.elem[k];
+  uint32_t s;
+  return gather_source_of(L, k, p, &s);
 }
+
+// The peer transport's sources: shard s's block where its owner wrote it (another rank's
+// arena, on this or a peer-mapped device); L.src is then relative to base[s].
+struct GatherSrc {
+  const uint8_t* base[MULTI_MAX];
+};
 
 // De-interleave: blockIdx.y = field, a grid-stride loop over the frame's pixels.  Reads
 // are coalesced within a band row (consecutive pixels of one row are consecutive in their
@@ -89,6 +113,36 @@ __global__ void __launch_bounds__(256) deinterleave_kernel(GatherLayout L, const
   for (uint64_t p = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; p < L.n_pixels;
        p += (uint64_t)gridDim.x * blockDim.x) {
     const uint8_t* s = g + gather_source(L, k, p);
+    uint8_t* t = out + p * e;
+    if (e == 32) {
+      const uint4 a = ((const uint4*)s)[0], b = ((const uint4*)s)[1];
+      ((uint4*)t)[0] = a;
+      ((uint4*)t)[1] = b;
+    } else if (e == 16) {
+      *(uint4*)t = *(const uint4*)s;
+    } else if (e == 4) {
+      *(uint32_t*)t = *(const uint32_t*)s;
+    } else {
+      for (uint32_t b = 0; b < e; ++b) t[b] = s[b];
+    }
+  }
+}
+
+// The de-interleave with a base pointer per shard (GRT_TRANSPORT_PEER): the same grid,
+// source function and moves as deinterleave_kernel, reading every block in its owner's
+// memory.  Consecutive pixels of a band row are consecutive in their shard's block, so a
+// wave's reads are contiguous runs of a row (or of the rows around a band edge); the
+// blocks and their field offsets are 256-B aligned, so the 32- and 16-B fields move as
+// 16-B vectors.  Reads of another GPU's block cross xGMI once per byte; writes are local.
+__global__ void __launch_bounds__(256) gather_peer_kernel(GatherLayout L, GatherSrc S, GatherDst d) {
+  const int k = blockIdx.y;
+  const uint32_t e = L.elem[k];
+  uint8_t* __restrict__ out = d.p[k];
+  for (uint64_t p = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; p < L.n_pixels;
+       p += (uint64_t)gridDim.x * blockDim.x) {
+    uint32_t sh;
+    const uint64_t off = gather_source_of(L, k, p, &sh);
+    const uint8_t* __restrict__ s = S.base[sh] + off;
     uint8_t* t = out + p * e;
     if (e == 32) {
       const uint4 a = ((const uint4*)s)[0], b = ((const uint4*)s)[1];
@@ -180,6 +234,11 @@ const Rccl& rccl() {
     if (_r != ncclSuccess) return fail(-EIO, std::string(#expr) + ": " + rccl().GetErrorString(_r)); \
   } while (0)
 
+// grt_set_multi_transport: read once per frame.
+std::atomic<int> g_transport{GRT_TRANSPORT_RCCL};
+// grt_debug_multi_fail: rank * 4 + stage of the injected failure, -1 when none is armed.
+std::atomic<int> g_inject{-1};
+
 constexpr uint64_t align256(uint64_t b) { return (b + 255) & ~255ull; }
 
 // Byte offset of field f in a block of n pixels holding the fields of `mask`; f = RF_N
@@ -210,6 +269,10 @@ struct MultiDev {
 // waits for them only before its first collective.
 struct MultiCtx {
   std::vector<int> devs;
+  int transport = GRT_TRANSPORT_RCCL;  // the transport asked for (part of the cache key)
+  // GRT_TRANSPORT_PEER: every pair of distinct devices is mapped both ways (a context
+  // with a pair that cannot be runs its frames staged)
+  bool peer_mapped = false;
   std::vector<ncclComm_t> comms;
   std::vector<MultiDev> d;
   std::mutex mu;
@@ -238,15 +301,43 @@ struct MultiCtx {
 std::mutex g_ctx_mu;
 std::vector<std::unique_ptr<MultiCtx>> g_ctx;
 
-int get_ctx(const std::vector<int>& devs, MultiCtx** out) {
+// Map every pair of distinct devices of `devs` into each other, once per context and
+// before any arena of it is allocated.  *mapped = false when some pair cannot be.
+int enable_peer_access(const std::vector<int>& devs, bool* mapped) {
+  *mapped = true;
+  for (int a : devs)
+    for (int b : devs) {
+      if (a == b) continue;
+      int can = 0;
+      HIP_TRY(hipDeviceCanAccessPeer(&can, a, b));
+      if (!can) {
+        *mapped = false;
+        continue;
+      }
+      HIP_TRY(hipSetDevice(a));
+      const hipError_t e = hipDeviceEnablePeerAccess(b, 0);
+      if (e == hipErrorPeerAccessAlreadyEnabled) {
+        (void)hipGetLastError();
+      } else if (e != hipSuccess) {
+        (void)hipGetLastError();
+        return fail(-EIO, std::string("hipDeviceEnablePeerAccess: ") + hipGetErrorString(e));
+      }
+    }
+  return 0;
+}
+
+int get_ctx(const std::vector<int>& devs, int transport, MultiCtx** out) {
   std::lock_guard<std::mutex> lk(g_ctx_mu);
   for (auto& c : g_ctx)
-    if (c->devs == devs) {
+    if (c->devs == devs && c->transport == transport) {
       *out = c.get();
       return 0;
     }
   auto c = std::make_unique<MultiCtx>();
   c->devs = devs;
+  c->transport = transport;
+  if (transport == GRT_TRANSPORT_PEER)
+    if (int rc = enable_peer_access(devs, &c->peer_mapped)) return rc;
   c->comms.resize(devs.size());
   c->d.resize(devs.size());
   for (size_t i = 0; i < devs.size(); ++i) {
@@ -261,12 +352,13 @@ int get_ctx(const std::vector<int>& devs, MultiCtx** out) {
   return 0;
 }
 
-// A device list: 1..GRT_MULTI_MAX_DEVICES distinct, valid ordinals.
-int check_devices(int n_devices, const int* devices, std::vector<int>* out) {
+// A device list: 1..GRT_MULTI_MAX_DEVICES valid ordinals, distinct unless `repeats` (the
+// peer transports: each entry is a rank of its own).
+int check_devices(int n_devices, const int* devices, bool repeats, std::vector<int>* out) {
   if (!devices) return fail(-EINVAL, "null argument");
   if (n_devices < 1 || n_devices > grt::MULTI_MAX) return fail(-EINVAL, "n_devices must be in 1..GRT_MULTI_MAX_DEVICES");
   std::vector<int> devs(devices, devices + n_devices);
-  for (int a = 0; a < n_devices; ++a)
+  for (int a = 0; a < n_devices && !repeats; ++a)
     for (int b = a + 1; b < n_devices; ++b)
       if (devs[a] == devs[b]) return fail(-EINVAL, "a device appears twice (one RCCL rank per GPU)");
   int ndev = 0;
@@ -324,7 +416,26 @@ struct Plan {
   uint64_t block_off[grt::MULTI_MAX + 1] = {};  // offsets in the gathered buffer
   uint64_t max_local = 0;
   uint64_t ag_bytes = 0;      // per-device allgather block: (Y, alpha) then class, padded to max_local
+  int transport = GRT_TRANSPORT_RCCL;  // the transport this frame runs
 };
+
+// The peer transports: where each rank's allgather record and send block are this frame.
+// A rank writes its own entries before the first barrier it arrives at with ok = true; the
+// others read them after that barrier, and only when it let them pass.
+struct PeerTable {
+  const uint8_t* ag_send[grt::MULTI_MAX] = {};
+  const uint8_t* block[grt::MULTI_MAX] = {};
+};
+
+// Failed sub-samples each device records before the merge truncates to the caller's
+// capacity (14 B each in the device's adaptive scratch).
+constexpr uint64_t FAIL_KEEP_MIN = 1ull << 16;
+
+// grt_debug_multi_fail: true once, for the armed (rank, stage).
+bool injected_failure(int rank, int stage) {
+  int want = rank * 4 + stage;
+  return g_inject.compare_exchange_strong(want, -1);
+}
 
 struct DevResult {
   int rc = 0;
@@ -384,7 +495,9 @@ uint8_t* field_ptr(uint8_t* block, uint32_t mask, uint64_t n, int f) {
   return (mask & (1u << f)) ? block + field_offset(mask, n, f) : nullptr;
 }
 
-grt::GatherLayout gather_layout(const Plan& P) {
+// in_place: each shard's offsets from the start of its own block (gather_peer_kernel), not
+// from the start of the gathered buffer.
+grt::GatherLayout gather_layout(const Plan& P, bool in_place = false) {
   grt::GatherLayout L;
   std::memset(&L, 0, sizeof(L));
   L.cols = P.cols;
@@ -395,9 +508,48 @@ grt::GatherLayout gather_layout(const Plan& P) {
     if (!(P.mask & (1u << f))) continue;
     const uint32_t k = L.n_fields++;
     L.elem[k] = grt::rec_field_bytes(f);
-    for (uint32_t s = 0; s < P.n_dev; ++s) L.src[s][k] = P.block_off[s] + field_offset(P.mask, P.n_local[s], f);
+    for (uint32_t s = 0; s < P.n_dev; ++s)
+      L.src[s][k] = (in_place ? 0 : P.block_off[s]) + field_offset(P.mask, P.n_local[s], f);
   }
   return L;
+}
+
+// The (Y, alpha, class) allgather's layout: every rank's record is ag_bytes long; stride
+// is the distance between two ranks' records (0: each from its own base pointer).
+grt::GatherLayout allgather_layout(const Plan& P, uint64_t stride) {
+  grt::GatherLayout L;
+  std::memset(&L, 0, sizeof(L));
+  L.cols = P.cols;
+  L.band_rows = P.band;
+  L.n_shards = P.n_dev;
+  L.n_pixels = (uint64_t)P.rows * P.cols;
+  L.n_fields = 2;
+  L.elem[0] = 16;
+  L.elem[1] = 1;
+  for (uint32_t s = 0; s < P.n_dev; ++s) {
+    L.src[s][0] = s * stride;
+    L.src[s][1] = s * stride + align256(P.max_local * 16);
+  }
+  return L;
+}
+
+int launch_gather_peer(const grt::GatherLayout& L, const grt::GatherSrc& S, const grt::GatherDst& d, hipStream_t st) {
+  if (L.n_pixels == 0 || L.n_fields == 0) return 0;
+  const uint64_t want = (L.n_pixels + 255) / 256;
+  const unsigned gx = (unsigned)std::min<uint64_t>(want, 8192);
+  hipLaunchKernelGGL(grt::gather_peer_kernel, dim3(gx, L.n_fields), dim3(256), 0, st, L, S, d);
+  HIP_TRY(hipGetLastError());
+  return 0;
+}
+
+// One block from its owner's arena into the reader's staging, on the reader's stream.
+int copy_block(void* dst, int dst_dev, const void* src, int src_dev, uint64_t bytes, hipStream_t st) {
+  if (bytes == 0) return 0;
+  if (dst_dev == src_dev)
+    HIP_TRY(hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToDevice, st));
+  else
+    HIP_TRY(hipMemcpyPeerAsync(dst, dst_dev, src, src_dev, bytes, st));
+  return 0;
 }
 
 int launch_deinterleave(const grt::GatherLayout& L, const uint8_t* g, const grt::GatherDst& d, hipStream_t st) {
@@ -411,11 +563,26 @@ int launch_deinterleave(const grt::GatherLayout& L, const uint8_t* g, const grt:
 
 // One device's part of one frame.  Every collective is entered only after a barrier that
 // all threads pass with no error so far.
+//
+// The peer transports (P.transport != GRT_TRANSPORT_RCCL; `i` is then a rank, and several
+// ranks may share a GPU) keep the barriers where RCCL has them and replace each collective
+// by reads of the other ranks' arenas on this rank's own stream.  What holds on every way
+// out, errors included:
+//  * a rank synchronises its stream before each barrier, so after one every rank's data
+//    is complete and nothing of this frame is still writing it;
+//  * an arena is written or regrown only by its own rank, before that rank's first
+//    barrier of the frame; others read it only after a barrier, and the last reader
+//    (devices[0]'s gather) is synchronised before its part returns, which is before the
+//    frame's threads are joined and so before the next frame or trace may touch an arena;
+//  * a part leaves its stream idle before it returns, on failure too (the wrapper below),
+//    and a failed rank arrives at the barriers it has not reached with ok = false.
 void device_part(grt_scene* scene, MultiCtx& C, const Plan& P, int i, const grt_adaptive_config* cfg,
                  const double* mask_xyza, const grt_frame_out* out, grt_subsample_failures* want_fail,
-                 Barrier& bar, DevResult& R) {
+                 Barrier& bar, PeerTable& T, DevResult& R) {
   MultiDev& M = C.d[i];
   const int dev = M.device;
+  const bool rccl_path = P.transport == GRT_TRANSPORT_RCCL;
+  const bool direct = P.transport == GRT_TRANSPORT_PEER;
   // every thread arrives at each of the frame's barriers exactly once (a failed thread
   // arrives at the ones it has not reached with ok = false, below)
   const int n_barriers = P.super ? 2 : 1;
@@ -427,6 +594,7 @@ void device_part(grt_scene* scene, MultiCtx& C, const Plan& P, int i, const grt_
   };
   auto run = [&]() -> int {
     HIP_TRY(hipSetDevice(dev));
+    if (!rccl_path && injected_failure(i, 1)) return fail(-EIO, "injected failure before the trace");
     Carve plan;
     DevBufs B;
     carve(plan, P, i, B);
@@ -442,6 +610,8 @@ void device_part(grt_scene* scene, MultiCtx& C, const Plan& P, int i, const grt_
     }
     Carve A{(char*)M.mem, 0};
     carve(A, P, i, B);
+    T.ag_send[i] = B.ag_send;
+    T.block[i] = B.block;
     const uint64_t n = P.n_local[i];
     const hipStream_t st = M.st;
     HIP_TRY(hipMemsetAsync(B.stats, 0, 8 * 8, st));
@@ -460,7 +630,7 @@ void device_part(grt_scene* scene, MultiCtx& C, const Plan& P, int i, const grt_
       if (rc) return rc;
     }
     noted = true;
-    C.note_launched();
+    if (rccl_path) C.note_launched();
     if (P.super) {
       // (Y, alpha) and class of every local pixel, then ONE allgather: every device gets
       // the whole frame's neighbourhood records, de-interleaved into frame order
@@ -471,28 +641,30 @@ void device_part(grt_scene* scene, MultiCtx& C, const Plan& P, int i, const grt_
         HIP_TRY(hipGetLastError());
       }
       HIP_TRY(hipStreamSynchronize(st));
-      if (int rc = comms_ready(C)) return rc;
+      if (rccl_path)
+        if (int rc = comms_ready(C)) return rc;
       if (!barrier()) return fail(-ECANCELED, "another device failed");
       HIP_TRY(hipEventRecord(M.ev[2], st));
-      NCCL_TRY(rccl().AllGather(B.ag_send, B.ag_recv, P.ag_bytes, ncclUint8, C.comms[i], st));
-      grt::GatherLayout L;
-      std::memset(&L, 0, sizeof(L));
-      L.cols = P.cols;
-      L.band_rows = P.band;
-      L.n_shards = P.n_dev;
-      L.n_pixels = (uint64_t)P.rows * P.cols;
-      L.n_fields = 2;
-      L.elem[0] = 16;
-      L.elem[1] = 1;
-      for (uint32_t s = 0; s < P.n_dev; ++s) {
-        L.src[s][0] = s * P.ag_bytes;
-        L.src[s][1] = s * P.ag_bytes + align256(P.max_local * 16);
-      }
+      grt::GatherLayout L = allgather_layout(P, direct ? 0 : P.ag_bytes);
       grt::GatherDst d{};
       d.p[0] = (uint8_t*)B.frame_ya;
       d.p[1] = B.frame_cls;
-      if (int rc = launch_deinterleave(L, B.ag_recv, d, st)) return rc;
+      if (direct) {  // every rank's record read where its owner packed it
+        grt::GatherSrc S{};
+        for (uint32_t s = 0; s < P.n_dev; ++s) S.base[s] = T.ag_send[s];
+        if (int rc = launch_gather_peer(L, S, d, st)) return rc;
+      } else {
+        if (rccl_path) {
+          NCCL_TRY(rccl().AllGather(B.ag_send, B.ag_recv, P.ag_bytes, ncclUint8, C.comms[i], st));
+        } else {
+          for (uint32_t s = 0; s < P.n_dev; ++s)
+            if (int rc = copy_block(B.ag_recv + s * P.ag_bytes, dev, T.ag_send[s], C.d[s].device, P.ag_bytes, st))
+              return rc;
+        }
+        if (int rc = launch_deinterleave(L, B.ag_recv, d, st)) return rc;
+      }
       HIP_TRY(hipEventRecord(M.ev[3], st));
+      if (!rccl_path && injected_failure(i, 2)) return fail(-EIO, "injected failure after the allgather");
       // the frame's exact 99th-percentile floor (or the configured minimum), then this
       // device's selection and sub-rays (grt_supersample_shard_device, longest first)
       const bool dev_floor = !cfg->has_minimum_luminance;
@@ -503,7 +675,10 @@ void device_part(grt_scene* scene, MultiCtx& C, const Plan& P, int i, const grt_
       grt_subsample_failures fl{};
       grt_subsample_failures* flp = nullptr;
       if (want_fail && want_fail->capacity && want_fail->pixel && want_fail->status) {
-        const uint64_t cap = want_fail->capacity;
+        // a device keeps whichever of its failures arrive first, so the merged list is the
+        // frame's first `capacity` in (pixel, sample) order only while every device holds
+        // all of its own: each keeps at least FAIL_KEEP_MIN, whatever the caller's capacity
+        const uint64_t cap = std::max<uint64_t>(want_fail->capacity, FAIL_KEEP_MIN);
         R.f_pix.resize(cap);
         R.f_smp.resize(cap);
         R.f_status.resize(cap);
@@ -529,22 +704,35 @@ void device_part(grt_scene* scene, MultiCtx& C, const Plan& P, int i, const grt_
     HIP_TRY(hipStreamSynchronize(st));
     // ONE gather: every device sends its block to devices[0] (grouped send / receive;
     // devices[0] sends to itself too, so every frame takes the same RCCL path)
-    if (int rc = comms_ready(C)) return rc;
+    if (rccl_path)
+      if (int rc = comms_ready(C)) return rc;
     if (!barrier()) return fail(-ECANCELED, "another device failed");
+    if (!rccl_path && injected_failure(i, 3)) return fail(-EIO, "injected failure before the gather");
     HIP_TRY(hipEventRecord(M.ev[4], st));
-    NCCL_TRY(rccl().GroupStart());
-    NCCL_TRY(rccl().Send(B.block, P.block[i], ncclUint8, 0, C.comms[i], st));
-    if (i == 0)
+    if (rccl_path) {
+      NCCL_TRY(rccl().GroupStart());
+      NCCL_TRY(rccl().Send(B.block, P.block[i], ncclUint8, 0, C.comms[i], st));
+      if (i == 0)
+        for (uint32_t s = 0; s < P.n_dev; ++s)
+          NCCL_TRY(rccl().Recv(B.gathered + P.block_off[s], P.block[s], ncclUint8, (int)s, C.comms[i], st));
+      NCCL_TRY(rccl().GroupEnd());
+    } else if (i == 0 && !direct) {
       for (uint32_t s = 0; s < P.n_dev; ++s)
-        NCCL_TRY(rccl().Recv(B.gathered + P.block_off[s], P.block[s], ncclUint8, (int)s, C.comms[i], st));
-    NCCL_TRY(rccl().GroupEnd());
+        if (int rc = copy_block(B.gathered + P.block_off[s], dev, T.block[s], C.d[s].device, P.block[s], st)) return rc;
+    }
     if (i == 0) {
-      const grt::GatherLayout L = gather_layout(P);
+      const grt::GatherLayout L = gather_layout(P, direct);
       grt::GatherDst d{};
       const uint64_t F = L.n_pixels;
       for (int f = 0, k = 0; f < grt::RF_N; ++f)
         if (P.mask & (1u << f)) d.p[k++] = B.frame + field_offset(P.mask, F, f);
-      if (int rc = launch_deinterleave(L, B.gathered, d, st)) return rc;
+      if (direct) {  // rank 0 reads every rank's block in place
+        grt::GatherSrc S{};
+        for (uint32_t s = 0; s < P.n_dev; ++s) S.base[s] = T.block[s];
+        if (int rc = launch_gather_peer(L, S, d, st)) return rc;
+      } else if (int rc = launch_deinterleave(L, B.gathered, d, st)) {
+        return rc;
+      }
     }
     HIP_TRY(hipEventRecord(M.ev[5], st));
     if (i == 0) {  // frame-order fields to the caller
@@ -571,9 +759,13 @@ void device_part(grt_scene* scene, MultiCtx& C, const Plan& P, int i, const grt_
     return 0;
   };
   R.rc = run();
-  if (!noted) C.note_launched();  // failed before its trace: the others must not wait
+  if (!noted && rccl_path) C.note_launched();  // failed before its trace: the others must not wait
   if (R.rc) {
     R.err = grt_last_error();
+    // peer transports: what this rank enqueued may read other ranks' arenas, and its own
+    // arena is read by the others once they pass a barrier; the stream is idle before
+    // this thread arrives anywhere or returns
+    if (!rccl_path && hipSetDevice(dev) == hipSuccess) (void)hipStreamSynchronize(M.st);
     // the barriers this thread has not reached: the other threads stop there instead of
     // entering a collective this device will not join
     for (; passed < n_barriers; ++passed) bar.arrive(false);
@@ -594,8 +786,9 @@ int grt_render_frame_multi(grt_scene* scene, int n_devices, const int* devices, 
   if (failures) failures->count = 0;
   if (!scene || !devices || !out) return fail(-EINVAL, "null argument");
   if (band_rows == 0) return fail(-EINVAL, "band_rows must be >= 1");
+  const int transport = g_transport.load();
   std::vector<int> devs;
-  if (int rc = check_devices(n_devices, devices, &devs)) return rc;
+  if (int rc = check_devices(n_devices, devices, transport != GRT_TRANSPORT_RCCL, &devs)) return rc;
   Plan P;
   P.n_dev = (uint32_t)n_devices;
   P.band = band_rows;
@@ -632,8 +825,11 @@ int grt_render_frame_multi(grt_scene* scene, int n_devices, const int* devices, 
   P.ag_bytes = align256(P.max_local * 16) + align256(P.max_local);
   if (P.super && (uint64_t)P.rows * P.cols > (uint64_t)INT32_MAX) return fail(-EOVERFLOW, "frame larger than INT_MAX pixels");
   MultiCtx* C;
-  if (int rc = get_ctx(devs, &C)) return rc;
+  if (int rc = get_ctx(devs, transport, &C)) return rc;
   std::lock_guard<std::mutex> lk(C->mu);
+  // a device pair that cannot be mapped: the frame moves its blocks by copies
+  P.transport = (transport == GRT_TRANSPORT_PEER && !C->peer_mapped) ? GRT_TRANSPORT_PEER_STAGED : transport;
+  const bool ranks = P.transport != GRT_TRANSPORT_RCCL;
   std::vector<DevResult> R;
   uint32_t attempt = 0;
   // a trace that lost hit candidates (a device's hit pool too small) grows that device's
@@ -642,11 +838,12 @@ int grt_render_frame_multi(grt_scene* scene, int n_devices, const int* devices, 
     ++attempt;
     R.assign(P.n_dev, DevResult());
     Barrier bar(n_devices);
+    PeerTable T;
     std::vector<std::thread> th;
     for (int i = 1; i < n_devices; ++i)
       th.emplace_back(device_part, scene, std::ref(*C), std::cref(P), i, cfg, sampling_mask_xyza, out, failures,
-                      std::ref(bar), std::ref(R[i]));
-    device_part(scene, *C, P, 0, cfg, sampling_mask_xyza, out, failures, bar, R[0]);
+                      std::ref(bar), std::ref(T), std::ref(R[i]));
+    device_part(scene, *C, P, 0, cfg, sampling_mask_xyza, out, failures, bar, T, R[0]);
     for (auto& t : th) t.join();
     {  // no communicator is still being created when this call returns (a frame that
        // failed before its collectives has not waited for them)
@@ -658,7 +855,10 @@ int grt_render_frame_multi(grt_scene* scene, int n_devices, const int* devices, 
       if (f.valid()) (void)f.get();
     }
     for (uint32_t i = 0; i < P.n_dev; ++i)
-      if (R[i].rc && R[i].rc != -ECANCELED) return fail(R[i].rc, "device " + std::to_string(devs[i]) + ": " + R[i].err);
+      if (R[i].rc && R[i].rc != -ECANCELED)
+        return fail(R[i].rc, (ranks ? "rank " + std::to_string(i) + " (device " + std::to_string(devs[i]) + ")"
+                                    : "device " + std::to_string(devs[i])) +
+                                 ": " + R[i].err);
     for (uint32_t i = 0; i < P.n_dev; ++i)
       if (R[i].rc) return fail(R[i].rc, R[i].err);
     uint64_t lost = 0;
@@ -714,6 +914,7 @@ int grt_render_frame_multi(grt_scene* scene, int n_devices, const int* devices, 
       if (P.mask & (1u << f)) rb += grt::rec_field_bytes(f);
     report->record_bytes = rb;
     report->attempts = attempt;
+    report->transport = (uint32_t)P.transport;
     report->gather_ms = R[0].gather_ms;
     for (uint32_t i = 0; i < P.n_dev; ++i) {
       report->trace_ms[i] = R[i].trace_ms;
@@ -743,6 +944,29 @@ void grt_multi_release(void) {
       for (auto& cm : c->comms) (void)rccl().CommDestroy(cm);
   }
   g_ctx.clear();
+}
+
+int grt_set_multi_transport(int mode) {
+  if (mode != GRT_TRANSPORT_RCCL && mode != GRT_TRANSPORT_PEER && mode != GRT_TRANSPORT_PEER_STAGED)
+    return fail(-EINVAL, "multi-GPU transport must be 0 (RCCL), 1 (peer) or 2 (peer, staged)");
+  g_transport.store(mode);
+  return 0;
+}
+
+int grt_get_multi_transport(void) { return g_transport.load(); }
+
+// Test hook (not in grt_api.h): the next frame of a peer transport fails on `rank` with
+// -EIO from host code, before it enqueues anything of `stage` (1: its trace, 2: the
+// supersample pass after the allgather, 3: devices[0]'s gather after the last barrier).
+// One-shot: it clears itself when it fires; rank < 0 disarms it.  No GPU state is touched.
+int grt_debug_multi_fail(int rank, int stage) {
+  if (rank < 0) {
+    g_inject.store(-1);
+    return 0;
+  }
+  if (rank >= grt::MULTI_MAX || stage < 1 || stage > 3) return fail(-EINVAL, "multi_fail: bad rank or stage");
+  g_inject.store(rank * 4 + stage);
+  return 0;
 }
 
 // Test hook (not in grt_api.h): the de-interleave of deinterleave_kernel run on the host
@@ -775,6 +999,40 @@ int grt_debug_deinterleave_host(uint32_t rows, uint32_t cols, uint32_t band_rows
     const uint32_t e = L.elem[k];
     if (dst[f])
       for (uint64_t p = 0; p < L.n_pixels; ++p) std::memcpy(dst[f] + p * e, gathered + grt::gather_source(L, k, p), e);
+    ++k;
+  }
+  return 0;
+}
+
+// Test hook (not in grt_api.h): gather_peer_kernel's assembly run on the host with the
+// same per-pixel source function (gather_source_of) and layout (gather_layout, in place):
+// blocks[s] is shard s's block as its owner holds it, an allocation of its own (unused for
+// a shard without rows); dst[f] as for grt_debug_deinterleave_host.
+int grt_debug_gather_peer_host(uint32_t rows, uint32_t cols, uint32_t band_rows, uint32_t n_shards, uint32_t mask,
+                               const uint8_t* const* blocks, uint8_t* const* dst) {
+  if (!blocks || !dst || n_shards == 0 || n_shards > (uint32_t)grt::MULTI_MAX || band_rows == 0 || mask >= 64u)
+    return fail(-EINVAL, "gather_peer: bad argument");
+  Plan P;
+  P.rows = rows;
+  P.cols = cols;
+  P.band = band_rows;
+  P.n_dev = n_shards;
+  P.mask = mask;
+  for (uint32_t s = 0; s < n_shards; ++s) {
+    grt_row_shard sh{band_rows, s, n_shards};
+    P.n_local[s] = (uint64_t)grt_shard_row_count(rows, &sh) * cols;
+    if (P.n_local[s] && !blocks[s]) return fail(-EINVAL, "gather_peer: a shard with rows has no block");
+  }
+  const grt::GatherLayout L = gather_layout(P, true);
+  for (int f = 0, k = 0; f < grt::RF_N; ++f) {
+    if (!(mask & (1u << f))) continue;
+    const uint32_t e = L.elem[k];
+    if (dst[f])
+      for (uint64_t p = 0; p < L.n_pixels; ++p) {
+        uint32_t s;
+        const uint64_t off = grt::gather_source_of(L, k, p, &s);
+        std::memcpy(dst[f] + p * e, blocks[s] + off, e);
+      }
     ++k;
   }
   return 0;

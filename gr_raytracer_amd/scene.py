@@ -235,10 +235,13 @@ class Scene:
 
     def render_frame_multi(self, devices=(0,), band_rows: int = 16, adaptive: Optional[L.AdaptiveConfig] = None,
                            supersample: bool = False, sampling_mask_xyza=None, fields=("xyza", "class", "status"),
-                           fail_capacity: int = 0) -> dict:
+                           fail_capacity: int = 0, transport=None) -> dict:
         """The whole frame over `devices` (grt_render_frame_multi: cyclic row bands, one host
-        thread per device, one RCCL gather to devices[0]).  fields: which of "xyza" (f32),
-        "xyza64", "class", "status", "stop", "steps" to return (frame order).  supersample:
+        thread per device, one gather to devices[0]).  transport: "rccl", "peer" or
+        "peer-staged" (or the grt_multi_transport number) sets grt_set_multi_transport for
+        this call and restores it afterwards; None leaves the knob as it is.  Under the peer
+        transports `devices` may repeat an ordinal (one rank per entry).  fields: which of
+        "xyza" (f32), "xyza64", "class", "status", "stop", "steps" to return (frame order).  supersample:
         the adaptive pass with `adaptive` (default: the scene's own configuration).
         Returns a dict of the fields plus "stats", "n_supersampled", "report" and, with
         fail_capacity, "failures" (pixel, sample, status, stop, steps arrays)."""
@@ -279,11 +282,22 @@ class Scene:
         nsel = C.c_uint64(0)
         st = L.Stats()
         rep = L.MultiReport()
-        L.check(L.lib().grt_render_frame_multi(self._s, len(devices), devs, band_rows,
-                                               C.byref(cfg) if cfg is not None else None,
-                                               L.dptr(mask) if mask is not None else None, C.byref(out),
-                                               C.byref(nsel), C.byref(st), C.byref(fails) if fails is not None else None,
-                                               C.byref(rep)), "grt_render_frame_multi")
+        lib = L.lib()
+        before = None
+        if transport is not None:
+            mode = L.MULTI_TRANSPORTS[transport] if isinstance(transport, str) else int(transport)
+            before = lib.grt_get_multi_transport()
+            L.check(lib.grt_set_multi_transport(mode), "grt_set_multi_transport")
+        try:
+            rc = lib.grt_render_frame_multi(self._s, len(devices), devs, band_rows,
+                                            C.byref(cfg) if cfg is not None else None,
+                                            L.dptr(mask) if mask is not None else None, C.byref(out),
+                                            C.byref(nsel), C.byref(st), C.byref(fails) if fails is not None else None,
+                                            C.byref(rep))
+        finally:
+            if before is not None:
+                lib.grt_set_multi_transport(before)
+        L.check(rc, "grt_render_frame_multi")
         arrays["stats"] = _stats_dict(st)
         arrays["n_supersampled"] = int(nsel.value)
         arrays["report"] = rep

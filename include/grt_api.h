@@ -456,8 +456,32 @@ int grt_render_shard_async(grt_scene* scene, int device, void* stream, const grt
  * (raytracer.rs:195-318) as Raytracer::render_section calls it (:460-497, main.rs:80-116).
  * Every pixel equals grt_render_pixels / grt_render_section_ex of the same frame on one
  * device.  The communicators, streams and device scratch are created on the first call
- * for a device list and kept (grt_multi_release frees them). */
+ * for a device list and kept (grt_multi_release frees them).
+ *
+ * Transports (grt_set_multi_transport, process-wide like grt_set_arithmetic, read once per
+ * grt_render_frame_multi call; default GRT_TRANSPORT_RCCL, the path above):
+ *  - GRT_TRANSPORT_PEER: no RCCL.  The devices are mapped into each other once per device
+ *    list (hipDeviceEnablePeerAccess); after the host barrier that follows each rank's
+ *    stream synchronise, a kernel on the reading device dereferences the owners' blocks in
+ *    place (all ranks for the (Y, alpha, class) exchange, devices[0] for the final gather).
+ *    A list with a device pair that cannot be mapped runs GRT_TRANSPORT_PEER_STAGED
+ *    (grt_multi_report.transport says which ran).
+ *  - GRT_TRANSPORT_PEER_STAGED: no RCCL and no mapping.  hipMemcpyPeerAsync copies each
+ *    block into the reader's staging, then the de-interleave kernel of the RCCL path.
+ * Neither loads librccl or creates a communicator, at n_devices = 1 too.  Under both, a
+ * device list may name one ordinal several times: each entry is a rank with its own
+ * stream, events and scratch ("virtual ranks"; {0, 0, 0} is three ranks on GPU 0), which is
+ * how the N > 1 host path is held to the single-device frame bit for bit on one GPU
+ * (tests/test_multi_peer.py).  Under GRT_TRANSPORT_RCCL a repeated ordinal is -EINVAL.  No
+ * N > 1 frame over distinct GPUs has run on hardware under any transport.  A failure on
+ * one rank ends the frame on all of them ("rank k (device d): ..."); the cached state
+ * stays usable. */
 #define GRT_MULTI_MAX_DEVICES 16
+
+enum grt_multi_transport { GRT_TRANSPORT_RCCL = 0, GRT_TRANSPORT_PEER = 1, GRT_TRANSPORT_PEER_STAGED = 2 };
+/* 0 on success, -EINVAL for a mode that is none of the above. */
+int grt_set_multi_transport(int mode);
+int grt_get_multi_transport(void);
 
 /* Host outputs in frame order (camera rows x cols); a NULL field is not gathered.  The
  * gather moves 2 B per pixel (class, status) plus the requested fields: f32 XYZA + class
@@ -476,17 +500,17 @@ typedef struct grt_multi_report {
   uint32_t n_devices;
   uint32_t record_bytes;     /* bytes per pixel the gather moved                                */
   uint32_t attempts;         /* traces of the frame (more than 1 when a hit pool had to grow)   */
-  uint32_t _pad;
+  uint32_t transport;        /* the grt_multi_transport that ran                                */
   double wall_ms;            /* the whole call, host clock                                      */
-  double gather_ms;          /* last trace: RCCL gather + de-interleave on devices[0] (events)  */
+  double gather_ms;          /* last trace: gather + de-interleave on devices[0] (events)       */
   double allgather_ms;       /* supersampling: the (Y, alpha, class) allgather, max over devices */
   double trace_ms[GRT_MULTI_MAX_DEVICES];        /* per device: its trace (+ supersample pass)   */
   uint64_t accepted_steps[GRT_MULTI_MAX_DEVICES];
   uint64_t rows[GRT_MULTI_MAX_DEVICES];          /* frame rows each device traced                */
 } grt_multi_report;
 
-/* Render the whole camera frame over n_devices distinct GPUs (1 <= n <= 16; n = 1 runs the
- * same RCCL path with a one-rank communicator).  cfg (nullable): the scene's adaptive
+/* Render the whole camera frame over n_devices GPUs (1 <= n <= 16; distinct under
+ * GRT_TRANSPORT_RCCL, where n = 1 runs the same RCCL path with a one-rank communicator).  cfg (nullable): the scene's adaptive
  * configuration (grt_host_scene_adaptive), NULL or !enabled = 1 spp; sampling_mask_xyza
  * (nullable): paint the selected pixels instead (--show-sampling-mask).  stats: summed
  * counters, kernel_ms the slowest device's trace.  failures (nullable): every device's
