@@ -137,6 +137,12 @@ class MultiReport(C.Structure):
                 ("rows", C.c_uint64 * GRT_MULTI_MAX_DEVICES)]
 
 
+class SequenceReport(C.Structure):
+    """grt_sequence_report: launch groups and event times of grt_render_sequence."""
+    _fields_ = [("n_frames", C.c_uint32), ("n_launches", C.c_uint32), ("frames_per_launch", C.c_uint32),
+                ("_pad", C.c_uint32), ("wall_ms", _d), ("trace_ms", _d), ("supersample_ms", _d)]
+
+
 class Health(C.Structure):
     _fields_ = [
         ("rays", C.c_uint64), ("failed", C.c_uint64), ("null_violations", C.c_uint64), ("max_null", _d),
@@ -259,6 +265,11 @@ def lib() -> C.CDLL:
         "grt_get_arithmetic": (C.c_int, []),
         "grt_set_multi_transport": (C.c_int, [C.c_int]),
         "grt_get_multi_transport": (C.c_int, []),
+        "grt_host_scene_camera": (C.c_int, [vp, _pd, _d, _d, _d, C.POINTER(CameraDesc)]),
+        "grt_render_sequence": (C.c_int, [vp, C.c_int, u32, C.POINTER(CameraDesc), C.POINTER(AdaptiveConfig), _pd,
+                                          C.POINTER(FrameOut), C.POINTER(C.c_uint64), C.POINTER(Stats),
+                                          C.POINTER(SubsampleFailures), C.POINTER(SequenceReport)]),
+        "grt_set_sequence_group": (C.c_int, [u64]),
     }
     # GRT_LIB_ALLOW_MISSING=1 (tools/time_variants.py only) binds an older experimental
     # build that lacks newer entry points; by default a missing symbol is an error.
@@ -307,6 +318,7 @@ EXPORTED_SYMBOLS = [
     "grt_supersample_shard_device", "grt_adaptive_floor_device", "grt_render_section_ex",
     "grt_write_png_rgb", "grt_write_hdr_xyz", "grt_render_frame_multi", "grt_multi_release",
     "grt_set_arithmetic", "grt_get_arithmetic", "grt_set_multi_transport", "grt_get_multi_transport",
+    "grt_host_scene_camera", "grt_render_sequence", "grt_set_sequence_group",
 ]
 
 

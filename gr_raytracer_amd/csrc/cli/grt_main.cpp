@@ -7,6 +7,7 @@
 //       [--sampling-mask-color r,g,b] --config-file scene.toml
 //       render [--filename out.png|out.hdr] [--from-row N] [--from-col N]
 //              [--to-row N] [--to-col N]
+//     | render-sequence --camera-path P [--filename-pattern frame-%04d.png] [--first-index 0]
 //     | render-ray -r ROW -c COL [--filename rendered-ray.csv]
 //     | render-ray-at -p x,y,z -d x,y,z [--filename rendered-ray-at.csv]
 //     | blackbody -t T [-r Z]
@@ -22,6 +23,11 @@
 // blocks move (grt_set_multi_transport; rccl by default; under the peer transports
 // --devices may name a GPU several times, one rank per entry); --arithmetic exact|fused
 // selects grt_set_arithmetic (exact, the reference's roundings, by default).
+// render-sequence (not in the reference, whose animations are one process per frame):
+// the frames of a camera path -- a text file, one camera per line `x,y,z,phi,theta,psi`
+// -- over one load of the scene, traced in stacked launches (grt_render_sequence); frame
+// k is what `render` writes for that line's --camera-position/--phi/--theta/--psi, to
+// --filename-pattern (and --raw-out, a pattern too) at index --first-index + k.
 #include <algorithm>
 #include <charconv>
 #include <chrono>
@@ -48,6 +54,8 @@ bool hdr_encode_rgb(const std::string& path, const float* rgb, uint32_t w, uint3
 static int usage(const char* msg) {
   std::fprintf(stderr,
                "error: %s\nusage: grt [global options] --config-file FILE render [--filename F]\n"
+               "       grt [global options] --config-file FILE render-sequence --camera-path P\n"
+               "           [--filename-pattern frame-%%04d.png] [--first-index N]\n"
                "       grt [global options] --config-file FILE render-ray -r ROW -c COL [--filename F]\n"
                "       grt [global options] --config-file FILE render-ray-at -p X,Y,Z -d X,Y,Z [--filename F]\n"
                "       grt [global options] blackbody -t T [-r Z]\n"
@@ -230,6 +238,137 @@ static int trace_and_save(grt_scene* scene, int device, const grt_scene_desc* d,
   return 0;
 }
 
+// The log lines of one rendered frame or section (origin r0, c0, width w), as the reference
+// prints them.  The 1-spp pass, in pixel order (the reference logs from its parallel loop):
+//  * raytracer.rs:232-239: a pixel whose color_of_ray failed (Debug form of the
+//    RaytracerError); it keeps the default colour;
+//  * scene.rs:178-183 / :196-202: an error-free ray that ended on NaN coordinates or
+//    without a terminal event (steps.len() counts the initial step too).
+// Then, with `supersampled`, supersample's line (raytracer.rs:325) and its sub-rays' lines.
+static void log_frame_rays(uint32_t r0, uint32_t c0, uint32_t w, const std::vector<uint8_t>& status,
+                           const std::vector<uint8_t>& stop, const std::vector<uint32_t>& steps, bool supersampled,
+                           uint64_t nsel, const grt_subsample_failures& fails) {
+  for (size_t i = 0; i < status.size(); ++i) {
+    const unsigned col = (unsigned)(c0 + i % w), row = (unsigned)(r0 + i / w);
+    if (status[i] & 0x7f)
+      std::fprintf(stderr, "[grt] ERROR Unable to compute color for ray at pixel (%u, %u): %s\n", col, row,
+                   error_debug_name(status[i] & 0x7f));
+    else
+      log_ray_event(row, col, stop[i], steps[i]);
+  }
+  if (!supersampled) return;
+  std::fprintf(stderr, "[grt] INFO Supersampling %llu pixels\n", (unsigned long long)nsel);
+  // :357-362: the same error line for each failed sub-sample ray of a supersampled pixel
+  for (uint64_t k = 0; k < std::min<uint64_t>(fails.count, fails.capacity); ++k) {
+    const unsigned col = (unsigned)(c0 + fails.pixel[k] % w), row = (unsigned)(r0 + fails.pixel[k] / w);
+    if (fails.status[k])
+      std::fprintf(stderr, "[grt] ERROR Unable to compute color for ray at pixel (%u, %u): %s\n", col, row,
+                   error_debug_name(fails.status[k]));
+    else
+      log_ray_event(row, col, fails.stop[k], fails.steps[k]);
+  }
+  if (fails.count > fails.capacity)
+    std::fprintf(stderr, "[grt] ERROR %llu more failed or unterminated sub-sample rays not listed\n",
+                 (unsigned long long)(fails.count - fails.capacity));
+}
+
+// The output stage of a frame: `.hdr` (f32 XYZ) or the tone-mapped PNG by the extension of
+// `filename`, and the raw f64 XYZA dump when asked for.  Adds its times to *ph_output (tone
+// map) and *ph_write (encode + write).  Returns 0 or the process exit code.
+static int write_frame(const std::string& filename, const std::string& raw_out, const std::vector<double>& xyza,
+                       uint32_t w, uint32_t h, int32_t tone_mapping, int device, double* ph_output, double* ph_write) {
+  using clk = std::chrono::steady_clock;
+  auto ms_since = [](clk::time_point t) { return std::chrono::duration<double, std::milli>(clk::now() - t).count(); };
+  const bool hdr = filename.size() >= 4 && filename.compare(filename.size() - 4, 4, ".hdr") == 0;
+  std::string err;
+  bool ok;
+  auto t_phase = clk::now();
+  if (hdr) {
+    std::vector<float> rgb((size_t)w * h * 3);
+    for (size_t i = 0; i < (size_t)w * h; ++i)
+      for (int k = 0; k < 3; ++k) rgb[3 * i + k] = (float)xyza[4 * i + k];
+    ok = grt_host::hdr_encode_rgb(filename, rgb.data(), w, h, err);
+  } else {
+    std::vector<uint8_t> rgb((size_t)w * h * 3);
+    // output stage on the GPU (color.rs:204-298 via output.hip), exposure 1 as in
+    // render_section (raytracer.rs:485)
+    if (grt_xyz_to_srgb8_device(device, xyza.data(), (size_t)w * h, tone_mapping, 1.0, rgb.data())) {
+      std::fprintf(stderr, "Error: %s\n", grt_last_error());
+      return 1;
+    }
+    *ph_output += ms_since(t_phase);
+    t_phase = clk::now();
+    ok = grt_host::png_encode_rgb(filename, rgb.data(), w, h, err);
+  }
+  if (!ok) {
+    std::fprintf(stderr, "Error: %s\n", err.c_str());
+    return 1;
+  }
+  if (!raw_out.empty()) {
+    FILE* f = std::fopen(raw_out.c_str(), "wb");
+    if (f) {
+      std::fwrite(xyza.data(), 8, xyza.size(), f);
+      std::fclose(f);
+    }
+  }
+  *ph_write += ms_since(t_phase);
+  return 0;
+}
+
+// render-sequence: a camera-path file, one camera per line `x,y,z,phi,theta,psi` (the
+// values --camera-position, --phi, --theta, --psi take); blank lines and lines starting
+// with `#` are skipped.  On error *err names the line.
+static bool load_camera_path(const std::string& path, std::vector<std::vector<double>>& cams, std::string* err) {
+  FILE* f = std::fopen(path.c_str(), "r");
+  if (!f) {
+    *err = "cannot read the camera path " + path;
+    return false;
+  }
+  std::string text;
+  char buf[4096];
+  size_t got;
+  while ((got = std::fread(buf, 1, sizeof buf, f)) > 0) text.append(buf, got);
+  std::fclose(f);
+  size_t no = 0;
+  for (size_t p = 0; p < text.size();) {
+    size_t q = text.find('\n', p);
+    if (q == std::string::npos) q = text.size();
+    std::string line = text.substr(p, q - p);
+    p = q + 1;
+    ++no;
+    const size_t a = line.find_first_not_of(" \t\r"), b = line.find_last_not_of(" \t\r");
+    if (a == std::string::npos || line[a] == '#') continue;
+    line = line.substr(a, b - a + 1);
+    std::vector<double> v;
+    if (!split_csv(line, v) || v.size() != 6) {
+      *err = path + ":" + std::to_string(no) + ": expected six numbers `x,y,z,phi,theta,psi`, found `" + line + "`";
+      return false;
+    }
+    cams.push_back(v);
+  }
+  if (cams.empty()) {
+    *err = path + ":1: the camera path holds no camera";
+    return false;
+  }
+  return true;
+}
+
+// `pattern` with its one `%d` / `%0Nd` conversion replaced by `index`; false when the
+// pattern has no such conversion (every frame would overwrite the last).
+static bool expand_pattern(const std::string& pattern, long long index, std::string* out) {
+  const size_t p = pattern.find('%');
+  if (p == std::string::npos) return false;
+  size_t q = p + 1;
+  const bool zero = q < pattern.size() && pattern[q] == '0';
+  int width = 0;
+  while (q < pattern.size() && std::isdigit((unsigned char)pattern[q])) width = width * 10 + (pattern[q++] - '0');
+  if (q >= pattern.size() || pattern[q] != 'd' || width > 32 || pattern.find('%', q) != std::string::npos) return false;
+  std::string num = std::to_string(index);
+  if ((int)num.size() < width) num.insert(0, (size_t)width - num.size(), zero ? '0' : ' ');
+  *out = pattern.substr(0, p) + num + pattern.substr(q + 1);
+  return true;
+}
+
 int main(int argc, char** argv) {
   auto t_start = std::chrono::steady_clock::now();
   grt_global_opts opts;
@@ -247,6 +386,8 @@ int main(int argc, char** argv) {
   int device = 0;
   std::vector<int> multi_devices;  // --gpus / --devices: the multi-GPU frame
   uint32_t band_rows = 16;
+  std::string camera_path, filename_pattern = "frame-%04d.png";  // render-sequence
+  long long first_index = 0;
   std::vector<std::string> args(argv + 1, argv + argc);
   for (size_t i = 0; i < args.size(); ++i) {
     std::string a = args[i], val;
@@ -267,8 +408,8 @@ int main(int argc, char** argv) {
       return true;
     };
     std::string v;
-    if (action.empty() && (a == "render" || a == "render-ray" || a == "render-ray-at" || a == "blackbody" ||
-                           a == "blackbody-spectrum")) {
+    if (action.empty() && (a == "render" || a == "render-sequence" || a == "render-ray" || a == "render-ray-at" ||
+                           a == "blackbody" || a == "blackbody-spectrum")) {
       action = a;
       continue;
     }
@@ -317,7 +458,13 @@ int main(int argc, char** argv) {
     if (a == "--resource-root") { resource_root = v; continue; }
     if (a == "--raw-out") { raw_out = v; continue; }
     if (!action.empty()) {  // subcommand options
-      if (a == "--filename") filename = v;
+      if (a == "--filename" && action != "render-sequence") filename = v;
+      else if (action == "render-sequence" && a == "--camera-path") camera_path = v;
+      else if (action == "render-sequence" && a == "--filename-pattern") filename_pattern = v;
+      else if (action == "render-sequence" && a == "--first-index") {
+        if (!int_in(0, 1000000000ull, &iv)) return bad();
+        first_index = iv;
+      }
       else if (action == "render" && (a == "--from-row" || a == "--from-col" || a == "--to-row" || a == "--to-col")) {
         if (!int_in(0, 4294967295ull, &iv)) return bad();  // Option<u32>
         (a == "--from-row" ? from_row : a == "--from-col" ? from_col : a == "--to-row" ? to_row : to_col) = (long)iv;
@@ -386,7 +533,8 @@ int main(int argc, char** argv) {
     } else if (a == "-c" || a == "--config-file") config_file = v;
     else return usage(("unknown argument " + a).c_str());
   }
-  if (action.empty()) return usage("missing subcommand (render, render-ray, render-ray-at, blackbody, blackbody-spectrum)");
+  if (action.empty())
+    return usage("missing subcommand (render, render-sequence, render-ray, render-ray-at, blackbody, blackbody-spectrum)");
   if (action == "blackbody") {  // run_blackbody (cli/blackbody.rs:7-25): no scene needed
     if (!have_temperature) return usage("blackbody needs --temperature");
     double xyz[3];
@@ -422,6 +570,17 @@ int main(int argc, char** argv) {
   if (filename.empty())
     filename = action == "render" ? "render.png" : (action == "render-ray" ? "rendered-ray.csv" : "rendered-ray-at.csv");
   if (config_file.empty()) return usage("Config file is required for this action");
+  std::vector<std::vector<double>> path_cams;  // render-sequence: x, y, z, phi, theta, psi per frame
+  if (action == "render-sequence") {  // every usage error before the GPU is touched
+    if (camera_path.empty()) return usage("render-sequence needs --camera-path");
+    if (!multi_devices.empty()) return usage("render-sequence runs on one GPU (--device); --gpus / --devices do not apply");
+    std::string probe, perr;
+    if (!expand_pattern(filename_pattern, first_index, &probe))
+      return usage("--filename-pattern needs one %d or %0Nd conversion for the frame index");
+    if (!raw_out.empty() && !expand_pattern(raw_out, first_index, &probe))
+      return usage("--raw-out of render-sequence is a pattern: it needs one %d or %0Nd conversion");
+    if (!load_camera_path(camera_path, path_cams, &perr)) return usage(perr.c_str());
+  }
 
   if (action == "render" && !multi_devices.empty() &&
       (from_row > 0 || from_col > 0 || (to_row >= 0 && to_row != (long long)opts.height) ||
@@ -473,7 +632,7 @@ int main(int argc, char** argv) {
     const double secs = std::chrono::duration<double>(std::chrono::steady_clock::now() - t_start).count();
     std::fprintf(stderr, "[grt] INFO Elapsed time: %s\n", rust_duration_2(secs).c_str());
   };
-  if (action == "render")  // main.rs:100-103
+  if (action == "render" || action == "render-sequence")  // main.rs:100-103
     std::fprintf(stderr, "[grt] INFO Using coordinate system: %s\n", coordinate_system_debug(d).c_str());
   {  // the scene setup's info lines (KerrTemperatureComputer::new, temperature.rs:55-102)
     const std::string log = grt_host_scene_log(hs);
@@ -483,6 +642,86 @@ int main(int argc, char** argv) {
       std::fprintf(stderr, "[grt] INFO %s\n", log.substr(p, q - p).c_str());
       p = q + 1;
     }
+  }
+  if (action == "render-sequence") {
+    const uint32_t K = (uint32_t)path_cams.size(), w = (uint32_t)opts.width, h = (uint32_t)opts.height;
+    const size_t n = (size_t)w * h;
+    std::vector<grt_camera_desc> cams(K);
+    for (uint32_t k = 0; k < K; ++k) {
+      const std::vector<double>& c = path_cams[k];
+      if (grt_host_scene_camera(hs, c.data(), c[3], c[4], c[5], &cams[k])) {
+        std::fprintf(stderr, "Error: camera %u of %s: %s\n", k, camera_path.c_str(), grt_last_error());
+        return 1;
+      }
+    }
+    double mask[4];
+    const double* maskp = nullptr;
+    if (opts.show_sampling_mask) {
+      grt_srgb_to_xyza(opts.sampling_mask_color[0], opts.sampling_mask_color[1], opts.sampling_mask_color[2], 255, mask);
+      maskp = mask;
+    }
+    const bool supersampled = ac.enabled || maskp;
+    std::vector<double> xyza(n * 4 * K);
+    std::vector<uint8_t> status(n * K), stop(n * K);
+    std::vector<uint32_t> steps(n * K);
+    // failed supersample sub-rays (raytracer.rs:357-362), up to 64K logged per frame
+    const uint64_t fail_cap = supersampled && !maskp ? 1u << 16 : 0;
+    std::vector<uint32_t> fail_pix(fail_cap * K), fail_sample(fail_cap * K), fail_steps(fail_cap * K);
+    std::vector<uint8_t> fail_status(fail_cap * K), fail_stop(fail_cap * K);
+    std::vector<grt_subsample_failures> fails(K);
+    for (uint32_t k = 0; k < K; ++k)
+      fails[k] = grt_subsample_failures{fail_cap, fail_pix.data() + fail_cap * k, fail_sample.data() + fail_cap * k,
+                                        fail_status.data() + fail_cap * k, 0, fail_stop.data() + fail_cap * k,
+                                        fail_steps.data() + fail_cap * k};
+    std::vector<uint64_t> nsel(K, 0);
+    grt_frame_out fo{nullptr, xyza.data(), nullptr, status.data(), stop.data(), steps.data()};
+    grt_stats st;
+    grt_sequence_report rep;
+    t_phase = clk::now();
+    if (grt_render_sequence(scene, device, K, cams.data(), &ac, maskp, &fo, nsel.data(), &st, fails.data(), &rep)) {
+      std::fprintf(stderr, "Error: %s\n", grt_last_error());
+      return 1;
+    }
+    ph_render = ms_since(t_phase);
+    for (uint32_t k = 0; k < K; ++k) {  // each frame: the lines and the output of `render`
+      std::string name, raw;
+      (void)expand_pattern(filename_pattern, first_index + k, &name);
+      if (!raw_out.empty()) (void)expand_pattern(raw_out, first_index + k, &raw);
+      const bool hdr = name.size() >= 4 && name.compare(name.size() - 4, 4, ".hdr") == 0;
+      if (hdr) {  // raytracer.rs:468-469, :481-483
+        std::fprintf(stderr, "[grt] INFO Creating HDR image\n");
+      } else {
+        std::fprintf(stderr, "[grt] INFO Creating non-HDR image\n");
+        std::fprintf(stderr, "[grt] INFO Tone mapping method: %s\n",
+                     opts.tone_mapping == GRT_TONE_GLOBAL_LINEAR ? "GlobalLinear" : "Reinhard");
+      }
+      if (supersampled)  // raytracer.rs:264-267
+        std::fprintf(stderr, "[grt] INFO Rendering section from (%u, %u) to (%u, %u) with supersampling\n", 0u, 0u, h, w);
+      const std::vector<uint8_t> f_status(status.begin() + n * k, status.begin() + n * (k + 1));
+      const std::vector<uint8_t> f_stop(stop.begin() + n * k, stop.begin() + n * (k + 1));
+      const std::vector<uint32_t> f_steps(steps.begin() + n * k, steps.begin() + n * (k + 1));
+      log_frame_rays(0, 0, w, f_status, f_stop, f_steps, supersampled && !maskp, nsel[k], fails[k]);
+      if (supersampled)  // raytracer.rs:313-316
+        std::fprintf(stderr, "[grt] INFO Finished rendering section from (%u, %u) to (%u, %u)\n", 0u, 0u, h, w);
+      const std::vector<double> f_xyza(xyza.begin() + n * 4 * k, xyza.begin() + n * 4 * (k + 1));
+      if (int wrc = write_frame(name, raw, f_xyza, w, h, opts.tone_mapping, device, &ph_output, &ph_write)) return wrc;
+      std::fprintf(stderr, "[grt] INFO saved image to %s\n", name.c_str());  // raytracer.rs:494
+    }
+    unsigned long long nsel_all = 0;
+    for (uint64_t v : nsel) nsel_all += v;
+    std::fprintf(stderr, "[grt] %llu rays, %llu accepted steps, %llu attempts, %llu supersampled pixels, kernel %.1f ms "
+                 "(%.3e steps/s)\n",
+                 (unsigned long long)st.rays, (unsigned long long)st.accepted_steps, (unsigned long long)st.attempts,
+                 nsel_all, st.kernel_ms, st.accepted_steps / (st.kernel_ms * 1e-3));
+    std::fprintf(stderr, "[grt] sequence: %u frames in %u stacked launch(es) of up to %u; trace %.1f ms, supersample "
+                 "%.1f ms\n", rep.n_frames, rep.n_launches, rep.frames_per_launch, rep.trace_ms, rep.supersample_ms);
+    std::fprintf(stderr, "[grt] phases (ms): load %.1f, create %.1f, hip init %.1f, render %.1f, output %.1f, "
+                 "write %.1f, since start %.1f\n", ph_load, ph_create, ph_init, ph_render, ph_output, ph_write,
+                 ms_since(t_start));
+    elapsed();
+    grt_scene_destroy(scene);
+    grt_host_scene_destroy(hs);
+    return 0;
   }
   if (action != "render") {
     int rc;
@@ -563,34 +802,7 @@ int main(int argc, char** argv) {
     return 1;
   }
   ph_render = ms_since(t_phase);
-  // The 1-spp pass, in pixel order (the reference logs from its parallel loop):
-  //  * raytracer.rs:232-239: a pixel whose color_of_ray failed (Debug form of the
-  //    RaytracerError); it keeps the default colour;
-  //  * scene.rs:178-183 / :196-202: an error-free ray that ended on NaN coordinates or
-  //    without a terminal event (steps.len() counts the initial step too).
-  for (size_t i = 0; i < status.size(); ++i) {
-    const unsigned col = (unsigned)(c0 + i % w), row = (unsigned)(r0 + i / w);
-    if (status[i] & 0x7f)
-      std::fprintf(stderr, "[grt] ERROR Unable to compute color for ray at pixel (%u, %u): %s\n", col, row,
-                   error_debug_name(status[i] & 0x7f));
-    else
-      log_ray_event(row, col, stop[i], steps[i]);
-  }
-  if (supersampled && !maskp) {  // supersample (raytracer.rs:325), then its sub-rays' lines
-    std::fprintf(stderr, "[grt] INFO Supersampling %llu pixels\n", (unsigned long long)nsel);
-    // :357-362: the same error line for each failed sub-sample ray of a supersampled pixel
-    for (uint64_t k = 0; k < std::min<uint64_t>(fails.count, fail_cap); ++k) {
-      const unsigned col = (unsigned)(c0 + fail_pix[k] % w), row = (unsigned)(r0 + fail_pix[k] / w);
-      if (fail_status[k])
-        std::fprintf(stderr, "[grt] ERROR Unable to compute color for ray at pixel (%u, %u): %s\n", col, row,
-                     error_debug_name(fail_status[k]));
-      else
-        log_ray_event(row, col, fail_stop[k], fail_steps[k]);
-    }
-    if (fails.count > fail_cap)
-      std::fprintf(stderr, "[grt] ERROR %llu more failed or unterminated sub-sample rays not listed\n",
-                   (unsigned long long)(fails.count - fail_cap));
-  }
+  log_frame_rays(r0, c0, w, status, stop, steps, supersampled && !maskp, nsel, fails);
   if (supersampled)  // raytracer.rs:313-316
     std::fprintf(stderr, "[grt] INFO Finished rendering section from (%u, %u) to (%u, %u)\n", r0, c0, r1, c1);
   std::fprintf(stderr, "[grt] %llu rays, %llu accepted steps, %llu attempts, %llu supersampled pixels, kernel %.1f ms "
@@ -613,39 +825,9 @@ int main(int argc, char** argv) {
     std::fprintf(stderr, "[grt] VolumetricDisc: %llu raymarches, %llu samples (%llu with noise, %llu emitting)\n",
                  (unsigned long long)st.march_jobs, (unsigned long long)st.march_samples,
                  (unsigned long long)st.march_noise_samples, (unsigned long long)st.march_emit_samples);
-  std::string err;
-  bool ok;
-  t_phase = clk::now();
-  if (hdr) {
-    std::vector<float> rgb((size_t)w * h * 3);
-    for (size_t i = 0; i < (size_t)w * h; ++i)
-      for (int k = 0; k < 3; ++k) rgb[3 * i + k] = (float)xyza[4 * i + k];
-    ok = grt_host::hdr_encode_rgb(filename, rgb.data(), w, h, err);
-  } else {
-    std::vector<uint8_t> rgb((size_t)w * h * 3);
-    // output stage on the GPU (color.rs:204-298 via output.hip), exposure 1 as in
-    // render_section (raytracer.rs:485)
-    if (grt_xyz_to_srgb8_device(multi ? multi_devices[0] : device, xyza.data(), (size_t)w * h, opts.tone_mapping,
-                                1.0, rgb.data())) {
-      std::fprintf(stderr, "Error: %s\n", grt_last_error());
-      return 1;
-    }
-    ph_output = ms_since(t_phase);
-    t_phase = clk::now();
-    ok = grt_host::png_encode_rgb(filename, rgb.data(), w, h, err);
-  }
-  if (!ok) {
-    std::fprintf(stderr, "Error: %s\n", err.c_str());
-    return 1;
-  }
-  if (!raw_out.empty()) {
-    FILE* f = std::fopen(raw_out.c_str(), "wb");
-    if (f) {
-      std::fwrite(xyza.data(), 8, xyza.size(), f);
-      std::fclose(f);
-    }
-  }
-  ph_write = ms_since(t_phase);
+  if (int wrc = write_frame(filename, raw_out, xyza, w, h, opts.tone_mapping, multi ? multi_devices[0] : device,
+                            &ph_output, &ph_write))
+    return wrc;
   std::fprintf(stderr, "[grt] INFO saved image to %s\n", filename.c_str());  // raytracer.rs:494
   // where the wall time went: TOML + texture decode + LUTs; the descriptor copy; the render
   // call (device upload on first use, trace, supersampling, D2H); tone map; encode + write

@@ -9,6 +9,7 @@
 
 #include <algorithm>
 #include <atomic>
+#include <chrono>
 #include <cerrno>
 #include <climits>
 #include <cmath>
@@ -286,6 +287,22 @@ void fill_dev_texture(const grt_texture_desc& t, grt::DevTexture& d) {
   }
 }
 
+// The device form of a camera (DevScene::cam, or an entry of a sequence's CamTable).
+void fill_dev_camera(const grt_camera_desc& c, grt::DevCamera& cam) {
+  for (int k = 0; k < 4; ++k) {
+    cam.pos[k] = c.position[k];
+    cam.vel[k] = c.velocity[k];
+    for (int j = 0; j < 4; ++j) cam.tet[k][j] = c.tetrad[k][j];
+  }
+  cam.tan_half_alpha = c.tan_half_alpha;
+  cam.rows = (double)c.rows;
+  cam.cols = (double)c.cols;
+  cam.sig_s = c.spatial_signature;
+  cam.hand = c.spatial_handedness;
+  cam.sin_theta = c.sin_theta;
+  cam.cos_theta = c.cos_theta;
+}
+
 int init_device_copy(grt_scene* s, int device, DeviceCopy& dc);
 
 // The scene's copy on `device`, uploaded on first use.  Safe from one host thread per device
@@ -385,19 +402,7 @@ int init_device_copy(grt_scene* s, int device, DeviceCopy& dc) {
     const double t = std::fmin(ds.pow_skip_err, ds.small_lo);
     ds.tiny_err_sq = (ok && t >= 1e-150) ? t * t * (1.0 - 1e-9) : 0.0;  // t^2 stays a normal
   }
-  const grt_camera_desc& c = d.camera;
-  for (int k = 0; k < 4; ++k) {
-    ds.cam.pos[k] = c.position[k];
-    ds.cam.vel[k] = c.velocity[k];
-    for (int j = 0; j < 4; ++j) ds.cam.tet[k][j] = c.tetrad[k][j];
-  }
-  ds.cam.tan_half_alpha = c.tan_half_alpha;
-  ds.cam.rows = (double)c.rows;
-  ds.cam.cols = (double)c.cols;
-  ds.cam.sig_s = c.spatial_signature;
-  ds.cam.hand = c.spatial_handedness;
-  ds.cam.sin_theta = c.sin_theta;
-  ds.cam.cos_theta = c.cos_theta;
+  fill_dev_camera(d.camera, ds.cam);
   fill_dev_texture(d.celestial, ds.celestial);
   ds.celestial_temperature = d.celestial_temperature;
   ds.hit_threshold = d.object_hit_opacity_threshold;
@@ -570,7 +575,8 @@ bool impact_wanted(const grt_scene* s, const grt::WorkList& wl, const Knobs& k) 
 // Enqueue the probe pass and the sort; returns the device tile order in *order.
 // quad: the Kerr-Schild probe on quads, -1 automatic, 0 never, 1 always (grt_debug_probe_keys).
 int enqueue_tile_order(grt_scene* s, DeviceCopy& dc, const grt::WorkList& wl, hipStream_t stream,
-                       const uint32_t** order, int quad_mode = -1, bool impact = false) {
+                       const uint32_t** order, int quad_mode = -1, bool impact = false,
+                       const grt::CamTable* ct = nullptr) {
   const uint32_t tiles_x = wl.tiles_x, tiles_y = (uint32_t)(wl.n_items / 64 / wl.tiles_x);
   const uint64_t n = (uint64_t)tiles_x * tiles_y;
   size_t temp_bytes = 0;
@@ -601,7 +607,8 @@ int enqueue_tile_order(grt_scene* s, DeviceCopy& dc, const grt::WorkList& wl, hi
   uint32_t* ord = (uint32_t*)take(n * 4);
   void* temp = take(temp_bytes);
   if (impact) {  // predicted lengths, no probe rays; no key counts as capped
-    HIP_TRY(grt::launch_impact_keys(dc.d_scene, wl, (uint32_t)n, probe, stream));
+    HIP_TRY(ct ? grt::seq::launch_impact_keys(dc.d_scene, wl, (uint32_t)n, probe, stream, *ct)
+               : grt::launch_impact_keys(dc.d_scene, wl, (uint32_t)n, probe, stream));
     HIP_TRY(grt::launch_tile_order(probe, tiles_x, tiles_y, 0xffffffffu, keys, keys_sorted, idx, ord, temp, &temp_bytes,
                                    stream));
     *order = ord;
@@ -612,7 +619,8 @@ int enqueue_tile_order(grt_scene* s, DeviceCopy& dc, const grt::WorkList& wl, hi
   // (probe_quad_kernel: a C4 1/8 shard's 32,768 probes); above that the one-lane probe,
   // whose pass is then bound by its work, not by one probe's latency
   const bool quad = quad_mode > 0 || (quad_mode < 0 && n <= (uint64_t)dc.cus * 128);
-  HIP_TRY(grt::launch_probe(s->desc.geometry, dc.d_scene, wl, (uint32_t)n, cap, probe, quad, stream));
+  HIP_TRY(ct ? grt::seq::launch_probe(s->desc.geometry, dc.d_scene, wl, (uint32_t)n, cap, probe, quad, stream, *ct)
+             : grt::launch_probe(s->desc.geometry, dc.d_scene, wl, (uint32_t)n, cap, probe, quad, stream));
   HIP_TRY(grt::launch_tile_order(probe, tiles_x, tiles_y, cap, keys, keys_sorted, idx, ord, temp, &temp_bytes, stream));
   *order = ord;
   return 0;
@@ -680,18 +688,20 @@ int ray_times_reserve(uint64_t n, hipStream_t stream) {
 #endif
 
 // Enqueue one trace over `wl` on `stream`; counters are zeroed first.
+// ct (camera sequences): `wl` is over a stack of frames, each ray takes the camera of its
+// frame from the table, and the sequence unit's exact kernels run (geodesic_seq.hip).
 int enqueue_trace(grt_scene* s, DeviceCopy& dc, const grt::WorkList& wl_in, const grt::Outputs& o,
-                  unsigned long long* d_stats, hipStream_t stream) {
+                  unsigned long long* d_stats, hipStream_t stream, const grt::CamTable* ct = nullptr) {
   grt::WorkList wl = wl_in;
   const Knobs k = Knobs::now();
   if (int rc0 = stream_order(dc, stream)) return rc0;
   if (schedule_wanted(s, wl, k)) {
-    int rc0 = enqueue_tile_order(s, dc, wl, stream, &wl.tile_order);
+    int rc0 = enqueue_tile_order(s, dc, wl, stream, &wl.tile_order, -1, false, ct);
     if (rc0) return rc0;
     // longest tiles to the priority wave of each SIMD, shortest to the others (WorkList)
     wl.two_ended = (k.two_ended != 0 && wl.n_items < (1ull << 31)) ? 1u : 0u;
   } else if (impact_wanted(s, wl, k)) {
-    int rc0 = enqueue_tile_order(s, dc, wl, stream, &wl.tile_order, -1, true);
+    int rc0 = enqueue_tile_order(s, dc, wl, stream, &wl.tile_order, -1, true, ct);
     if (rc0) return rc0;
   }
   HIP_TRY(hipMemsetAsync(dc.d_counter, 0, sizeof(unsigned long long), stream));
@@ -738,8 +748,12 @@ int enqueue_trace(grt_scene* s, DeviceCopy& dc, const grt::WorkList& wl_in, cons
   const auto launch = fused ? grt::fused::launch_trace
                             : (s->desc.geometry == GRT_GEOM_KERR_BL ? grt::kerr_bl::launch_trace : grt::launch_trace);
   // the exact KerrBL kernels are a unit of their own (geodesic_kerr_bl.hip)
-  HIP_TRY(launch(s->desc.geometry, dc.d_scene, wl, ws, o, dc.d_counter, d_stats, blocks, threads, dc.vol, tl,
-                 tail_blocks, stream));
+  if (ct)  // a camera sequence: always the exact sequence unit
+    HIP_TRY(grt::seq::launch_trace(s->desc.geometry, dc.d_scene, wl, ws, o, dc.d_counter, d_stats, blocks, threads,
+                                   dc.vol, tl, tail_blocks, stream, *ct));
+  else
+    HIP_TRY(launch(s->desc.geometry, dc.d_scene, wl, ws, o, dc.d_counter, d_stats, blocks, threads, dc.vol, tl,
+                   tail_blocks, stream));
   return stream_done(dc, stream);
 }
 
@@ -1101,13 +1115,14 @@ struct HostTrace {
 // accepted, attempts, rays, overflows; [4..7] march jobs, samples, noise, emitting
 // samples) and its event time to *ms; *need = hit-pool records it asked for.
 static int trace_sync(grt_scene* s, DeviceCopy& dc, const grt::WorkList& wl, const grt::Outputs& o,
-                      unsigned long long acc[8], float* ms, unsigned long long* need) {
+                      unsigned long long acc[8], float* ms, unsigned long long* need,
+                      const grt::CamTable* ct = nullptr) {
   hipStream_t st = nullptr;
   HIP_TRY(hipMemsetAsync(dc.d_stats, 0, 4 * sizeof(unsigned long long), st));
   HIP_TRY(hipMemsetAsync(dc.d_march, 0, 8 * sizeof(unsigned long long), st));
   HIP_TRY(hipMemsetAsync(dc.d_counter + 6, 0, sizeof(unsigned long long), st));
   HIP_TRY(hipEventRecord(dc.ev0, st));
-  if (int rc = enqueue_trace(s, dc, wl, o, dc.d_stats, st)) return rc;
+  if (int rc = enqueue_trace(s, dc, wl, o, dc.d_stats, st, ct)) return rc;
   HIP_TRY(hipEventRecord(dc.ev1, st));
   HIP_TRY(hipEventSynchronize(dc.ev1));
   unsigned long long h[4], m[8];
@@ -1131,10 +1146,10 @@ static int trace_sync(grt_scene* s, DeviceCopy& dc, const grt::WorkList& wl, con
 // centres (get_ray_for_offset at (0.5, 0.5) is get_ray_for, camera.rs:338-363), with the
 // pool grown once that subset alone does not fit; their outputs replace the flagged ones.
 // `offs` (host, nullable): the offsets list wl was built from.  The stats count the work
-// done, the re-traced rays included.
+// done, the re-traced rays included.  ct: a camera sequence (enqueue_trace), `wl` its stack.
 static int run_to_host(grt_scene* s, DeviceCopy* dc_, const grt::WorkList& wl, uint64_t n, const grt_offsets* offs,
                        float* xyza_out, uint8_t* class_out, uint8_t* status_out, const grt_aux_out* aux,
-                       grt_stats* stats) {
+                       grt_stats* stats, const grt::CamTable* ct = nullptr) {
   int rc;
   DeviceCopy& dc = *dc_;
   unsigned long long acc[8] = {0, 0, 0, 0, 0, 0, 0, 0};
@@ -1142,7 +1157,7 @@ static int run_to_host(grt_scene* s, DeviceCopy* dc_, const grt::WorkList& wl, u
   unsigned long long need = 0;
   {
     HostTrace T;
-    if ((rc = T.alloc(n, aux)) || (rc = trace_sync(s, dc, wl, T.o, acc, &ms, &need))) return rc;
+    if ((rc = T.alloc(n, aux)) || (rc = trace_sync(s, dc, wl, T.o, acc, &ms, &need, ct))) return rc;
     HIP_TRY(hipMemcpy(xyza_out, T.xyza.p, n * 16, hipMemcpyDeviceToHost));
     HIP_TRY(hipMemcpy(class_out, T.cls.p, n, hipMemcpyDeviceToHost));
     HIP_TRY(hipMemcpy(status_out, T.status.p, n, hipMemcpyDeviceToHost));
@@ -1200,7 +1215,7 @@ static int run_to_host(grt_scene* s, DeviceCopy* dc_, const grt::WorkList& wl, u
     wo.dy = (const double*)b_dy.p;
     HostTrace T;
     acc[3] = 0;  // the overflows of the last round are the ones left
-    if ((rc = T.alloc(m, aux)) || (rc = trace_sync(s, dc, wo, T.o, acc, &ms, &need))) return rc;
+    if ((rc = T.alloc(m, aux)) || (rc = trace_sync(s, dc, wo, T.o, acc, &ms, &need, ct))) return rc;
     std::vector<float> x(m * 4);
     std::vector<uint8_t> c(m), st(m), sp(T.o.stop ? m : 0);
     std::vector<double> x64(T.o.xyza64 ? m * 4 : 0);
@@ -1469,7 +1484,8 @@ struct SuperBufs {
 static int enqueue_supersample(grt_scene* s, DeviceCopy& dc, hipStream_t st, const SuperBufs& B, uint32_t row0,
                         uint32_t col0, uint32_t rows, uint32_t cols, const uint32_t* sel_px, const uint32_t* sel_out,
                         const unsigned long long* d_count, uint32_t spa, double* d_out64, unsigned long long* d_stats,
-                        const grt::SubsampleFailures& fails_in) {
+                        const grt::SubsampleFailures& fails_in, const grt::CamTable* ct = nullptr,
+                        uint32_t stack_row0 = 0) {
   grt::SubsampleFailures fails = fails_in;
   fails.ray_stop = B.stop;
   fails.ray_steps = B.steps;
@@ -1480,7 +1496,9 @@ static int enqueue_supersample(grt_scene* s, DeviceCopy& dc, hipStream_t st, con
                                      B.dy, st));
     grt::WorkList wo;
     std::memset(&wo, 0, sizeof(wo));
-    wo.row0 = row0;
+    // a camera sequence: the rect is a frame of the stack, stack_row0 its first stacked row
+    // (the jitter above hashes the frame's own pixel coordinates, as a frame alone does)
+    wo.row0 = row0 + stack_row0;
     wo.col0 = col0;
     wo.rows = rows;
     wo.cols = cols;
@@ -1490,7 +1508,7 @@ static int enqueue_supersample(grt_scene* s, DeviceCopy& dc, hipStream_t st, con
     wo.dy = B.dy;
     wo.n_live = B.live + c;
     grt::Outputs so{B.xyza, B.cls, B.status, B.x64, B.steps, B.stop};
-    int rc = enqueue_trace(s, dc, wo, so, d_stats, st);
+    int rc = enqueue_trace(s, dc, wo, so, d_stats, st, ct);
     if (rc) return rc;
     HIP_TRY(grt::launch_average(sel_out + base, sel_px + base, B.chunk_pix, d_count, base, spa, B.x64, B.status,
                                 d_out64, fails, st));
@@ -1739,6 +1757,280 @@ int grt_render_section(grt_scene* s, int device, uint32_t from_row, uint32_t fro
                                n_supersampled, stats, status_out, nullptr, nullptr, nullptr);
 }
 
+// ------------------------------------------------------------- camera sequences ----
+// K cameras over one resident scene (grt_api.h).  The frames of a launch group are one
+// stacked rectangle of kg * rows rows: its 1-spp trace is one work queue through the
+// sequence unit (enqueue_trace with the group's camera table), and output slot
+// R * cols + c of the stack is pixel (R % rows, c) of frame R / rows, so the stacked
+// buffers are the frames back to back.
+constexpr uint64_t SEQ_GROUP = 1ull << 22;            // rays per launch group
+static std::atomic<uint64_t> g_seq_group{SEQ_GROUP};  // grt_set_sequence_group
+
+int grt_set_sequence_group(uint64_t rays) {
+  g_seq_group.store(rays ? rays : SEQ_GROUP, std::memory_order_relaxed);
+  return 0;
+}
+
+namespace {
+struct SeqTimes {
+  unsigned long long acc[8] = {0, 0, 0, 0, 0, 0, 0, 0};  // as trace_sync's
+  double trace_ms = 0.0, super_ms = 0.0;
+};
+
+// One launch group with supersampling (or the sampling mask): the stacked 1-spp trace,
+// then frame by frame the passes of grt_render_section_ex on that frame's slice of the
+// stacked buffers -- the luminance floor, the selection stencil (neither sees another
+// frame), compaction, work order, and the sub-rays through the sequence unit as an offset
+// list whose rows lie in the frame's part of the stack.  The per-frame scratch is reused
+// from frame to frame (one stream).  Host outputs: the group's first frame onwards.
+int sequence_group_super(grt_scene* s, DeviceCopy& dc, const grt::CamTable& ct, uint32_t rows, uint32_t cols,
+                         const grt_adaptive_config* cfg, const double* mask_xyza, const grt_frame_out& out,
+                         uint64_t* n_supersampled, grt_subsample_failures* failures, SeqTimes* T) {
+  int rc;
+  const uint32_t kg = ct.n_cams;
+  const uint64_t per = (uint64_t)rows * cols, n = per * kg;
+  const bool device_floor = !cfg->has_minimum_luminance;
+  const bool ordered = !mask_xyza;
+  const uint32_t spa = cfg->samples_per_axis;
+  const uint64_t sub_chunk = g_sub_chunk.load(std::memory_order_relaxed);
+  size_t sort_bytes = 0, select_bytes = 0, order_bytes = 0;
+  if (device_floor)
+    HIP_TRY(grt::luminance_floor_device(nullptr, 4, per, floor_index(per), nullptr, &sort_bytes, nullptr, 0));
+  HIP_TRY(grt::compact_flags(nullptr, per, nullptr, nullptr, nullptr, &select_bytes, 0));
+  if (ordered)
+    HIP_TRY(grt::order_selection(nullptr, nullptr, per, nullptr, cols, rows, nullptr, nullptr, &order_bytes, 0));
+  std::vector<grt::SubsampleFailures> fails(kg, grt::SubsampleFailures{nullptr, nullptr, nullptr, 0});
+  for (uint32_t f = 0; f < kg && failures; ++f)
+    if (failures[f].pixel && failures[f].status) fails[f].cap = failures[f].capacity;
+  float* b_xyza = nullptr;
+  uint8_t *b_cls = nullptr, *b_status = nullptr, *b_stop = nullptr, *b_flags = nullptr;
+  double *b_x64 = nullptr, *d_floor = nullptr;
+  uint32_t *b_steps = nullptr, *b_order = nullptr, *b_sel = nullptr;
+  unsigned long long* d_cnt = nullptr;  // per frame: [0] selected pixels, [1] failed sub-samples
+  void *b_order_tmp = nullptr, *b_sort = nullptr, *b_select = nullptr;
+  SuperBufs B;
+  auto carve = [&](AdArena& A) {
+    b_xyza = (float*)A.take(n * 16);
+    b_cls = (uint8_t*)A.take(n);
+    b_status = (uint8_t*)A.take(n);
+    b_x64 = (double*)A.take(n * 32);
+    b_stop = (uint8_t*)A.take(n);
+    b_steps = (uint32_t*)A.take(n * 4);
+    if (ordered) {
+      b_order = (uint32_t*)A.take(per * 4);
+      b_order_tmp = A.take(order_bytes);
+    }
+    b_flags = (uint8_t*)A.take(per);
+    b_sel = (uint32_t*)A.take(per * 4);
+    d_cnt = (unsigned long long*)A.take(16ull * kg);
+    d_floor = (double*)A.take(8);
+    b_sort = A.take(sort_bytes);
+    b_select = A.take(select_bytes);
+    if (!mask_xyza) B.carve(A, per, spa, sub_chunk);
+    for (uint32_t f = 0; f < kg; ++f) {
+      const bool events = fails[f].cap && failures[f].stop;
+      fails[f].key = (uint64_t*)A.take(fails[f].cap * 8);
+      fails[f].status = (uint8_t*)A.take(fails[f].cap);
+      fails[f].stop = events ? (uint8_t*)A.take(fails[f].cap) : nullptr;
+      fails[f].steps = events ? (uint32_t*)A.take(fails[f].cap * 4) : nullptr;
+    }
+  };
+  {
+    AdArena plan;
+    carve(plan);
+    if ((rc = ad_reserve(dc, plan.off))) return rc;
+    AdArena A{(char*)dc.ad_mem, 0};
+    carve(A);
+  }
+  hipStream_t st = nullptr;
+  hipEvent_t ev_mid = nullptr;
+  HIP_TRY(hipEventCreate(&ev_mid));
+  struct EvGuard {
+    hipEvent_t e;
+    ~EvGuard() { (void)hipEventDestroy(e); }
+  } guard{ev_mid};
+  grt::AdaptiveParams ap;
+  ap.w = cols;
+  ap.h = rows;
+  ap.exclude_background_contrast = cfg->exclude_background_contrast;
+  ap._pad = 0;
+  ap.min_lum = cfg->minimum_luminance;
+  ap.luminance_contrast_threshold = cfg->luminance_contrast_threshold;
+  ap.opacity_contrast_threshold = cfg->opacity_contrast_threshold;
+  for (bool again = true; again;) {
+    HIP_TRY(hipMemsetAsync(dc.d_stats, 0, 4 * sizeof(unsigned long long), st));
+    HIP_TRY(hipMemsetAsync(dc.d_march, 0, 8 * sizeof(unsigned long long), st));
+    HIP_TRY(hipMemsetAsync(dc.d_counter + 6, 0, sizeof(unsigned long long), st));
+    HIP_TRY(hipMemsetAsync(d_cnt, 0, 16ull * kg, st));
+    HIP_TRY(hipEventRecord(dc.ev0, st));
+    const grt::WorkList wl = rect_worklist(0, 0, kg * rows, cols);
+    const grt::Outputs o{b_xyza, b_cls, b_status, b_x64, b_steps, b_stop};
+    if ((rc = enqueue_trace(s, dc, wl, o, dc.d_stats, st, &ct))) return rc;
+    HIP_TRY(hipEventRecord(ev_mid, st));
+    for (uint32_t f = 0; f < kg; ++f) {
+      double* x64 = b_x64 + 4 * per * f;
+      unsigned long long* cnt = d_cnt + 2 * f;
+      if (device_floor)
+        HIP_TRY(grt::luminance_floor_device(x64 + 1, 4, per, floor_index(per), b_sort, &sort_bytes, d_floor, st));
+      HIP_TRY(grt::launch_select(x64, b_cls + per * f, ap, device_floor ? d_floor : nullptr, b_flags, st));
+      HIP_TRY(grt::compact_flags(b_flags, per, b_sel, cnt, b_select, &select_bytes, st));
+      if (mask_xyza) {
+        HIP_TRY(grt::launch_paint(b_sel, per, cnt, mask_xyza, x64, st));
+      } else {
+        grt::SubsampleFailures ff = fails[f];
+        ff.count = cnt + 1;
+        HIP_TRY(grt::order_selection(b_sel, cnt, per, b_steps + per * f, cols, rows, b_order, b_order_tmp, &order_bytes,
+                                     st));
+        if ((rc = enqueue_supersample(s, dc, st, B, 0, 0, rows, cols, b_order, b_order, cnt, spa, x64, dc.d_stats, ff,
+                                      &ct, f * rows)))
+          return rc;
+      }
+    }
+    HIP_TRY(hipEventRecord(dc.ev1, st));
+    HIP_TRY(hipEventSynchronize(dc.ev1));
+    float t0 = 0, t1 = 0;
+    HIP_TRY(hipEventElapsedTime(&t0, dc.ev0, ev_mid));
+    HIP_TRY(hipEventElapsedTime(&t1, ev_mid, dc.ev1));
+    T->trace_ms += t0;
+    T->super_ms += t1;
+    unsigned long long hs[4], m[8];
+    HIP_TRY(hipMemcpy(hs, dc.d_stats, sizeof(hs), hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(m, dc.d_march, sizeof(m), hipMemcpyDeviceToHost));
+    if ((rc = pool_check(dc, &again))) return rc;
+    if (again) continue;  // as grt_render_section_ex: the counters of the attempt that stands
+    for (int k = 0; k < 4; ++k) T->acc[k] += hs[k];
+    T->acc[4] += m[3];
+    T->acc[5] += m[2];
+    T->acc[6] += m[4];
+    T->acc[7] += m[5];
+  }
+  HIP_TRY(hipMemcpy(out.xyza64, b_x64, n * 32, hipMemcpyDeviceToHost));
+  if (out.ray_class) HIP_TRY(hipMemcpy(out.ray_class, b_cls, n, hipMemcpyDeviceToHost));
+  if (out.status) HIP_TRY(hipMemcpy(out.status, b_status, n, hipMemcpyDeviceToHost));
+  if (out.stop) HIP_TRY(hipMemcpy(out.stop, b_stop, n, hipMemcpyDeviceToHost));
+  if (out.steps) HIP_TRY(hipMemcpy(out.steps, b_steps, n * 4, hipMemcpyDeviceToHost));
+  std::vector<unsigned long long> cnt(2 * (size_t)kg);
+  HIP_TRY(hipMemcpy(cnt.data(), d_cnt, 16ull * kg, hipMemcpyDeviceToHost));
+  for (uint32_t f = 0; f < kg; ++f) {
+    if (n_supersampled) n_supersampled[f] = cnt[2 * f];
+    if (failures) {
+      failures[f].count = cnt[2 * f + 1];
+      if ((rc = copy_failures(fails[f], cnt[2 * f + 1], spa, &failures[f]))) return rc;
+    }
+  }
+  return 0;
+}
+}  // namespace
+
+int grt_render_sequence(grt_scene* s, int device, uint32_t n_cameras, const grt_camera_desc* cameras,
+                        const grt_adaptive_config* cfg, const double* mask_xyza, const grt_frame_out* out,
+                        uint64_t* n_supersampled, grt_stats* stats, grt_subsample_failures* failures,
+                        grt_sequence_report* report) {
+  const auto wall0 = std::chrono::steady_clock::now();
+  if (!s || !cameras || !out) return fail(-EINVAL, "null argument");
+  if (n_cameras == 0) return fail(-EINVAL, "a sequence needs at least one camera");
+  const int64_t rows64 = s->desc.camera.rows, cols64 = s->desc.camera.cols;
+  for (uint32_t f = 0; f < n_cameras; ++f)
+    if (cameras[f].rows != rows64 || cameras[f].cols != cols64)
+      return fail(-EINVAL, "camera " + std::to_string(f) + " of the sequence has " + std::to_string(cameras[f].rows) +
+                               " x " + std::to_string(cameras[f].cols) + " pixels, the scene's frame " +
+                               std::to_string(rows64) + " x " + std::to_string(cols64));
+  const bool supersampled = (cfg && cfg->enabled) || mask_xyza != nullptr;
+  if (supersampled && !cfg) return fail(-EINVAL, "the sampling mask needs the adaptive configuration");
+  if (supersampled && !out->xyza64) return fail(-EINVAL, "supersampling needs grt_frame_out.xyza64");
+  if (supersampled && cfg->samples_per_axis == 0)
+    return fail(-EINVAL, "adaptive_sampling.samples_per_axis must be greater than zero");
+  const uint32_t rows = (uint32_t)rows64, cols = (uint32_t)cols64;
+  const uint64_t per = (uint64_t)rows * cols;
+  if (per > (uint64_t)INT_MAX) return fail(-EOVERFLOW, "frame larger than INT_MAX pixels");
+  // frames per launch group: whole frames within the group's rays, at least one; the
+  // stack's slots and rows are 32-bit indices
+  uint64_t g = std::max<uint64_t>(1, g_seq_group.load(std::memory_order_relaxed) / per);
+  g = std::min<uint64_t>(g, n_cameras);
+  g = std::min<uint64_t>(g, std::max<uint64_t>(1, (uint64_t)INT_MAX / per));
+  g = std::min<uint64_t>(g, std::max<uint64_t>(1, 0xffffffffull / rows));
+  DeviceCopy* dc;
+  int rc = ensure_device(s, device, &dc);
+  if (rc) return rc;
+  std::lock_guard<std::mutex> lk(dc->mu);
+  HIP_TRY(hipSetDevice(device));
+  if (stats) std::memset(stats, 0, sizeof(*stats));
+  for (uint32_t f = 0; f < n_cameras; ++f) {
+    if (n_supersampled) n_supersampled[f] = 0;
+    if (failures) failures[f].count = 0;
+  }
+  // the camera table, in device form
+  std::vector<grt::DevCamera> cams(n_cameras);
+  for (uint32_t f = 0; f < n_cameras; ++f) fill_dev_camera(cameras[f], cams[f]);
+  DevBuf b_cams;
+  if ((rc = b_cams.alloc(n_cameras * sizeof(grt::DevCamera)))) return rc;
+  HIP_TRY(hipMemcpy(b_cams.p, cams.data(), n_cameras * sizeof(grt::DevCamera), hipMemcpyHostToDevice));
+  SeqTimes T;
+  uint32_t launches = 0;
+  // 1 spp: run_to_host needs the f32 colour, class and status on the host even when the
+  // caller does not ask for them (the re-trace of overflowed pixels reads the status)
+  std::vector<float> tmp_xyza;
+  std::vector<uint8_t> tmp_cls, tmp_status;
+  for (uint32_t f0 = 0; f0 < n_cameras; f0 += (uint32_t)g, ++launches) {
+    const uint32_t kg = (uint32_t)std::min<uint64_t>(g, n_cameras - f0);
+    const uint64_t n = per * kg, at = per * f0;
+    const grt::CamTable ct{(const grt::DevCamera*)b_cams.p + f0, rows, kg};
+    if (supersampled) {
+      grt_frame_out go{nullptr, out->xyza64 + 4 * at, out->ray_class ? out->ray_class + at : nullptr,
+                       out->status ? out->status + at : nullptr, out->stop ? out->stop + at : nullptr,
+                       out->steps ? out->steps + at : nullptr};
+      if ((rc = sequence_group_super(s, *dc, ct, rows, cols, cfg, mask_xyza, go, n_supersampled ? n_supersampled + f0 : nullptr,
+                                     failures ? failures + f0 : nullptr, &T)))
+        return rc;
+      continue;
+    }
+    if (!out->xyza) tmp_xyza.resize(n * 4);
+    if (!out->ray_class) tmp_cls.resize(n);
+    if (!out->status) tmp_status.resize(n);
+    grt_aux_out aux;
+    std::memset(&aux, 0, sizeof(aux));
+    aux.xyza64 = out->xyza64 ? out->xyza64 + 4 * at : nullptr;
+    aux.steps = out->steps ? out->steps + at : nullptr;
+    aux.stop_reason = out->stop ? out->stop + at : nullptr;
+    grt_stats gs;
+    std::memset(&gs, 0, sizeof(gs));
+    const grt::WorkList wl = rect_worklist(0, 0, kg * rows, cols);
+    if ((rc = run_to_host(s, dc, wl, n, nullptr, out->xyza ? out->xyza + 4 * at : tmp_xyza.data(),
+                          out->ray_class ? out->ray_class + at : tmp_cls.data(),
+                          out->status ? out->status + at : tmp_status.data(), &aux, &gs, &ct)))
+      return rc;
+    T.acc[0] += gs.accepted_steps;
+    T.acc[1] += gs.attempts;
+    T.acc[2] += gs.rays;
+    T.acc[3] += gs.hit_overflows;
+    T.acc[4] += gs.march_jobs;
+    T.acc[5] += gs.march_samples;
+    T.acc[6] += gs.march_noise_samples;
+    T.acc[7] += gs.march_emit_samples;
+    T.trace_ms += gs.kernel_ms;
+  }
+  if (stats) {
+    stats->accepted_steps = T.acc[0];
+    stats->attempts = T.acc[1];
+    stats->rays = T.acc[2];
+    stats->hit_overflows = T.acc[3];
+    stats->kernel_ms = T.trace_ms + T.super_ms;
+    stats->march_jobs = T.acc[4];
+    stats->march_samples = T.acc[5];
+    stats->march_noise_samples = T.acc[6];
+    stats->march_emit_samples = T.acc[7];
+  }
+  if (report) {
+    std::memset(report, 0, sizeof(*report));
+    report->n_frames = n_cameras;
+    report->n_launches = launches;
+    report->frames_per_launch = (uint32_t)g;
+    report->trace_ms = T.trace_ms;
+    report->supersample_ms = T.super_ms;
+    report->wall_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - wall0).count();
+  }
+  return 0;
+}
 
 // ------------------------------------------------------------- row-band shards ----
 static int check_shard(const grt_row_shard* sh) {

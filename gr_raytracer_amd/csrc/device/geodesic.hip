@@ -45,13 +45,40 @@
 #ifndef GRT_KERR_BL_TU
 #define GRT_KERR_BL_TU 0
 #endif
-#define GRT_MAIN_TU (!GRT_FUSED && !GRT_KERR_BL_TU)
+// GRT_SEQ: this file compiled a fourth time, by geodesic_seq.hip, into namespace grt::seq:
+// the exact trace and probe kernels of every chart over a stack of frames that share the
+// scene but not the camera (grt_render_sequence).  Each ray takes its camera from a table
+// (CamTable, an extra kernel parameter of this unit's kernels only) by the frame its
+// stacked row lies in; everything else is the code of the other units.
+#ifndef GRT_SEQ
+#define GRT_SEQ 0
+#endif
+#define GRT_MAIN_TU (!GRT_FUSED && !GRT_KERR_BL_TU && !GRT_SEQ)
 
 namespace grt {
 #if GRT_FUSED
 namespace fused {
 #elif GRT_KERR_BL_TU
 namespace kerr_bl {
+#elif GRT_SEQ
+namespace seq {
+#endif
+
+// The camera of a ray.  The other units read the scene's; the sequence unit hands its
+// camera table down to the places that create a camera ray (CAMS_*), and those pass the
+// entry of the ray's frame on (CAM_*).
+#if GRT_SEQ
+#define CAMS_PARAM , CamTable ct
+#define CAMS_ARG , ct
+#define CAM_PARAM , const DevCamera& ray_cam
+#define CAM_ARG(c) , c
+#define CAM_OF(S) ray_cam
+#else
+#define CAMS_PARAM
+#define CAMS_ARG
+#define CAM_PARAM
+#define CAM_ARG(c)
+#define CAM_OF(S) (S).cam
 #endif
 
 #ifndef GDEV
@@ -1563,6 +1590,36 @@ GDEV void init_state(const DevScene& S, const double* pos, double st, double ct,
 // The image coordinates of the ray in output slot idx of a work list: an offset list's
 // jittered pixel (get_ray_for_offset, camera.rs:247-254), or the pixel of a rectangle /
 // row-band shard (local row idx / cols, mapped to its frame row).
+#if GRT_SEQ
+// Stacked frames: integer row R of the stack is row R % cam_rows of frame R / cam_rows.
+// Returns that frame's camera and turns *R into the frame row: always from the integer
+// row, before any sub-pixel jitter (a jittered row may leave its frame by half a pixel).
+// A row past the table (the host never makes one) takes the last camera, so that no load
+// leaves the table.
+GDEV const DevCamera& stacked_camera(const CamTable& ct, uint32_t* R) {
+  const uint32_t f = min(*R / ct.cam_rows, ct.n_cams - 1u);
+  *R -= f * ct.cam_rows;
+  return ct.cams[f];
+}
+// ray_pixel over the stack: the image coordinates within the ray's frame, and its camera.
+GDEV const DevCamera& ray_pixel(const WorkList& wl, const CamTable& ct, uint64_t idx, double* row, double* col) {
+  if (wl.pixel_index) {
+    const uint32_t pix = wl.pixel_index[idx];
+    uint32_t ri = wl.row0 + pix / wl.cols;
+    const DevCamera& cam = stacked_camera(ct, &ri);
+    const double r = (double)ri, cc = (double)(wl.col0 + pix % wl.cols);
+    *row = r + (wl.dy[idx] - 0.5);
+    *col = cc + (wl.dx[idx] - 0.5);
+    return cam;
+  }
+  const uint32_t r = (uint32_t)(idx / wl.cols), cc = (uint32_t)(idx % wl.cols);
+  uint32_t ri = wl.row0 + shard_frame_row(wl.band_rows, wl.shard, wl.n_shards, r);
+  const DevCamera& cam = stacked_camera(ct, &ri);
+  *row = (double)ri;
+  *col = (double)(wl.col0 + cc);
+  return cam;
+}
+#else
 GDEV void ray_pixel(const WorkList& wl, uint64_t idx, double* row, double* col) {
   if (wl.pixel_index) {
     const uint32_t pix = wl.pixel_index[idx];
@@ -1575,12 +1632,13 @@ GDEV void ray_pixel(const WorkList& wl, uint64_t idx, double* row, double* col) 
     *col = (double)(wl.col0 + cc);
   }
 }
+#endif
 
 // Create a camera ray's state (camera.rs:234-254 + init_state); also the observer
 // energy the redshift needs (redshift.rs:40-43).
 template <int G, bool FREQ = false>
-GDEV void init_ray(const DevScene& S, double row, double col, double* y, RayConst& rc) {
-  const DevCamera& cam = S.cam;
+GDEV void init_ray(const DevScene& S, double row, double col, double* y, RayConst& rc CAM_PARAM) {
+  const DevCamera& cam = CAM_OF(S);
   double p[4];
   camera_momentum(cam, row, col, p);
   init_state<G>(S, cam.pos, cam.sin_theta, cam.cos_theta, p, y, rc);
@@ -1820,10 +1878,14 @@ hipError_t path_read(unsigned long long* out, bool reset) {
 // The observer energy of the camera ray in output slot idx (init_ray's rc.obs, recomputed
 // by the shade kernels instead of stored).
 template <int G>
-GDEV double observer_energy(const DevScene& S, const WorkList& wl, uint64_t idx) {
+GDEV double observer_energy(const DevScene& S, const WorkList& wl, uint64_t idx CAMS_PARAM) {
   double row, col, p[4];
+#if GRT_SEQ
+  const DevCamera& cam = ray_pixel(wl, ct, idx, &row, &col);
+#else
   ray_pixel(wl, idx, &row, &col);
   const DevCamera& cam = S.cam;
+#endif
   camera_momentum(cam, row, col, p);
   return inner<G>(S, cam.pos, cam.sin_theta, cam.cos_theta, cam.vel, p);
 }
@@ -2060,7 +2122,7 @@ GDEV unsigned hw_wave_slot() { return __builtin_amdgcn_s_getreg(4 | (3 << 11)); 
 template <int G, bool VOL>
 __global__ void __launch_bounds__(256, integrate_waves(G, VOL)) integrate_kernel(
     const DevScene* __restrict__ Sp, WorkList wl, Workspace ws, unsigned long long* __restrict__ counter,
-    unsigned long long* __restrict__ stats, TailList tl) {
+    unsigned long long* __restrict__ stats, TailList tl CAMS_PARAM) {
   const DevScene& S = *Sp;
   // items present: the capacity, or the count the adaptive pass decided on the device
   const uint64_t n_items = wl.n_live ? (uint64_t)min((unsigned long long)wl.n_items, *wl.n_live) : wl.n_items;
@@ -2151,9 +2213,16 @@ __global__ void __launch_bounds__(256, integrate_waves(G, VOL)) integrate_kernel
         } else {
           double row, col;
           bool valid = true;
+#if GRT_SEQ
+          const DevCamera* cam = ct.cams;  // this lane's camera: the frame of its ray (a per-lane load)
+#endif
           if (wl.pixel_index) {  // offset list (get_ray_for_offset, camera.rs:247-254)
             idx = item;
+#if GRT_SEQ
+            cam = &ray_pixel(wl, ct, idx, &row, &col);
+#else
             ray_pixel(wl, idx, &row, &col);
+#endif
           } else {  // 8x8 pixel tiles, row-major tiles: a wave starts on a compact patch
             uint64_t tile = item >> 6;
             if (wl.tile_order) tile = wl.tile_order[tile];  // longest-predicted tiles first
@@ -2162,12 +2231,18 @@ __global__ void __launch_bounds__(256, integrate_waves(G, VOL)) integrate_kernel
             uint32_t r = tr * 8 + (w >> 3), cc = tc * 8 + (w & 7);
             valid = (r < wl.rows) && (cc < wl.cols);
             // ray_pixel's rectangle / shard case, from (r, cc) directly
+#if GRT_SEQ
+            uint32_t ri = wl.row0 + shard_frame_row(wl.band_rows, wl.shard, wl.n_shards, r);
+            cam = &stacked_camera(ct, &ri);
+            row = (double)ri;
+#else
             row = (double)(wl.row0 + shard_frame_row(wl.band_rows, wl.shard, wl.n_shards, r));
+#endif
             col = (double)(wl.col0 + cc);
             idx = (uint64_t)r * wl.cols + cc;
           }
           if (valid) {
-            init_ray<G, VOL>(S, row, col, y, rc);
+            init_ray<G, VOL>(S, row, col, y, rc CAM_ARG(*cam));
             if constexpr (VOL) {  // the raymarch's frequency data (march_kernel)
               ws.rc[0 * n + idx] = rc.obs;
               ws.rc[1 * n + idx] = rc.e;
@@ -2792,6 +2867,8 @@ hipError_t launch_health(int geometry, const DevScene* d_scene, const WorkList& 
   return hipGetLastError();
 }
 
+#endif  // GRT_MAIN_TU
+#if GRT_MAIN_TU || GRT_SEQ  // the work-order probes: the exact builds of every chart
 // ============================================================ probe kernel =======
 // Work-order probe (scheduling only, never an output): one ray per 8x8 tile, the
 // tile's pixel (3, 3), integrated for at most `cap` accepted steps.  A frame's cost is
@@ -2840,7 +2917,7 @@ GDEV double probe_r0(const DevScene& S, const double* y) {
 
 template <int G>
 __global__ void __launch_bounds__(64) probe_kernel(const DevScene* __restrict__ Sp, WorkList wl, uint32_t n_tiles,
-                                                   uint32_t cap, uint32_t* __restrict__ steps_out) {
+                                                   uint32_t cap, uint32_t* __restrict__ steps_out CAMS_PARAM) {
   const DevScene& S = *Sp;
   glibc::tables_to_lds();
   const uint32_t t = blockIdx.x * blockDim.x + threadIdx.x;
@@ -2849,8 +2926,14 @@ __global__ void __launch_bounds__(64) probe_kernel(const DevScene* __restrict__ 
   const uint32_t r = min(tr * 8 + 3, wl.rows - 1), c = min(tc * 8 + 3, wl.cols - 1);
   double y[8];
   RayConst rc;
+#if GRT_SEQ
+  uint32_t ri = wl.row0 + shard_frame_row(wl.band_rows, wl.shard, wl.n_shards, r);
+  const DevCamera& cam = stacked_camera(ct, &ri);
+  init_ray<G>(S, (double)ri, (double)(wl.col0 + c), y, rc, cam);
+#else
   init_ray<G>(S, (double)(wl.row0 + shard_frame_row(wl.band_rows, wl.shard, wl.n_shards, r)),
               (double)(wl.col0 + c), y, rc);
+#endif
   const uint64_t end = S.max_steps < (uint64_t)cap ? S.max_steps : (uint64_t)cap;
   uint64_t i = 1;
   double h = S.step_size;
@@ -2894,7 +2977,7 @@ __global__ void __launch_bounds__(64) probe_kernel(const DevScene* __restrict__ 
 // both wind round the photon sphere for ~ln(1 / |b / b_c - 1|) more turns.  Only the
 // queue order depends on it, never a result.
 __global__ void __launch_bounds__(64) impact_key_kernel(const DevScene* __restrict__ Sp, WorkList wl,
-                                                        uint32_t n_tiles, uint32_t* __restrict__ keys_out) {
+                                                        uint32_t n_tiles, uint32_t* __restrict__ keys_out CAMS_PARAM) {
   const DevScene& S = *Sp;
   glibc::tables_to_lds();
   const uint32_t t = blockIdx.x * blockDim.x + threadIdx.x;
@@ -2903,8 +2986,14 @@ __global__ void __launch_bounds__(64) impact_key_kernel(const DevScene* __restri
   const uint32_t r = min(tr * 8 + 3, wl.rows - 1), c = min(tc * 8 + 3, wl.cols - 1);
   double y[8];
   RayConst rc;
+#if GRT_SEQ
+  uint32_t ri = wl.row0 + shard_frame_row(wl.band_rows, wl.shard, wl.n_shards, r);
+  const DevCamera& cam = stacked_camera(ct, &ri);
+  init_ray<GRT_GEOM_SCHWARZSCHILD>(S, (double)ri, (double)(wl.col0 + c), y, rc, cam);
+#else
   init_ray<GRT_GEOM_SCHWARZSCHILD>(S, (double)(wl.row0 + shard_frame_row(wl.band_rows, wl.shard, wl.n_shards, r)),
                                    (double)(wl.col0 + c), y, rc);
+#endif
   const double rs = S.radius, rr = y[1], sn = sin(y[2]);
   const double e = fabs((1.0 - rs / rr) * y[4]);
   const double l = rr * rr * sqrt(y[6] * y[6] + sn * sn * y[7] * y[7]);
@@ -2916,9 +3005,10 @@ __global__ void __launch_bounds__(64) impact_key_kernel(const DevScene* __restri
 }
 
 hipError_t launch_impact_keys(const DevScene* d_scene, const WorkList& wl, uint32_t n_tiles, uint32_t* d_keys,
-                              hipStream_t stream) {
+                              hipStream_t stream CAMS_PARAM) {
   if (n_tiles == 0) return hipSuccess;
-  hipLaunchKernelGGL(impact_key_kernel, dim3((n_tiles + 63) / 64), dim3(64), 0, stream, d_scene, wl, n_tiles, d_keys);
+  hipLaunchKernelGGL(impact_key_kernel, dim3((n_tiles + 63) / 64), dim3(64), 0, stream, d_scene, wl, n_tiles,
+                     d_keys CAMS_ARG);
   return hipGetLastError();
 }
 
@@ -2930,7 +3020,7 @@ hipError_t launch_impact_keys(const DevScene* d_scene, const WorkList& wl, uint3
 // quad cuts that latency, at 4x the lanes (2 waves per SIMD here).
 __global__ void __launch_bounds__(256, 2) probe_quad_kernel(const DevScene* __restrict__ Sp, WorkList wl,
                                                             uint32_t n_tiles, uint32_t cap,
-                                                            uint32_t* __restrict__ steps_out) {
+                                                            uint32_t* __restrict__ steps_out CAMS_PARAM) {
   constexpr int G = GRT_GEOM_KERR;
   const DevScene& S = *Sp;
   glibc::tables_to_lds();
@@ -2941,8 +3031,14 @@ __global__ void __launch_bounds__(256, 2) probe_quad_kernel(const DevScene* __re
   const uint32_t r = min(tr * 8 + 3, wl.rows - 1), c = min(tc * 8 + 3, wl.cols - 1);
   double y[8];
   RayConst rc;
+#if GRT_SEQ
+  uint32_t ri = wl.row0 + shard_frame_row(wl.band_rows, wl.shard, wl.n_shards, r);
+  const DevCamera& cam = stacked_camera(ct, &ri);
+  init_ray<G>(S, (double)ri, (double)(wl.col0 + c), y, rc, cam);
+#else
   init_ray<G>(S, (double)(wl.row0 + shard_frame_row(wl.band_rows, wl.shard, wl.n_shards, r)),
               (double)(wl.col0 + c), y, rc);
+#endif
   const uint64_t end = S.max_steps < (uint64_t)cap ? S.max_steps : (uint64_t)cap;
   uint64_t i = 1;
   double h = S.step_size;
@@ -2977,34 +3073,34 @@ __global__ void __launch_bounds__(256, 2) probe_quad_kernel(const DevScene* __re
 }
 
 hipError_t launch_probe(int geometry, const DevScene* d_scene, const WorkList& wl, uint32_t n_tiles, uint32_t cap,
-                        uint32_t* d_steps, bool quad, hipStream_t stream) {
+                        uint32_t* d_steps, bool quad, hipStream_t stream CAMS_PARAM) {
   if (n_tiles == 0) return hipSuccess;
   if (quad && geometry == GRT_GEOM_KERR) {
     hipLaunchKernelGGL(probe_quad_kernel, dim3((n_tiles * 4ull + 255) / 256), dim3(256), 0, stream, d_scene, wl,
-                       n_tiles, cap, d_steps);
+                       n_tiles, cap, d_steps CAMS_ARG);
     return hipGetLastError();
   }
   const unsigned blocks = (n_tiles + 63) / 64;
   switch (geometry) {
     case GRT_GEOM_EUCLIDEAN:
       hipLaunchKernelGGL(probe_kernel<GRT_GEOM_EUCLIDEAN>, dim3(blocks), dim3(64), 0, stream, d_scene, wl, n_tiles,
-                         cap, d_steps);
+                         cap, d_steps CAMS_ARG);
       break;
     case GRT_GEOM_SCHWARZSCHILD:
       hipLaunchKernelGGL(probe_kernel<GRT_GEOM_SCHWARZSCHILD>, dim3(blocks), dim3(64), 0, stream, d_scene, wl,
-                         n_tiles, cap, d_steps);
+                         n_tiles, cap, d_steps CAMS_ARG);
       break;
     case GRT_GEOM_KERR:
       hipLaunchKernelGGL(probe_kernel<GRT_GEOM_KERR>, dim3(blocks), dim3(64), 0, stream, d_scene, wl, n_tiles, cap,
-                         d_steps);
+                         d_steps CAMS_ARG);
       break;
     case GRT_GEOM_KERR_BL:
       hipLaunchKernelGGL(probe_kernel<GRT_GEOM_KERR_BL>, dim3(blocks), dim3(64), 0, stream, d_scene, wl, n_tiles,
-                         cap, d_steps);
+                         cap, d_steps CAMS_ARG);
       break;
     case GRT_GEOM_EUCLIDEAN_SPHERICAL:
       hipLaunchKernelGGL(probe_kernel<GRT_GEOM_EUCLIDEAN_SPHERICAL>, dim3(blocks), dim3(64), 0, stream, d_scene, wl,
-                         n_tiles, cap, d_steps);
+                         n_tiles, cap, d_steps CAMS_ARG);
       break;
     default:
       return hipErrorInvalidValue;
@@ -3013,7 +3109,7 @@ hipError_t launch_probe(int geometry, const DevScene* d_scene, const WorkList& w
 }
 
 
-#endif  // GRT_MAIN_TU
+#endif  // GRT_MAIN_TU || GRT_SEQ
 // ============================================================ shade kernel =======
 // Evaluate one recorded candidate: the emitter step at the intersection
 // (objects.rs:27-44 + :95-115), its redshift, temperature and texture colour.
@@ -3172,12 +3268,12 @@ GDEV uint32_t rec_read(const Workspace& ws, const RecRef& r, double* p, double* 
 // error (an error aborts the pixel, scene.rs:146, so its marches would be wasted).
 // Workspace slots come back as a mask; pool records get their jobs appended here.
 template <int G>
-GDEV uint32_t march_slots(const DevScene& S, const WorkList& wl, const Workspace& ws, uint64_t idx) {
+GDEV uint32_t march_slots(const DevScene& S, const WorkList& wl, const Workspace& ws, uint64_t idx CAMS_PARAM) {
   RayConst rc;
   double y[8];
   const RayMeta mt = fin_get<G>(ws, idx, y, rc);
   if (mt.status != GRT_OK) return 0u;
-  if constexpr (G != GRT_GEOM_KERR_BL) rc.obs = observer_energy<G>(S, wl, idx);
+  if constexpr (G != GRT_GEOM_KERR_BL) rc.obs = observer_energy<G>(S, wl, idx CAMS_ARG);
   bool lost;
   const uint32_t nr = rec_count(ws, idx, mt.nrec, &lost);
   uint32_t mask = 0u, pool_jobs = 0u, pos = HIT_NIL;
@@ -3214,7 +3310,7 @@ GDEV uint32_t march_slots(const DevScene& S, const WorkList& wl, const Workspace
 //   MODE 2: volumetric scenes, pass 3 -- composite with the raymarched colours (ws.vcol).
 template <int G, int MODE>
 __global__ void __launch_bounds__(256) shade_kernel(const DevScene* __restrict__ Sp, WorkList wl, Workspace ws,
-                                                    Outputs out, unsigned long long* __restrict__ stats) {
+                                                    Outputs out, unsigned long long* __restrict__ stats CAMS_PARAM) {
   const DevScene& S = *Sp;
   const uint64_t n = ws.n;
   const uint64_t n_live = ws.n_live ? (uint64_t)min((unsigned long long)n, *ws.n_live) : n;
@@ -3224,7 +3320,7 @@ __global__ void __launch_bounds__(256) shade_kernel(const DevScene* __restrict__
   glibc::tables_to_lds();  // whole block, before the early return
   const uint64_t idx = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
   if constexpr (MODE == 1) {
-    const uint32_t mask = idx < n_live ? march_slots<G>(S, wl, ws, idx) : 0u;
+    const uint32_t mask = idx < n_live ? march_slots<G>(S, wl, ws, idx CAMS_ARG) : 0u;
     const int lane = threadIdx.x & 63;
     const uint32_t c = __popc(mask);
     uint32_t incl = c;  // inclusive wave prefix sum of the job counts
@@ -3256,7 +3352,7 @@ __global__ void __launch_bounds__(256) shade_kernel(const DevScene* __restrict__
     write_out(out, idx, fail, GRT_CLASS_ESCAPED, status, stop, 0u);
     return;
   }
-  if constexpr (G != GRT_GEOM_KERR_BL) rc.obs = observer_energy<G>(S, wl, idx);
+  if constexpr (G != GRT_GEOM_KERR_BL) rc.obs = observer_energy<G>(S, wl, idx CAMS_ARG);
   bool lost;
   const uint32_t nr = rec_count(ws, idx, mt.nrec, &lost);
   // window-nearest hits: the first ones in registers, the later ones (pool records of
@@ -3350,7 +3446,7 @@ __global__ void __launch_bounds__(256) shade_kernel(const DevScene* __restrict__
 template <int G>
 static hipError_t launch_g(const DevScene* d_scene, const WorkList& wl, const Workspace& ws_in, const Outputs& out,
                            unsigned long long* d_counter, unsigned long long* d_stats, int blocks, int threads,
-                           bool vol, const TailList& tl_in, int tail_blocks, hipStream_t stream) {
+                           bool vol, const TailList& tl_in, int tail_blocks, hipStream_t stream CAMS_PARAM) {
   const unsigned nb = (unsigned)((ws_in.n + 255) / 256);
   Workspace ws = ws_in;
   ws.steps = G == GRT_GEOM_KERR_BL ? nullptr : out.steps;  // store_ray writes the per-pixel step counts
@@ -3358,7 +3454,7 @@ static hipError_t launch_g(const DevScene* d_scene, const WorkList& wl, const Wo
   if (G != GRT_GEOM_KERR || tail_blocks <= 0) tl.cap = 0;
   if (!vol) {
     hipLaunchKernelGGL((integrate_kernel<G, false>), dim3(blocks), dim3(threads), 0, stream, d_scene, wl, ws,
-                       d_counter, d_stats, tl);
+                       d_counter, d_stats, tl CAMS_ARG);
     hipError_t e = hipGetLastError();
     if (e != hipSuccess) return e;
     if constexpr (G == GRT_GEOM_KERR) {
@@ -3368,12 +3464,12 @@ static hipError_t launch_g(const DevScene* d_scene, const WorkList& wl, const Wo
         if ((e = hipGetLastError()) != hipSuccess) return e;
       }
     }
-    hipLaunchKernelGGL((shade_kernel<G, 0>), dim3(nb), dim3(256), 0, stream, d_scene, wl, ws, out, d_stats);
+    hipLaunchKernelGGL((shade_kernel<G, 0>), dim3(nb), dim3(256), 0, stream, d_scene, wl, ws, out, d_stats CAMS_ARG);
     return hipGetLastError();
   }
   if (!ws.rec_dir || !ws.vcol || !ws.jobs || !ws.march) return hipErrorInvalidValue;
   hipLaunchKernelGGL((integrate_kernel<G, true>), dim3(blocks), dim3(threads), 0, stream, d_scene, wl, ws,
-                     d_counter, d_stats, tl);
+                     d_counter, d_stats, tl CAMS_ARG);
   hipError_t e = hipGetLastError();
   if (e != hipSuccess) return e;
   if constexpr (G == GRT_GEOM_KERR) {
@@ -3382,48 +3478,51 @@ static hipError_t launch_g(const DevScene* d_scene, const WorkList& wl, const Wo
       if ((e = hipGetLastError()) != hipSuccess) return e;
     }
   }
-  hipLaunchKernelGGL((shade_kernel<G, 1>), dim3(nb), dim3(256), 0, stream, d_scene, wl, ws, out, d_stats);
+  hipLaunchKernelGGL((shade_kernel<G, 1>), dim3(nb), dim3(256), 0, stream, d_scene, wl, ws, out, d_stats CAMS_ARG);
   if ((e = hipGetLastError()) != hipSuccess) return e;
   hipLaunchKernelGGL((march_kernel<G>), dim3(blocks), dim3(256), 0, stream, d_scene, ws);
   if ((e = hipGetLastError()) != hipSuccess) return e;
-  hipLaunchKernelGGL((shade_kernel<G, 2>), dim3(nb), dim3(256), 0, stream, d_scene, wl, ws, out, d_stats);
+  hipLaunchKernelGGL((shade_kernel<G, 2>), dim3(nb), dim3(256), 0, stream, d_scene, wl, ws, out, d_stats CAMS_ARG);
   return hipGetLastError();
 }
 
 hipError_t launch_trace(int geometry, const DevScene* d_scene, const WorkList& wl, const Workspace& ws,
                         const Outputs& out, unsigned long long* d_counter, unsigned long long* d_stats, int blocks,
-                        int threads, bool vol, const TailList& tl, int tail_blocks, hipStream_t stream) {
+                        int threads, bool vol, const TailList& tl, int tail_blocks, hipStream_t stream CAMS_PARAM) {
   if (ws.n == 0) return hipSuccess;
+#if GRT_SEQ
+  if (!ct.cams || ct.cam_rows == 0 || ct.n_cams == 0) return hipErrorInvalidValue;
+#endif
   switch (geometry) {
 #if !GRT_KERR_BL_TU
     case GRT_GEOM_EUCLIDEAN:
       return launch_g<GRT_GEOM_EUCLIDEAN>(d_scene, wl, ws, out, d_counter, d_stats, blocks, threads, vol, tl,
-                                          tail_blocks, stream);
+                                          tail_blocks, stream CAMS_ARG);
     case GRT_GEOM_SCHWARZSCHILD:
       return launch_g<GRT_GEOM_SCHWARZSCHILD>(d_scene, wl, ws, out, d_counter, d_stats, blocks, threads, vol, tl,
-                                              tail_blocks, stream);
+                                              tail_blocks, stream CAMS_ARG);
 #endif
-#if GRT_MAIN_TU  // Kerr-Schild always runs exact (grt_set_arithmetic)
+#if GRT_MAIN_TU || GRT_SEQ  // Kerr-Schild always runs exact (grt_set_arithmetic)
     case GRT_GEOM_KERR:
       return launch_g<GRT_GEOM_KERR>(d_scene, wl, ws, out, d_counter, d_stats, blocks, threads, vol, tl, tail_blocks,
-                                     stream);
+                                     stream CAMS_ARG);
 #endif
 #if !GRT_MAIN_TU  // the exact KerrBL trace is grt::kerr_bl's
     case GRT_GEOM_KERR_BL:
       return launch_g<GRT_GEOM_KERR_BL>(d_scene, wl, ws, out, d_counter, d_stats, blocks, threads, vol, tl,
-                                        tail_blocks, stream);
+                                        tail_blocks, stream CAMS_ARG);
 #endif
 #if !GRT_KERR_BL_TU
     case GRT_GEOM_EUCLIDEAN_SPHERICAL:
       return launch_g<GRT_GEOM_EUCLIDEAN_SPHERICAL>(d_scene, wl, ws, out, d_counter, d_stats, blocks, threads, vol,
-                                                    tl, tail_blocks, stream);
+                                                    tl, tail_blocks, stream CAMS_ARG);
 #endif
     default:
       return hipErrorInvalidValue;
   }
 }
 
-#if GRT_FUSED || GRT_KERR_BL_TU
-}  // namespace fused / kerr_bl
+#if GRT_FUSED || GRT_KERR_BL_TU || GRT_SEQ
+}  // namespace fused / kerr_bl / seq
 #endif
 }  // namespace grt

@@ -80,6 +80,27 @@ hipError_t set_ray_times(unsigned long long* p);
 hipError_t path_read(unsigned long long* out, bool reset);
 #endif
 }  // namespace kerr_bl
+// The exact trace over a stack of frames that share the scene but not the camera
+// (geodesic_seq.hip, grt_render_sequence).  `wl` describes the stack as one rectangle of
+// n_cams * cam_rows rows (or an offset list over it); row R of the stack is row
+// R % cam_rows of frame R / cam_rows, traced with cams[R / cam_rows] in place of the
+// scene's camera.  The table is a kernel parameter of this unit's kernels only: WorkList,
+// Workspace and DevScene are the tuned units' arguments and stay as they are.
+struct CamTable {
+  const DevCamera* cams;  // device memory, n_cams entries
+  uint32_t cam_rows;      // rows of one frame
+  uint32_t n_cams;
+};
+namespace seq {
+hipError_t launch_trace(int geometry, const DevScene* d_scene, const WorkList& wl, const Workspace& ws,
+                        const Outputs& out, unsigned long long* d_counter, unsigned long long* d_stats,
+                        int blocks, int threads, bool vol, const TailList& tl, int tail_blocks,
+                        hipStream_t stream, CamTable ct);
+hipError_t launch_probe(int geometry, const DevScene* d_scene, const WorkList& wl, uint32_t n_tiles, uint32_t cap,
+                        uint32_t* d_steps, bool quad, hipStream_t stream, CamTable ct);
+hipError_t launch_impact_keys(const DevScene* d_scene, const WorkList& wl, uint32_t n_tiles, uint32_t* d_keys,
+                              hipStream_t stream, CamTable ct);
+}  // namespace seq
 hipError_t launch_trajectories(int geometry, const DevScene* d_scene, const TrajectoryList& tl, hipStream_t stream);
 
 // Invariant monitors of the n = rows x cols rays of a rectangle (health_kernel):

@@ -42,6 +42,9 @@ struct grt_host_scene {
   std::vector<double> bb_log_t, bb_xyz;
   std::string error;
   std::string info_log;  // the reference's info! lines of the scene setup, one per line
+  // the TOML's camera_velocity mode (and the Explicit components), for grt_host_scene_camera
+  std::string cam_velocity = "StaticObserver";
+  double cam_explicit[4] = {0.0, 0.0, 0.0, 0.0};
 };
 
 namespace grt_host {
@@ -296,6 +299,41 @@ int grt_host_geometry_load(const char* toml_path, const grt_global_opts* opts, g
   return 0;
 }
 
+// The observer of a camera at Cartesian `position`: the position in the geometry's native
+// chart (cli/<geometry>.rs) and the four-velocity of the scene's camera_velocity mode
+// (resolve_camera_velocity, cli/shared.rs:48-77), checked to be future-directed.
+static int camera_observer(const grt_host_scene* hs, const double position[3], double pos[4], double vel[4]) {
+  const grt_scene_desc& d = hs->desc;
+  double cart[4] = {0.0, position[0], position[1], position[2]};
+  if (d.geometry == GRT_GEOM_SCHWARZSCHILD || d.geometry == GRT_GEOM_EUCLIDEAN_SPHERICAL)
+    grt_cartesian_to_spherical(cart, pos);
+  else if (d.geometry == GRT_GEOM_KERR_BL) grt_cartesian_to_boyer_lindquist(d.a, cart, pos);
+  else std::memcpy(pos, cart, sizeof(cart));
+
+  const std::string& vname = hs->cam_velocity;
+  if (vname == "StaticObserver") {
+    grt_stationary_velocity(d.geometry, d.radius, d.a, pos, vel);
+  } else if (vname == "Zamo") {
+    grt_zamo_velocity(d.geometry, d.radius, d.a, pos, vel);
+  } else if (vname == "Explicit") {
+    for (int i = 0; i < 4; ++i) vel[i] = hs->cam_explicit[i];
+    double norm = inner(d.geometry, d.radius, d.a, pos, vel, vel);
+    if (std::fabs(norm - signature0(d.geometry)) > 1e-6) return fail("Explicit camera_velocity is not normalized");
+  } else {
+    return fail("unknown camera_velocity `" + vname + "`");
+  }
+  if (!future_directed(d.geometry, d.radius, d.a, pos, vel)) return fail("camera four-velocity has wrong time orientation");
+  return 0;
+}
+// Camera::new for the scene's frame (alpha = pi/4).
+static int camera_of_observer(const grt_scene_desc& d, const double pos[4], const double vel[4], int64_t rows,
+                              int64_t cols, double phi, double theta, double psi, grt_camera_desc* out) {
+  int rc = grt_camera_build(d.geometry, d.radius, d.a, pos, vel, 3.14159265358979323846 / 4.0, rows, cols, phi, theta,
+                            psi, out);
+  if (rc) return fail("Camera error: Tetrad is not orthonormal");
+  return 0;
+}
+
 int grt_host_scene_load(const char* toml_path, const char* resource_root, const grt_global_opts* opts,
                         grt_host_scene** out) {
   if (!toml_path || !opts || !out) return fail("null argument");
@@ -337,35 +375,19 @@ int grt_host_scene_load(const char* toml_path, const char* resource_root, const 
     return fail("adaptive_sampling.minimum_luminance must be finite and non-negative");
   d.object_hit_opacity_threshold = ac.object_hit_opacity_threshold;
 
-  // camera position in the geometry's native chart (cli/<geometry>.rs)
-  double cart[4] = {0.0, opts->camera_position[0], opts->camera_position[1], opts->camera_position[2]};
-  double pos[4];
-  if (d.geometry == GRT_GEOM_SCHWARZSCHILD || d.geometry == GRT_GEOM_EUCLIDEAN_SPHERICAL)
-    grt_cartesian_to_spherical(cart, pos);
-  else if (d.geometry == GRT_GEOM_KERR_BL) grt_cartesian_to_boyer_lindquist(d.a, cart, pos);
-  else std::memcpy(pos, cart, sizeof(pos));
-
-  // resolve_camera_velocity (cli/shared.rs:48-77)
-  double vel[4];
-  std::string vname = "StaticObserver";
-  const TomlTable* vb = nullptr;
+  // camera position and four-velocity (camera_observer); the TOML's velocity mode stays with
+  // the host scene for grt_host_scene_camera
   if (const TomlValue* cv = get(root, "camera_velocity")) {
-    if (!variant(cv, vname, &vb)) return fail("invalid `camera_velocity`");
+    const TomlTable* vb = nullptr;
+    if (!variant(cv, hs->cam_velocity, &vb)) return fail("invalid `camera_velocity`");
+    if (hs->cam_velocity == "Explicit") {
+      const TomlValue* c = vb ? get(*vb, "components") : nullptr;
+      if (!c || c->kind != TomlValue::Array || c->arr.size() != 4) return fail("Explicit camera_velocity needs 4 components");
+      for (int i = 0; i < 4; ++i) hs->cam_explicit[i] = c->arr[i]->number();
+    }
   }
-  if (vname == "StaticObserver") {
-    grt_stationary_velocity(d.geometry, d.radius, d.a, pos, vel);
-  } else if (vname == "Zamo") {
-    grt_zamo_velocity(d.geometry, d.radius, d.a, pos, vel);
-  } else if (vname == "Explicit") {
-    const TomlValue* c = vb ? get(*vb, "components") : nullptr;
-    if (!c || c->kind != TomlValue::Array || c->arr.size() != 4) return fail("Explicit camera_velocity needs 4 components");
-    for (int i = 0; i < 4; ++i) vel[i] = c->arr[i]->number();
-    double norm = inner(d.geometry, d.radius, d.a, pos, vel, vel);
-    if (std::fabs(norm - signature0(d.geometry)) > 1e-6) return fail("Explicit camera_velocity is not normalized");
-  } else {
-    return fail("unknown camera_velocity `" + vname + "`");
-  }
-  if (!future_directed(d.geometry, d.radius, d.a, pos, vel)) return fail("camera four-velocity has wrong time orientation");
+  double pos[4], vel[4];
+  if (int rcv = camera_observer(hs.get(), opts->camera_position, pos, vel)) return rcv;
 
   // celestial texture + Camera::new (alpha = pi/4, rows = height, cols = width)
   bool need_bb = false;
@@ -375,9 +397,8 @@ int grt_host_scene_load(const char* toml_path, const char* resource_root, const 
   int rc = fill_texture(hs.get(), ct, resource_root, d.celestial, &need_bb, &patches);
   if (rc) return rc;
   if (!num(root, "celestial_temperature", &d.celestial_temperature, err)) return fail(err);
-  rc = grt_camera_build(d.geometry, d.radius, d.a, pos, vel, 3.14159265358979323846 / 4.0, opts->height, opts->width,
-                        opts->phi, opts->theta, opts->psi, &d.camera);
-  if (rc) return fail("Camera error: Tetrad is not orthonormal");
+  rc = camera_of_observer(d, pos, vel, opts->height, opts->width, opts->phi, opts->theta, opts->psi, &d.camera);
+  if (rc) return rc;
 
   // objects, in config order (cli/shared.rs:176-308)
   const TomlValue* objs = get(root, "objects");
@@ -486,6 +507,15 @@ int grt_host_scene_load(const char* toml_path, const char* resource_root, const 
   }
   *out = hs.release();
   return 0;
+}
+
+int grt_host_scene_camera(const grt_host_scene* s, const double position[3], double phi, double theta, double psi,
+                          grt_camera_desc* out) {
+  if (!s || !position || !out) return fail("null argument");
+  double pos[4], vel[4];
+  if (int rc = camera_observer(s, position, pos, vel)) return rc;
+  std::memset(out, 0, sizeof(*out));
+  return camera_of_observer(s->desc, pos, vel, s->desc.camera.rows, s->desc.camera.cols, phi, theta, psi, out);
 }
 
 const grt_scene_desc* grt_host_scene_desc(const grt_host_scene* s) { return s ? &s->desc : nullptr; }

@@ -95,6 +95,16 @@ class HostScene:
         L.lib().grt_host_scene_adaptive(self._h, C.byref(c))
         return c
 
+    def camera(self, position, phi: float = 0.0, theta: float = 0.0, psi: float = 0.0) -> L.CameraDesc:
+        """The camera a load of this scene with these --camera-position / --phi / --theta /
+        --psi values would have built (grt_host_scene_camera): the cameras of
+        Scene.render_sequence."""
+        pos = (C.c_double * 3)(*[float(x) for x in position])
+        cam = L.CameraDesc()
+        L.check(L.lib().grt_host_scene_camera(self._h, pos, float(phi), float(theta), float(psi), C.byref(cam)),
+                "grt_host_scene_camera")
+        return cam
+
     def close(self) -> None:
         if self._h:
             L.lib().grt_host_scene_destroy(self._h)
@@ -307,6 +317,70 @@ class Scene:
             arrays["failures"]["count"] = int(fails.count)
         return arrays
 
+    def render_sequence(self, cameras, adaptive: Optional[L.AdaptiveConfig] = None, mask=None, device: int = 0,
+                        supersample: bool = False, fields=("xyza", "xyza64", "class", "status", "stop", "steps"),
+                        failure_capacity: int = 1 << 16) -> dict:
+        """K cameras (CameraDesc, each with the scene's rows and cols) over this scene in
+        stacked launches (grt_render_sequence); every frame is bit-identical to rendering
+        its camera alone.  supersample: the adaptive pass with `adaptive` (default: the
+        scene's own configuration), per frame; mask: paint the selected pixels instead.
+        Returns a dict of the `fields` as arrays with a leading frame axis ("xyza" only at
+        1 spp), plus "stats", "report" (SequenceReport) and, with supersampling,
+        "n_supersampled" (K,) and "failures": per frame an (m, 3) uint32 array of (pixel,
+        stratum, status) and "n_failed" the counts."""
+        cams = list(cameras)
+        k, n = len(cams), self.rows * self.cols
+        table = (L.CameraDesc * max(k, 1))(*cams)
+        ss = supersample or mask is not None
+        want = set(fields)
+        arrays = {}
+        if "xyza" in want and not ss:
+            arrays["xyza"] = np.zeros((k, n, 4), np.float32)
+        if "xyza64" in want or ss:
+            arrays["xyza64"] = np.zeros((k, n, 4), np.float64)
+        for name, dt in (("class", np.uint8), ("status", np.uint8), ("stop", np.uint8), ("steps", np.uint32)):
+            if name in want:
+                arrays[name] = np.zeros((k, n), dt)
+        out = L.FrameOut(L.ptr(arrays["xyza"], C.c_float) if "xyza" in arrays else None,
+                         L.dptr(arrays["xyza64"]) if "xyza64" in arrays else None,
+                         L.ptr(arrays["class"], C.c_uint8) if "class" in arrays else None,
+                         L.ptr(arrays["status"], C.c_uint8) if "status" in arrays else None,
+                         L.ptr(arrays["stop"], C.c_uint8) if "stop" in arrays else None,
+                         L.ptr(arrays["steps"], C.c_uint32) if "steps" in arrays else None)
+        cfg = None
+        if ss:
+            cfg = L.AdaptiveConfig()
+            C.memmove(C.byref(cfg), C.byref(adaptive if adaptive is not None else self.adaptive), C.sizeof(cfg))
+            cfg.enabled = 1 if supersample else cfg.enabled
+        m = np.ascontiguousarray(mask, np.float64) if mask is not None else None
+        nsel = (C.c_uint64 * max(k, 1))()
+        fails, farr = None, []
+        if ss and failure_capacity:
+            fails = (L.SubsampleFailures * max(k, 1))()
+            for f in range(k):
+                a = (np.zeros(failure_capacity, np.uint32), np.zeros(failure_capacity, np.uint32),
+                     np.zeros(failure_capacity, np.uint8))
+                farr.append(a)
+                fails[f] = L.SubsampleFailures(failure_capacity, L.ptr(a[0], C.c_uint32), L.ptr(a[1], C.c_uint32),
+                                               L.ptr(a[2], C.c_uint8), 0, None, None)
+        st = L.Stats()
+        rep = L.SequenceReport()
+        L.check(L.lib().grt_render_sequence(self._s, device, k, table, C.byref(cfg) if cfg is not None else None,
+                                            L.dptr(m) if m is not None else None, C.byref(out), nsel, C.byref(st),
+                                            fails, C.byref(rep)), "grt_render_sequence")
+        arrays["stats"] = _stats_dict(st)
+        arrays["report"] = rep
+        if ss:
+            arrays["n_supersampled"] = np.array([int(nsel[f]) for f in range(k)], np.uint64)
+            if fails is not None:
+                arrays["n_failed"] = [int(fails[f].count) for f in range(k)]
+                arrays["failures"] = []
+                for f in range(k):
+                    c = min(int(fails[f].count), failure_capacity)
+                    a = farr[f]
+                    arrays["failures"].append(np.stack([a[0][:c], a[1][:c], a[2][:c].astype(np.uint32)], axis=1))
+        return arrays
+
     def render_section(self, from_row: int = 0, from_col: int = 0, to_row: Optional[int] = None,
                        to_col: Optional[int] = None, adaptive: Optional[L.AdaptiveConfig] = None,
                        sampling_mask_xyza=None, device: int = 0):
@@ -433,6 +507,35 @@ def set_two_ended(on: bool = True) -> None:
     priority wave of each SIMD the longest tiles, the others the shortest.  Scheduling
     only; results are identical in both modes."""
     L.check(L.lib().grt_set_two_ended(1 if on else 0), "grt_set_two_ended")
+
+
+def set_sequence_group(rays: int = 0) -> None:
+    """Rays per launch group of Scene.render_sequence (grt_set_sequence_group; 0 = the
+    default 2^22).  A group holds whole frames, at least one.  Scheduling only."""
+    L.check(L.lib().grt_set_sequence_group(int(rays)), "grt_set_sequence_group")
+
+
+def load_camera_path(path) -> np.ndarray:
+    """A camera-path file: one camera per line, `x,y,z,phi,theta,psi` -- the values
+    --camera-position, --phi, --theta and --psi take; blank lines and lines starting with
+    `#` are skipped.  Returns an (n, 6) float64 array; ValueError names the bad line."""
+    rows = []
+    with open(path, "r", encoding="utf-8") as f:
+        for no, line in enumerate(f, 1):
+            t = line.strip()
+            if not t or t.startswith("#"):
+                continue
+            parts = [x.strip() for x in t.split(",")]
+            if len(parts) != 6:
+                raise ValueError(f"{path}:{no}: expected 6 values `x,y,z,phi,theta,psi`, found {len(parts)}")
+            try:
+                vals = [float(x) for x in parts]
+            except ValueError:
+                raise ValueError(f"{path}:{no}: `{t}` is not six numbers") from None
+            rows.append(vals)
+    if not rows:
+        raise ValueError(f"{path}:1: the camera path holds no camera")
+    return np.array(rows, np.float64)
 
 
 ARITH_EXACT, ARITH_FUSED = 0, 1

@@ -245,6 +245,14 @@ int grt_host_scene_load(const char* toml_path, const char* resource_root,
 int grt_host_geometry_load(const char* toml_path, const grt_global_opts* opts,
                            grt_host_scene** out);
 const grt_scene_desc* grt_host_scene_desc(const grt_host_scene* s);
+/* The camera grt_host_scene_load would have built for this scene had its options carried
+ * these --camera-position / --phi / --theta / --psi values: the chart conversion, the
+ * TOML's camera_velocity mode (StaticObserver, Zamo, Explicit), the future-directed check
+ * and grt_camera_build with the scene's rows and cols.  Byte for byte the `camera` of
+ * such a load's descriptor; the same errors (-EINVAL, grt_last_error) where that load
+ * fails on the camera.  The cameras of grt_render_sequence. */
+int grt_host_scene_camera(const grt_host_scene* s, const double position[3], double phi, double theta,
+                          double psi, grt_camera_desc* out);
 /* The info-level lines the reference logs while it builds this scene, one per line, in
  * order (today the temperature LUT's, KerrTemperatureComputer::new, temperature.rs:55-102:
  * the r_isco clamp, "Computed r_isco: ...", "Max f: ...", "Computed m_dot: ..."; numbers
@@ -525,6 +533,50 @@ int grt_render_frame_multi(grt_scene* scene, int n_devices, const int* devices, 
  * be in flight). */
 void grt_multi_release(void);
 
+/* ---- camera sequences: K cameras over one resident scene ------------------------------
+ * An animation along a camera path changes nothing of the scene but the camera, so the
+ * frames share the scene's device copy (textures, LUTs, workspace) and are traced stacked:
+ * K frames of rows x cols as one rectangle of K * rows rows, one tile queue, each ray with
+ * the camera of the frame its row lies in (geodesic_seq.hip).  Small frames that cannot
+ * fill the GPU one by one then run side by side.  Every frame is bit-identical to
+ * rendering its camera alone (grt_render_pixels / grt_render_section_ex on a scene created
+ * with that camera): the operations are the same.
+ * The sequence trace always runs the exact arithmetic: grt_set_arithmetic(1) does not
+ * apply (there is no fused sequence unit).  grt_set_schedule, grt_set_two_ended and
+ * grt_set_tail apply to the stacked rectangle as to any other (scheduling only). */
+typedef struct grt_sequence_report {
+  uint32_t n_frames;
+  uint32_t n_launches;         /* launch groups = stacked 1-spp traces of whole frames       */
+  uint32_t frames_per_launch;  /* frames in a full group (the last one may hold fewer)       */
+  uint32_t _pad;
+  double wall_ms;              /* the whole call, host clock                                 */
+  double trace_ms;             /* summed event time of the stacked 1-spp traces (re-traces of
+                                  pixels that overflowed the hit pool included)              */
+  double supersample_ms;       /* summed event time of the per-frame selection and
+                                  supersample passes                                         */
+} grt_sequence_report;
+
+/* Render n_cameras frames of `scene` on `device`.  Every camera must have the scene's rows
+ * and cols (grt_host_scene_camera builds such cameras), else -EINVAL; only whole frames.
+ * out: host arrays, frame-major [n_cameras][rows][cols], a NULL field is not written;
+ * xyza is for 1 spp, xyza64 is required with supersampling (cfg->enabled or a mask; cfg
+ * and sampling_mask_xyza as in grt_render_frame_multi).  n_supersampled and failures
+ * (nullable): arrays of n_cameras, one per frame, each filled as grt_render_section_ex
+ * fills its own.  stats (nullable): the counters of the whole call, kernel_ms =
+ * trace_ms + supersample_ms.  Frames go to the device in launch groups
+ * (grt_set_sequence_group); results are identical for every group size.  Pixels that
+ * lost hit candidates (GRT_FLAG_HIT_OVERFLOW) are traced again with a grown pool as the
+ * synchronous single-frame calls do. */
+int grt_render_sequence(grt_scene* scene, int device, uint32_t n_cameras,
+                        const grt_camera_desc* cameras, const grt_adaptive_config* cfg,
+                        const double* sampling_mask_xyza, const grt_frame_out* out,
+                        uint64_t* n_supersampled, grt_stats* stats,
+                        grt_subsample_failures* failures, grt_sequence_report* report);
+/* Rays per launch group of grt_render_sequence (0 = default 2^22: ~4.6 GB of workspace at
+ * 64 B + 16 x 64 B per ray).  A group holds as many whole frames as fit, at least one.
+ * Scheduling only.  Process-wide; read once per call. */
+int grt_set_sequence_group(uint64_t rays);
+
 /* The device hit pool that keeps the window candidates past a ray's GRT_MAX_HITS slots
  * (no reference counterpart: the reference's per-ray Vec grows, scene.rs:139-152).
  * A trace starts with the pool at its minimum (grt_set_hit_pool_min, 2^20 records) or
@@ -683,7 +735,8 @@ int grt_xyz_to_srgb8_device(int device, const double* xyza, size_t n, int32_t to
  * (tests/test_fused.py), but no longer bit-identical; Kerr-Schild always runs exact (its
  * finite-difference metric turns the changed roundings into other step sequences).
  * It applies to frame traces (grt_render_*, grt_supersample_shard*, grt_render_frame_multi);
- * trajectories (grt_trace_*), monitors and the work-order probe always run exact.
+ * trajectories (grt_trace_*), monitors, the work-order probe and camera sequences
+ * (grt_render_sequence) always run exact.
  * Process-wide; each trace reads it once when it is enqueued. */
 int grt_set_arithmetic(int mode);
 int grt_get_arithmetic(void);

@@ -1,0 +1,411 @@
+"""Camera sequences on the GPU (grt_render_sequence, geodesic_seq.hip; marker `gpu`).
+
+K cameras over one resident scene are traced stacked: K frames of rows x cols as one
+rectangle of K * rows rows, each ray with the camera of the frame its stacked row lies in.
+The reference of every comparison is the existing single-frame path on a scene created
+with that camera, and the comparisons are exact (array_equal on the f32 / f64 bits, class,
+status, stop, steps and the summed accepted steps): the operations are the same, so no
+tolerance is involved.
+
+Frames are 24 cols x 20 rows: rows % 8 != 0, so 8x8 tiles straddle two frames, and the
+three cameras differ in position and in all three angles.
+"""
+import ctypes as C
+import math
+import subprocess
+
+import numpy as np
+import pytest
+
+from conftest import RESOURCES, ROOT, SCENES
+
+pytestmark = pytest.mark.gpu
+
+ROWS, COLS, K = 20, 24, 3
+N = ROWS * COLS
+GRT = ROOT / "gr_raytracer_amd" / "lib" / "grt"
+
+# (Cartesian position, phi, theta, psi) of the three cameras
+CAMS_FRONT = [((-16.0, 0.0, 3.5), 0.0, -3.142, 0.0), ((-15.0, 4.0, 3.0), 0.1, -3.0, 0.05),
+              ((-12.0, -9.0, 5.0), -0.2, -3.3, -0.1)]
+CAMS_KERR = [((-20.0, 0.0, -1.0), 0.0, 1.52, -1.57), ((-18.0, 6.0, -2.0), 0.05, 1.6, -1.5),
+             ((-14.0, -14.0, 3.0), -0.1, 1.45, -1.65)]
+CAMS_KERR_BL = [((-10.0, 0.0, -0.5), 0.0, -3.14159, 0.0), ((-9.5, 2.5, -1.0), 0.08, -3.1, 0.02),
+                ((-8.0, -6.0, 2.0), -0.15, -3.2, -0.07)]
+CAMS_FLAT = [((0.0, 0.0, -12.0), 0.0, 0.0, 0.0), ((1.0, 2.0, -11.0), 0.1, 0.1, 0.05),
+             ((-3.0, -2.0, -10.0), -0.2, -0.15, -0.1)]
+CAMS_WINDING = [((-8.0, 0.0, 0.1), 0.0, -3.142, 0.0), ((-7.9, 0.6, 0.15), 0.01, -3.13, 0.02),
+                ((-7.8, -0.8, 0.05), -0.015, -3.15, -0.03)]
+
+
+def _native(grt, geometry, a, cart):
+    L = grt._lib
+    p = (0.0,) + tuple(cart)
+    if geometry in (L.GEOM_SCHWARZSCHILD, L.GEOM_EUCLIDEAN_SPHERICAL):
+        return grt.cartesian_to_spherical(p)
+    if geometry == L.GEOM_KERR_BL:
+        return grt.cartesian_to_boyer_lindquist(a, p)
+    return np.array(p)
+
+
+class Built:
+    """A programmatic scene: builder(camera row) -> descriptor with that camera."""
+
+    def __init__(self, grt, geometry, radius, a, eps, integration, populate, cams, alpha=math.pi / 4):
+        self.grt, self.cams, self.args = grt, cams, (geometry, radius, a, eps, integration, populate, alpha)
+
+    def desc(self, k):
+        grt = self.grt
+        geometry, radius, a, eps, integration, populate, alpha = self.args
+        cart, phi, theta, psi = self.cams[k]
+        b = grt.SceneBuilder(geometry, radius=radius, a=a, horizon_epsilon=eps)
+        b.integration(*integration)
+        pos = _native(grt, geometry, a, cart)
+        b.camera(pos, grt.stationary_velocity(geometry, radius, a, pos), alpha, ROWS, COLS, phi, theta, psi)
+        populate(b)
+        return b.build()
+
+    def scene(self, k):
+        d = self.desc(k)
+        return self.grt.Scene(C.pointer(d), keepalive=d)
+
+    def cameras(self):
+        return [self.desc(k).camera for k in range(len(self.cams))]
+
+
+class Loaded:
+    """A stock TOML scene: one load per camera for the references, HostScene.camera for
+    the sequence."""
+
+    def __init__(self, grt, toml, cams, **opts):
+        self.grt, self.toml, self.cams, self.opts = grt, toml, cams, opts
+
+    def host(self, k):
+        cart, phi, theta, psi = self.cams[k]
+        o = self.grt.GlobalOpts(width=COLS, height=ROWS, camera_position=cart, phi=phi, theta=theta, psi=psi,
+                                **self.opts)
+        return self.grt.HostScene(str(SCENES / self.toml), o, str(RESOURCES))
+
+    def desc(self, k):
+        hs = self.host(k)
+        d = hs.desc
+        d._keepalive = hs
+        return d
+
+    def scene(self, k):
+        hs = self.host(k)
+        return self.grt.Scene(hs.desc_ptr(), keepalive=hs, adaptive=hs.adaptive)
+
+    def cameras(self):
+        hs = self.host(0)
+        return [hs.camera(*row) for row in self.cams]
+
+
+def _schwarzschild(b):
+    b.celestial(b_checker(0.0, 16.0, 8.0, (20, 20, 80), (200, 200, 255)))
+    b.add_disc(3.0, 6.0, b_checker(3.0, 12.0, 4.0, (255, 160, 0), (120, 40, 0)), temperature=2000.0)
+    b.add_sphere(1.5, (0.0, 7.0, 1.0), b_checker(0.0, 6.0, 6.0, (0, 200, 0), (255, 255, 255)), temperature=3000.0)
+
+
+def _kerr_disc(b):
+    b.celestial(b_checker(0.0, 16.0, 8.0, (20, 20, 80), (200, 200, 255)))
+    b.add_disc(2.0, 6.0, b_checker(3.0, 12.0, 4.0, (255, 160, 0), (120, 40, 0)), temperature=2000.0)
+
+
+def _kerr_schild_disc(b):  # M = 1, a = 0.5: r_isco = 4.23
+    b.celestial(b_checker(0.0, 16.0, 8.0, (20, 20, 80), (200, 200, 255)))
+    b.add_disc(5.0, 9.0, b_checker(3.0, 12.0, 4.0, (255, 160, 0), (120, 40, 0)), temperature=2000.0)
+
+
+def _flat(b):
+    b.celestial(b_checker(0.0, 16.0, 8.0, (20, 20, 80), (200, 200, 255)))
+    b.add_disc(3.0, 6.0, b_checker(0.0, 12.0, 4.0, (255, 160, 0), (120, 40, 0)), temperature=2000.0)
+    b.add_sphere(2.0, (0.0, 0.0, 0.0), b_checker(0.0, 6.0, 6.0, (0, 200, 0), (255, 255, 255)), temperature=3000.0)
+
+
+def _winding(b):  # tests/test_hit_pool.py: rays cross the spheres up to ~100 times
+    b.celestial(b_checker(0.0, 20.0, 20.0, (0, 255, 0), (0, 100, 0)))
+    for k in range(4):
+        ang = k * math.pi / 2 + 0.3
+        b.add_sphere(0.2, (0.73 * math.cos(ang), 0.73 * math.sin(ang), 0.0),
+                     b_checker(0.0, 8.0, 8.0, (255, 0, 0), (0, 0, 255)), temperature=3000.0)
+
+
+def b_checker(beaming, w, h, c1, c2):
+    import gr_raytracer_amd as g
+
+    return g.Checker(beaming, w, h, c1, c2)
+
+
+def make_case(grt, name):
+    L = grt._lib
+    if name == "schwarzschild":
+        return Built(grt, L.GEOM_SCHWARZSCHILD, 1.0, 0.0, 1e-4, (20000, 100.0, 0.01, 1e-5), _schwarzschild, CAMS_FRONT)
+    if name == "kerr-bl":
+        return Built(grt, L.GEOM_KERR_BL, 1.0, 0.499, 1e-4, (20000, 100.0, 0.01, 1e-5), _kerr_disc, CAMS_KERR_BL)
+    if name == "kerr-schild":
+        return Built(grt, L.GEOM_KERR, 2.0, 0.5, 1e-4, (10000, 100.0, 0.01, 1e-5), _kerr_schild_disc, CAMS_KERR)
+    if name == "euclidean":
+        return Built(grt, L.GEOM_EUCLIDEAN, 0.0, 0.0, 0.0, (20000, 100.0, 0.01, 1e-5), _flat, CAMS_FLAT)
+    if name == "volumetric":
+        return Loaded(grt, "schwarzschild-volumetric-stony.toml", CAMS_FRONT, max_steps=20000)
+    if name == "winding":  # a narrow view of the winding region, horizon_epsilon 1e-6
+        return Built(grt, L.GEOM_KERR_BL, 1.0, 0.499, 1e-6, (200000, 100.0, 0.01, 1e-7), _winding, CAMS_WINDING,
+                     alpha=0.21)
+    raise KeyError(name)
+
+
+FIELDS = ("xyza", "xyza64", "ray_class", "status", "stop_reason", "steps")
+
+
+def single_frames(case):
+    """The reference: each camera rendered alone by the single-frame path."""
+    out = []
+    for k in range(K):
+        r = case.scene(k).render_pixels(0, 0, ROWS, COLS)
+        out.append(r)
+    return out
+
+
+_REFS = {}
+
+
+def reference(grt, name):
+    """(case, single-frame results), computed once per scene and shared (never modified)."""
+    if name not in _REFS:
+        case = make_case(grt, name)
+        _REFS[name] = (case, single_frames(case))
+    return _REFS[name]
+
+
+def assert_frames_equal(seq, refs, what=""):
+    for k, r in enumerate(refs):
+        assert np.array_equal(seq["xyza"][k].view(np.uint32), r.xyza.view(np.uint32)), (what, k, "xyza")
+        assert np.array_equal(seq["xyza64"][k].view(np.uint64), r.xyza64.view(np.uint64)), (what, k, "xyza64")
+        assert np.array_equal(seq["class"][k], r.ray_class), (what, k, "class")
+        assert np.array_equal(seq["status"][k], r.status), (what, k, "status")
+        assert np.array_equal(seq["stop"][k], r.stop_reason), (what, k, "stop")
+        assert np.array_equal(seq["steps"][k], r.steps), (what, k, "steps")
+
+
+def assert_counters_equal(seq, refs, what=""):
+    for key in ("accepted_steps", "attempts", "rays"):
+        assert seq["stats"][key] == sum(r.stats[key] for r in refs), (what, key)
+    assert seq["stats"]["hit_overflows"] == 0
+
+
+def sequence_scene(case):
+    return case.scene(0), case.cameras()
+
+
+# ------------------------------------------------------------------ 1. parity ------
+@pytest.mark.parametrize("name", ["schwarzschild", "kerr-bl", "kerr-schild", "euclidean", "volumetric"])
+def test_sequence_equals_single_frames(grt, gpu, name):
+    case, refs = reference(grt, name)
+    # the references are three different pictures with something in them
+    assert not np.array_equal(refs[0].xyza, refs[1].xyza) and not np.array_equal(refs[1].xyza, refs[2].xyza)
+    assert all(len(np.unique(r.ray_class)) >= 2 for r in refs), [np.unique(r.ray_class) for r in refs]
+    sc, cams = sequence_scene(case)
+    seq = sc.render_sequence(cams)
+    assert_frames_equal(seq, refs, name)
+    assert_counters_equal(seq, refs, name)
+    rep = seq["report"]
+    assert (rep.n_frames, rep.n_launches, rep.frames_per_launch) == (K, 1, K)
+    assert rep.trace_ms > 0 and rep.supersample_ms == 0 and rep.wall_ms >= rep.trace_ms
+    if name == "volumetric":
+        for key in ("march_jobs", "march_samples", "march_noise_samples", "march_emit_samples"):
+            assert seq["stats"][key] == sum(r.stats[key] for r in refs) > 0, key
+
+
+# ------------------------------------------------------------- 2. launch groups ----
+def test_group_sizes_give_identical_frames(grt, gpu):
+    case, refs = reference(grt, "schwarzschild")
+    sc, cams = sequence_scene(case)
+    try:
+        for frames, launches in ((1, 3), (2, 2), (3, 1)):
+            grt.set_sequence_group(frames * N)
+            seq = sc.render_sequence(cams)
+            rep = seq["report"]
+            assert (rep.n_launches, rep.frames_per_launch) == (launches, frames)
+            assert_frames_equal(seq, refs, frames)
+            assert_counters_equal(seq, refs, frames)
+        grt.set_sequence_group(1)  # below one frame: a group still holds one
+        assert sc.render_sequence(cams)["report"].n_launches == 3
+    finally:
+        grt.set_sequence_group(0)
+
+
+# ---------------------------------------------------------------- 3. scheduling ----
+def test_schedule_and_two_ended_queue_change_nothing(grt, gpu):
+    L = grt._lib
+    try:
+        for name in ("schwarzschild", "kerr-schild"):
+            case, refs = reference(grt, name)
+            sc, cams = sequence_scene(case)
+            L.check(L.lib().grt_set_schedule(1))
+            for two in (True, False):
+                grt.scene.set_two_ended(two)
+                seq = sc.render_sequence(cams)
+                assert_frames_equal(seq, refs, (name, two))
+                assert_counters_equal(seq, refs, (name, two))
+    finally:
+        L.check(L.lib().grt_set_schedule(-1))
+        grt.scene.set_two_ended(True)
+
+
+TAIL_THRESHOLD = 37  # live rays (tests/test_tail.py's partial hand-off): above one frame's long rays
+
+
+def test_tail_hand_off_changes_nothing(grt, gpu):
+    case, refs = reference(grt, "kerr-schild")
+    # each frame has a few long rays (captured, thousands of steps) left when the others
+    # (hundreds of steps) are done: what the hand-off takes
+    for r in refs:
+        long_rays = int((r.steps >= 2000).sum())
+        assert 0 < long_rays <= TAIL_THRESHOLD and (r.steps < 2000).sum() > 400, long_rays
+    try:
+        grt.scene.set_tail(TAIL_THRESHOLD)
+        single = case.scene(1)
+        alone = single.render_pixels(0, 0, ROWS, COLS)
+        assert single.tail_handoffs() > 0  # the tail takes rays at this threshold
+        assert np.array_equal(alone.xyza64, refs[1].xyza64) and np.array_equal(alone.steps, refs[1].steps)
+        sc, cams = sequence_scene(case)
+        seq = sc.render_sequence(cams)
+        assert sc.tail_handoffs() > 0
+        assert_frames_equal(seq, refs, "tail")
+        assert_counters_equal(seq, refs, "tail")
+        grt.scene.set_tail(0)
+        off, cams = sequence_scene(case)  # a fresh device copy: its hand-off count starts at 0
+        seq = off.render_sequence(cams)
+        assert off.tail_handoffs() == 0
+        assert_frames_equal(seq, refs, "no tail")
+    finally:
+        grt.scene.set_tail(-1)
+
+
+# ------------------------------------------------------------------ 4. adaptive ----
+MASK = (0.25, 0.5, 0.125, 1.0)
+
+
+def test_adaptive_frames_equal_render_section_ex(grt, gpu):
+    case, _ = reference(grt, "schwarzschild")
+    ad = grt.default_adaptive()  # the stock configuration: enabled, 4 x 4 samples
+    assert ad.enabled == 1 and ad.samples_per_axis == 4
+    refs = [case.scene(k).render_section_ex(adaptive=ad) for k in range(K)]
+    masks = [case.scene(k).render_section_ex(adaptive=ad, sampling_mask_xyza=MASK) for k in range(K)]
+    # every frame selects pixels, and not the same ones
+    selected = [np.all(m.xyza64 == np.array(MASK), axis=1) for m in masks]
+    for k in range(K):
+        assert refs[k].n_supersampled >= 1 and selected[k].sum() == refs[k].n_supersampled
+    assert not np.array_equal(selected[0], selected[1]) and not np.array_equal(selected[1], selected[2])
+    sc, cams = sequence_scene(case)
+    for group in (0, N):  # one stacked launch, and one frame per launch
+        try:
+            grt.set_sequence_group(group)
+            seq = sc.render_sequence(cams, adaptive=ad, supersample=True)
+            msk = sc.render_sequence(cams, adaptive=ad, mask=MASK)
+        finally:
+            grt.set_sequence_group(0)
+        assert "xyza" not in seq
+        for k in range(K):
+            assert np.array_equal(seq["xyza64"][k].view(np.uint64), refs[k].xyza64.view(np.uint64)), (group, k)
+            assert np.array_equal(seq["class"][k], refs[k].ray_class) and np.array_equal(seq["status"][k], refs[k].status)
+            assert int(seq["n_supersampled"][k]) == refs[k].n_supersampled
+            assert seq["n_failed"][k] == refs[k].n_failed_subsamples
+            assert np.array_equal(seq["failures"][k], refs[k].failed_subsamples)
+            assert np.array_equal(msk["xyza64"][k].view(np.uint64), masks[k].xyza64.view(np.uint64)), (group, k)
+            assert int(msk["n_supersampled"][k]) == masks[k].n_supersampled
+        for key in ("accepted_steps", "attempts", "rays"):
+            assert seq["stats"][key] == sum(r.stats[key] for r in refs), key
+        assert seq["report"].supersample_ms > 0 and seq["report"].n_launches == (1 if group == 0 else K)
+
+
+# ------------------------------------------------------------ 5. hit-pool overflow --
+def test_hit_pool_overflow_is_traced_again(grt, gpu):
+    L = grt._lib
+    case, refs = reference(grt, "winding")  # with the roomy default pool
+    heavy = sum(int((r.hits > L.GRT_MAX_HITS).sum()) for r in refs)
+    assert heavy > 30 and max(int(r.hits.max()) for r in refs) > 40
+    before = 1 << 20
+    L.check(L.lib().grt_set_hit_pool_min(64))
+    try:
+        sc, cams = sequence_scene(case)  # a fresh device copy: a 64-record pool
+        seq = sc.render_sequence(cams)
+        assert_frames_equal(seq, refs, "overflow")
+        assert seq["stats"]["hit_overflows"] == 0
+        assert not np.any(seq["status"] & L.FLAG_HIT_OVERFLOW)
+        # the first trace lost candidates: flagged (hence heavy) pixels were traced again
+        assert K * N < seq["stats"]["rays"] <= K * N + 3 * heavy, (seq["stats"]["rays"], heavy)
+    finally:
+        L.check(L.lib().grt_set_hit_pool_min(before))
+
+
+# ---------------------------------------------------------------------- 6. oracle --
+def test_sequence_frame_against_the_oracle(grt, oracle, gpu):
+    """Frame 1 of the Schwarzschild sequence against the CPU oracle on that camera's
+    descriptor, at the project's 1e-4 relative per channel."""
+    case, _ = reference(grt, "schwarzschild")
+    sc, cams = sequence_scene(case)
+    seq = sc.render_sequence(cams)
+    ref = oracle.render_pixels(case.desc(1), 0, 0, ROWS, COLS, threads=16)
+    got = seq["xyza64"][1]
+    ok = np.abs(got - ref["xyza"]) <= 1e-4 * np.maximum(np.abs(ref["xyza"]), 1e-6)
+    assert np.all(ok), np.argwhere(~ok)[:5]
+    assert np.array_equal(seq["class"][1], ref["ray_class"]) and np.array_equal(seq["status"][1], ref["status"])
+
+
+# ---------------------------------------------------------------------- 7. errors --
+def test_invalid_sequences_are_rejected(grt, gpu):
+    L = grt._lib
+    case, refs = reference(grt, "euclidean")
+    sc, cams = sequence_scene(case)
+    lib = L.lib()
+    xyza, x64 = np.zeros((K, N, 4), np.float32), np.zeros((K, N, 4), np.float64)
+    out = L.FrameOut(L.ptr(xyza, C.c_float), L.dptr(x64), None, None, None, None)
+    table = (L.CameraDesc * K)(*cams)
+
+    def call(n, tab, cfg=None, o=out):
+        return lib.grt_render_sequence(sc._s, 0, n, tab, C.byref(cfg) if cfg is not None else None, None, C.byref(o),
+                                       None, None, None, None)
+
+    def valid():
+        assert call(K, table) == 0
+        assert np.array_equal(xyza[2], refs[2].xyza)
+
+    valid()
+    for rows, cols in ((ROWS + 1, COLS), (ROWS, COLS - 8)):
+        bad = (L.CameraDesc * K)(*cams)
+        bad[1].rows, bad[1].cols = rows, cols
+        assert call(K, bad) == -22 and "camera 1" in lib.grt_last_error().decode()
+        valid()
+    assert call(0, table) == -22 and "at least one camera" in lib.grt_last_error().decode()
+    valid()
+    ad = grt.default_adaptive()
+    no64 = L.FrameOut(L.ptr(xyza, C.c_float), None, None, None, None, None)
+    assert call(K, table, ad, no64) == -22 and "xyza64" in lib.grt_last_error().decode()
+    valid()
+
+
+# ------------------------------------------------------------------------- 8. CLI --
+@pytest.mark.parametrize("toml,tone", [("schwarzschild.toml", "reinhard"), ("euclidean.toml", "global-linear")])
+def test_cli_render_sequence_writes_the_frames_of_render(grt, gpu, tmp_path, toml, tone):
+    rows = CAMS_FRONT
+    path = tmp_path / "path.txt"
+    path.write_text("# x,y,z,phi,theta,psi\n" + "".join(
+        f"{c[0]},{c[1]},{c[2]},{phi},{theta},{psi}\n\n" for c, phi, theta, psi in rows))
+    common = [str(GRT), "--width", "32", "--height", "24", "--max-steps", "20000", "--tone-mapping", tone,
+              "--resource-root", str(RESOURCES), "--config-file", str(SCENES / toml)]
+    r = subprocess.run(common + ["--raw-out", str(tmp_path / "raw-%d.bin"), "render-sequence", "--camera-path",
+                                 str(path), "--filename-pattern", str(tmp_path / "seq-%03d.png"), "--first-index", "7"],
+                       capture_output=True, text=True, timeout=120)
+    assert r.returncode == 0, r.stderr
+    assert r.stderr.count("INFO saved image to") == 3 and "3 frames in 1 stacked launch" in r.stderr
+    for k, (c, phi, theta, psi) in enumerate(rows):
+        one = tmp_path / f"one-{k}.png"
+        q = subprocess.run(common + ["--camera-position", f"{c[0]},{c[1]},{c[2]}", f"--phi={phi}", f"--theta={theta}",
+                                     f"--psi={psi}", "--raw-out", str(tmp_path / f"one-{k}.bin"), "render",
+                                     "--filename", str(one)], capture_output=True, text=True, timeout=120)
+        assert q.returncode == 0, q.stderr
+        assert (tmp_path / f"seq-{7 + k:03d}.png").read_bytes() == one.read_bytes(), k
+        assert (tmp_path / f"raw-{7 + k}.bin").read_bytes() == (tmp_path / f"one-{k}.bin").read_bytes(), k
+    assert len({(tmp_path / f"seq-{7 + k:03d}.png").read_bytes() for k in range(3)}) == 3
