@@ -957,6 +957,22 @@ int grt_debug_arith_map(int device, uint32_t samples, uint64_t seed, uint8_t* ma
   return 0;
 }
 
+// Test hook (not in grt_api.h): the seeded reciprocals of the region-B Schwarzschild RHS
+// (rcp_seed.h) against the compiler's division on n host tuples (r, radius, a, sin, cos):
+// flags[n], one bit per differing quotient (rcp_seed_check_kernel).
+int grt_debug_rcp_seed(int device, uint64_t n, const double* tuples, uint8_t* flags) {
+  if (!tuples || !flags || n == 0 || n > (1ull << 26)) return fail(-EINVAL, "rcp seed check: 1 <= n <= 2^26");
+  HIP_TRY(hipSetDevice(device));
+  DevBuf b_t, b_f;
+  int rc;
+  if ((rc = b_t.alloc(n * 40)) || (rc = b_f.alloc(n))) return rc;
+  HIP_TRY(hipMemcpy(b_t.p, tuples, n * 40, hipMemcpyHostToDevice));
+  HIP_TRY(grt::launch_rcp_seed_check(n, (const double*)b_t.p, (uint8_t*)b_f.p, nullptr));
+  HIP_TRY(hipDeviceSynchronize());
+  HIP_TRY(hipMemcpy(flags, b_f.p, n, hipMemcpyDeviceToHost));
+  return 0;
+}
+
 // Test hook (not in grt_api.h): the scene's RHS in its range-free and IEEE forms on n
 // host states (8 doubles each; KerrBL: e, l_z, q per state in consts), out[16 n], pred[n]
 // (rhs_check_kernel).
@@ -987,7 +1003,7 @@ int grt_debug_rhs_check(grt_scene* s, int device, uint64_t n, const double* stat
 
 #if GRT_PATH_COUNT
 // Diagnostic builds only (not in grt_api.h): the integrate kernels' path counters since the
-// last reset (geodesic.hip path_count): out[16], [k] wave-level, [8 + k] lane-level.
+// last reset (geodesic.hip path_count): out[24], [k] wave-level, [12 + k] lane-level.
 int grt_debug_path_counts(uint64_t* out, int reset) {
   if (!out) return fail(-EINVAL, "null argument");
   HIP_TRY(grt::path_read((unsigned long long*)out, reset != 0));

@@ -31,6 +31,7 @@
 #define GRT_GLIBC_LDS 1  // glibc tables staged in LDS per workgroup (measured -1..2%)
 #endif
 #include "glibc_math.h"
+#include "rcp_seed.h"
 #include "kernels.h"
 
 // GRT_FUSED: this file compiled a second time, by geodesic_fused.hip, with FMA contraction
@@ -337,6 +338,34 @@ __global__ void arith_map_kernel(uint32_t samples, uint64_t seed, uint8_t* map, 
   if (ex == 0) zmap[ey] = (uint8_t)zflags;
   if (ey == 0) smap[ex] = (uint8_t)sflags;
 }
+
+// Device check of the seeded reciprocals of the region-B Schwarzschild RHS (rcp_seed.h)
+// against the compiler's division (tests/test_gpu_rcp_seed.py): tuple i = (r, radius, a,
+// sin, cos) in t[5 i ..]; flags[i] gets bit
+//   1 radius / r   2 2 / r   4 radius / (r r)   8 (radius / (r r)) / a   16 (2 cos) / sin
+// for each quotient whose bits differ.  a comes from the tuple, not from r, so that the
+// test can put it on the predicate's edge.
+__global__ void rcp_seed_check_kernel(uint64_t n, const double* __restrict__ t, uint8_t* __restrict__ flags) {
+  const uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  const double r = t[5 * i], radius = t[5 * i + 1], a = t[5 * i + 2], st = t[5 * i + 3], ct = t[5 * i + 4];
+  auto bits = [](double v) { return (uint64_t)__double_as_longlong(v); };
+  auto hw_rcp = [](double v) { return __builtin_amdgcn_rcp(v); };
+  const double rr = r * r, two_ct = 2.0 * ct;
+  double Yr, Yrr, Ya, Yst;
+  rcpseed::rcp_r_rr(r, rr, hw_rcp, &Yr, &Yrr);
+  rcpseed::rcp_pair(a, st, hw_rcp, &Ya, &Yst);
+  const double a_prime = rcpseed::div_by_rcp(radius, rr, Yrr);
+  volatile double v_r = r, v_radius = radius, v_a = a, v_st = st, v_rr = rr, v_two = 2.0, v_two_ct = two_ct,
+                  v_a_prime = a_prime;  // keep the reference divisions as divisions
+  uint32_t f = 0;
+  if (bits(rcpseed::div_by_rcp(radius, r, Yr)) != bits(v_radius / v_r)) f |= 1u;
+  if (bits(rcpseed::div_by_rcp(2.0, r, Yr)) != bits(v_two / v_r)) f |= 2u;
+  if (bits(a_prime) != bits(v_radius / v_rr)) f |= 4u;
+  if (bits(rcpseed::div_by_rcp(a_prime, a, Ya)) != bits(v_a_prime / v_a)) f |= 8u;
+  if (bits(rcpseed::div_by_rcp(two_ct, st, Yst)) != bits(v_two_ct / v_st)) f |= 16u;
+  flags[i] = (uint8_t)f;
+}
 #endif  // GRT_MAIN_TU
 
 constexpr double PI = 3.14159265358979323846;
@@ -553,8 +582,10 @@ GDEV void metric_bl(double r_s, double a, double r, double sin_t, double cos_t, 
 // [8 + k] the same in lanes.  Kerr-Schild RHS: 0 range-free form, 1 IEEE form.  Light
 // charts' RHS: 0 region-B table with range-free divisions, 1 region-B Taylor with them,
 // 2 region-B with the IEEE divisions, 3 general (branchy) sincos.  All: 4 near-field window
-// pass, 5 accepted step, 6 attempt.
-constexpr int NPATH = 8;
+// pass, 5 accepted step, 6 attempt.  What the waves of path 3 hold: 8 every lane in glibc's
+// region A (2^-27 <= |x| < 0.855469) on do_sin's table path, 9 every lane in region A
+// otherwise, 10 every lane in region C (|x| >= 2.426265) with quadrant n = 2, 11 mixed.
+constexpr int NPATH = 12;
 __shared__ unsigned long long path_lds[2 * NPATH];
 __device__ unsigned long long g_path[2 * NPATH];
 GDEV void path_count(int k) {
@@ -613,6 +644,18 @@ GDEV void with_sincos(double theta, bool fast_ok, F&& body, bool div_ok = false)
   }
 #endif
   PATH_COUNT(3);
+#if GRT_PATH_COUNT
+  {
+    const uint32_t k = (uint32_t)(glibc::as_u64(theta) >> 32) & 0x7fffffffu;
+    const bool ra = k >= 0x3e400000u && k < 0x3feb6000u, ra_tab = ra && !(fabs(theta) < glibc::TAYLOR_MAX);
+    double ca, cda;
+    const bool rc2 = k >= 0x400368fdu && k < 0x419921fbu && glibc::reduce_sincos_nf(theta, &ca, &cda) == 2;
+    if (__ballot(!ra_tab) == 0) PATH_COUNT(8);
+    else if (__ballot(!ra) == 0) PATH_COUNT(9);
+    else if (__ballot(!rc2) == 0) PATH_COUNT(10);
+    else PATH_COUNT(11);
+  }
+#endif
   double st, ct;
   rsincos(theta, &st, &ct);
   body(st, ct, false, std::false_type{});
@@ -667,11 +710,17 @@ GDEV void rhs(const DevScene& S, const RayConst& rc, const double* y, double* o)
     double v_t = y[4], v_r = y[5], v_theta = y[6], v_phi = y[7];
     auto body = [&](double st, double ct, bool fast, auto fdiv) {
       if constexpr (decltype(fdiv)::value) {
-        double radius_over_r, two_over_r;
-        div2_inrange(radius, 2.0, r, &radius_over_r, &two_over_r);
+        // rcp_seed.h: 1 / (r r) seeded from the refined 1 / r
+        auto hw_rcp = [](double v) { return __builtin_amdgcn_rcp(v); };
+        const double rr = r * r;
+        double Yr, Yrr, Ya, Yst;
+        rcpseed::rcp_r_rr(r, rr, hw_rcp, &Yr, &Yrr);
+        double radius_over_r = rcpseed::div_by_rcp(radius, r, Yr);
+        double two_over_r = rcpseed::div_by_rcp(2.0, r, Yr);
         double a = 1.0 - radius_over_r;
-        double a_prime = div_inrange(radius, r * r);
-        double aprime_over_a = div_inrange(a_prime, a);
+        rcpseed::rcp_pair(a, st, hw_rcp, &Ya, &Yst);
+        double a_prime = rcpseed::div_by_rcp(radius, rr, Yrr);
+        double aprime_over_a = rcpseed::div_by_rcp(a_prime, a, Ya);
         o[0] = v_t;
         o[1] = v_r;
         o[2] = v_theta;
@@ -680,7 +729,7 @@ GDEV void rhs(const DevScene& S, const RayConst& rc, const double* y, double* o)
         o[5] = -0.5 * a * a_prime * v_t * v_t + 0.5 * (aprime_over_a)*v_r * v_r +
                a * r * (v_theta * v_theta + v_phi * v_phi * st * st);
         o[6] = -(two_over_r)*v_r * v_theta + st * ct * v_phi * v_phi;
-        o[7] = -(two_over_r)*v_phi * v_r - div_inrange(2.0 * ct, st) * v_theta * v_phi;
+        o[7] = -(two_over_r)*v_phi * v_r - rcpseed::div_by_rcp(2.0 * ct, st, Yst) * v_theta * v_phi;
         return;
       }
       double radius_over_r, two_over_r;
@@ -712,7 +761,11 @@ GDEV void rhs(const DevScene& S, const RayConst& rc, const double* y, double* o)
     // 2^-100 < |r| < 2^100 and |r - radius| > 2^-40 radius (so |a| > 2^-42), every operand
     // and quotient of the five divisions is within 2^+-600 (schw_div_ok; device check of the
     // two forms at the predicate's edges: tests/test_gpu_arith.py
-    // ::test_rhs_schwarzschild_fast_form_matches_ieee).
+    // ::test_rhs_schwarzschild_fast_form_matches_ieee).  1 / (r r) takes its seed from the
+    // refined 1 / r instead of a v_rcp_f64 of its own (rcp_seed.h: 16 cycles of the SIMD
+    // against a multiply's 4, tools/valu_issue_cost.hip); the new intermediates are the seed
+    // Y_r Y_r within 2^+-200 and its Newton residual 1 - (r r) Y_r Y_r within 2^-50 of 0,
+    // both inside E with the box to spare (tests/test_gpu_rcp_seed.py).
     if constexpr (MODE != 0) {
       double st, ct;
       if (glibc::sincos_b_table_ok(theta)) glibc::sincos_b_table(theta, &st, &ct);
@@ -1860,6 +1913,10 @@ hipError_t set_ray_times(unsigned long long* p) {
 #elif GRT_KERR_BL_TU
 hipError_t set_ray_times(unsigned long long* p) { return hipMemcpyToSymbol(HIP_SYMBOL(g_ray_times), &p, sizeof(p)); }
 #endif
+#define RAY_TIME(n, idx, k, v) ray_time(n, idx, k, v)
+#else
+#define RAY_TIME(n, idx, k, v) ((void)0)
+#endif
 #if GRT_KERR_BL_TU && GRT_PATH_COUNT
 hipError_t path_read(unsigned long long* out, bool reset) {
   hipError_t e = hipMemcpyFromSymbol(out, HIP_SYMBOL(g_path), sizeof(g_path));
@@ -1869,10 +1926,6 @@ hipError_t path_read(unsigned long long* out, bool reset) {
   }
   return e;
 }
-#endif
-#define RAY_TIME(n, idx, k, v) ray_time(n, idx, k, v)
-#else
-#define RAY_TIME(n, idx, k, v) ((void)0)
 #endif
 
 // The observer energy of the camera ray in output slot idx (init_ray's rc.obs, recomputed
@@ -2614,6 +2667,11 @@ hipError_t launch_arith_map(uint32_t samples, uint64_t seed, uint8_t* d_map, uin
                             hipStream_t stream) {
   hipLaunchKernelGGL(arith_map_kernel, dim3((2047u * 2047u + 255u) / 256u), dim3(256), 0, stream, samples, seed, d_map,
                      d_zmap, d_smap);
+  return hipGetLastError();
+}
+
+hipError_t launch_rcp_seed_check(uint64_t n, const double* d_tuples, uint8_t* d_flags, hipStream_t stream) {
+  hipLaunchKernelGGL(rcp_seed_check_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, stream, n, d_tuples, d_flags);
   return hipGetLastError();
 }
 

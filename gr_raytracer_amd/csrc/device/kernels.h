@@ -54,6 +54,8 @@ struct TrajectoryList {
 // test hook: div_inrange / div2_inrange against the compiler's division on n random pairs
 hipError_t launch_arith_map(uint32_t samples, uint64_t seed, uint8_t* d_map, uint8_t* d_zmap, uint8_t* d_smap,
                             hipStream_t stream);
+// test hook: the seeded reciprocals of rcp_seed.h against the compiler's division on n tuples
+hipError_t launch_rcp_seed_check(uint64_t n, const double* d_tuples, uint8_t* d_flags, hipStream_t stream);
 hipError_t launch_rhs_check(int geometry, const DevScene* d_scene, const double* d_states, const double* d_consts,
                             uint64_t n, double* d_out, uint8_t* d_pred, hipStream_t stream);
 #if GRT_PATH_COUNT

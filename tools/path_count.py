@@ -3,7 +3,10 @@
 times a wave executed it (counted by its first active lane) and how many lanes did.
 Kerr-Schild RHS: 0 range-free, 1 IEEE.  Schwarzschild / KerrBL RHS: 0 region-B table
 with range-free divisions, 1 region-B Taylor with them, 2 region B with IEEE divisions,
-3 general sincos (7: of those, with the range-free divisions).  All: 4 near-field window pass, 5 accepted step, 6 attempt.
+3 general sincos (7: of those, with the range-free divisions); what the waves of 3 hold:
+8 every lane in glibc's region A on the table path, 9 every lane in region A otherwise,
+10 every lane in region C with n = 2, 11 mixed.  All: 4 near-field window pass,
+5 accepted step, 6 attempt.
 usage: tools/path_count.py c2|c3|c4 (c4: row-band shard 2 of 8)"""
 import ctypes as C
 import hashlib
@@ -33,7 +36,8 @@ sc = g.Scene(hs.desc_ptr(), keepalive=hs)
 fn = L.lib().grt_debug_path_counts
 fn.restype = C.c_int
 fn.argtypes = [C.POINTER(C.c_uint64), C.c_int]
-cnt = (C.c_uint64 * 16)()
+NPATH = 12
+cnt = (C.c_uint64 * (2 * NPATH))()
 L.check(fn(cnt, 1), "grt_debug_path_counts")  # reset
 t = time.time()
 r = sc.render_shard(16, 2, 8, aux=False) if which == "c4" else sc.render_pixels(0, 0, 1500, 1500, aux=False)
@@ -44,12 +48,13 @@ names += ["near_window", "accepted_general_path", "attempt"]
 keys = [0, 1] if which == "c4" else [0, 1, 2, 3]
 keys += [4, 5, 6]
 if which != "c4":  # general sincos with the range-free divisions (GRT_FAST_DIV_GEN builds)
-    names.append("rhs_general_range_free")
-    keys.append(7)
+    names += ["rhs_general_range_free", "rhs_general_uniform_a_table", "rhs_general_uniform_a_other",
+              "rhs_general_uniform_c_n2", "rhs_general_mixed"]
+    keys += [7, 8, 9, 10, 11]
 out = {"workload": which, "kernel_ms": r.stats["kernel_ms"], "wall_s": round(time.time() - t, 3),
        "accepted_steps": r.stats["accepted_steps"], "attempts_total": r.stats["attempts"],
        "md5": hashlib.md5(r.xyza.tobytes() + r.ray_class.tobytes()).hexdigest()[:12]}
 for nm, k in zip(names, keys):
-    w, ln = int(cnt[k]), int(cnt[8 + k])
+    w, ln = int(cnt[k]), int(cnt[NPATH + k])
     out[nm] = {"waves": w, "lanes": ln, "lanes_per_wave": round(ln / w, 2) if w else 0.0}
 print(json.dumps(out), flush=True)
