@@ -973,6 +973,40 @@ int grt_debug_rcp_seed(int device, uint64_t n, const double* tuples, uint8_t* fl
   return 0;
 }
 
+// Test hook (not in grt_api.h): the render's glibc wrappers as the device units compile
+// them, on n host inputs x (pow: x, y; y unused otherwise).  unit 0: geodesic.hip's
+// glibc_check_kernel, tables in LDS, blocks of threads_per_block (what grt_set_launch_config
+// admits); unit 1: output.hip's opow (fn GLIBC_FN_POW only), tables in constant memory.
+// fn, out0[n], out1[n], path[n]: glibc_check.h.  The host counterpart is
+// grt_debug_glibc_host (host/glibc_check.cpp).
+int grt_debug_glibc_device(int device, int unit, int fn, int threads_per_block, uint64_t n, const double* x,
+                           const double* y, double* out0, double* out1, uint8_t* path) {
+  if (!x || !out0 || !out1 || !path || n == 0 || n > (1ull << 26)) return fail(-EINVAL, "glibc check: 1 <= n <= 2^26");
+  if (unit < 0 || unit > 1 || fn < 0 || fn >= grt::GLIBC_FN_COUNT || (unit == 1 && fn != grt::GLIBC_FN_POW))
+    return fail(-EINVAL, "glibc check: unit 0 with fn 0..6, or unit 1 with fn 0 (pow)");
+  if (fn == grt::GLIBC_FN_POW && !y) return fail(-EINVAL, "glibc check: pow needs y");
+  if (threads_per_block != 64 && threads_per_block != 128 && threads_per_block != 192 && threads_per_block != 256)
+    return fail(-EINVAL, "glibc check: 64, 128, 192 or 256 threads per block");
+  HIP_TRY(hipSetDevice(device));
+  DevBuf b_x, b_y, b_0, b_1, b_p;
+  int rc;
+  if ((rc = b_x.alloc(n * 8)) || (rc = b_y.alloc(n * 8)) || (rc = b_0.alloc(n * 8)) || (rc = b_1.alloc(n * 8)) ||
+      (rc = b_p.alloc(n)))
+    return rc;
+  HIP_TRY(hipMemcpy(b_x.p, x, n * 8, hipMemcpyHostToDevice));
+  if (y) HIP_TRY(hipMemcpy(b_y.p, y, n * 8, hipMemcpyHostToDevice));
+  else HIP_TRY(hipMemset(b_y.p, 0, n * 8));
+  HIP_TRY(unit == 0 ? grt::launch_glibc_check(fn, threads_per_block, n, (const double*)b_x.p, (const double*)b_y.p,
+                                              (double*)b_0.p, (double*)b_1.p, (uint8_t*)b_p.p, nullptr)
+                    : grt::launch_opow_check(threads_per_block, n, (const double*)b_x.p, (const double*)b_y.p,
+                                             (double*)b_0.p, (double*)b_1.p, (uint8_t*)b_p.p, nullptr));
+  HIP_TRY(hipDeviceSynchronize());
+  HIP_TRY(hipMemcpy(out0, b_0.p, n * 8, hipMemcpyDeviceToHost));
+  HIP_TRY(hipMemcpy(out1, b_1.p, n * 8, hipMemcpyDeviceToHost));
+  HIP_TRY(hipMemcpy(path, b_p.p, n, hipMemcpyDeviceToHost));
+  return 0;
+}
+
 // Test hook (not in grt_api.h): the scene's RHS in its range-free and IEEE forms on n
 // host states (8 doubles each; KerrBL: e, l_z, q per state in consts), out[16 n], pred[n]
 // (rhs_check_kernel).

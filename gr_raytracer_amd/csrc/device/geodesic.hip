@@ -2675,6 +2675,70 @@ hipError_t launch_rcp_seed_check(uint64_t n, const double* d_tuples, uint8_t* d_
   return hipGetLastError();
 }
 
+// Device check of the glibc restatement (glibc_math.h) as this unit compiles and runs it
+// (tests/test_gpu_glibc_math.py): the tables staged in LDS as the trace kernels stage them,
+// then the wrappers the render calls -- rpow, rsin, rcos, rsincos, vdisc_density's sincos
+// line, glibc::exp_ and the region-B straight-line pair -- on x[i] (pow: x[i], y[i]).  fn,
+// out0 / out1 / path: glibc_check.h.  Blocks of 64, 128, 192 or 256 threads.
+__global__ void __launch_bounds__(256) glibc_check_kernel(int fn, uint64_t n, const double* __restrict__ x,
+                                                          const double* __restrict__ y, double* __restrict__ out0,
+                                                          double* __restrict__ out1, uint8_t* __restrict__ path) {
+  glibc::tables_to_lds();  // whole block, before the early return
+  const uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  const double xi = x[i];
+  double o0 = 0.0, o1 = 0.0, t0, t1;
+  uint32_t p = 0;
+  switch (fn) {
+    case GLIBC_FN_POW: {
+      const double yi = y[i];
+      o0 = rpow(xi, yi);
+      p = glibc::pow_fast(xi, yi, &t0) ? 1u : 0u;
+      break;
+    }
+    case GLIBC_FN_SIN:
+      o0 = rsin(xi);
+      p = glibc::sin_fast(xi, &t0) ? 1u : 0u;
+      break;
+    case GLIBC_FN_COS:
+      o0 = rcos(xi);
+      p = glibc::cos_fast(xi, &t0) ? 1u : 0u;
+      break;
+    case GLIBC_FN_SINCOS:
+      rsincos(xi, &o0, &o1);
+      p = glibc::sincos_fast(xi, &t0, &t1) ? 1u : 0u;
+      break;
+    case GLIBC_FN_VDISC_SINCOS:  // vdisc_density's line, restated (volumetric.h)
+      if (!glibc::sincos_fast_uniform(xi, &o0, &o1)) sincos(xi, &o0, &o1);
+      p = glibc::sincos_fast_uniform(xi, &t0, &t1) ? 1u : 0u;
+      break;
+    case GLIBC_FN_EXP:
+      o0 = glibc::exp_(xi);
+      p = 1u;
+      break;
+    case GLIBC_FN_SINCOS_B:
+      if (glibc::sincos_b_table_ok(xi)) {
+        glibc::sincos_b_table(xi, &o0, &o1);
+        p = 1u;
+      } else if (glibc::sincos_b_taylor_ok(xi)) {
+        glibc::sincos_b_taylor(xi, &o0, &o1);
+        p = 2u;
+      }
+      break;
+    default: break;
+  }
+  out0[i] = o0;
+  out1[i] = o1;
+  path[i] = (uint8_t)p;
+}
+
+hipError_t launch_glibc_check(int fn, int threads, uint64_t n, const double* d_x, const double* d_y, double* d_out0,
+                              double* d_out1, uint8_t* d_path, hipStream_t stream) {
+  hipLaunchKernelGGL(glibc_check_kernel, dim3((unsigned)((n + threads - 1) / threads)), dim3(threads), 0, stream, fn, n,
+                     d_x, d_y, d_out0, d_out1, d_path);
+  return hipGetLastError();
+}
+
 // Device check of the range-free RHS forms (tests/test_gpu_parity.py
 // ::test_rhs_fast_forms_match_ieee): for state i (y[8]; KerrBL: e, l_z, q in consts[3 i ..])
 // out[16 i ..] = the range-free form (rhs MODE 1), out[16 i + 8 ..] = the IEEE form (MODE 2),

@@ -18,7 +18,9 @@
 // Outside that domain (x <= 0, subnormal, inf/nan, results near under/overflow) the
 // caller falls back to OCML's pow.  The step controller's argument eps/err lies in
 // (1e-300, 1800) and y = 0.2, always on the fast path.  tests/test_glibc_math.py
-// compiles this file for the host and checks it against glibc pow, bit for bit.
+// compiles this file for the host and checks it against glibc pow, bit for bit;
+// tests/test_gpu_glibc_math.py holds the device build, as the GPU runs it, to that host
+// build (glibc_check.h).
 #pragma once
 #include <stdint.h>
 #include <string.h>

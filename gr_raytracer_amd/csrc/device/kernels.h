@@ -3,6 +3,7 @@
 #include <hip/hip_runtime.h>
 
 #include "dev_scene.h"
+#include "glibc_check.h"
 
 namespace grt {
 
@@ -56,6 +57,13 @@ hipError_t launch_arith_map(uint32_t samples, uint64_t seed, uint8_t* d_map, uin
                             hipStream_t stream);
 // test hook: the seeded reciprocals of rcp_seed.h against the compiler's division on n tuples
 hipError_t launch_rcp_seed_check(uint64_t n, const double* d_tuples, uint8_t* d_flags, hipStream_t stream);
+// test hook: the render's glibc wrappers on n inputs (glibc_check.h): unit 0, tables in LDS
+// (geodesic.hip glibc_check_kernel), `threads` per block; unit 1, opow with the tables in
+// constant memory (output.hip opow_check_kernel)
+hipError_t launch_glibc_check(int fn, int threads, uint64_t n, const double* d_x, const double* d_y, double* d_out0,
+                              double* d_out1, uint8_t* d_path, hipStream_t stream);
+hipError_t launch_opow_check(int threads, uint64_t n, const double* d_x, const double* d_y, double* d_out0,
+                             double* d_out1, uint8_t* d_path, hipStream_t stream);
 hipError_t launch_rhs_check(int geometry, const DevScene* d_scene, const double* d_states, const double* d_consts,
                             uint64_t n, double* d_out, uint8_t* d_pred, hipStream_t stream);
 #if GRT_PATH_COUNT

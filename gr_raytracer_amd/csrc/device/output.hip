@@ -121,11 +121,25 @@ __global__ void __launch_bounds__(256) tonemap_kernel(const double* __restrict__
   for (int k = 0; k < 3; ++k) rgb[3 * i + k] = to_u8(compand(fmax(c[k], 0.0)));
 }
 
+// Device check of opow as this unit compiles it, the glibc tables in constant memory
+// (tests/test_gpu_glibc_math.py; outputs as glibc_check.h's GLIBC_FN_POW)
+__global__ void __launch_bounds__(256) opow_check_kernel(uint64_t n, const double* __restrict__ x,
+                                                         const double* __restrict__ y, double* __restrict__ out0,
+                                                         double* __restrict__ out1, uint8_t* __restrict__ path) {
+  const uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  const double xi = x[i], yi = y[i];
+  double t;
+  out0[i] = opow(xi, yi);
+  out1[i] = 0.0;
+  path[i] = glibc::pow_fast(xi, yi, &t) ? 1 : 0;
+}
+
 int fail(int code, const std::string& msg) {
   grt_host::set_error(msg);
   return code;
 }
-#define OUT_TRY(expr)                                                                    \
+#define OUT_TRY(expr)                                                                   \
   do {                                                                                   \
     hipError_t _e = (expr);                                                              \
     if (_e != hipSuccess) return grt::fail(-EIO, std::string(#expr) + ": " + hipGetErrorString(_e)); \
@@ -137,6 +151,14 @@ int grid_for(uint64_t n, int cap) {
 }
 
 }  // namespace
+
+// kernels.h (this unit does not include it)
+hipError_t launch_opow_check(int threads, uint64_t n, const double* d_x, const double* d_y, double* d_out0,
+                             double* d_out1, uint8_t* d_path, hipStream_t stream) {
+  hipLaunchKernelGGL(opow_check_kernel, dim3((unsigned)((n + threads - 1) / threads)), dim3(threads), 0, stream, n, d_x,
+                     d_y, d_out0, d_out1, d_path);
+  return hipGetLastError();
+}
 }  // namespace grt
 
 extern "C" {

@@ -87,3 +87,56 @@ def test_device_exp_is_bit_identical_to_glibc(exp_checker, mode):
     out = subprocess.run([str(exp_checker), str(mode), "400000"], check=True, capture_output=True, text=True).stdout
     n, _, bad = map(int, out.strip().splitlines()[-1].split())
     assert bad == 0, (EXP_MODES[mode], out)
+
+
+# ------------------------------------------------- the host hook on the shared sets ----
+# grt_debug_glibc_host (csrc/host/glibc_check.cpp, in libgrt.so; no GPU) evaluates the same
+# glibc_math.h through the render's wrappers on tests/glibc_inputs.py's sets: the random
+# modes above restated, every branch threshold +- a few ulps, and what the fast paths
+# refuse.  tests/test_gpu_glibc_math.py holds the device to this hook bit for bit; here the
+# hook is tied to the installed libm.  Bit identity holds for glibc 2.35 on x86-64 with FMA
+# (sin / cos / exp / pow: the FMA ifunc builds; sincos: the baseline build), the libm
+# test_tables_match_the_installed_libm insists on.
+import glibc_inputs as GI  # noqa: E402
+
+
+@pytest.mark.parametrize("fn", sorted(GI.FN_NAMES), ids=lambda f: GI.FN_NAMES[f])
+def test_host_hook_is_bit_identical_to_libm_on_the_shared_sets(grt, fn):
+    """Wherever the hook takes a glibc_math.h path (path != 0) its (out0, out1) are the
+    bits of this libm's pow / sin / cos / sincos / exp (sincos for the VolumetricDisc line
+    and the region-B pair), on every render, edge, off-path and mixed set; exp_ on every
+    lane.  The sets reach both sides of every threshold, and the render sets that must be
+    all fast are."""
+    import os
+
+    import numpy as np
+
+    lib = grt._lib.lib()
+    family = GI.FAMILY[fn]
+    libc = os.confstr("CS_GNU_LIBC_VERSION")
+    shares = {}
+    for name, x, y in GI.all_sets(family):
+        assert x.size == GI.N and x.size % 64 != 0
+        got = GI.run_host(lib, fn, x, y)
+        want = GI.run_host(lib, fn | GI.FN_LIBM, x, y)
+        assert (want[2] == 0).all()
+        on = got[2] != 0
+        n_bad, rows = GI.differing(x, y, got, want, on)
+        assert n_bad == 0, (GI.FN_NAMES[fn], name, libc, n_bad, rows)
+        shares[name] = float(on.mean())
+        if fn == GI.FN_EXP:
+            assert on.all()
+        elif fn != GI.FN_SINCOS_B and name in GI.ALL_FAST[family]:
+            assert on.all(), (GI.FN_NAMES[fn], name, shares[name])
+        elif fn != GI.FN_SINCOS_B and name.startswith("offpath"):
+            assert not on.any(), (GI.FN_NAMES[fn], name, shares[name])
+    print(GI.FN_NAMES[fn], libc, "fast share per set:", shares)
+    if fn == GI.FN_POW:  # both sides of |y log x| = 2^-54 / 512 and of the table split
+        assert 0.2 < shares["edge_y_log_x"] < 0.8 and 0.3 < shares["edge_x_table"] < 1.0
+        assert shares["edge_y_limits"] == 0.0  # |y| at 2^-65 / 2^63: y log x is out of range either way
+    elif fn == GI.FN_SINCOS_B:  # both region-B forms on either side of |a| = TAYLOR_MAX
+        p = GI.run_host(lib, fn, GI.trig_sets()["edge_region_b_taylor"])[2]
+        assert (p[:GI.N // 2] == 1).sum() > 100 and (p[:GI.N // 2] == 2).sum() > 100
+        assert set(np.unique(GI.run_host(lib, fn, GI.trig_sets()["render_region_b"])[2])) == {1, 2}
+    elif family == "trig":  # the reduction limit's neighbours fall on both sides
+        assert 0.5 < shares["edge_thresholds"] < 1.0
