@@ -31,6 +31,7 @@ namespace {
 // on other threads: the knobs are atomics, and a trace reads them once, into a Knobs
 // snapshot, so that one call never sees two settings.
 std::atomic<long long> g_launch{256};  // grt_set_launch_config: blocks per CU << 16 | threads per block
+std::atomic<int> g_rkf_short{1};       // grt_debug_rkf_short: 0 = every Schwarzschild attempt with the full RKF sums, 2 = the fallback forced (tests)
 std::atomic<int> g_range_free{1};      // grt_debug_range_free: 0 = every division and sqrt in its IEEE form (tests)
 std::atomic<int> g_schedule{-1};       // grt_set_schedule: -1 auto, 0 row-major tiles, 1 probe-ordered tiles
 std::atomic<int> g_two_ended{1};       // grt_set_two_ended: probe-ordered traces take the queue from both ends
@@ -384,6 +385,10 @@ int init_device_copy(grt_scene* s, int device, DeviceCopy& dc) {
     const bool a_ok = d.geometry == GRT_GEOM_KERR_BL ? a_mod : (d.geometry != GRT_GEOM_KERR || a_mod || d.a == 0.0);
     ds.div_fast = (g_range_free.load(std::memory_order_relaxed) && std::fpclassify(d.radius) == FP_NORMAL && d.radius > 0.0 && ex > -lim && ex < lim &&
                    a_ok) ? 1 : 0;
+    // radius == 1.0, the unit of every black-hole scene of the reference: the region-B
+    // Schwarzschild quotients drop their multiplies by it (rcp_seed.h unit_radius_quotients)
+    ds.unit_radius = (d.radius == 1.0 && ds.div_fast) ? 1 : 0;
+    ds.rkf_short = g_rkf_short.load(std::memory_order_relaxed);
     // ks_fd_ok's coordinate bound: 2^ceil(log2(2 max_radius)) covers every state of a ray
     // (it stops one step beyond max_radius), within the proven 2^10 .. 2^32
     int em = 0;
@@ -1051,6 +1056,45 @@ int grt_debug_path_counts(uint64_t* out, int reset) {
 int grt_debug_range_free(int on) {
   if (on != 0 && on != 1) return fail(-EINVAL, "range-free arithmetic: 0 or 1");
   g_range_free.store(on);
+  return 0;
+}
+
+// Test hook (not in grt_api.h): 0 makes the device copies of scenes created (first rendered)
+// afterwards take every attempt of the Schwarzschild integrate kernels with the full RKF
+// sums (DevScene::rkf_short = 0), so a test can hold the short sums to them end to end;
+// 2 keeps the short attempts and makes every attempt that leaves the quick step take the
+// full form after them, which runs the fallback of a missed rkf_short_ok on ordinary rays.
+int grt_debug_rkf_short(int on) {
+  if (on < 0 || on > 2) return fail(-EINVAL, "short RKF sums: 0, 1 or 2");
+  g_rkf_short.store(on);
+  return 0;
+}
+
+// Test hook (not in grt_api.h): one RKF45 attempt per host state (8 doubles each) at step
+// h[i] in the short and the full form (rkf_check_kernel): out_short[9 n] and out_full[9 n]
+// hold yn[8] and err_sq, guard[i] whether rkf_short_ok admits the short result.
+int grt_debug_rkf_check(grt_scene* s, int device, uint64_t n, const double* states, const double* h,
+                        double* out_short, double* out_full, uint8_t* guard) {
+  if (!s || !states || !h || !out_short || !out_full || !guard || n == 0 || n > (1ull << 26))
+    return fail(-EINVAL, "rkf check: 1 <= n <= 2^26");
+  if (s->desc.geometry != GRT_GEOM_SCHWARZSCHILD) return fail(-EINVAL, "rkf check: Schwarzschild only");
+  DeviceCopy* dc;
+  int rc = ensure_device(s, device, &dc);
+  if (rc) return rc;
+  std::lock_guard<std::mutex> lk(dc->mu);
+  HIP_TRY(hipSetDevice(device));
+  DevBuf b_st, b_h, b_s, b_f, b_g;
+  if ((rc = b_st.alloc(n * 64)) || (rc = b_h.alloc(n * 8)) || (rc = b_s.alloc(n * 72)) || (rc = b_f.alloc(n * 72)) ||
+      (rc = b_g.alloc(n)))
+    return rc;
+  HIP_TRY(hipMemcpy(b_st.p, states, n * 64, hipMemcpyHostToDevice));
+  HIP_TRY(hipMemcpy(b_h.p, h, n * 8, hipMemcpyHostToDevice));
+  HIP_TRY(grt::launch_rkf_check(dc->d_scene, (const double*)b_st.p, (const double*)b_h.p, n, (double*)b_s.p,
+                                (double*)b_f.p, (uint8_t*)b_g.p, nullptr));
+  HIP_TRY(hipDeviceSynchronize());
+  HIP_TRY(hipMemcpy(out_short, b_s.p, n * 72, hipMemcpyDeviceToHost));
+  HIP_TRY(hipMemcpy(out_full, b_f.p, n * 72, hipMemcpyDeviceToHost));
+  HIP_TRY(hipMemcpy(guard, b_g.p, n, hipMemcpyDeviceToHost));
   return 0;
 }
 

@@ -96,10 +96,14 @@ struct DevScene {
   const double* bb_log_t;
   const double* bb_xyz;
   uint32_t bb_n;
-  uint32_t _pad1;
+  // (the two flags below sit in what was padding, so every other field keeps its offset)
+  int32_t unit_radius;     // radius == 1.0 and div_fast: the region-B quotients without their multiplies (rcp_seed.h)
   const double* srgb_lin;  // 256 entries
   int32_t has_vol;         // any GRT_OBJ_VOLUMETRIC_DISC: integrate records chord directions and
-  int32_t _pad2;           // the frequency data (p_t, p_phi), the shade pass raymarches
+                           // the frequency data (p_t, p_phi), the shade pass raymarches
+  int32_t rkf_short;       // Schwarzschild integrate kernels: attempts without the zero-weight k2 terms
+                           // (geodesic.hip rkf_short_ok); grt_debug_rkf_short: 0 = every attempt in the full
+                           // form, 2 = short attempts with the full-form fallback forced on the general path
   DevObject obj[8];
   uint8_t perm[8][256];    // Perlin permutation tables (noise 0.9.0 PermutationTable), per object
 };

@@ -32,6 +32,7 @@
 #endif
 #include "glibc_math.h"
 #include "rcp_seed.h"
+#include "rkf_weights.h"
 #include "kernels.h"
 
 // GRT_FUSED: this file compiled a second time, by geodesic_fused.hip, with FMA contraction
@@ -112,6 +113,12 @@ namespace seq {
 // spills land elsewhere: 1.71 GB written per frame with it, 20.9 GB without
 // (profiles/r04n_c3_pmc.json, r04o_c3_pmc.json)
 #define GRT_FAST_DIV_BL 1
+#endif
+#ifndef GRT_UNIT_RADIUS
+#define GRT_UNIT_RADIUS 1  // Schwarzschild region-B RHS: the quotients of radius == 1.0 without their multiplies (rcp_seed.h)
+#endif
+#ifndef GRT_RKF_SHORT
+#define GRT_RKF_SHORT 1  // Schwarzschild integrate kernels: attempts without the zero-weight CH2 / CT2 terms (rkf_short_ok)
 #endif
 #ifndef GRT_QUICK_STEP
 #define GRT_QUICK_STEP 1  // Schwarzschild: the far-field accepted step as one straight-line block
@@ -378,10 +385,7 @@ constexpr double B41 = 69.0 / 128.0, B42 = -243.0 / 128.0, B43 = 135.0 / 64.0;
 constexpr double B51 = -17.0 / 12.0, B52 = 27.0 / 4.0, B53 = -27.0 / 5.0, B54 = 16.0 / 15.0;
 constexpr double B61 = 65.0 / 432.0, B62 = -5.0 / 16.0, B63 = 13.0 / 16.0, B64 = 4.0 / 27.0,
                  B65 = 5.0 / 144.0;
-constexpr double CH1 = 47.0 / 450.0, CH2 = 0.0, CH3 = 12.0 / 25.0, CH4 = 32.0 / 225.0,
-                 CH5 = 1.0 / 30.0, CH6 = 6.0 / 25.0;
-constexpr double CT1 = 1.0 / 150.0, CT2 = 0.0, CT3 = -3.0 / 100.0, CT4 = 16.0 / 75.0,
-                 CT5 = 1.0 / 20.0, CT6 = -6.0 / 25.0;
+// CH1..CH6, CT1..CT6 (CH2 = CT2 = 0.0): rkf_weights.h, shared with the host check
 constexpr double BETA = 0.9;
 constexpr double INV_ORDER = 1.0 / 5.0;
 constexpr double SMALL_ERR = 1e-5;
@@ -582,9 +586,10 @@ GDEV void metric_bl(double r_s, double a, double r, double sin_t, double cos_t, 
 // [8 + k] the same in lanes.  Kerr-Schild RHS: 0 range-free form, 1 IEEE form.  Light
 // charts' RHS: 0 region-B table with range-free divisions, 1 region-B Taylor with them,
 // 2 region-B with the IEEE divisions, 3 general (branchy) sincos.  All: 4 near-field window
-// pass, 5 accepted step, 6 attempt.  What the waves of path 3 hold: 8 every lane in glibc's
-// region A (2^-27 <= |x| < 0.855469) on do_sin's table path, 9 every lane in region A
-// otherwise, 10 every lane in region C (|x| >= 2.426265) with quadrant n = 2, 11 mixed.
+// pass, 5 accepted step, 6 attempt, 7 attempt taken again in the full form (rkf_short_ok
+// missed).  What the waves of path 3 hold: 8 every lane in glibc's region A
+// (2^-27 <= |x| < 0.855469) on do_sin's table path, 9 every lane in region A otherwise,
+// 10 every lane in region C (|x| >= 2.426265) with quadrant n = 2, 11 mixed.
 constexpr int NPATH = 12;
 __shared__ unsigned long long path_lds[2 * NPATH];
 __device__ unsigned long long g_path[2 * NPATH];
@@ -609,8 +614,14 @@ GDEV void path_count(int k) {
 // div_ok (per lane): the body's divisions may drop their range steps (div_inrange) in the
 // region-B cases; body's fourth argument says so at compile time (std::true_type), so
 // each form is one basic block from the sincos through the body.
-template <bool FDIV = false, class F>
-GDEV void with_sincos(double theta, bool fast_ok, F&& body, bool div_ok = false) {
+// UNIT (Schwarzschild only): with `unit` set (DevScene::unit_radius, a scene constant in a
+// scalar register) the range-free cases hand body its unit-radius form, div_form<2>.  The
+// scalar branch is taken before the sincos, so that form too is one basic block from the
+// sincos through the body (a ballot between the two cost 1 %: DESIGN.md 3).
+template <int K>
+using div_form = std::integral_constant<int, K>;  // 0 IEEE, 1 range-free, 2 range-free with radius == 1.0
+template <bool FDIV = false, bool UNIT = false, class F>
+GDEV void with_sincos(double theta, bool fast_ok, F&& body, bool div_ok = false, bool unit = false) {
 #if GRT_SINCOS_B
   if (fast_ok) {
     double st, ct;
@@ -618,12 +629,26 @@ GDEV void with_sincos(double theta, bool fast_ok, F&& body, bool div_ok = false)
     if constexpr (FDIV) {
       if (__ballot(!(tab & div_ok)) == 0) {
         PATH_COUNT(0);
+        if constexpr (UNIT) {
+          if (unit) {
+            glibc::sincos_b_table(theta, &st, &ct);
+            body(st, ct, true, div_form<2>{});
+            return;
+          }
+        }
         glibc::sincos_b_table(theta, &st, &ct);
         body(st, ct, true, std::true_type{});
         return;
       }
       if (__ballot(!(tay & div_ok)) == 0) {
         PATH_COUNT(1);
+        if constexpr (UNIT) {
+          if (unit) {
+            glibc::sincos_b_taylor(theta, &st, &ct);
+            body(st, ct, true, div_form<2>{});
+            return;
+          }
+        }
         glibc::sincos_b_taylor(theta, &st, &ct);
         body(st, ct, true, std::true_type{});
         return;
@@ -709,17 +734,24 @@ GDEV void rhs(const DevScene& S, const RayConst& rc, const double* y, double* o)
     double r = y[1], theta = y[2];
     double v_t = y[4], v_r = y[5], v_theta = y[6], v_phi = y[7];
     auto body = [&](double st, double ct, bool fast, auto fdiv) {
-      if constexpr (decltype(fdiv)::value) {
+      if constexpr (decltype(fdiv)::value != 0) {
         // rcp_seed.h: 1 / (r r) seeded from the refined 1 / r
         auto hw_rcp = [](double v) { return __builtin_amdgcn_rcp(v); };
         const double rr = r * r;
         double Yr, Yrr, Ya, Yst;
         rcpseed::rcp_r_rr(r, rr, hw_rcp, &Yr, &Yrr);
-        double radius_over_r = rcpseed::div_by_rcp(radius, r, Yr);
-        double two_over_r = rcpseed::div_by_rcp(2.0, r, Yr);
-        double a = 1.0 - radius_over_r;
-        rcpseed::rcp_pair(a, st, hw_rcp, &Ya, &Yst);
-        double a_prime = rcpseed::div_by_rcp(radius, rr, Yrr);
+        double radius_over_r, two_over_r, a, a_prime;
+        if constexpr (decltype(fdiv)::value == 2) {
+          // radius == 1.0 (S.unit_radius): the same bits from 6 fewer instructions (rcp_seed.h)
+          rcpseed::unit_radius_quotients(r, rr, Yr, Yrr, &radius_over_r, &two_over_r, &a, &a_prime);
+          rcpseed::rcp_pair(a, st, hw_rcp, &Ya, &Yst);
+        } else {
+          radius_over_r = rcpseed::div_by_rcp(radius, r, Yr);
+          two_over_r = rcpseed::div_by_rcp(2.0, r, Yr);
+          a = 1.0 - radius_over_r;
+          rcpseed::rcp_pair(a, st, hw_rcp, &Ya, &Yst);
+          a_prime = rcpseed::div_by_rcp(radius, rr, Yrr);
+        }
         double aprime_over_a = rcpseed::div_by_rcp(a_prime, a, Ya);
         o[0] = v_t;
         o[1] = v_r;
@@ -765,16 +797,20 @@ GDEV void rhs(const DevScene& S, const RayConst& rc, const double* y, double* o)
     // refined 1 / r instead of a v_rcp_f64 of its own (rcp_seed.h: 16 cycles of the SIMD
     // against a multiply's 4, tools/valu_issue_cost.hip); the new intermediates are the seed
     // Y_r Y_r within 2^+-200 and its Newton residual 1 - (r r) Y_r Y_r within 2^-50 of 0,
-    // both inside E with the box to spare (tests/test_gpu_rcp_seed.py).
+    // both inside E with the box to spare (tests/test_gpu_rcp_seed.py).  S.unit_radius
+    // (radius == 1.0 and S.div_fast, every black-hole scene of the reference): the third
+    // form, value-identical there, so it needs no predicate of its own.
     if constexpr (MODE != 0) {
       double st, ct;
       if (glibc::sincos_b_table_ok(theta)) glibc::sincos_b_table(theta, &st, &ct);
       else glibc::sincos_b_taylor(theta, &st, &ct);
-      if constexpr (MODE == 1) body(st, ct, true, std::true_type{});
-      else body(st, ct, true, std::false_type{});
+      if constexpr (MODE == 1) {  // the form the render takes for this scene
+        if (S.unit_radius) body(st, ct, true, div_form<2>{});
+        else body(st, ct, true, std::true_type{});
+      } else body(st, ct, true, std::false_type{});
       return;
     }
-    with_sincos<GRT_FAST_DIV>(theta, S.div_share, body, schw_div_ok(S, r));
+    with_sincos<GRT_FAST_DIV, GRT_UNIT_RADIUS>(theta, S.div_share, body, schw_div_ok(S, r), S.unit_radius != 0);
   } else if constexpr (G == GRT_GEOM_EUCLIDEAN_SPHERICAL) {  // euclidean_spherical.rs:48-70
     double r = y[1], theta = y[2];
     double v_t = y[4], v_r = y[5], v_theta = y[6], v_phi = y[7];
@@ -1031,9 +1067,45 @@ GDEV double err_norm_sq(const double* e, int z = -1, double zz = 0.0) {
 //   - the others keep k1..k3 until k4 exists, then fold k1..k4 into the stage-5 input, the
 //     stage-6 partial, y_new and the error: 3 live values across RHS 5 and 2 across RHS 6,
 //     instead of 4 and 5.
-template <int G, bool UNIT_H, bool QUAD, int NKL>
+//
+// SHORT: the sums without their k2 terms.  The Fehlberg weights CH2 and CT2 are 0.0, but
+// without fast-math `X + 0.0 * k2` stays a multiply and an add (0 * k2 is -0, or NaN for a
+// non-finite k2, and X + (+-0) can turn a -0 into +0): 24 instructions per attempt that
+// change a result bit only in the cases of this lemma.
+//   Lemma (Schwarzschild chart; 0 < h <= 1, which rclamp to [H_MIN, H_MAX] gives).
+//   If every yn'[i] of the short attempt is finite and not -0 and its err_sq' is finite,
+//   then yn and err_sq of the full attempt have the same bits.  (rkf_short_ok)
+// Proof.  Both forms compute the same k1..k6 (the stage inputs never hold a CH / CT term).
+//  * Zeros, a2 = k2[i] finite: t = 0.0 * a2 is +-0, and X + t differs from X only for
+//    X = -0 with t = +0 (a2 sign-positive), giving +0.  The running sums then add the same
+//    later terms to -0 (short) and +0 (full): the first non-zero term makes them equal for
+//    good, and while every later term is a zero the short sum is -0 (all of them -0) or
+//    both are +0.  So a difference that survives to yn shows as yn'[i] = -0 against
+//    yn[i] = +0, which the premise excludes.  The same holds for e[i], where it is a
+//    difference in the sign of a zero only, and e[i] enters err_sq as e[i] * e[i] alone:
+//    err_sq needs no premise beyond the one on a2.
+//  * a2 not finite: then 0.0 * a2 is NaN and yn[i], e[i] of the full form are NaN.  In this
+//    chart o[0..3] are the stage input's velocities (rhs: o[i] = y[4 + i]), so the short
+//    outputs are non-finite as well, against the premise:
+//      i >= 4: tmp3[i] = y[i] + B31 k1[i] + B32 k2[i] is non-finite (B32 != 0, and no sum
+//        of non-finite terms is finite), hence k3[i - 4] = h tmp3[i], hence yn'[i - 4]
+//        through CH3 k3[i - 4] (CH3 != 0).
+//      i < 4: k2[i] = h v with v = y[4 + i] + B21 k1[4 + i], stage 2's input velocity, and
+//        h <= 1, so v is non-finite.  Either y[4 + i] or k1[4 + i] is non-finite, hence
+//        yn'[4 + i] = y[4 + i] + CH1 k1[4 + i] + ... (CH1 != 0); or both are finite and the
+//        sum overflowed (two values near 1e308), which can leave yn'[4 + i] finite: but then
+//        stage 2's o[5] holds a term (coefficient) v v, non-finite whatever the coefficient
+//        (inf times 0 is NaN), so k2[5] is non-finite and the case i >= 4 gives yn'[1].
+// The identities hold under FMA contraction too: fma(0.0, a2, X) follows the same zero and
+// NaN rules (geodesic_fused.hip).  Host check over every combination of the special values:
+// tests/test_rkf_zero_terms.py; device check of both forms: tests/test_gpu_rkf_short.py.
+// KerrBL is out of scope: its k2[0] and k2[3] come from formulas (l_z / sin^2 ...) and reach
+// nothing but the dropped terms (o[6] = o[7] = 0 and the RHS reads neither t nor phi), so a
+// non-finite k2[0] or k2[3] can leave the short outputs finite where the full sum is NaN.
+template <int G, bool UNIT_H, bool QUAD, int NKL, bool SHORT = false>
 GDEV double rkf_attempt_fold(const DevScene& S, const RayConst& rc, const double* y, double h, double* yn,
                              int sub) {
+  static_assert(!SHORT || G == GRT_GEOM_SCHWARZSCHILD, "short RKF sums: the lemma is the Schwarzschild chart's");
   constexpr int D = Dim<G>::D;
   double k1[8], k2[8], k3[8], k4[8], k5[8], k6[8], tmp[8], o[8], p6[8], e[8];
   int t = 0;  // LDS slot, re-derived after each stage (kl_slot_after)
@@ -1056,7 +1128,7 @@ GDEV double rkf_attempt_fold(const DevScene& S, const RayConst& rc, const double
   STAGE(k2)
 #pragma unroll
   for (int i = 0; i < D; ++i)
-    if (!rhs_reads<G>(i)) {
+    if (!rhs_reads<G>(i) && !SHORT) {
       yn[i] = yn[i] + CH2 * k2[i];
       e[i] = e[i] + CT2 * k2[i];
     }
@@ -1088,8 +1160,13 @@ GDEV double rkf_attempt_fold(const DevScene& S, const RayConst& rc, const double
       const double a1 = KV(1, i), a2 = KV(2, i), a3 = KV(3, i), a4 = k4[i];
       tmp[i] = y[i] + B51 * a1 + B52 * a2 + B53 * a3 + B54 * a4;
       p6[i] = y[i] + B61 * a1 + B62 * a2 + B63 * a3 + B64 * a4;
-      yn[i] = y[i] + CH1 * a1 + CH2 * a2 + CH3 * a3 + CH4 * a4;
-      e[i] = CT1 * a1 + CT2 * a2 + CT3 * a3 + CT4 * a4;
+      if constexpr (SHORT) {
+        yn[i] = y[i] + CH1 * a1 + CH3 * a3 + CH4 * a4;
+        e[i] = CT1 * a1 + CT3 * a3 + CT4 * a4;
+      } else {
+        yn[i] = y[i] + CH1 * a1 + CH2 * a2 + CH3 * a3 + CH4 * a4;
+        e[i] = CT1 * a1 + CT2 * a2 + CT3 * a3 + CT4 * a4;
+      }
     }
   }
   if (D < 8) { tmp[6] = 0.0; tmp[7] = 0.0; }
@@ -1119,13 +1196,16 @@ GDEV double rkf_attempt_fold(const DevScene& S, const RayConst& rc, const double
 
 // QUAD: the Kerr-Schild RHS split over a quad (rhs_ks_quad), `sub` = lane & 3.
 // NKL: stages k1..k_NKL kept in LDS (see kl_put), 0 = none.
-template <int G, bool UNIT_H = false, bool QUAD = false, int NKL = 0>
+// SHORT: without the zero-weight k2 terms (rkf_attempt_fold's lemma; the caller checks
+// rkf_short_ok and takes the attempt again in the full form where it fails).
+template <int G, bool UNIT_H = false, bool QUAD = false, int NKL = 0, bool SHORT = false>
 GDEV double rkf_attempt(const DevScene& S, const RayConst& rc, const double* y, double h,
                         double* yn, int sub = 0) {
+  static_assert(!SHORT || (GRT_RK_FOLD && G == GRT_GEOM_SCHWARZSCHILD), "short RKF sums: rkf_attempt_fold only");
   // Kerr-Schild keeps the plain form: its stages k1..k4 sit in LDS (NKL), which frees
   // more registers than the running sums (measured: 17 -> 122 spilled VGPRs with them)
   if constexpr (GRT_RK_FOLD && G != GRT_GEOM_KERR) {
-    return rkf_attempt_fold<G, UNIT_H, QUAD, NKL>(S, rc, y, h, yn, sub);
+    return rkf_attempt_fold<G, UNIT_H, QUAD, NKL, SHORT>(S, rc, y, h, yn, sub);
   }
   constexpr int D = Dim<G>::D;
   constexpr int Z = zero_k<G>();  // component with k_j = kz in every stage (zero_k)
@@ -1823,6 +1903,20 @@ GDEV bool window_far(const DevScene& S, const double* ya, const double* yb) {
   }
 }
 
+// The premise of rkf_attempt_fold's lemma for the result of a short attempt: every yn[k]
+// finite and not -0 (one v_cmp_class_f64 each: -normal, -subnormal, +0, +subnormal,
+// +normal), and err_sq finite.  Where it holds, the full attempt has the same bits.
+constexpr int FINITE_NOT_NEG_ZERO = 0x008 | 0x010 | 0x040 | 0x080 | 0x100;
+GDEV bool finite_not_neg_zero8(const double* yn) {
+  bool ok = true;
+#pragma unroll
+  for (int k = 0; k < 8; ++k) ok = ok & __builtin_amdgcn_class(yn[k], FINITE_NOT_NEG_ZERO);
+  return ok;
+}
+GDEV bool rkf_short_ok(double err_sq, const double* yn) {
+  return finite_not_neg_zero8(yn) & (bool)isfinite(err_sq);
+}
+
 // The commonest accepted step of a curvilinear chart as one predicate, evaluated without
 // branches over the lanes (integrate_kernel's quick step): step_control's first case
 // (err_sq < tiny_err_sq: accepted, next h = clamp(4h)), window_far for every object (no
@@ -1830,7 +1924,11 @@ GDEV bool window_far(const DevScene& S, const double* ya, const double* yb) {
 // celestial test decided by r (finite, outside the horizon, inside the celestial shell,
 // not the last step).  True only where the general path does exactly the quick step's
 // updates; every other case takes the general path.
-template <int G>
+// SHORT: yn and err_sq come from a short attempt (rkf_attempt_fold).  The finiteness
+// tests on yn become "finite and not -0", which with err_sq < tiny_err_sq is rkf_short_ok:
+// a wave on the quick path holds the full attempt's bits at no extra cost, and a ray with a
+// +0 component stays on it.
+template <int G, bool SHORT = false>
 GDEV bool quick_step_ok(const DevScene& S, double err_sq, const double* y, const double* yn, uint64_t i_next) {
   static_assert(G == GRT_GEOM_SCHWARZSCHILD, "quick step: Schwarzschild only");
   constexpr double N_LO = -1.5707963257948966, N_HI = 1.5707963257948966;
@@ -1847,8 +1945,12 @@ GDEV bool quick_step_ok(const DevScene& S, double err_sq, const double* y, const
     ok = ok & ((o.kind == GRT_OBJ_DISC) ? ((north | south) & ratio) : (out_a & out_b));
   }
   bool fin = true;
+  if constexpr (SHORT) {
+    fin = finite_not_neg_zero8(yn);
+  } else {
 #pragma unroll
-  for (int k = 0; k < 8; ++k) fin = fin & (bool)isfinite(yn[k]);
+    for (int k = 0; k < 8; ++k) fin = fin & (bool)isfinite(yn[k]);
+  }
   const double ar = fabs(rb), hi = ar + S.far_a;
   return ok & fin & (rb > S.horizon_r) & (hi * hi < S.cel_lo2) & (i_next != S.max_steps - 1);
 }
@@ -2407,15 +2509,24 @@ __global__ void __launch_bounds__(256, integrate_waves(G, VOL)) integrate_kernel
 
     // ---------------- one RKF45 attempt (runge_kutta.rs:148-178) ----------------
     double yn[8];
-    double err_sq;
+    double err_sq = 0.0;
     // Kerr-Schild: the RHS dwarfs the saved products, and a second copy of its attempt
     // (+80 KB of code) is not worth them
     constexpr bool UNIT_H_COPY = GRT_UNIT_H && G != GRT_GEOM_KERR;
     constexpr bool QUICK = GRT_QUICK_STEP && G == GRT_GEOM_SCHWARZSCHILD && !VOL;
-    while (true) {
+    // Schwarzschild: the attempt without its zero-weight k2 terms (rkf_attempt_fold's lemma)
+    constexpr bool SHORT = GRT_RKF_SHORT && GRT_RK_FOLD && G == GRT_GEOM_SCHWARZSCHILD;
+    // grt_debug_rkf_short: 0 every attempt in the full form; 2 the short attempt, then on the
+    // general path always the full one after it, as if a lane had missed rkf_short_ok (tests)
+    bool full = false, again = false;
+    if constexpr (SHORT) {
+      full = S.rkf_short == 0;
+      again = S.rkf_short == 2;
+    }
+    while (!full) {
       err_sq = (UNIT_H_COPY && __ballot(active && h_cur != 1.0) == 0)
-                   ? rkf_attempt<G, UNIT_H_COPY, false, NKL>(S, rc, y, h_cur, yn)
-                   : rkf_attempt<G, false, false, NKL>(S, rc, y, h_cur, yn);
+                   ? rkf_attempt<G, UNIT_H_COPY, false, NKL, SHORT>(S, rc, y, h_cur, yn)
+                   : rkf_attempt<G, false, false, NKL, SHORT>(S, rc, y, h_cur, yn);
       n_att++;
       PATH_COUNT(6);
 #if GRT_RAY_TIMES
@@ -2425,7 +2536,7 @@ __global__ void __launch_bounds__(256, integrate_waves(G, VOL)) integrate_kernel
         // every lane of the wave on the commonest accepted step (quick_step_ok): the
         // general path's updates in one straight-line block, then straight on to the next
         // attempt (no ray ended, so no lane needs a refill)
-        if (__ballot(!quick_step_ok<G>(S, err_sq, y, yn, i + 1)) == 0) {
+        if (__ballot(!quick_step_ok<G, SHORT>(S, err_sq, y, yn, i + 1)) == 0) {
           h = rclamp(h_cur * H_GROWTH, H_MIN, H_MAX);
           i++;
           n_acc++;
@@ -2438,6 +2549,25 @@ __global__ void __launch_bounds__(256, integrate_waves(G, VOL)) integrate_kernel
         }
       }
       break;
+    }
+    if constexpr (SHORT) {
+      // The quick step tested the lemma's premise itself (quick_step_ok); on this, the
+      // general path, the wave tests it here and, if a lane misses it, takes the attempt
+      // again in the full form: a ray with a persistent -0 component (v_phi = -0 in a
+      // meridional plane) or one going non-finite; lanes that met the premise get their bits
+      // again.  One copy, without UNIT_H (h * o with h == 1 is o), inlined: out of line it
+      // cost the kernel 464 B of scratch per lane for the call's saves, against 112 B.
+      if (full || again || __ballot(!rkf_short_ok(err_sq, yn)) != 0) {
+        PATH_COUNT(7);
+        err_sq = rkf_attempt<G, false, false, NKL>(S, rc, y, h_cur, yn);
+        if (full) {
+          n_att++;
+          PATH_COUNT(6);
+#if GRT_RAY_TIMES
+          ray_att++;
+#endif
+        }
+      }
     }
     double h_next;
     const int ctl = step_control(S, err_sq, h_cur, retries, h_next);
@@ -2794,6 +2924,41 @@ hipError_t launch_rhs_check(int geometry, const DevScene* d_scene, const double*
     default:
       return hipErrorInvalidValue;
   }
+  return hipGetLastError();
+}
+
+// Device check of the short RKF sums (tests/test_gpu_rkf_short.py): one Schwarzschild attempt
+// from state i (y[8]) at step h[i] in both forms, out_short[9 i ..] and out_full[9 i ..] =
+// yn[8], err_sq; guard[i] = rkf_short_ok of the short result (rkf_attempt_fold's lemma).
+__global__ void __launch_bounds__(64) rkf_check_kernel(const DevScene* __restrict__ Sp, const double* __restrict__ states,
+                                                      const double* __restrict__ hs, uint64_t n, double* out_short,
+                                                      double* out_full, uint8_t* guard) {
+  constexpr int G = GRT_GEOM_SCHWARZSCHILD;
+  const DevScene& S = *Sp;
+  glibc::tables_to_lds();  // whole block, before the early return
+  const uint64_t i = (uint64_t)blockIdx.x * 64 + threadIdx.x;
+  if (i >= n) return;
+  double y[8], ys[8], yf[8];
+#pragma unroll
+  for (int k = 0; k < 8; ++k) y[k] = states[8 * i + k];
+  const double h = hs[i];
+  const RayConst rc{};
+  const double es = rkf_attempt<G, false, false, 0, GRT_RKF_SHORT && GRT_RK_FOLD>(S, rc, y, h, ys);
+  const double ef = rkf_attempt<G>(S, rc, y, h, yf);
+#pragma unroll
+  for (int k = 0; k < 8; ++k) {
+    out_short[9 * i + k] = ys[k];
+    out_full[9 * i + k] = yf[k];
+  }
+  out_short[9 * i + 8] = es;
+  out_full[9 * i + 8] = ef;
+  guard[i] = rkf_short_ok(es, ys) ? 1 : 0;
+}
+
+hipError_t launch_rkf_check(const DevScene* d_scene, const double* d_states, const double* d_h, uint64_t n,
+                            double* d_short, double* d_full, uint8_t* d_guard, hipStream_t stream) {
+  hipLaunchKernelGGL(rkf_check_kernel, dim3((unsigned)((n + 63) / 64)), dim3(64), 0, stream, d_scene, d_states, d_h, n,
+                     d_short, d_full, d_guard);
   return hipGetLastError();
 }
 

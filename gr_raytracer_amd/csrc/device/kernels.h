@@ -66,6 +66,8 @@ hipError_t launch_opow_check(int threads, uint64_t n, const double* d_x, const d
                              double* d_out1, uint8_t* d_path, hipStream_t stream);
 hipError_t launch_rhs_check(int geometry, const DevScene* d_scene, const double* d_states, const double* d_consts,
                             uint64_t n, double* d_out, uint8_t* d_pred, hipStream_t stream);
+hipError_t launch_rkf_check(const DevScene* d_scene, const double* d_states, const double* d_h, uint64_t n,
+                            double* d_short, double* d_full, uint8_t* d_guard, hipStream_t stream);
 #if GRT_PATH_COUNT
 hipError_t path_read(unsigned long long* out, bool reset);  // 16 words
 #endif

@@ -66,5 +66,28 @@ GRT_RCP_FN void rcp_pair(double a, double s, RCP&& rcp, double* Ya, double* Ys) 
   *Ys = rcp_refine2(s, rcp(s));
 }
 
+// The first three quotients for radius == 1.0 (the unit of every black-hole scene of the
+// reference; DevScene::unit_radius), from the same Y_r and Y_rr, each with the general
+// form's bits:
+//  * q = radius / r:  div_by_rcp(1.0, r, Y_r), whose m = 1.0 Y_r is Y_r itself (x 1.0 == x
+//    for every x), so the multiply folds away and the two FMAs are the general form's.
+//  * 2 / r = 2 q:  the general form is m2 = 2 Y_r, fma(fma(-r, m2, 2), Y_r, m2).  With
+//    2^-100 < |r| < 2^100 every value of q's chain (Y_r, the residual fma(-r, Y_r, 1) within
+//    2^-52 of 0 or exactly 0, the correction, q) is normal or zero and far from overflow, so
+//    doubling each is exact and commutes with every rounding: m2 = 2 m, the residual
+//    fma(-r, 2 m, 2) = 2 fma(-r, m, 1), and the result 2 q.  One exact multiply stands for a
+//    multiply and two FMAs.
+//  * a' = radius / (r r):  div_by_rcp(1.0, rr, Y_rr), the multiply folded as for q.
+// a = 1 - q is the general form's own subtraction.  Host check against `/` with the modelled
+// estimate: tests/test_rkf_zero_terms.py (tests/native/unit_radius_check.cpp); on the device
+// the whole block against the IEEE form: rhs_check_kernel.
+GRT_RCP_FN void unit_radius_quotients(double r, double rr, double Yr, double Yrr, double* q, double* two_over_r,
+                                      double* a, double* a_prime) {
+  *q = div_by_rcp(1.0, r, Yr);
+  *two_over_r = 2.0 * *q;
+  *a = 1.0 - *q;
+  *a_prime = div_by_rcp(1.0, rr, Yrr);
+}
+
 }  // namespace rcpseed
 }  // namespace grt

@@ -3,10 +3,11 @@
 times a wave executed it (counted by its first active lane) and how many lanes did.
 Kerr-Schild RHS: 0 range-free, 1 IEEE.  Schwarzschild / KerrBL RHS: 0 region-B table
 with range-free divisions, 1 region-B Taylor with them, 2 region B with IEEE divisions,
-3 general sincos (7: of those, with the range-free divisions); what the waves of 3 hold:
+3 general sincos; what the waves of 3 hold:
 8 every lane in glibc's region A on the table path, 9 every lane in region A otherwise,
 10 every lane in region C with n = 2, 11 mixed.  All: 4 near-field window pass,
-5 accepted step, 6 attempt.
+5 accepted step, 6 attempt, 7 Schwarzschild attempt taken again with the full RKF sums
+(rkf_short_ok missed).
 usage: tools/path_count.py c2|c3|c4 (c4: row-band shard 2 of 8)"""
 import ctypes as C
 import hashlib
@@ -47,8 +48,8 @@ names = (["rhs_range_free", "rhs_ieee"] if which == "c4" else
 names += ["near_window", "accepted_general_path", "attempt"]
 keys = [0, 1] if which == "c4" else [0, 1, 2, 3]
 keys += [4, 5, 6]
-if which != "c4":  # general sincos with the range-free divisions (GRT_FAST_DIV_GEN builds)
-    names += ["rhs_general_range_free", "rhs_general_uniform_a_table", "rhs_general_uniform_a_other",
+if which != "c4":
+    names += ["rkf_full_form_recompute", "rhs_general_uniform_a_table", "rhs_general_uniform_a_other",
               "rhs_general_uniform_c_n2", "rhs_general_mixed"]
     keys += [7, 8, 9, 10, 11]
 out = {"workload": which, "kernel_ms": r.stats["kernel_ms"], "wall_s": round(time.time() - t, 3),
