@@ -143,6 +143,34 @@ class SequenceReport(C.Structure):
                 ("_pad", C.c_uint32), ("wall_ms", _d), ("trace_ms", _d), ("supersample_ms", _d)]
 
 
+class GBufferObjectShape(C.Structure):
+    _fields_ = [("kind", C.c_int32), ("temp_kind", C.c_int32), ("radius", _d), ("center", _d * 3),
+                ("inner_radius", _d), ("outer_radius", _d), ("r_isco", _d)]
+
+
+class GBufferShape(C.Structure):
+    """grt_gbuffer_shape: everything of a scene that decides hits, window errors and the recorded numbers."""
+    _fields_ = [("geometry", C.c_int32), ("n_objects", C.c_uint32), ("radius", _d), ("a", _d),
+                ("objects", GBufferObjectShape * GRT_MAX_OBJECTS)]
+
+
+class GBufferInfo(C.Structure):
+    _fields_ = [("row0", C.c_uint32), ("col0", C.c_uint32), ("rows", C.c_uint32), ("cols", C.c_uint32),
+                ("n_pixels", C.c_uint64), ("n_layers", C.c_uint64), ("device", C.c_int32), ("_pad", C.c_uint32),
+                ("shape", GBufferShape), ("camera", CameraDesc), ("max_steps", C.c_uint64), ("max_radius", _d),
+                ("step_size", _d), ("epsilon", _d), ("horizon_epsilon", _d)]
+
+
+class GBufferArrays(C.Structure):
+    """grt_gbuffer_arrays: host arrays of a g-buffer (per pixel, then per layer)."""
+    _fields_ = [("status", C.POINTER(C.c_uint8)), ("stop", C.POINTER(C.c_uint8)), ("steps", C.POINTER(C.c_uint32)),
+                ("sky_u", _pd), ("sky_v", _pd), ("sky_redshift", _pd), ("layer_start", C.POINTER(C.c_uint64)),
+                ("object", C.POINTER(C.c_uint8)), ("u", _pd), ("v", _pd), ("redshift", _pd), ("radius", _pd)]
+
+
+GBUFFER_FILE_VERSION = 1
+
+
 class Health(C.Structure):
     _fields_ = [
         ("rays", C.c_uint64), ("failed", C.c_uint64), ("null_violations", C.c_uint64), ("max_null", _d),
@@ -270,6 +298,19 @@ def lib() -> C.CDLL:
                                           C.POINTER(FrameOut), C.POINTER(C.c_uint64), C.POINTER(Stats),
                                           C.POINTER(SubsampleFailures), C.POINTER(SequenceReport)]),
         "grt_set_sequence_group": (C.c_int, [u64]),
+        "grt_gbuffer_trace": (C.c_int, [vp, C.c_int, u32, u32, u32, u32, C.POINTER(vp), C.POINTER(Stats)]),
+        "grt_gbuffer_trace_times": (C.c_int, [vp, _pd]),
+        "grt_gbuffer_info_get": (C.c_int, [vp, C.POINTER(GBufferInfo)]),
+        "grt_gbuffer_download": (C.c_int, [vp, C.POINTER(GBufferArrays)]),
+        "grt_gbuffer_upload": (C.c_int, [C.POINTER(GBufferInfo), C.POINTER(GBufferArrays), C.c_int, C.POINTER(vp)]),
+        "grt_gbuffer_shade": (C.c_int, [vp, vp, C.POINTER(C.c_float), C.POINTER(C.c_uint8), C.POINTER(C.c_uint8), _pd,
+                                        C.POINTER(C.c_float)]),
+        "grt_gbuffer_destroy": (C.c_int, [vp]),
+        "grt_gbuffer_shape_of": (None, [C.POINTER(SceneDesc), C.POINTER(GBufferShape)]),
+        "grt_gbuffer_compatible": (C.c_int, [C.POINTER(SceneDesc), C.POINTER(SceneDesc)]),
+        "grt_gbuffer_shape_compatible": (C.c_int, [C.POINTER(GBufferShape), C.POINTER(SceneDesc)]),
+        "grt_gbuffer_write_file": (C.c_int, [C.c_char_p, C.POINTER(GBufferInfo), C.POINTER(GBufferArrays)]),
+        "grt_gbuffer_read_file": (C.c_int, [C.c_char_p, C.POINTER(GBufferInfo), C.POINTER(GBufferArrays)]),
     }
     # GRT_LIB_ALLOW_MISSING=1 (tools/time_variants.py only) binds an older experimental
     # build that lacks newer entry points; by default a missing symbol is an error.
@@ -319,6 +360,9 @@ EXPORTED_SYMBOLS = [
     "grt_write_png_rgb", "grt_write_hdr_xyz", "grt_render_frame_multi", "grt_multi_release",
     "grt_set_arithmetic", "grt_get_arithmetic", "grt_set_multi_transport", "grt_get_multi_transport",
     "grt_host_scene_camera", "grt_render_sequence", "grt_set_sequence_group",
+    "grt_gbuffer_trace", "grt_gbuffer_trace_times", "grt_gbuffer_info_get", "grt_gbuffer_download", "grt_gbuffer_upload",
+    "grt_gbuffer_shade", "grt_gbuffer_destroy", "grt_gbuffer_shape_of", "grt_gbuffer_compatible",
+    "grt_gbuffer_shape_compatible", "grt_gbuffer_write_file", "grt_gbuffer_read_file",
 ]
 
 

@@ -10,6 +10,8 @@
 //     | render-sequence --camera-path P [--filename-pattern frame-%04d.png] [--first-index 0]
 //     | render-ray -r ROW -c COL [--filename rendered-ray.csv]
 //     | render-ray-at -p x,y,z -d x,y,z [--filename rendered-ray-at.csv]
+//     | gbuffer --filename a.grtg
+//     | reshade --gbuffer a.grtg [--filename out.png|out.hdr]
 //     | blackbody -t T [-r Z]
 //     | blackbody-spectrum [--min-temperature T] [--max-temperature T] [--min-redshift Z]
 //                          [--max-redshift Z] [--width N] [--height N] [-f FILE]
@@ -28,6 +30,15 @@
 // -- over one load of the scene, traced in stacked launches (grt_render_sequence); frame
 // k is what `render` writes for that line's --camera-position/--phi/--theta/--psi, to
 // --filename-pattern (and --raw-out, a pattern too) at index --first-index + k.
+// gbuffer / reshade (not in the reference): `gbuffer` traces the whole frame at 1 spp with
+// the exact kernels and writes its geometry buffer (grt_gbuffer_trace, the file of
+// grt_gbuffer_write_file); `reshade` loads one, shades it under the appearance of its own
+// --config-file (textures, temperatures, beaming, celestial sphere, hit threshold;
+// grt_gbuffer_shade) and writes the image as `render` does, tone mapping and --raw-out
+// included -- what `render` of that config writes at 1 spp, without integrating.  The scene
+// must have the buffer's shape key and --width / --height its frame; the camera flags
+// (--camera-position, --phi, --theta, --psi) and the integration flags are ignored by
+// `reshade`: the frame is the traced one.
 #include <algorithm>
 #include <charconv>
 #include <chrono>
@@ -58,6 +69,9 @@ static int usage(const char* msg) {
                "           [--filename-pattern frame-%%04d.png] [--first-index N]\n"
                "       grt [global options] --config-file FILE render-ray -r ROW -c COL [--filename F]\n"
                "       grt [global options] --config-file FILE render-ray-at -p X,Y,Z -d X,Y,Z [--filename F]\n"
+               "       grt [global options] --config-file FILE gbuffer --filename F.grtg\n"
+               "       grt [global options] --config-file FILE reshade --gbuffer F.grtg [--filename F]\n"
+               "           (reshade: --width/--height must be the buffer's frame; camera flags are ignored)\n"
                "       grt [global options] blackbody -t T [-r Z]\n"
                "       grt [global options] blackbody-spectrum [--min-temperature T] [--max-temperature T]\n"
                "           [--min-redshift Z] [--max-redshift Z] [--width N] [--height N] [-f FILE]\n",
@@ -315,6 +329,22 @@ static int write_frame(const std::string& filename, const std::string& raw_out, 
   return 0;
 }
 
+// Host arrays of a geometry buffer of n pixels and nl layers (gbuffer, reshade).
+struct GBufferHost {
+  size_t n, nl;
+  std::vector<uint8_t> status, stop, object;
+  std::vector<uint32_t> steps;
+  std::vector<uint64_t> layer_start;
+  std::vector<double> sky, layer;  // [3][n] u, v, redshift; [4][nl] u, v, redshift, radius
+  GBufferHost(size_t n_, size_t nl_)
+      : n(n_), nl(nl_), status(n_), stop(n_), object(nl_), steps(n_), layer_start(n_ + 1), sky(3 * n_), layer(4 * nl_) {}
+  grt_gbuffer_arrays arrays() {
+    return grt_gbuffer_arrays{status.data(),        stop.data(),        steps.data(),          sky.data(),
+                              sky.data() + n,       sky.data() + 2 * n, layer_start.data(),    object.data(),
+                              layer.data(),         layer.data() + nl,  layer.data() + 2 * nl, layer.data() + 3 * nl};
+  }
+};
+
 // render-sequence: a camera-path file, one camera per line `x,y,z,phi,theta,psi` (the
 // values --camera-position, --phi, --theta, --psi take); blank lines and lines starting
 // with `#` are skipped.  On error *err names the line.
@@ -387,6 +417,7 @@ int main(int argc, char** argv) {
   std::vector<int> multi_devices;  // --gpus / --devices: the multi-GPU frame
   uint32_t band_rows = 16;
   std::string camera_path, filename_pattern = "frame-%04d.png";  // render-sequence
+  std::string gbuffer_file;  // reshade
   long long first_index = 0;
   std::vector<std::string> args(argv + 1, argv + argc);
   for (size_t i = 0; i < args.size(); ++i) {
@@ -409,7 +440,7 @@ int main(int argc, char** argv) {
     };
     std::string v;
     if (action.empty() && (a == "render" || a == "render-sequence" || a == "render-ray" || a == "render-ray-at" ||
-                           a == "blackbody" || a == "blackbody-spectrum")) {
+                           a == "blackbody" || a == "blackbody-spectrum" || a == "gbuffer" || a == "reshade")) {
       action = a;
       continue;
     }
@@ -459,6 +490,7 @@ int main(int argc, char** argv) {
     if (a == "--raw-out") { raw_out = v; continue; }
     if (!action.empty()) {  // subcommand options
       if (a == "--filename" && action != "render-sequence") filename = v;
+      else if (action == "reshade" && a == "--gbuffer") gbuffer_file = v;
       else if (action == "render-sequence" && a == "--camera-path") camera_path = v;
       else if (action == "render-sequence" && a == "--filename-pattern") filename_pattern = v;
       else if (action == "render-sequence" && a == "--first-index") {
@@ -534,7 +566,8 @@ int main(int argc, char** argv) {
     else return usage(("unknown argument " + a).c_str());
   }
   if (action.empty())
-    return usage("missing subcommand (render, render-sequence, render-ray, render-ray-at, blackbody, blackbody-spectrum)");
+    return usage("missing subcommand (render, render-sequence, render-ray, render-ray-at, gbuffer, reshade, blackbody, "
+                 "blackbody-spectrum)");
   if (action == "blackbody") {  // run_blackbody (cli/blackbody.rs:7-25): no scene needed
     if (!have_temperature) return usage("blackbody needs --temperature");
     double xyz[3];
@@ -567,8 +600,12 @@ int main(int argc, char** argv) {
   if (action == "render-ray" && !(have_row && have_col)) return usage("render-ray needs --row and --col");
   if (action == "render-ray-at" && !(have_position && have_direction))
     return usage("render-ray-at needs --position and --direction");
+  if (action == "gbuffer" && filename.empty()) return usage("gbuffer needs --filename");
+  if (action == "reshade" && gbuffer_file.empty()) return usage("reshade needs --gbuffer");
+  if ((action == "gbuffer" || action == "reshade") && !multi_devices.empty())
+    return usage("gbuffer and reshade run on one GPU (--device); --gpus / --devices do not apply");
   if (filename.empty())
-    filename = action == "render" ? "render.png" : (action == "render-ray" ? "rendered-ray.csv" : "rendered-ray-at.csv");
+    filename = (action == "render" || action == "reshade") ? "render.png" : (action == "render-ray" ? "rendered-ray.csv" : "rendered-ray-at.csv");
   if (config_file.empty()) return usage("Config file is required for this action");
   std::vector<std::vector<double>> path_cams;  // render-sequence: x, y, z, phi, theta, psi per frame
   if (action == "render-sequence") {  // every usage error before the GPU is touched
@@ -580,6 +617,23 @@ int main(int argc, char** argv) {
     if (!raw_out.empty() && !expand_pattern(raw_out, first_index, &probe))
       return usage("--raw-out of render-sequence is a pattern: it needs one %d or %0Nd conversion");
     if (!load_camera_path(camera_path, path_cams, &perr)) return usage(perr.c_str());
+  }
+
+  grt_gbuffer_info gb_info;
+  if (action == "reshade") {  // the file's header and length, before the GPU is touched
+    if (config_file.empty()) return usage("Config file is required for this action");
+    if (grt_gbuffer_read_file(gbuffer_file.c_str(), &gb_info, nullptr)) {
+      std::fprintf(stderr, "Error: %s\n", grt_last_error());
+      return 1;
+    }
+    if (gb_info.row0 != 0 || gb_info.col0 != 0 || (int64_t)gb_info.rows != gb_info.camera.rows ||
+        (int64_t)gb_info.cols != gb_info.camera.cols) {
+      std::fprintf(stderr, "Error: %s holds a rectangle, not a whole frame\n", gbuffer_file.c_str());
+      return 1;
+    }
+    if ((int64_t)gb_info.cols != opts.width || (int64_t)gb_info.rows != opts.height)
+      return usage(("--width / --height must be the g-buffer's frame, " + std::to_string(gb_info.cols) + " x " +
+                    std::to_string(gb_info.rows)).c_str());
   }
 
   if (action == "render" && !multi_devices.empty() &&
@@ -642,6 +696,79 @@ int main(int argc, char** argv) {
       std::fprintf(stderr, "[grt] INFO %s\n", log.substr(p, q - p).c_str());
       p = q + 1;
     }
+  }
+  if (action == "gbuffer") {  // trace the frame once at 1 spp, keep its geometry buffer
+    grt_gbuffer* gb = nullptr;
+    grt_stats st;
+    t_phase = clk::now();
+    if (grt_gbuffer_trace(scene, device, 0, 0, (uint32_t)opts.height, (uint32_t)opts.width, &gb, &st) ||
+        grt_gbuffer_info_get(gb, &gb_info)) {
+      std::fprintf(stderr, "Error: %s\n", grt_last_error());
+      return 1;
+    }
+    ph_render = ms_since(t_phase);
+    t_phase = clk::now();
+    const size_t n = gb_info.n_pixels, nl = gb_info.n_layers;
+    GBufferHost host(n, nl);
+    const grt_gbuffer_arrays arr = host.arrays();
+    double times[2] = {0, 0};
+    (void)grt_gbuffer_trace_times(gb, times);
+    if (grt_gbuffer_download(gb, &arr) || grt_gbuffer_write_file(filename.c_str(), &gb_info, &arr)) {
+      std::fprintf(stderr, "Error: %s\n", grt_last_error());
+      return 1;
+    }
+    ph_write = ms_since(t_phase);
+    std::fprintf(stderr, "[grt] %llu rays, %llu accepted steps, %llu attempts, kernel %.1f ms; g-buffer: %llu layers, "
+                 "scan + fill %.2f ms\n", (unsigned long long)st.rays, (unsigned long long)st.accepted_steps,
+                 (unsigned long long)st.attempts, st.kernel_ms, (unsigned long long)nl, times[1]);
+    std::fprintf(stderr, "[grt] INFO saved g-buffer to %s\n", filename.c_str());
+    std::fprintf(stderr, "[grt] phases (ms): load %.1f, create %.1f, hip init %.1f, render %.1f, output %.1f, "
+                 "write %.1f, since start %.1f\n", ph_load, ph_create, ph_init, ph_render, ph_output, ph_write,
+                 ms_since(t_start));
+    elapsed();
+    grt_gbuffer_destroy(gb);
+    grt_scene_destroy(scene);
+    grt_host_scene_destroy(hs);
+    return 0;
+  }
+  if (action == "reshade") {  // the traced frame under this config's appearance
+    const size_t n = gb_info.n_pixels, nl = gb_info.n_layers;
+    GBufferHost host(n, nl);
+    const grt_gbuffer_arrays arr = host.arrays();
+    grt_gbuffer* gb = nullptr;
+    std::vector<float> x32(4 * n);
+    std::vector<uint8_t> cls(n), status(n);
+    std::vector<double> xyza(4 * n);
+    float shade_ms = 0;
+    t_phase = clk::now();
+    if (grt_gbuffer_read_file(gbuffer_file.c_str(), &gb_info, &arr) || grt_gbuffer_upload(&gb_info, &arr, device, &gb) ||
+        grt_gbuffer_shade(scene, gb, x32.data(), cls.data(), status.data(), xyza.data(), &shade_ms)) {
+      std::fprintf(stderr, "Error: %s\n", grt_last_error());
+      return 1;
+    }
+    ph_render = ms_since(t_phase);
+    const bool hdr = filename.size() >= 4 && filename.compare(filename.size() - 4, 4, ".hdr") == 0;
+    if (hdr) {
+      std::fprintf(stderr, "[grt] INFO Creating HDR image\n");
+    } else {
+      std::fprintf(stderr, "[grt] INFO Creating non-HDR image\n");
+      std::fprintf(stderr, "[grt] INFO Tone mapping method: %s\n",
+                   opts.tone_mapping == GRT_TONE_GLOBAL_LINEAR ? "GlobalLinear" : "Reinhard");
+    }
+    std::fprintf(stderr, "[grt] re-shaded %llu pixels, %llu layers from %s, kernel %.2f ms\n", (unsigned long long)n,
+                 (unsigned long long)nl, gbuffer_file.c_str(), shade_ms);
+    if (int wrc = write_frame(filename, raw_out, xyza, gb_info.cols, gb_info.rows, opts.tone_mapping, device, &ph_output,
+                              &ph_write))
+      return wrc;
+    std::fprintf(stderr, "[grt] INFO saved image to %s\n", filename.c_str());
+    std::fprintf(stderr, "[grt] phases (ms): load %.1f, create %.1f, hip init %.1f, render %.1f, output %.1f, "
+                 "write %.1f, since start %.1f\n", ph_load, ph_create, ph_init, ph_render, ph_output, ph_write,
+                 ms_since(t_start));
+    elapsed();
+    grt_gbuffer_destroy(gb);
+    grt_scene_destroy(scene);
+    grt_host_scene_destroy(hs);
+    return 0;
   }
   if (action == "render-sequence") {
     const uint32_t K = (uint32_t)path_cams.size(), w = (uint32_t)opts.width, h = (uint32_t)opts.height;

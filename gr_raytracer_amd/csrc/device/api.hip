@@ -695,8 +695,10 @@ int ray_times_reserve(uint64_t n, hipStream_t stream) {
 // Enqueue one trace over `wl` on `stream`; counters are zeroed first.
 // ct (camera sequences): `wl` is over a stack of frames, each ray takes the camera of its
 // frame from the table, and the sequence unit's exact kernels run (geodesic_seq.hip).
+// exact (the geometry buffer): the exact kernels whatever grt_set_arithmetic says.
 int enqueue_trace(grt_scene* s, DeviceCopy& dc, const grt::WorkList& wl_in, const grt::Outputs& o,
-                  unsigned long long* d_stats, hipStream_t stream, const grt::CamTable* ct = nullptr) {
+                  unsigned long long* d_stats, hipStream_t stream, const grt::CamTable* ct = nullptr,
+                  bool exact = false) {
   grt::WorkList wl = wl_in;
   const Knobs k = Knobs::now();
   if (int rc0 = stream_order(dc, stream)) return rc0;
@@ -749,7 +751,7 @@ int enqueue_trace(grt_scene* s, DeviceCopy& dc, const grt::WorkList& wl_in, cons
   if (tl.cap) HIP_TRY(hipMemsetAsync(dc.d_tail_ctl, 0, 16 * sizeof(unsigned long long), stream));
   // grt_set_arithmetic(1): the light charts' kernels built with FMA contraction
   // (geodesic_fused.hip); Kerr-Schild always runs the exact ones
-  const bool fused = k.arith == 1 && s->desc.geometry != GRT_GEOM_KERR;
+  const bool fused = k.arith == 1 && !exact && s->desc.geometry != GRT_GEOM_KERR;
   const auto launch = fused ? grt::fused::launch_trace
                             : (s->desc.geometry == GRT_GEOM_KERR_BL ? grt::kerr_bl::launch_trace : grt::launch_trace);
   // the exact KerrBL kernels are a unit of their own (geodesic_kerr_bl.hip)
@@ -1210,13 +1212,13 @@ struct HostTrace {
 // samples) and its event time to *ms; *need = hit-pool records it asked for.
 static int trace_sync(grt_scene* s, DeviceCopy& dc, const grt::WorkList& wl, const grt::Outputs& o,
                       unsigned long long acc[8], float* ms, unsigned long long* need,
-                      const grt::CamTable* ct = nullptr) {
+                      const grt::CamTable* ct = nullptr, bool exact = false) {
   hipStream_t st = nullptr;
   HIP_TRY(hipMemsetAsync(dc.d_stats, 0, 4 * sizeof(unsigned long long), st));
   HIP_TRY(hipMemsetAsync(dc.d_march, 0, 8 * sizeof(unsigned long long), st));
   HIP_TRY(hipMemsetAsync(dc.d_counter + 6, 0, sizeof(unsigned long long), st));
   HIP_TRY(hipEventRecord(dc.ev0, st));
-  if (int rc = enqueue_trace(s, dc, wl, o, dc.d_stats, st, ct)) return rc;
+  if (int rc = enqueue_trace(s, dc, wl, o, dc.d_stats, st, ct, exact)) return rc;
   HIP_TRY(hipEventRecord(dc.ev1, st));
   HIP_TRY(hipEventSynchronize(dc.ev1));
   unsigned long long h[4], m[8];
@@ -2393,6 +2395,237 @@ int grt_adaptive_floor_device(grt_scene* s, int device, void* stream, const doub
   if ((rc = stream_order(*dc, st))) return rc;
   HIP_TRY(grt::luminance_floor_device(d_y, stride, n, floor_index(n), dc->ad_mem, &bytes, d_min_lum, st));
   return stream_done(*dc, st);
+}
+
+}  // extern "C"
+
+// ---- geometry buffer (grt_api.h): trace once, re-shade many times -------------------------
+// The device-resident buffer: its arrays belong to it, not to a scene's scratch, so later
+// traces on the device leave it alone.
+struct grt_gbuffer {
+  grt_gbuffer_info info;
+  double times[2] = {0.0, 0.0};  // trace, scan + fill (ms)
+  DevBuf status, stop, steps, sky_u, sky_v, sky_z, layer_start, object, u, v, z, radius;
+  grt_gbuffer() { std::memset(&info, 0, sizeof(info)); }
+  int alloc_pixels() {
+    const uint64_t n = info.n_pixels;
+    int rc;
+    if ((rc = status.alloc(n)) || (rc = stop.alloc(n)) || (rc = steps.alloc(4 * n)) || (rc = sky_u.alloc(8 * n)) ||
+        (rc = sky_v.alloc(8 * n)) || (rc = sky_z.alloc(8 * n)) || (rc = layer_start.alloc(8 * (n + 1))))
+      return rc;
+    return 0;
+  }
+  int alloc_layers() {
+    const uint64_t l = info.n_layers;
+    int rc;
+    if ((rc = object.alloc(l)) || (rc = u.alloc(8 * l)) || (rc = v.alloc(8 * l)) || (rc = z.alloc(8 * l)) ||
+        (rc = radius.alloc(8 * l)))
+      return rc;
+    return 0;
+  }
+  grt::GBufferArrays view() const {
+    return grt::GBufferArrays{info.n_pixels,      (const uint8_t*)status.p, (const uint8_t*)stop.p,
+                              (const uint64_t*)layer_start.p, (double*)sky_u.p, (double*)sky_v.p,
+                              (double*)sky_z.p,   (uint8_t*)object.p,       (double*)u.p,
+                              (double*)v.p,       (double*)z.p,             (double*)radius.p};
+  }
+};
+
+extern "C" {
+
+int grt_gbuffer_trace(grt_scene* s, int device, uint32_t row0, uint32_t col0, uint32_t rows, uint32_t cols,
+                      grt_gbuffer** out, grt_stats* stats) {
+  if (!s || !out) return fail(-EINVAL, "null argument");
+  *out = nullptr;
+  if (rows == 0 || cols == 0) return fail(-EINVAL, "empty rectangle");
+  int rc = check_rect(s, row0, col0, rows, cols);
+  if (rc) return rc;
+  for (uint32_t k = 0; k < s->desc.n_objects; ++k)
+    if (s->desc.objects[k].kind == GRT_OBJ_VOLUMETRIC_DISC)
+      return fail(-ENOTSUP, "a VolumetricDisc's colour is raymarched: the scene has no geometry buffer");
+  const uint64_t n = (uint64_t)rows * cols;
+  if (n + 1 > (uint64_t)INT_MAX) return fail(-EOVERFLOW, "more than INT_MAX - 1 pixels");
+  DeviceCopy* dc;
+  if ((rc = ensure_device(s, device, &dc))) return rc;
+  std::lock_guard<std::mutex> lk(dc->mu);
+  HIP_TRY(hipSetDevice(device));
+  std::unique_ptr<grt_gbuffer> gb(new grt_gbuffer());
+  grt_gbuffer_info& info = gb->info;
+  info.row0 = row0;
+  info.col0 = col0;
+  info.rows = rows;
+  info.cols = cols;
+  info.n_pixels = n;
+  info.device = device;
+  grt_gbuffer_shape_of(&s->desc, &info.shape);
+  info.camera = s->desc.camera;
+  info.max_steps = s->desc.max_steps;
+  info.max_radius = s->desc.max_radius;
+  info.step_size = s->desc.step_size;
+  info.epsilon = s->desc.epsilon;
+  info.horizon_epsilon = s->desc.horizon_epsilon;
+  if ((rc = gb->alloc_pixels())) return rc;
+  // the trace's other outputs, and the scan's scratch
+  DevBuf xyza, cls, hits, counts, temp;
+  if ((rc = xyza.alloc(16 * n)) || (rc = cls.alloc(n)) || (rc = hits.alloc(4 * n)) || (rc = counts.alloc(8 * (n + 1))))
+    return rc;
+  size_t temp_bytes = 0;
+  HIP_TRY(grt::gbuffer_layer_scan(nullptr, nullptr, n, nullptr, nullptr, nullptr, &temp_bytes, nullptr));
+  if ((rc = temp.alloc(temp_bytes))) return rc;
+  const grt::WorkList wl = rect_worklist(row0, col0, rows, cols);
+  const grt::Outputs o{(float*)xyza.p,          (uint8_t*)cls.p,         (uint8_t*)gb->status.p, nullptr,
+                       (uint32_t*)gb->steps.p,  (uint8_t*)gb->stop.p,    (uint32_t*)hits.p};
+  unsigned long long acc[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+  float ms = 0;
+  // the whole rectangle again while a trace loses candidates: the workspace and pool the
+  // fill reads must be one complete trace's
+  for (int traces = 1;; ++traces) {
+    unsigned long long need = 0;
+    acc[3] = 0;
+    if ((rc = trace_sync(s, *dc, wl, o, acc, &ms, &need, nullptr, true))) return rc;
+    if (acc[3] == 0) break;
+    if (traces == 3 || dc->pool_cap >= POOL_MAX)
+      return fail(-ENOMEM, "the hit pool still overflows after " + std::to_string(traces) + " traces");
+    if ((rc = ensure_pool(*dc, need + need / 4))) return rc;
+  }
+  hipStream_t st = nullptr;
+  if ((rc = stream_order(*dc, st))) return rc;
+  HIP_TRY(hipEventRecord(dc->ev0, st));
+  HIP_TRY(grt::gbuffer_layer_scan((const uint8_t*)gb->status.p, (const uint32_t*)hits.p, n, (uint64_t*)counts.p,
+                                  (uint64_t*)gb->layer_start.p, temp.p, &temp_bytes, st));
+  uint64_t n_layers = 0;
+  HIP_TRY(hipMemcpy(&n_layers, (const uint64_t*)gb->layer_start.p + n, 8, hipMemcpyDeviceToHost));
+  info.n_layers = n_layers;
+  if ((rc = gb->alloc_layers())) return rc;
+  grt::Workspace ws;
+  if ((rc = ensure_workspace(*dc, n, &ws))) return rc;  // the carving of the trace above
+  ws.pool = dc->d_pool;
+  const auto fill = s->desc.geometry == GRT_GEOM_KERR_BL ? grt::kerr_bl::launch_gbuffer_fill : grt::launch_gbuffer_fill;
+  HIP_TRY(fill(s->desc.geometry, dc->d_scene, wl, ws, gb->view(), st));
+  HIP_TRY(hipEventRecord(dc->ev1, st));
+  HIP_TRY(hipEventSynchronize(dc->ev1));
+  float fill_ms = 0;
+  HIP_TRY(hipEventElapsedTime(&fill_ms, dc->ev0, dc->ev1));
+  if ((rc = stream_done(*dc, st))) return rc;
+  gb->times[0] = ms;
+  gb->times[1] = fill_ms;
+  if (stats) {
+    std::memset(stats, 0, sizeof(*stats));
+    stats->accepted_steps = acc[0];
+    stats->attempts = acc[1];
+    stats->rays = acc[2];
+    stats->kernel_ms = ms;
+  }
+  *out = gb.release();
+  return 0;
+}
+
+int grt_gbuffer_trace_times(const grt_gbuffer* gb, double ms[2]) {
+  if (!gb || !ms) return fail(-EINVAL, "null argument");
+  ms[0] = gb->times[0];
+  ms[1] = gb->times[1];
+  return 0;
+}
+
+int grt_gbuffer_info_get(const grt_gbuffer* gb, grt_gbuffer_info* out) {
+  if (!gb || !out) return fail(-EINVAL, "null argument");
+  *out = gb->info;
+  return 0;
+}
+
+int grt_gbuffer_download(const grt_gbuffer* gb, const grt_gbuffer_arrays* h) {
+  if (!gb || !h || !h->status || !h->stop || !h->steps || !h->sky_u || !h->sky_v || !h->sky_redshift ||
+      !h->layer_start)
+    return fail(-EINVAL, "null argument");
+  const uint64_t n = gb->info.n_pixels, l = gb->info.n_layers;
+  if (l && (!h->object || !h->u || !h->v || !h->redshift || !h->radius)) return fail(-EINVAL, "null layer array");
+  HIP_TRY(hipSetDevice(gb->info.device));
+  HIP_TRY(hipMemcpy(h->status, gb->status.p, n, hipMemcpyDeviceToHost));
+  HIP_TRY(hipMemcpy(h->stop, gb->stop.p, n, hipMemcpyDeviceToHost));
+  HIP_TRY(hipMemcpy(h->steps, gb->steps.p, 4 * n, hipMemcpyDeviceToHost));
+  HIP_TRY(hipMemcpy(h->sky_u, gb->sky_u.p, 8 * n, hipMemcpyDeviceToHost));
+  HIP_TRY(hipMemcpy(h->sky_v, gb->sky_v.p, 8 * n, hipMemcpyDeviceToHost));
+  HIP_TRY(hipMemcpy(h->sky_redshift, gb->sky_z.p, 8 * n, hipMemcpyDeviceToHost));
+  HIP_TRY(hipMemcpy(h->layer_start, gb->layer_start.p, 8 * (n + 1), hipMemcpyDeviceToHost));
+  if (l) {
+    HIP_TRY(hipMemcpy(h->object, gb->object.p, l, hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(h->u, gb->u.p, 8 * l, hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(h->v, gb->v.p, 8 * l, hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(h->redshift, gb->z.p, 8 * l, hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(h->radius, gb->radius.p, 8 * l, hipMemcpyDeviceToHost));
+  }
+  return 0;
+}
+
+int grt_gbuffer_upload(const grt_gbuffer_info* info, const grt_gbuffer_arrays* h, int device, grt_gbuffer** out) {
+  if (!out) return fail(-EINVAL, "null argument");
+  *out = nullptr;
+  // the shade kernel indexes by layer_start and object: hold them to their ranges first
+  int rc = grt_host::gbuffer_check_arrays(info, h);
+  if (rc) return rc;
+  int ndev = 0;
+  HIP_TRY(hipGetDeviceCount(&ndev));
+  if (device < 0 || device >= ndev) return fail(-ENODEV, "invalid device ordinal");
+  HIP_TRY(hipSetDevice(device));
+  std::unique_ptr<grt_gbuffer> gb(new grt_gbuffer());
+  gb->info = *info;
+  gb->info.device = device;
+  gb->info._pad = 0;
+  const uint64_t n = info->n_pixels, l = info->n_layers;
+  if ((rc = gb->alloc_pixels()) || (rc = gb->alloc_layers())) return rc;
+  HIP_TRY(hipMemcpy(gb->status.p, h->status, n, hipMemcpyHostToDevice));
+  HIP_TRY(hipMemcpy(gb->stop.p, h->stop, n, hipMemcpyHostToDevice));
+  HIP_TRY(hipMemcpy(gb->steps.p, h->steps, 4 * n, hipMemcpyHostToDevice));
+  HIP_TRY(hipMemcpy(gb->sky_u.p, h->sky_u, 8 * n, hipMemcpyHostToDevice));
+  HIP_TRY(hipMemcpy(gb->sky_v.p, h->sky_v, 8 * n, hipMemcpyHostToDevice));
+  HIP_TRY(hipMemcpy(gb->sky_z.p, h->sky_redshift, 8 * n, hipMemcpyHostToDevice));
+  HIP_TRY(hipMemcpy(gb->layer_start.p, h->layer_start, 8 * (n + 1), hipMemcpyHostToDevice));
+  if (l) {
+    HIP_TRY(hipMemcpy(gb->object.p, h->object, l, hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(gb->u.p, h->u, 8 * l, hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(gb->v.p, h->v, 8 * l, hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(gb->z.p, h->redshift, 8 * l, hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(gb->radius.p, h->radius, 8 * l, hipMemcpyHostToDevice));
+  }
+  *out = gb.release();
+  return 0;
+}
+
+int grt_gbuffer_shade(grt_scene* s, const grt_gbuffer* gb, float* xyza_out, uint8_t* class_out, uint8_t* status_out,
+                      double* xyza64_out, float* kernel_ms) {
+  if (!s || !gb || !xyza_out || !class_out || !status_out) return fail(-EINVAL, "null argument");
+  int rc = grt_gbuffer_shape_compatible(&gb->info.shape, &s->desc);
+  if (rc) return rc;
+  const int device = gb->info.device;
+  DeviceCopy* dc;
+  if ((rc = ensure_device(s, device, &dc))) return rc;
+  std::lock_guard<std::mutex> lk(dc->mu);
+  HIP_TRY(hipSetDevice(device));
+  const uint64_t n = gb->info.n_pixels;
+  DevBuf xyza, cls, status, x64;
+  if ((rc = xyza.alloc(16 * n)) || (rc = cls.alloc(n)) || (rc = status.alloc(n))) return rc;
+  if (xyza64_out && (rc = x64.alloc(32 * n))) return rc;
+  const grt::Outputs o{(float*)xyza.p, (uint8_t*)cls.p, (uint8_t*)status.p, (double*)x64.p, nullptr, nullptr, nullptr};
+  hipStream_t st = nullptr;
+  HIP_TRY(hipEventRecord(dc->ev0, st));
+  HIP_TRY(grt::launch_gbuffer_shade(dc->d_scene, gb->view(), o, st));
+  HIP_TRY(hipEventRecord(dc->ev1, st));
+  HIP_TRY(hipEventSynchronize(dc->ev1));
+  float t = 0;
+  HIP_TRY(hipEventElapsedTime(&t, dc->ev0, dc->ev1));
+  if (kernel_ms) *kernel_ms = t;
+  HIP_TRY(hipMemcpy(xyza_out, xyza.p, 16 * n, hipMemcpyDeviceToHost));
+  HIP_TRY(hipMemcpy(class_out, cls.p, n, hipMemcpyDeviceToHost));
+  HIP_TRY(hipMemcpy(status_out, status.p, n, hipMemcpyDeviceToHost));
+  if (xyza64_out) HIP_TRY(hipMemcpy(xyza64_out, x64.p, 32 * n, hipMemcpyDeviceToHost));
+  return 0;
+}
+
+int grt_gbuffer_destroy(grt_gbuffer* gb) {
+  if (!gb) return 0;
+  (void)hipSetDevice(gb->info.device);
+  delete gb;
+  return 0;
 }
 
 }  // extern "C"

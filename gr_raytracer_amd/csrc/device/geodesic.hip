@@ -3403,9 +3403,12 @@ hipError_t launch_probe(int geometry, const DevScene* d_scene, const WorkList& w
 // A VolumetricDisc candidate gets its energy and temperature (and their errors) here;
 // its colour is the raymarch of march_kernel (volumetric_disc.rs:580-601), so *col is
 // left untouched.  color = false: errors only (the job-gathering pass).
+// geo (nullable, the geometry buffer's fill): the appearance-independent numbers the colour
+// is a function of -- texture_color's (u, v, redshift) and compute_temperature's radius
+// (+0.0 for a sphere, whose temperature is a constant of the object).
 template <int G>
 GDEV int shade_record(const DevScene& S, const RayConst& rc, const DevObject& o, const double* p,
-                      const double* pt, XYZA* col, bool color = true) {
+                      const double* pt, XYZA* col, bool color = true, double* geo = nullptr) {
   double u_tex = 0.0, v_tex = 0.0, wx, wy, wz;
   if (o.kind == GRT_OBJ_VOLUMETRIC_DISC) {  // world hit point (its uv is not used for colour)
     wx = pt[0];
@@ -3472,6 +3475,12 @@ GDEV int shade_record(const DevScene& S, const RayConst& rc, const DevObject& o,
   double sig0 = signature0<G>();
   double redshift = (sig0 * rc.obs) / (sig0 * em);  // redshift.rs:36-38
   double temperature;
+  if (geo) {
+    geo[0] = u_tex;
+    geo[1] = v_tex;
+    geo[2] = redshift;
+    geo[3] = 0.0;
+  }
   if (o.kind != GRT_OBJ_SPHERE) {  // disc.rs:112-120, volumetric_disc.rs:614-622
     double rad;  // get_radial_coordinate of the Cartesian intersection point
     if constexpr (G == GRT_GEOM_KERR || G == GRT_GEOM_KERR_BL) {
@@ -3479,6 +3488,7 @@ GDEV int shade_record(const DevScene& S, const RayConst& rc, const DevObject& o,
     } else {
       rad = sqrt(wx * wx + wy * wy + wz * wz);
     }
+    if (geo) geo[3] = rad;
     int e = compute_temperature(o, rad, &temperature);
     if (e != GRT_OK) return e;
   } else {
@@ -3590,6 +3600,35 @@ GDEV uint32_t march_slots(const DevScene& S, const WorkList& wl, const Workspace
   return mask;
 }
 
+// The celestial sphere's texture arguments of a ray that ended on it (scene.rs:184-195):
+// get_as_spherical of the final position (point.rs:172-188) as (1 - u, v), and the redshift
+// against a static emitter there.
+template <int G>
+GDEV void celestial_args(const DevScene& S, const RayConst& rc, const double* y, double* u_tex, double* v_tex,
+                         double* redshift) {
+  double th, ph;
+  double st = 0.0, ct = 0.0;
+  if constexpr (G == GRT_GEOM_SCHWARZSCHILD || G == GRT_GEOM_KERR_BL || G == GRT_GEOM_EUCLIDEAN_SPHERICAL) {
+    th = rem_euclid(y[2], PI);
+    ph = rem_euclid(y[3] + PI, TWO_PI) - PI;
+    if constexpr (G != GRT_GEOM_KERR_BL) st = rsin(y[2]);  // inner_product: sin only
+    else rsincos(y[2], &st, &ct);
+  } else {
+    double rr;
+    cart_to_sph(y[1], y[2], y[3], &rr, &th, &ph);
+  }
+  double u = (PI + ph) / TWO_PI;
+  double v = th / PI;
+  double vel[4], p[4];
+  stationary_velocity<G>(S, y, vel);
+  momentum<G>(S, rc, y, p);
+  double em = inner<G>(S, y, st, ct, vel, p);
+  double sig0 = signature0<G>();
+  *redshift = (sig0 * rc.obs) / (sig0 * em);
+  *u_tex = 1.0 - u;
+  *v_tex = v;
+}
+
 // Scene::color_of_ray's window pass, terminal colour and composite (scene.rs:141-219),
 // one lane per ray, over the candidates the integrate kernel recorded.
 //   MODE 0: scenes without volumetric objects.
@@ -3690,26 +3729,9 @@ __global__ void __launch_bounds__(256) shade_kernel(const DevScene* __restrict__
   if (stop == GRT_STOP_HORIZON || stop == GRT_STOP_CLOSED_ORBIT) {
     result = blend(result, XYZA{0.0, 0.0, 0.0, 1.0});
   } else if (stop == GRT_STOP_CELESTIAL) {
-    double th, ph;  // get_as_spherical (point.rs:172-188)
-    double st = 0.0, ct = 0.0;
-    if constexpr (G == GRT_GEOM_SCHWARZSCHILD || G == GRT_GEOM_KERR_BL || G == GRT_GEOM_EUCLIDEAN_SPHERICAL) {
-      th = rem_euclid(y[2], PI);
-      ph = rem_euclid(y[3] + PI, TWO_PI) - PI;
-      if constexpr (G != GRT_GEOM_KERR_BL) st = rsin(y[2]);  // inner_product: sin only
-      else rsincos(y[2], &st, &ct);
-    } else {
-      double rr;
-      cart_to_sph(y[1], y[2], y[3], &rr, &th, &ph);
-    }
-    double u = (PI + ph) / TWO_PI;
-    double v = th / PI;
-    double vel[4], p[4];
-    stationary_velocity<G>(S, y, vel);
-    momentum<G>(S, rc, y, p);
-    double em = inner<G>(S, y, st, ct, vel, p);
-    double sig0 = signature0<G>();
-    double redshift = (sig0 * rc.obs) / (sig0 * em);
-    result = blend(result, texture_color(S, S.celestial, 1.0 - u, v, redshift, S.celestial_temperature));
+    double u_tex, v_tex, redshift;
+    celestial_args<G>(S, rc, y, &u_tex, &v_tex, &redshift);
+    result = blend(result, texture_color(S, S.celestial, u_tex, v_tex, redshift, S.celestial_temperature));
     cls = GRT_CLASS_ESCAPED;
   }
   // back to front: the pool's hits (the farthest windows), then the first ones
@@ -3725,6 +3747,154 @@ __global__ void __launch_bounds__(256) shade_kernel(const DevScene* __restrict__
   }
   write_out(out, idx, result, cls, status, stop, nh + n_pool_hits);
 }
+
+#if GRT_MAIN_TU || GRT_KERR_BL_TU  // the geometry buffer: the exact units only
+// ============================================================ geometry buffer =====
+// After a 1-spp trace of a rectangle whose outputs (status, stop) are gb's: the numbers
+// shade_kernel<G, 0> reduces each ray to before any texture or temperature is applied --
+// per window-nearest hit (a "layer", front to back) its object and shade_record's (u, v,
+// redshift, radius), at layer_start[idx] + k; per ray that ended on the celestial sphere
+// celestial_args' (1 - u, v, redshift).  The same record walk as shade_kernel; one lane per
+// ray.  A ray whose status is not 0 has no layers (layer_start is the scan of the trace's
+// own hit counts, zeroed for those rays).
+template <int G>
+__global__ void __launch_bounds__(256) gbuffer_fill_kernel(const DevScene* __restrict__ Sp, WorkList wl, Workspace ws,
+                                                           GBufferArrays gb) {
+  const DevScene& S = *Sp;
+  glibc::tables_to_lds();  // whole block, before the early return
+  const uint64_t idx = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (idx >= gb.n) return;
+  double sky_u = 0.0, sky_v = 0.0, sky_z = 0.0;
+  if (gb.status[idx] == GRT_OK) {
+    RayConst rc;
+    double y[8];
+    const RayMeta mt = fin_get<G>(ws, idx, y, rc);
+    if constexpr (G != GRT_GEOM_KERR_BL) rc.obs = observer_energy<G>(S, wl, idx);
+    bool lost;
+    const uint32_t nr = rec_count(ws, idx, mt.nrec, &lost);
+    uint64_t at = gb.layer_start[idx];
+    const uint64_t end = gb.layer_start[idx + 1];
+    uint32_t pos = HIT_NIL;
+    for (uint32_t j = 0; j < nr; ++j) {
+      const RecRef r = rec_at(ws, idx, j, &pos);
+      const uint32_t win = rec_win(ws, r);
+      double p[4], pt[3], geo[4];
+      const uint32_t oi = rec_read(ws, r, p, pt);
+      XYZA col;
+      if (shade_record<G>(S, rc, S.obj[oi], p, pt, &col, false, geo) != GRT_OK) break;  // status would not be 0
+      const bool last_in_window = (j + 1 == nr) || (rec_next_win(ws, idx, j, r) != win);
+      if (last_in_window && at < end) {
+        gb.object[at] = (uint8_t)oi;
+        gb.u[at] = geo[0];
+        gb.v[at] = geo[1];
+        gb.redshift[at] = geo[2];
+        gb.radius[at] = geo[3];
+        ++at;
+      }
+    }
+    if (mt.stop == GRT_STOP_CELESTIAL) celestial_args<G>(S, rc, y, &sky_u, &sky_v, &sky_z);
+  }
+  gb.sky_u[idx] = sky_u;
+  gb.sky_v[idx] = sky_v;
+  gb.sky_redshift[idx] = sky_z;
+}
+
+template <int G>
+static hipError_t gbuffer_fill_g(const DevScene* d_scene, const WorkList& wl, const Workspace& ws,
+                                 const GBufferArrays& gb, hipStream_t stream) {
+  hipLaunchKernelGGL((gbuffer_fill_kernel<G>), dim3((unsigned)((gb.n + 255) / 256)), dim3(256), 0, stream, d_scene, wl,
+                     ws, gb);
+  return hipGetLastError();
+}
+
+hipError_t launch_gbuffer_fill(int geometry, const DevScene* d_scene, const WorkList& wl, const Workspace& ws,
+                               const GBufferArrays& gb, hipStream_t stream) {
+  if (gb.n == 0) return hipSuccess;
+  switch (geometry) {
+#if GRT_MAIN_TU
+    case GRT_GEOM_EUCLIDEAN: return gbuffer_fill_g<GRT_GEOM_EUCLIDEAN>(d_scene, wl, ws, gb, stream);
+    case GRT_GEOM_SCHWARZSCHILD: return gbuffer_fill_g<GRT_GEOM_SCHWARZSCHILD>(d_scene, wl, ws, gb, stream);
+    case GRT_GEOM_KERR: return gbuffer_fill_g<GRT_GEOM_KERR>(d_scene, wl, ws, gb, stream);
+    case GRT_GEOM_EUCLIDEAN_SPHERICAL:
+      return gbuffer_fill_g<GRT_GEOM_EUCLIDEAN_SPHERICAL>(d_scene, wl, ws, gb, stream);
+#else
+    case GRT_GEOM_KERR_BL: return gbuffer_fill_g<GRT_GEOM_KERR_BL>(d_scene, wl, ws, gb, stream);
+#endif
+    default: return hipErrorInvalidValue;
+  }
+}
+#endif  // GRT_MAIN_TU || GRT_KERR_BL_TU
+
+#if GRT_MAIN_TU
+// Deferred shade: shade_kernel's window colours, terminal colour and composite from a
+// geometry buffer and the appearance scene S (textures, LUTs, temperatures, the celestial
+// sphere, the hit threshold) -- no geometry, one lane per pixel.  The operations and their
+// order are shade_kernel's, so the pixel has its bits.  Two passes over a pixel's layers:
+// front to back for the opacity, back to front for the blend (each layer's colour is
+// evaluated in both; a pixel may have any number of layers).
+GDEV int gbuffer_layer_color(const DevScene& S, const GBufferArrays& gb, uint64_t k, XYZA* col) {
+  const DevObject& o = S.obj[gb.object[k]];
+  double temperature;
+  if (o.kind != GRT_OBJ_SPHERE) {
+    int e = compute_temperature(o, gb.radius[k], &temperature);
+    if (e != GRT_OK) return e;
+  } else {
+    temperature = o.temperature;
+  }
+  *col = texture_color(S, o.tex, gb.u[k], gb.v[k], gb.redshift[k], temperature);
+  return GRT_OK;
+}
+
+__global__ void __launch_bounds__(256) gbuffer_shade_kernel(const DevScene* __restrict__ Sp, GBufferArrays gb,
+                                                            Outputs out) {
+  const DevScene& S = *Sp;
+  glibc::tables_to_lds();  // whole block, before the early return
+  const uint64_t idx = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (idx >= gb.n) return;
+  const int status = gb.status[idx];
+  const int stop = gb.stop[idx];
+  const XYZA fail{0.0, 0.0, 0.0, 1.0};
+  if (status != GRT_OK) {
+    write_out(out, idx, fail, GRT_CLASS_ESCAPED, status, stop, 0u);
+    return;
+  }
+  const uint64_t l0 = gb.layer_start[idx], l1 = gb.layer_start[idx + 1];
+  double opacity = 0.0;
+  for (uint64_t k = l0; k < l1; ++k) {
+    XYZA col;
+    int e = gbuffer_layer_color(S, gb, k, &col);
+    if (e != GRT_OK) {  // a temperature error the traced scene did not have: the window error's pixel
+      write_out(out, idx, fail, GRT_CLASS_ESCAPED, e, stop, (uint32_t)(k - l0));
+      return;
+    }
+    double alpha = rclamp(col.a, 0.0, 1.0);
+    opacity = alpha + opacity * (1.0 - alpha);
+  }
+  XYZA result{0.0, 0.0, 0.0, 1.0};
+  int cls = GRT_CLASS_CAPTURED;
+  if (stop == GRT_STOP_HORIZON || stop == GRT_STOP_CLOSED_ORBIT) {
+    result = blend(result, XYZA{0.0, 0.0, 0.0, 1.0});
+  } else if (stop == GRT_STOP_CELESTIAL) {
+    result = blend(result, texture_color(S, S.celestial, gb.sky_u[idx], gb.sky_v[idx], gb.sky_redshift[idx],
+                                         S.celestial_temperature));
+    cls = GRT_CLASS_ESCAPED;
+  }
+  for (uint64_t k = l1; k > l0; --k) {
+    XYZA col{0.0, 0.0, 0.0, 0.0};
+    (void)gbuffer_layer_color(S, gb, k - 1, &col);
+    result = blend(result, col);
+  }
+  if (opacity >= S.hit_threshold) cls = GRT_CLASS_HIT;
+  write_out(out, idx, result, cls, status, stop, (uint32_t)(l1 - l0));
+}
+
+hipError_t launch_gbuffer_shade(const DevScene* d_scene, const GBufferArrays& gb, const Outputs& out,
+                                hipStream_t stream) {
+  if (gb.n == 0) return hipSuccess;
+  hipLaunchKernelGGL(gbuffer_shade_kernel, dim3((unsigned)((gb.n + 255) / 256)), dim3(256), 0, stream, d_scene, gb, out);
+  return hipGetLastError();
+}
+#endif  // GRT_MAIN_TU
 
 // ------------------------------------------------------------------ launch -------
 // Plain scenes: integrate [-> tail] -> shade.  Volumetric scenes: integrate [-> tail] ->

@@ -115,6 +115,37 @@ hipError_t launch_impact_keys(const DevScene* d_scene, const WorkList& wl, uint3
 }  // namespace seq
 hipError_t launch_trajectories(int geometry, const DevScene* d_scene, const TrajectoryList& tl, hipStream_t stream);
 
+// The geometry buffer of a traced rectangle (grt_gbuffer_*), device arrays, structure of
+// arrays.  Per pixel, in output-slot order: the trace's status and stop reason, the
+// celestial sphere's texture arguments, and layer_start (n + 1 entries, the exclusive
+// prefix sum of the layer counts).  Per layer (a window-nearest hit), pixel-major and front
+// to back: the object and texture_color's / compute_temperature's arguments.
+struct GBufferArrays {
+  uint64_t n;
+  const uint8_t* status;
+  const uint8_t* stop;
+  const uint64_t* layer_start;
+  double *sky_u, *sky_v, *sky_redshift;
+  uint8_t* object;
+  double *u, *v, *redshift, *radius;
+};
+// Layer counts (the trace's `hits`, 0 where status != 0; counts[n] = 0) and their exclusive
+// prefix sum over n + 1 entries, so layer_start[n] is the total (gbuffer.hip; n < INT_MAX).
+// Call with d_temp == NULL for *temp_bytes.
+hipError_t gbuffer_layer_scan(const uint8_t* d_status, const uint32_t* d_hits, uint64_t n, uint64_t* d_counts,
+                              uint64_t* d_layer_start, void* d_temp, size_t* temp_bytes, hipStream_t stream);
+// Fill `gb` from the workspace and hit pool a 1-spp rectangle trace of `wl` left behind
+// (gbuffer_fill_kernel: geodesic.hip for every chart but KerrBL, whose exact unit has its own).
+hipError_t launch_gbuffer_fill(int geometry, const DevScene* d_scene, const WorkList& wl, const Workspace& ws,
+                               const GBufferArrays& gb, hipStream_t stream);
+namespace kerr_bl {
+hipError_t launch_gbuffer_fill(int geometry, const DevScene* d_scene, const WorkList& wl, const Workspace& ws,
+                               const GBufferArrays& gb, hipStream_t stream);
+}
+// Deferred shade of `gb` under the appearance scene (gbuffer_shade_kernel, geodesic.hip).
+hipError_t launch_gbuffer_shade(const DevScene* d_scene, const GBufferArrays& gb, const Outputs& out,
+                                hipStream_t stream);
+
 // Invariant monitors of the n = rows x cols rays of a rectangle (health_kernel):
 // d_out n x 5 doubles, d_status n bytes.
 hipError_t launch_health(int geometry, const DevScene* d_scene, const WorkList& wl, uint64_t n, double* d_out,

@@ -1,0 +1,218 @@
+// gbuffer.cpp — host side of the geometry buffer (grt_api.h, grt_gbuffer_*): the shape key
+// of a scene, its comparison, the consistency checks of a buffer's arrays, and the file.
+// No device code: api.hip owns the device-resident buffer.
+#include <cerrno>
+#include <cstdio>
+#include <cstring>
+#include <string>
+
+#include "host_internal.h"
+
+namespace {
+
+int fail(int code, const std::string& msg) {
+  grt_host::set_error(msg);
+  return code;
+}
+
+const char MAGIC[8] = {'G', 'R', 'T', 'G', 'B', 'U', 'F', '\0'};
+constexpr uint64_t HEADER_BYTES = 16 + sizeof(grt_gbuffer_info);
+// no frame comes near these; they keep the size arithmetic below far from overflow
+constexpr uint64_t MAX_PIXELS = (1ull << 31) - 2;
+constexpr uint64_t MAX_LAYERS = 1ull << 40;
+
+bool same(double a, double b) { return std::memcmp(&a, &b, sizeof(double)) == 0; }
+
+// bytes of the arrays after the header
+uint64_t payload_bytes(uint64_t n, uint64_t l) { return 8 * (n + 1) + 24 * n + 32 * l + 4 * n + 2 * n + l; }
+
+struct File {
+  FILE* f = nullptr;
+  ~File() {
+    if (f) std::fclose(f);
+  }
+};
+
+}  // namespace
+
+namespace grt_host {
+
+int gbuffer_check_info(const grt_gbuffer_info* info) {
+  if (!info) return fail(-EINVAL, "g-buffer: null info");
+  if (info->rows == 0 || info->cols == 0) return fail(-EINVAL, "g-buffer: empty rectangle");
+  if (info->n_pixels != (uint64_t)info->rows * info->cols)
+    return fail(-EINVAL, "g-buffer: n_pixels is not rows * cols");
+  if (info->n_pixels > MAX_PIXELS) return fail(-EINVAL, "g-buffer: too many pixels");
+  if (info->n_layers > MAX_LAYERS) return fail(-EINVAL, "g-buffer: too many layers");
+  if (info->shape.n_objects > GRT_MAX_OBJECTS) return fail(-EINVAL, "g-buffer: more than GRT_MAX_OBJECTS objects");
+  return 0;
+}
+
+int gbuffer_check_arrays(const grt_gbuffer_info* info, const grt_gbuffer_arrays* a) {
+  if (int rc = gbuffer_check_info(info)) return rc;
+  if (!a || !a->status || !a->stop || !a->steps || !a->sky_u || !a->sky_v || !a->sky_redshift || !a->layer_start)
+    return fail(-EINVAL, "g-buffer: null array");
+  if (info->n_layers && (!a->object || !a->u || !a->v || !a->redshift || !a->radius))
+    return fail(-EINVAL, "g-buffer: null layer array");
+  const uint64_t n = info->n_pixels;
+  if (a->layer_start[0] != 0) return fail(-EINVAL, "g-buffer: layer_start does not begin at 0");
+  for (uint64_t i = 0; i < n; ++i)
+    if (a->layer_start[i + 1] < a->layer_start[i])
+      return fail(-EINVAL, "g-buffer: layer_start decreases at pixel " + std::to_string(i));
+  if (a->layer_start[n] != info->n_layers) return fail(-EINVAL, "g-buffer: layer_start does not end at n_layers");
+  for (uint64_t k = 0; k < info->n_layers; ++k)
+    if (a->object[k] >= info->shape.n_objects)
+      return fail(-EINVAL, "g-buffer: layer " + std::to_string(k) + " names object " + std::to_string(a->object[k]) +
+                               " of " + std::to_string(info->shape.n_objects));
+  return 0;
+}
+
+}  // namespace grt_host
+
+extern "C" {
+
+void grt_gbuffer_shape_of(const grt_scene_desc* d, grt_gbuffer_shape* out) {
+  std::memset(out, 0, sizeof(*out));
+  out->geometry = d->geometry;
+  out->n_objects = std::min<uint32_t>(d->n_objects, GRT_MAX_OBJECTS);
+  out->radius = d->radius;
+  out->a = d->a;
+  for (uint32_t k = 0; k < out->n_objects; ++k) {
+    const grt_object_desc& o = d->objects[k];
+    grt_gbuffer_object_shape& s = out->objects[k];
+    s.kind = o.kind;
+    s.temp_kind = o.temp_kind;
+    s.radius = o.radius;
+    for (int q = 0; q < 3; ++q) s.center[q] = o.center[q];
+    s.inner_radius = o.inner_radius;
+    s.outer_radius = o.outer_radius;
+    s.r_isco = o.r_isco;
+  }
+}
+
+int grt_gbuffer_shape_compatible(const grt_gbuffer_shape* t, const grt_scene_desc* appearance) {
+  if (!t || !appearance) return fail(-EINVAL, "null argument");
+  if (appearance->n_objects > GRT_MAX_OBJECTS) return fail(-EINVAL, "too many objects");
+  grt_gbuffer_shape b;
+  grt_gbuffer_shape_of(appearance, &b);
+  auto differs = [](const std::string& field) {
+    return fail(-EINVAL, "g-buffer: the appearance scene differs from the traced one in " + field);
+  };
+  if (t->geometry != b.geometry) return differs("geometry");
+  if (!same(t->radius, b.radius)) return differs("radius");
+  if (!same(t->a, b.a)) return differs("a");
+  if (t->n_objects != b.n_objects) return differs("n_objects");
+  for (uint32_t k = 0; k < b.n_objects; ++k) {
+    const grt_gbuffer_object_shape &x = t->objects[k], &y = b.objects[k];
+    const std::string o = "objects[" + std::to_string(k) + "].";
+    if (x.kind != y.kind) return differs(o + "kind");
+    if (x.temp_kind != y.temp_kind) return differs(o + "temp_kind");
+    if (!same(x.radius, y.radius)) return differs(o + "radius");
+    for (int q = 0; q < 3; ++q)
+      if (!same(x.center[q], y.center[q])) return differs(o + "center");
+    if (!same(x.inner_radius, y.inner_radius)) return differs(o + "inner_radius");
+    if (!same(x.outer_radius, y.outer_radius)) return differs(o + "outer_radius");
+    if (!same(x.r_isco, y.r_isco)) return differs(o + "r_isco");
+  }
+  return 0;
+}
+
+int grt_gbuffer_compatible(const grt_scene_desc* traced, const grt_scene_desc* appearance) {
+  if (!traced || !appearance) return fail(-EINVAL, "null argument");
+  if (traced->n_objects > GRT_MAX_OBJECTS) return fail(-EINVAL, "too many objects");
+  grt_gbuffer_shape a;
+  grt_gbuffer_shape_of(traced, &a);
+  return grt_gbuffer_shape_compatible(&a, appearance);
+}
+
+int grt_gbuffer_write_file(const char* path, const grt_gbuffer_info* info, const grt_gbuffer_arrays* a) {
+  if (!path) return fail(-EINVAL, "null path");
+  if (int rc = grt_host::gbuffer_check_arrays(info, a)) return rc;
+  File file;
+  file.f = std::fopen(path, "wb");
+  if (!file.f) return fail(-EIO, std::string("cannot create ") + path);
+  const uint64_t n = info->n_pixels, l = info->n_layers;
+  const uint32_t head[2] = {GRT_GBUFFER_FILE_VERSION, (uint32_t)sizeof(grt_gbuffer_info)};
+  bool ok = true;
+  auto put = [&](const void* p, uint64_t bytes) {
+    if (ok && bytes) ok = std::fwrite(p, 1, bytes, file.f) == bytes;
+  };
+  put(MAGIC, 8);
+  put(head, 8);
+  put(info, sizeof(*info));
+  put(a->layer_start, 8 * (n + 1));
+  put(a->sky_u, 8 * n);
+  put(a->sky_v, 8 * n);
+  put(a->sky_redshift, 8 * n);
+  put(a->u, 8 * l);
+  put(a->v, 8 * l);
+  put(a->redshift, 8 * l);
+  put(a->radius, 8 * l);
+  put(a->steps, 4 * n);
+  put(a->status, n);
+  put(a->stop, n);
+  put(a->object, l);
+  FILE* f = file.f;
+  file.f = nullptr;
+  if (std::fclose(f) != 0) ok = false;
+  if (!ok) return fail(-EIO, std::string("cannot write ") + path);
+  return 0;
+}
+
+int grt_gbuffer_read_file(const char* path, grt_gbuffer_info* info, const grt_gbuffer_arrays* a) {
+  if (!path || !info) return fail(-EINVAL, "null argument");
+  File file;
+  file.f = std::fopen(path, "rb");
+  if (!file.f) return fail(-EIO, std::string("cannot open ") + path);
+  const std::string name = std::string(path) + ": ";
+  if (std::fseek(file.f, 0, SEEK_END) != 0) return fail(-EIO, name + "cannot seek");
+  const long end = std::ftell(file.f);
+  if (end < 0 || std::fseek(file.f, 0, SEEK_SET) != 0) return fail(-EIO, name + "cannot seek");
+  const uint64_t length = (uint64_t)end;
+  if (length < HEADER_BYTES) return fail(-EINVAL, name + "too short for a g-buffer header");
+  char magic[8];
+  uint32_t head[2];
+  grt_gbuffer_info in;
+  if (std::fread(magic, 1, 8, file.f) != 8 || std::fread(head, 1, 8, file.f) != 8)
+    return fail(-EIO, name + "cannot read the header");
+  if (std::memcmp(magic, MAGIC, 8) != 0) return fail(-EINVAL, name + "not a g-buffer file (magic)");
+  if (head[0] != GRT_GBUFFER_FILE_VERSION)
+    return fail(-EINVAL, name + "g-buffer file version " + std::to_string(head[0]) + ", this library reads " +
+                             std::to_string(GRT_GBUFFER_FILE_VERSION));
+  if (head[1] != sizeof(grt_gbuffer_info)) return fail(-EINVAL, name + "info block of another size");
+  if (std::fread(&in, 1, sizeof(in), file.f) != sizeof(in)) return fail(-EIO, name + "cannot read the info block");
+  if (int rc = grt_host::gbuffer_check_info(&in)) return rc;
+  const uint64_t n = in.n_pixels, l = in.n_layers;
+  if (length != HEADER_BYTES + payload_bytes(n, l))
+    return fail(-EINVAL, name + "file length " + std::to_string(length) + " disagrees with its sizes (" +
+                             std::to_string(HEADER_BYTES + payload_bytes(n, l)) + " expected)");
+  if (!a) {  // size query
+    *info = in;
+    return 0;
+  }
+  if (!a->status || !a->stop || !a->steps || !a->sky_u || !a->sky_v || !a->sky_redshift || !a->layer_start ||
+      (l && (!a->object || !a->u || !a->v || !a->redshift || !a->radius)))
+    return fail(-EINVAL, "g-buffer: null array");
+  bool ok = true;
+  auto get = [&](void* p, uint64_t bytes) {
+    if (ok && bytes) ok = std::fread(p, 1, bytes, file.f) == bytes;
+  };
+  get(a->layer_start, 8 * (n + 1));
+  get(a->sky_u, 8 * n);
+  get(a->sky_v, 8 * n);
+  get(a->sky_redshift, 8 * n);
+  get(a->u, 8 * l);
+  get(a->v, 8 * l);
+  get(a->redshift, 8 * l);
+  get(a->radius, 8 * l);
+  get(a->steps, 4 * n);
+  get(a->status, n);
+  get(a->stop, n);
+  get(a->object, l);
+  if (!ok) return fail(-EIO, name + "cannot read the arrays");
+  if (int rc = grt_host::gbuffer_check_arrays(&in, a)) return rc;
+  *info = in;
+  return 0;
+}
+
+}  // extern "C"

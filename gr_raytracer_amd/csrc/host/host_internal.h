@@ -40,6 +40,10 @@ int supersample_shard(grt_scene* s, int device, void* stream, const grt_row_shar
                       double min_lum, const double* d_min_lum, const double* d_frame_ya, const uint8_t* d_frame_class,
                       const double* sampling_mask_xyza, double* d_xyza64, const uint32_t* d_local_steps,
                       uint64_t* d_n_supersampled, uint64_t* d_stats, grt_subsample_failures* failures);
+// Consistency of a g-buffer's sizes, and of its arrays with them (gbuffer.cpp): what a file
+// reader or an upload must hold before a kernel indexes by them.  -EINVAL with a message.
+int gbuffer_check_info(const grt_gbuffer_info* info);
+int gbuffer_check_arrays(const grt_gbuffer_info* info, const grt_gbuffer_arrays* arrays);
 double rclamp_pub(double v, double lo, double hi);
 int camera_build(int geometry, double radius, double a, const double position[4], const double velocity[4],
                  double alpha, int64_t rows, int64_t cols, double phi, double theta, double psi,

@@ -223,6 +223,18 @@ class Scene:
         res.stats = _stats_dict(st)
         return res
 
+    def trace_gbuffer(self, row0: int = 0, col0: int = 0, rows: Optional[int] = None, cols: Optional[int] = None,
+                      device: int = 0) -> "GBuffer":
+        """1-spp exact trace of a rectangle that keeps its geometry buffer (grt_gbuffer_trace):
+        shade it again under any scene with the same shape key without integrating."""
+        rows = self.rows - row0 if rows is None else rows
+        cols = self.cols - col0 if cols is None else cols
+        h = C.c_void_p()
+        st = L.Stats()
+        L.check(L.lib().grt_gbuffer_trace(self._s, device, row0, col0, rows, cols, C.byref(h), C.byref(st)),
+                "grt_gbuffer_trace")
+        return GBuffer(h, _stats_dict(st))
+
     def render_shard(self, band_rows: int, shard: int, n_shards: int, device: int = 0,
                      aux: bool = True) -> RenderResult:
         """The local rows of one cyclic row-band shard (grt_render_shard), full width."""
@@ -500,6 +512,126 @@ class Scene:
         k = min(n.value, capacity)
         return {"handed_off": n.value, "drained_s": tl[0], "handoff_s": tl[1], "tail_end_s": tl[2],
                 "slot": slot[:k], "step": step[:k]}
+
+
+_GB_PIXEL = (("status", np.uint8), ("stop", np.uint8), ("steps", np.uint32), ("sky_u", np.float64),
+             ("sky_v", np.float64), ("sky_redshift", np.float64))
+_GB_LAYER = (("object", np.uint8), ("u", np.float64), ("v", np.float64), ("redshift", np.float64),
+             ("radius", np.float64))
+_GB_CTYPE = {np.uint8: C.c_uint8, np.uint32: C.c_uint32, np.uint64: C.c_uint64, np.float64: C.c_double}
+
+
+def _gbuffer_host_arrays(info: L.GBufferInfo, arrays: Optional[dict] = None):
+    """(dict of numpy arrays sized by `info`, the grt_gbuffer_arrays over them); `arrays`
+    given: those, made contiguous and of the right type, after a length check."""
+    n, nl = int(info.n_pixels), int(info.n_layers)
+    spec = [(k, t, n) for k, t in _GB_PIXEL] + [("layer_start", np.uint64, n + 1)] + [(k, t, nl) for k, t in _GB_LAYER]
+    out = {}
+    for k, t, m in spec:
+        if arrays is None:
+            out[k] = np.zeros(m, t)
+        else:
+            out[k] = np.ascontiguousarray(arrays[k], t)
+            if out[k].shape != (m,):
+                raise L.GrtError(f"g-buffer array {k}: shape {out[k].shape}, expected ({m},)")
+    c = L.GBufferArrays(**{k: L.ptr(out[k], _GB_CTYPE[t]) for k, t, _ in spec})
+    return out, c
+
+
+class GBuffer:
+    """Device-resident geometry buffer of a traced rectangle (grt_gbuffer): per pixel the
+    trace's status, stop reason, steps and the celestial sphere's texture arguments; per
+    layer (a window's nearest hit, front to back) the object and its texture / temperature
+    arguments.  `shade(scene)` is bit-identical to `scene.render_pixels` of the rectangle
+    for any scene with the traced shape key, camera and integration parameters."""
+
+    def __init__(self, handle, stats: Optional[dict] = None):
+        self._h = handle
+        self.stats = stats or {}
+
+    @property
+    def info(self) -> L.GBufferInfo:
+        out = L.GBufferInfo()
+        L.check(L.lib().grt_gbuffer_info_get(self._h, C.byref(out)), "grt_gbuffer_info_get")
+        return out
+
+    @property
+    def trace_times(self) -> dict:
+        """Event times of the trace that filled the buffer, ms (zeros for a loaded one)."""
+        ms = (C.c_double * 2)()
+        L.check(L.lib().grt_gbuffer_trace_times(self._h, ms), "grt_gbuffer_trace_times")
+        return {"trace_ms": float(ms[0]), "fill_ms": float(ms[1])}
+
+    def arrays(self) -> dict:
+        """The buffer's arrays, downloaded: numpy arrays by the names of grt_gbuffer_arrays."""
+        out, c = _gbuffer_host_arrays(self.info)
+        L.check(L.lib().grt_gbuffer_download(self._h, C.byref(c)), "grt_gbuffer_download")
+        return out
+
+    def shade(self, scene: "Scene", device: Optional[int] = None) -> RenderResult:
+        """Shade under `scene`'s appearance on the buffer's device.  `device`, when given,
+        must be that device (a scene has a copy per GPU; the buffer lives on one)."""
+        info = self.info
+        if device is not None and device != info.device:
+            raise L.GrtError(f"grt_gbuffer_shade failed (-22): the g-buffer is on device {info.device}, not {device}")
+        n = int(info.n_pixels)
+        res = RenderResult(np.zeros((n, 4), np.float32), np.zeros(n, np.uint8), np.zeros(n, np.uint8),
+                           xyza64=np.zeros((n, 4), np.float64))
+        ms = C.c_float()
+        L.check(L.lib().grt_gbuffer_shade(scene._s, self._h, L.ptr(res.xyza, C.c_float), L.ptr(res.ray_class, C.c_uint8),
+                                          L.ptr(res.status, C.c_uint8), L.dptr(res.xyza64), C.byref(ms)),
+                "grt_gbuffer_shade")
+        res.stats = {"kernel_ms": float(ms.value)}
+        return res
+
+    def save(self, path) -> None:
+        info = self.info
+        out, c = _gbuffer_host_arrays(info)
+        L.check(L.lib().grt_gbuffer_download(self._h, C.byref(c)), "grt_gbuffer_download")
+        L.check(L.lib().grt_gbuffer_write_file(str(path).encode(), C.byref(info), C.byref(c)), "grt_gbuffer_write_file")
+
+    @staticmethod
+    def read_file(path):
+        """(info, dict of arrays) of a g-buffer file, on the host (no GPU needed)."""
+        info = L.GBufferInfo()
+        L.check(L.lib().grt_gbuffer_read_file(str(path).encode(), C.byref(info), None), "grt_gbuffer_read_file")
+        out, c = _gbuffer_host_arrays(info)
+        L.check(L.lib().grt_gbuffer_read_file(str(path).encode(), C.byref(info), C.byref(c)), "grt_gbuffer_read_file")
+        return info, out
+
+    @staticmethod
+    def write_file(path, info: L.GBufferInfo, arrays: dict) -> None:
+        held, c = _gbuffer_host_arrays(info, arrays)  # `held`: the converted arrays `c` points into
+        L.check(L.lib().grt_gbuffer_write_file(str(path).encode(), C.byref(info), C.byref(c)), "grt_gbuffer_write_file")
+
+    @classmethod
+    def from_arrays(cls, info: L.GBufferInfo, arrays: dict, device: int = 0) -> "GBuffer":
+        held, c = _gbuffer_host_arrays(info, arrays)  # `held`: the converted arrays `c` points into
+        h = C.c_void_p()
+        L.check(L.lib().grt_gbuffer_upload(C.byref(info), C.byref(c), device, C.byref(h)), "grt_gbuffer_upload")
+        return cls(h)
+
+    @classmethod
+    def load(cls, path, device: int = 0) -> "GBuffer":
+        info, arrays = cls.read_file(path)
+        return cls.from_arrays(info, arrays, device)
+
+    def close(self) -> None:
+        if self._h:
+            L.lib().grt_gbuffer_destroy(self._h)
+            self._h = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+def gbuffer_compatible(traced: L.SceneDesc, appearance: L.SceneDesc) -> None:
+    """Raise GrtError (-EINVAL, naming the first differing field) unless a g-buffer traced
+    under `traced` can be shaded under `appearance`: equal shape keys (grt_gbuffer_compatible)."""
+    L.check(L.lib().grt_gbuffer_compatible(C.byref(traced), C.byref(appearance)), "grt_gbuffer_compatible")
 
 
 def set_two_ended(on: bool = True) -> None:

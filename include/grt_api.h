@@ -577,6 +577,140 @@ int grt_render_sequence(grt_scene* scene, int device, uint32_t n_cameras,
  * Scheduling only.  Process-wide; read once per call. */
 int grt_set_sequence_group(uint64_t rays);
 
+/* ---- geometry buffer: trace a rectangle once, re-shade it many times --------------------
+ * The integration depends on the geometry, the camera and the shapes of the objects; the
+ * textures, beaming exponents, temperatures, the celestial sphere, the hit-opacity threshold
+ * and the tone mapping play no part in it.  A geometry buffer ("g-buffer", the lensing map
+ * of the rectangle) keeps what the shade pass reduces each 1-spp ray to before any of those
+ * is applied (Scene::color_of_ray, scene.rs:141-219), so the rectangle can be shaded again
+ * under any scene with the same shape key without integrating a geodesic.  Re-shading is
+ * bit-identical to grt_render_pixels of the appearance scene with the traced camera and
+ * integration parameters.  The reference has no counterpart.
+ *
+ * Per pixel, row-major over the rectangle:
+ *   status, stop, steps   what grt_render_pixels returns (window errors included);
+ *   sky_u, sky_v, sky_redshift
+ *                         the arguments of the celestial sphere's texture lookup (1 - u, v,
+ *                         redshift) for a pixel with status 0 that ended on it (stop =
+ *                         GRT_STOP_CELESTIAL), +0.0 for every other pixel;
+ *   layer_start           n_pixels + 1 entries: the exclusive prefix sum of the pixels' layer
+ *                         counts; layer_start[n_pixels] = n_layers.
+ * Per layer, pixel-major, front to back.  A layer is one window's nearest intersection,
+ * the hits that enter the blend (grt_aux_out.hits counts them); a pixel whose status is not
+ * 0 has none, and there is no cap per pixel:
+ *   object                index into grt_scene_desc.objects;
+ *   u, v, redshift        the arguments of the object's texture lookup;
+ *   radius                the argument of the disc's temperature model; +0.0 for a sphere.
+ *
+ * The shape key is everything of a scene that decides hits, window errors and the recorded
+ * numbers: geometry, radius, a, n_objects and per object kind, temp_kind, radius, center,
+ * inner_radius, outer_radius, r_isco.  Textures, temperatures, LUT contents, the celestial
+ * sphere, the hit threshold, the camera and the integration parameters are free to differ
+ * between the traced scene and an appearance scene.
+ *
+ * The g-buffer trace always runs the exact arithmetic, whatever grt_set_arithmetic says (as
+ * Kerr-Schild and the camera sequences do): re-shading reproduces the exact frame.  Scenes
+ * with a GRT_OBJ_VOLUMETRIC_DISC are refused (-ENOTSUP): its colour is raymarched, not a
+ * function of (u, v, redshift, temperature).  One rectangle at 1 spp on one device: no
+ * offset lists, supersampling, row shards, sequences or multi-GPU frames.
+ * A grt_gbuffer is not synchronised: one host thread at a time per buffer. */
+typedef struct grt_gbuffer grt_gbuffer; /* device-resident, owns its arrays */
+
+typedef struct grt_gbuffer_object_shape {
+  int32_t kind;       /* grt_object_kind */
+  int32_t temp_kind;  /* grt_temperature_kind */
+  double radius;
+  double center[3];
+  double inner_radius, outer_radius;
+  double r_isco;
+} grt_gbuffer_object_shape;
+
+typedef struct grt_gbuffer_shape {
+  int32_t geometry;   /* grt_geometry_kind */
+  uint32_t n_objects;
+  double radius, a;
+  grt_gbuffer_object_shape objects[GRT_MAX_OBJECTS]; /* entries past n_objects are zero */
+} grt_gbuffer_shape;
+
+typedef struct grt_gbuffer_info {
+  uint32_t row0, col0, rows, cols; /* the rectangle in the traced camera's frame */
+  uint64_t n_pixels;               /* rows * cols */
+  uint64_t n_layers;
+  int32_t device;                  /* where the buffer lives (the traced device in a file) */
+  uint32_t _pad;
+  grt_gbuffer_shape shape;
+  /* provenance only, never compared: what was traced */
+  grt_camera_desc camera;
+  uint64_t max_steps;
+  double max_radius, step_size, epsilon, horizon_epsilon;
+} grt_gbuffer_info;
+
+/* Host arrays of a g-buffer (caller-allocated; sizes from grt_gbuffer_info). */
+typedef struct grt_gbuffer_arrays {
+  uint8_t* status;       /* n_pixels */
+  uint8_t* stop;         /* n_pixels */
+  uint32_t* steps;       /* n_pixels */
+  double* sky_u;         /* n_pixels */
+  double* sky_v;         /* n_pixels */
+  double* sky_redshift;  /* n_pixels */
+  uint64_t* layer_start; /* n_pixels + 1 */
+  uint8_t* object;       /* n_layers */
+  double* u;             /* n_layers */
+  double* v;             /* n_layers */
+  double* redshift;      /* n_layers */
+  double* radius;        /* n_layers */
+} grt_gbuffer_arrays;
+
+/* Trace rows x cols at (row0, col0) at 1 spp on `device` with the exact kernels and keep
+ * its g-buffer.  A trace that lost hit candidates grows the hit pool to its need and traces
+ * the rectangle again (at most 3 traces, else -ENOMEM): a g-buffer never holds a pixel
+ * flagged GRT_FLAG_HIT_OVERFLOW.  stats (nullable): the counters of the traces,
+ * kernel_ms their event time.  -EINVAL for an empty rectangle or one outside the frame,
+ * -ENOTSUP for a scene with a VolumetricDisc. */
+int grt_gbuffer_trace(grt_scene* scene, int device, uint32_t row0, uint32_t col0, uint32_t rows,
+                      uint32_t cols, grt_gbuffer** out, grt_stats* stats);
+/* Event times of grt_gbuffer_trace in ms: [0] the trace(s), [1] the layer scan and the
+ * fill.  Zeros for an uploaded buffer. */
+int grt_gbuffer_trace_times(const grt_gbuffer* gb, double ms[2]);
+int grt_gbuffer_info_get(const grt_gbuffer* gb, grt_gbuffer_info* out);
+/* Copy the arrays to the host (every pointer non-null, sized by grt_gbuffer_info_get). */
+int grt_gbuffer_download(const grt_gbuffer* gb, const grt_gbuffer_arrays* host);
+/* A device buffer on `device` from host arrays (info->device is ignored).  The arrays are
+ * checked like a file's (grt_gbuffer_read_file): -EINVAL, never a crash. */
+int grt_gbuffer_upload(const grt_gbuffer_info* info, const grt_gbuffer_arrays* host, int device,
+                       grt_gbuffer** out);
+/* Shade the buffer under `appearance` on the buffer's device (the scene's copy there,
+ * created on demand): host outputs per pixel as grt_render_pixels writes them; xyza64
+ * (4 f64 per pixel) and kernel_ms (event time of the shade kernel) are nullable.  -EINVAL
+ * when the scene's shape key differs from the buffer's (grt_last_error names the field). */
+int grt_gbuffer_shade(grt_scene* appearance, const grt_gbuffer* gb, float* xyza_out, uint8_t* class_out,
+                      uint8_t* status_out, double* xyza64_out, float* kernel_ms);
+int grt_gbuffer_destroy(grt_gbuffer* gb);
+
+/* Host only.  The shape key of a scene descriptor. */
+void grt_gbuffer_shape_of(const grt_scene_desc* desc, grt_gbuffer_shape* out);
+/* 0 when a g-buffer traced under `traced` can be shaded under `appearance` (equal shape
+ * keys), else -EINVAL and grt_last_error() names the first differing field. */
+int grt_gbuffer_compatible(const grt_scene_desc* traced, const grt_scene_desc* appearance);
+/* The same for a buffer's recorded key. */
+int grt_gbuffer_shape_compatible(const grt_gbuffer_shape* traced, const grt_scene_desc* appearance);
+
+/* Host only: the g-buffer file.  Little-endian, no padding:
+ *   8 B   magic "GRTGBUF\0"
+ *   u32   version (GRT_GBUFFER_FILE_VERSION), u32 sizeof(grt_gbuffer_info)
+ *   grt_gbuffer_info
+ *   layer_start u64[n_pixels + 1]; sky_u, sky_v, sky_redshift f64[n_pixels];
+ *   u, v, redshift, radius f64[n_layers]; steps u32[n_pixels];
+ *   status, stop u8[n_pixels]; object u8[n_layers]
+ * Reading takes two calls: with arrays == NULL it checks the header and the file length
+ * and fills *info (the sizes); with the arrays allocated it fills them.  It rejects, with
+ * -EINVAL and a message, a wrong magic or version, sizes that disagree with each other or
+ * with the file length, a layer_start that is not non-decreasing from 0 to n_layers, and an
+ * object index >= shape.n_objects; -EIO when the file cannot be read or written. */
+#define GRT_GBUFFER_FILE_VERSION 1
+int grt_gbuffer_write_file(const char* path, const grt_gbuffer_info* info, const grt_gbuffer_arrays* arrays);
+int grt_gbuffer_read_file(const char* path, grt_gbuffer_info* info, const grt_gbuffer_arrays* arrays);
+
 /* The device hit pool that keeps the window candidates past a ray's GRT_MAX_HITS slots
  * (no reference counterpart: the reference's per-ray Vec grows, scene.rs:139-152).
  * A trace starts with the pool at its minimum (grt_set_hit_pool_min, 2^20 records) or
