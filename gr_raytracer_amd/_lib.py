@@ -169,6 +169,19 @@ class GBufferArrays(C.Structure):
 
 
 GBUFFER_FILE_VERSION = 1
+GBUFFER_SUB_FILE_VERSION = 1
+
+
+class GBufferSubInfo(C.Structure):
+    """grt_gbuffer_sub_info: the sizes of a g-buffer's sub-sample set (samples_per_axis 0: none)."""
+    _fields_ = [("samples_per_axis", C.c_uint32), ("_pad", C.c_uint32), ("n_sub_pixels", C.c_uint64),
+                ("n_sub_rays", C.c_uint64), ("n_sub_layers", C.c_uint64)]
+
+
+class GBufferSectionReport(C.Structure):
+    """grt_gbuffer_section_report: what one adaptive re-shade selected, held and traced."""
+    _fields_ = [("n_selected", C.c_uint64), ("n_held", C.c_uint64), ("n_traced", C.c_uint64),
+                ("n_missing", C.c_uint64), ("shade_ms", _d), ("trace_ms", _d), ("top_up", Stats)]
 
 
 class Health(C.Structure):
@@ -311,6 +324,18 @@ def lib() -> C.CDLL:
         "grt_gbuffer_shape_compatible": (C.c_int, [C.POINTER(GBufferShape), C.POINTER(SceneDesc)]),
         "grt_gbuffer_write_file": (C.c_int, [C.c_char_p, C.POINTER(GBufferInfo), C.POINTER(GBufferArrays)]),
         "grt_gbuffer_read_file": (C.c_int, [C.c_char_p, C.POINTER(GBufferInfo), C.POINTER(GBufferArrays)]),
+        "grt_gbuffer_supersample": (C.c_int, [vp, vp, u32, u64, C.POINTER(C.c_uint32), C.POINTER(Stats)]),
+        "grt_gbuffer_shade_section": (C.c_int, [vp, vp, C.POINTER(AdaptiveConfig), _pd, vp, _pd, C.POINTER(C.c_uint8),
+                                                C.POINTER(C.c_uint8), C.POINTER(C.c_uint64),
+                                                C.POINTER(SubsampleFailures), C.POINTER(GBufferSectionReport)]),
+        "grt_gbuffer_sub_info_get": (C.c_int, [vp, C.POINTER(GBufferSubInfo)]),
+        "grt_gbuffer_sub_download": (C.c_int, [vp, C.POINTER(C.c_uint32), C.POINTER(GBufferArrays)]),
+        "grt_gbuffer_sub_upload": (C.c_int, [vp, C.POINTER(GBufferSubInfo), C.POINTER(C.c_uint32),
+                                             C.POINTER(GBufferArrays)]),
+        "grt_gbuffer_sub_write_file": (C.c_int, [C.c_char_p, C.POINTER(GBufferInfo), C.POINTER(GBufferSubInfo),
+                                                 C.POINTER(C.c_uint32), C.POINTER(GBufferArrays)]),
+        "grt_gbuffer_sub_read_file": (C.c_int, [C.c_char_p, C.POINTER(GBufferInfo), C.POINTER(GBufferSubInfo),
+                                                C.POINTER(C.c_uint32), C.POINTER(GBufferArrays)]),
     }
     # GRT_LIB_ALLOW_MISSING=1 (tools/time_variants.py only) binds an older experimental
     # build that lacks newer entry points; by default a missing symbol is an error.
@@ -363,6 +388,8 @@ EXPORTED_SYMBOLS = [
     "grt_gbuffer_trace", "grt_gbuffer_trace_times", "grt_gbuffer_info_get", "grt_gbuffer_download", "grt_gbuffer_upload",
     "grt_gbuffer_shade", "grt_gbuffer_destroy", "grt_gbuffer_shape_of", "grt_gbuffer_compatible",
     "grt_gbuffer_shape_compatible", "grt_gbuffer_write_file", "grt_gbuffer_read_file",
+    "grt_gbuffer_supersample", "grt_gbuffer_shade_section", "grt_gbuffer_sub_info_get", "grt_gbuffer_sub_download",
+    "grt_gbuffer_sub_upload", "grt_gbuffer_sub_write_file", "grt_gbuffer_sub_read_file",
 ]
 
 

@@ -10,8 +10,8 @@
 //     | render-sequence --camera-path P [--filename-pattern frame-%04d.png] [--first-index 0]
 //     | render-ray -r ROW -c COL [--filename rendered-ray.csv]
 //     | render-ray-at -p x,y,z -d x,y,z [--filename rendered-ray-at.csv]
-//     | gbuffer --filename a.grtg
-//     | reshade --gbuffer a.grtg [--filename out.png|out.hdr]
+//     | gbuffer --filename a.grtg [--adaptive]
+//     | reshade --gbuffer a.grtg [--filename out.png|out.hdr] [--adaptive]
 //     | blackbody -t T [-r Z]
 //     | blackbody-spectrum [--min-temperature T] [--max-temperature T] [--min-redshift Z]
 //                          [--max-redshift Z] [--width N] [--height N] [-f FILE]
@@ -38,7 +38,12 @@
 // included -- what `render` of that config writes at 1 spp, without integrating.  The scene
 // must have the buffer's shape key and --width / --height its frame; the camera flags
 // (--camera-position, --phi, --theta, --psi) and the integration flags are ignored by
-// `reshade`: the frame is the traced one.
+// `reshade`: the frame is the traced one.  With --adaptive on both, the config's
+// [adaptive_sampling] applies: `gbuffer` also traces the sub-rays of the pixels its own
+// adaptive frame supersamples and writes them to the sidecar `<file>.sub`; `reshade` loads
+// the sidecar if there is one, traces the sub-rays of the pixels its appearance selects
+// and the set does not hold (with the file's camera and integration parameters), writes
+// what `render` of its config writes, and rewrites the sidecar when the set grew.
 #include <algorithm>
 #include <charconv>
 #include <chrono>
@@ -69,8 +74,9 @@ static int usage(const char* msg) {
                "           [--filename-pattern frame-%%04d.png] [--first-index N]\n"
                "       grt [global options] --config-file FILE render-ray -r ROW -c COL [--filename F]\n"
                "       grt [global options] --config-file FILE render-ray-at -p X,Y,Z -d X,Y,Z [--filename F]\n"
-               "       grt [global options] --config-file FILE gbuffer --filename F.grtg\n"
-               "       grt [global options] --config-file FILE reshade --gbuffer F.grtg [--filename F]\n"
+               "       grt [global options] --config-file FILE gbuffer --filename F.grtg [--adaptive]\n"
+               "       grt [global options] --config-file FILE reshade --gbuffer F.grtg [--filename F] [--adaptive]\n"
+               "           (--adaptive: the config's [adaptive_sampling]; the sub-rays live in F.grtg.sub)\n"
                "           (reshade: --width/--height must be the buffer's frame; camera flags are ignored)\n"
                "       grt [global options] blackbody -t T [-r Z]\n"
                "       grt [global options] blackbody-spectrum [--min-temperature T] [--max-temperature T]\n"
@@ -345,6 +351,25 @@ struct GBufferHost {
   }
 };
 
+// The sub-sample set of a buffer on the host (gbuffer / reshade --adaptive): the sidecar
+// `<file>.sub` of grt_gbuffer_sub_write_file.
+struct GBufferSubHost {
+  grt_gbuffer_sub_info sub;
+  std::vector<uint32_t> sub_pixel;
+  GBufferHost rays;
+  explicit GBufferSubHost(const grt_gbuffer_sub_info& s)
+      : sub(s), sub_pixel(s.n_sub_pixels), rays(s.n_sub_rays, s.n_sub_layers) {}
+};
+
+static int save_sub_sidecar(const grt_gbuffer* gb, const grt_gbuffer_info& info, const std::string& path) {
+  grt_gbuffer_sub_info sub;
+  if (grt_gbuffer_sub_info_get(gb, &sub)) return 1;
+  GBufferSubHost h(sub);
+  const grt_gbuffer_arrays arr = h.rays.arrays();
+  return grt_gbuffer_sub_download(gb, h.sub_pixel.data(), &arr) ||
+         grt_gbuffer_sub_write_file(path.c_str(), &info, &sub, h.sub_pixel.data(), &arr);
+}
+
 // render-sequence: a camera-path file, one camera per line `x,y,z,phi,theta,psi` (the
 // values --camera-position, --phi, --theta, --psi take); blank lines and lines starting
 // with `#` are skipped.  On error *err names the line.
@@ -418,6 +443,7 @@ int main(int argc, char** argv) {
   uint32_t band_rows = 16;
   std::string camera_path, filename_pattern = "frame-%04d.png";  // render-sequence
   std::string gbuffer_file;  // reshade
+  bool gbuffer_adaptive = false;  // gbuffer / reshade --adaptive: the config's [adaptive_sampling]
   long long first_index = 0;
   std::vector<std::string> args(argv + 1, argv + argc);
   for (size_t i = 0; i < args.size(); ++i) {
@@ -445,6 +471,7 @@ int main(int argc, char** argv) {
       continue;
     }
     if (action.empty() && a == "--show-sampling-mask") { opts.show_sampling_mask = 1; continue; }
+    if ((action == "gbuffer" || action == "reshade") && a == "--adaptive") { gbuffer_adaptive = true; continue; }
     if (!next(v)) return usage(("missing value for " + a).c_str());
     std::vector<double> nums;
     auto bad = [&]() { return usage(("invalid value '" + v + "' for '" + a + "'").c_str()); };
@@ -706,6 +733,15 @@ int main(int argc, char** argv) {
       std::fprintf(stderr, "Error: %s\n", grt_last_error());
       return 1;
     }
+    grt_gbuffer_section_report srep;
+    if (gbuffer_adaptive) {  // this scene's own adaptive frame: the buffer then holds its selection's sub-rays
+      std::vector<double> frame(4 * (size_t)gb_info.n_pixels);
+      if (grt_gbuffer_shade_section(scene, gb, &ac, nullptr, scene, frame.data(), nullptr, nullptr, nullptr, nullptr,
+                                    &srep)) {
+        std::fprintf(stderr, "Error: %s\n", grt_last_error());
+        return 1;
+      }
+    }
     ph_render = ms_since(t_phase);
     t_phase = clk::now();
     const size_t n = gb_info.n_pixels, nl = gb_info.n_layers;
@@ -713,10 +749,15 @@ int main(int argc, char** argv) {
     const grt_gbuffer_arrays arr = host.arrays();
     double times[2] = {0, 0};
     (void)grt_gbuffer_trace_times(gb, times);
-    if (grt_gbuffer_download(gb, &arr) || grt_gbuffer_write_file(filename.c_str(), &gb_info, &arr)) {
+    if (grt_gbuffer_download(gb, &arr) || grt_gbuffer_write_file(filename.c_str(), &gb_info, &arr) ||
+        (gbuffer_adaptive && save_sub_sidecar(gb, gb_info, filename + ".sub"))) {
       std::fprintf(stderr, "Error: %s\n", grt_last_error());
       return 1;
     }
+    if (gbuffer_adaptive)
+      std::fprintf(stderr, "[grt] sub-sample set: %llu selected pixels traced (%llu sub-rays, %.1f ms), saved to %s.sub\n",
+                   (unsigned long long)srep.n_traced, (unsigned long long)srep.top_up.rays, srep.trace_ms,
+                   filename.c_str());
     ph_write = ms_since(t_phase);
     std::fprintf(stderr, "[grt] %llu rays, %llu accepted steps, %llu attempts, kernel %.1f ms; g-buffer: %llu layers, "
                  "scan + fill %.2f ms\n", (unsigned long long)st.rays, (unsigned long long)st.accepted_steps,
@@ -741,8 +782,75 @@ int main(int argc, char** argv) {
     std::vector<double> xyza(4 * n);
     float shade_ms = 0;
     t_phase = clk::now();
-    if (grt_gbuffer_read_file(gbuffer_file.c_str(), &gb_info, &arr) || grt_gbuffer_upload(&gb_info, &arr, device, &gb) ||
-        grt_gbuffer_shade(scene, gb, x32.data(), cls.data(), status.data(), xyza.data(), &shade_ms)) {
+    if (grt_gbuffer_read_file(gbuffer_file.c_str(), &gb_info, &arr) || grt_gbuffer_upload(&gb_info, &arr, device, &gb)) {
+      std::fprintf(stderr, "Error: %s\n", grt_last_error());
+      return 1;
+    }
+    grt_scene* tracer = nullptr;
+    grt_gbuffer_section_report srep;
+    uint64_t nsel = 0;
+    const uint64_t fail_cap = gbuffer_adaptive ? 1u << 20 : 0;
+    std::vector<uint32_t> fail_pix(fail_cap), fail_sample(fail_cap), fail_steps(fail_cap);
+    std::vector<uint8_t> fail_status(fail_cap), fail_stop(fail_cap);
+    grt_subsample_failures fails{fail_cap, fail_pix.data(), fail_sample.data(), fail_status.data(), 0,
+                                 fail_stop.data(), fail_steps.data()};
+    double mask[4];
+    const double* maskp = nullptr;
+    if (gbuffer_adaptive) {
+      // this config's scene with the file's recorded camera and integration parameters: it
+      // traces the sub-rays the set does not hold yet, and its appearance is the one applied
+      grt_scene_desc td = *d;
+      td.camera = gb_info.camera;
+      td.max_steps = gb_info.max_steps;
+      td.max_radius = gb_info.max_radius;
+      td.step_size = gb_info.step_size;
+      td.epsilon = gb_info.epsilon;
+      td.horizon_epsilon = gb_info.horizon_epsilon;
+      if (grt_scene_create(&td, &tracer)) {
+        std::fprintf(stderr, "Error: %s\n", grt_last_error());
+        return 1;
+      }
+      const std::string sidecar = gbuffer_file + ".sub";
+      grt_gbuffer_sub_info before;
+      std::memset(&before, 0, sizeof(before));
+      if (FILE* f = std::fopen(sidecar.c_str(), "rb")) {  // the sidecar, if present
+        std::fclose(f);
+        if (grt_gbuffer_sub_read_file(sidecar.c_str(), &gb_info, &before, nullptr, nullptr)) {
+          std::fprintf(stderr, "Error: %s\n", grt_last_error());
+          return 1;
+        }
+        GBufferSubHost h(before);
+        const grt_gbuffer_arrays sarr = h.rays.arrays();
+        if (grt_gbuffer_sub_read_file(sidecar.c_str(), &gb_info, &before, h.sub_pixel.data(), &sarr) ||
+            grt_gbuffer_sub_upload(gb, &before, h.sub_pixel.data(), &sarr)) {
+          std::fprintf(stderr, "Error: %s\n", grt_last_error());
+          return 1;
+        }
+      }
+      if (opts.show_sampling_mask) {
+        grt_srgb_to_xyza(opts.sampling_mask_color[0], opts.sampling_mask_color[1], opts.sampling_mask_color[2], 255, mask);
+        maskp = mask;
+      }
+      if (grt_gbuffer_shade_section(tracer, gb, &ac, maskp, tracer, xyza.data(), cls.data(), status.data(), &nsel, &fails,
+                                    &srep)) {
+        std::fprintf(stderr, "Error: %s\n", grt_last_error());
+        return 1;
+      }
+      shade_ms = (float)srep.shade_ms;
+      log_frame_rays(0, 0, gb_info.cols, status, host.stop, host.steps, ac.enabled && !maskp, nsel, fails);
+      std::fprintf(stderr, "[grt] adaptive re-shade: %llu selected pixels, %llu held, %llu traced (%llu sub-rays, %.1f ms)\n",
+                   (unsigned long long)srep.n_selected, (unsigned long long)srep.n_held,
+                   (unsigned long long)srep.n_traced, (unsigned long long)srep.top_up.rays, srep.trace_ms);
+      grt_gbuffer_sub_info after;
+      if (grt_gbuffer_sub_info_get(gb, &after)) return 1;
+      if (after.n_sub_pixels > before.n_sub_pixels) {  // the set grew: the next re-shade finds it
+        if (save_sub_sidecar(gb, gb_info, sidecar)) {
+          std::fprintf(stderr, "Error: %s\n", grt_last_error());
+          return 1;
+        }
+        std::fprintf(stderr, "[grt] INFO saved sub-sample set to %s\n", sidecar.c_str());
+      }
+    } else if (grt_gbuffer_shade(scene, gb, x32.data(), cls.data(), status.data(), xyza.data(), &shade_ms)) {
       std::fprintf(stderr, "Error: %s\n", grt_last_error());
       return 1;
     }
@@ -766,6 +874,7 @@ int main(int argc, char** argv) {
                  ms_since(t_start));
     elapsed();
     grt_gbuffer_destroy(gb);
+    if (tracer) grt_scene_destroy(tracer);
     grt_scene_destroy(scene);
     grt_host_scene_destroy(hs);
     return 0;

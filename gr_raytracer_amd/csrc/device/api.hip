@@ -2402,10 +2402,91 @@ int grt_adaptive_floor_device(grt_scene* s, int device, void* stream, const doub
 // ---- geometry buffer (grt_api.h): trace once, re-shade many times -------------------------
 // The device-resident buffer: its arrays belong to it, not to a scene's scratch, so later
 // traces on the device leave it alone.
+// Grow a device array to `want` bytes, keeping its first `keep` bytes.
+static int grow_buf(DevBuf& b, size_t keep, size_t want) {
+  void* p = nullptr;
+  if (hipMalloc(&p, want ? want : 16) != hipSuccess) {
+    (void)hipGetLastError();
+    return fail(-ENOMEM, "cannot grow the g-buffer's sub-sample set");
+  }
+  if (keep && b.p) {
+    hipError_t e = hipMemcpy(p, b.p, keep, hipMemcpyDeviceToDevice);
+    if (e != hipSuccess) {
+      (void)hipFree(p);
+      return fail(-EIO, std::string("HIP error: ") + hipGetErrorString(e));
+    }
+  }
+  if (b.p) (void)hipFree(b.p);
+  b.p = p;
+  return 0;
+}
+
+// The sub-sample set of a buffer (grt_api.h): append-only, capacities grow geometrically.
+// Block b holds the per sub-rays of pixel sub_pixel[b] at rays [b * per, (b + 1) * per).
+struct GBufferSub {
+  uint32_t spa = 0;  // 0: no set
+  uint64_t n_pix = 0, cap_pix = 0, n_layers = 0, cap_layers = 0;
+  DevBuf sub_pixel;  // u32[cap_pix]
+  DevBuf sub_block;  // u32[n_pixels], GBUFFER_NIL where a pixel has no block (derived, never stored)
+  std::vector<uint32_t> h_block;  // host copy of sub_block
+  DevBuf status, stop, steps, sky_u, sky_v, sky_z, layer_start, object, u, v, z, radius;
+  uint64_t per() const { return (uint64_t)spa * spa; }
+  uint64_t n_rays() const { return n_pix * per(); }
+  // the pixel -> block map, all NIL, before any block exists
+  int ensure_map(uint64_t n_pixels) {
+    if (sub_block.p) return 0;
+    if (int rc = sub_block.alloc(4 * n_pixels)) return rc;
+    HIP_TRY(hipMemset(sub_block.p, 0xff, 4 * n_pixels));
+    h_block.assign(n_pixels, grt::GBUFFER_NIL);
+    return 0;
+  }
+  int reserve_pixels(uint64_t want) {
+    if (want <= cap_pix) return 0;
+    const uint64_t cap = std::max<uint64_t>({want, 2 * cap_pix, 1024}), p = per(), r0 = n_rays(), r1 = cap * p;
+    int rc;
+    if ((rc = grow_buf(sub_pixel, 4 * n_pix, 4 * cap)) || (rc = grow_buf(status, r0, r1)) ||
+        (rc = grow_buf(stop, r0, r1)) || (rc = grow_buf(steps, 4 * r0, 4 * r1)) ||
+        (rc = grow_buf(sky_u, 8 * r0, 8 * r1)) || (rc = grow_buf(sky_v, 8 * r0, 8 * r1)) ||
+        (rc = grow_buf(sky_z, 8 * r0, 8 * r1)))
+      return rc;
+    const bool first = layer_start.p == nullptr;
+    if ((rc = grow_buf(layer_start, first ? 0 : 8 * (r0 + 1), 8 * (r1 + 1)))) return rc;
+    if (first) HIP_TRY(hipMemset(layer_start.p, 0, 8));
+    cap_pix = cap;
+    return 0;
+  }
+  int reserve_layers(uint64_t want) {
+    if (want <= cap_layers && object.p) return 0;
+    const uint64_t cap = std::max<uint64_t>({want, 2 * cap_layers, 4096}), l = n_layers;
+    int rc;
+    if ((rc = grow_buf(object, l, cap)) || (rc = grow_buf(u, 8 * l, 8 * cap)) || (rc = grow_buf(v, 8 * l, 8 * cap)) ||
+        (rc = grow_buf(z, 8 * l, 8 * cap)) || (rc = grow_buf(radius, 8 * l, 8 * cap)))
+      return rc;
+    cap_layers = cap;
+    return 0;
+  }
+  // the rays from `first_ray` on (layer offsets stay the set's own)
+  grt::GBufferArrays view(uint64_t first_ray, uint64_t n) const {
+    return grt::GBufferArrays{n,
+                              (const uint8_t*)status.p + first_ray,
+                              (const uint8_t*)stop.p + first_ray,
+                              (const uint64_t*)layer_start.p + first_ray,
+                              (double*)sky_u.p + first_ray,
+                              (double*)sky_v.p + first_ray,
+                              (double*)sky_z.p + first_ray,
+                              (uint8_t*)object.p,
+                              (double*)u.p,
+                              (double*)v.p,
+                              (double*)z.p,
+                              (double*)radius.p};
+  }
+};
+
 struct grt_gbuffer {
   grt_gbuffer_info info;
   double times[2] = {0.0, 0.0};  // trace, scan + fill (ms)
   DevBuf status, stop, steps, sky_u, sky_v, sky_z, layer_start, object, u, v, z, radius;
+  GBufferSub sub;
   grt_gbuffer() { std::memset(&info, 0, sizeof(info)); }
   int alloc_pixels() {
     const uint64_t n = info.n_pixels;
@@ -2618,6 +2699,450 @@ int grt_gbuffer_shade(grt_scene* s, const grt_gbuffer* gb, float* xyza_out, uint
   HIP_TRY(hipMemcpy(class_out, cls.p, n, hipMemcpyDeviceToHost));
   HIP_TRY(hipMemcpy(status_out, status.p, n, hipMemcpyDeviceToHost));
   if (xyza64_out) HIP_TRY(hipMemcpy(xyza64_out, x64.p, 32 * n, hipMemcpyDeviceToHost));
+  return 0;
+}
+
+}  // extern "C"
+
+// ---- the sub-sample set and the adaptive re-shade (grt_api.h) ----
+// The sub-rays of a buffer belong to the frame it holds: the tracer's geometry (shape key),
+// camera and integration parameters must be the recorded ones.
+static int check_tracer(const grt_gbuffer* gb, const grt_scene* t) {
+  if (int rc = grt_gbuffer_shape_compatible(&gb->info.shape, &t->desc)) return rc;
+  auto differs = [](const char* field) {
+    return fail(-EINVAL, std::string("g-buffer: the tracer differs from the traced scene in ") + field);
+  };
+  const grt_gbuffer_info& i = gb->info;
+  if (std::memcmp(&i.camera, &t->desc.camera, sizeof(i.camera)) != 0) return differs("camera");
+  if (i.max_steps != t->desc.max_steps) return differs("max_steps");
+  if (std::memcmp(&i.max_radius, &t->desc.max_radius, 8) != 0) return differs("max_radius");
+  if (std::memcmp(&i.step_size, &t->desc.step_size, 8) != 0) return differs("step_size");
+  if (std::memcmp(&i.epsilon, &t->desc.epsilon, 8) != 0) return differs("epsilon");
+  if (std::memcmp(&i.horizon_epsilon, &t->desc.horizon_epsilon, 8) != 0) return differs("horizon_epsilon");
+  return 0;
+}
+
+static int check_spa(const grt_gbuffer* gb, uint32_t spa) {
+  if (spa == 0) return fail(-EINVAL, "adaptive_sampling.samples_per_axis must be greater than zero");
+  if (spa > 64) return fail(-EINVAL, "samples_per_axis is more than 64");
+  if (gb->sub.spa && gb->sub.spa != spa)
+    return fail(-EINVAL, "g-buffer: samples_per_axis " + std::to_string(spa) + " differs from the sub-sample set's " +
+                             std::to_string(gb->sub.spa));
+  return 0;
+}
+
+// Trace the sub-rays of `px` (ascending, unique, none held) and append them to the set:
+// enqueue_supersample's machinery -- jitter offsets, the offset-list trace, in chunks of
+// grt_set_sub_chunk -- with the exact kernels and the `hits` output, then per chunk the
+// layer scan (one host sync for the layer total), the growth of the arrays and the fill.
+// The fill is gbuffer_fill_kernel over the chunk's own work list, its arrays pointing at
+// the chunk's place in the set; a chunk launches exactly its rays, so no live count.
+// acc / ms[2]: counters and event times (trace; scan + fill), added to.
+static int sub_fill(grt_scene* tracer, grt_gbuffer* gb, uint32_t spa, const std::vector<uint32_t>& px,
+                    unsigned long long acc[8], double ms[2]) {
+  const uint64_t m = px.size();
+  if (m == 0) return 0;
+  const grt_gbuffer_info& info = gb->info;
+  GBufferSub& S = gb->sub;
+  DeviceCopy* dc;
+  int rc;
+  if ((rc = ensure_device(tracer, info.device, &dc))) return rc;
+  std::lock_guard<std::mutex> lk(dc->mu);
+  HIP_TRY(hipSetDevice(info.device));
+  if ((rc = S.ensure_map(info.n_pixels))) return rc;
+  S.spa = spa;
+  const uint64_t per = S.per();
+  if ((S.n_pix + m) * per + 1 > (uint64_t)INT_MAX) return fail(-EOVERFLOW, "more than INT_MAX - 1 sub-rays");
+  const uint64_t chunk_pix = std::max<uint64_t>(1, std::min<uint64_t>(m, g_sub_chunk.load(std::memory_order_relaxed) / per));
+  const uint64_t cap = chunk_pix * per;
+  DevBuf d_px, pix, dx, dy, xyza, cls, hits, counts, local, temp;
+  if ((rc = d_px.alloc(4 * m)) || (rc = pix.alloc(4 * cap)) || (rc = dx.alloc(8 * cap)) || (rc = dy.alloc(8 * cap)) ||
+      (rc = xyza.alloc(16 * cap)) || (rc = cls.alloc(cap)) || (rc = hits.alloc(4 * cap)) ||
+      (rc = counts.alloc(8 * (cap + 1))) || (rc = local.alloc(8 * (cap + 1))))
+    return rc;
+  size_t temp_bytes = 0;
+  HIP_TRY(grt::gbuffer_layer_scan(nullptr, nullptr, cap, nullptr, nullptr, nullptr, &temp_bytes, nullptr));
+  if ((rc = temp.alloc(temp_bytes))) return rc;
+  HIP_TRY(hipMemcpy(d_px.p, px.data(), 4 * m, hipMemcpyHostToDevice));
+  hipStream_t st = nullptr;
+  const auto fill =
+      tracer->desc.geometry == GRT_GEOM_KERR_BL ? grt::kerr_bl::launch_gbuffer_fill : grt::launch_gbuffer_fill;
+  for (uint64_t base = 0; base < m; base += chunk_pix) {
+    const uint64_t mc = std::min(chunk_pix, m - base), nr = mc * per;
+    if ((rc = S.reserve_pixels(S.n_pix + mc))) return rc;
+    const uint64_t off = S.n_rays();
+    const uint32_t* d_chunk = (const uint32_t*)d_px.p + base;
+    HIP_TRY(grt::launch_make_offsets(d_chunk, mc, nullptr, 0, spa, info.row0, info.col0, info.cols, (uint32_t*)pix.p,
+                                     (double*)dx.p, (double*)dy.p, st));
+    grt::WorkList wo;
+    std::memset(&wo, 0, sizeof(wo));
+    wo.row0 = info.row0;
+    wo.col0 = info.col0;
+    wo.rows = info.rows;
+    wo.cols = info.cols;
+    wo.n_items = nr;
+    wo.pixel_index = (const uint32_t*)pix.p;
+    wo.dx = (const double*)dx.p;
+    wo.dy = (const double*)dy.p;
+    const grt::Outputs o{(float*)xyza.p,
+                         (uint8_t*)cls.p,
+                         (uint8_t*)S.status.p + off,
+                         nullptr,
+                         (uint32_t*)S.steps.p + off,
+                         (uint8_t*)S.stop.p + off,
+                         (uint32_t*)hits.p};
+    float t_ms = 0;
+    // the chunk again while a trace loses candidates, as grt_gbuffer_trace does
+    for (int traces = 1;; ++traces) {
+      unsigned long long need = 0;
+      acc[3] = 0;
+      if ((rc = trace_sync(tracer, *dc, wo, o, acc, &t_ms, &need, nullptr, true))) return rc;
+      if (acc[3] == 0) break;
+      if (traces == 3 || dc->pool_cap >= POOL_MAX)
+        return fail(-ENOMEM, "the hit pool still overflows after " + std::to_string(traces) + " traces");
+      if ((rc = ensure_pool(*dc, need + need / 4))) return rc;
+    }
+    ms[0] += t_ms;
+    if ((rc = stream_order(*dc, st))) return rc;
+    HIP_TRY(hipEventRecord(dc->ev0, st));
+    HIP_TRY(grt::gbuffer_layer_scan((const uint8_t*)S.status.p + off, (const uint32_t*)hits.p, nr, (uint64_t*)counts.p,
+                                    (uint64_t*)local.p, temp.p, &temp_bytes, st));
+    uint64_t n_new = 0;
+    HIP_TRY(hipMemcpy(&n_new, (const uint64_t*)local.p + nr, 8, hipMemcpyDeviceToHost));
+    if ((rc = S.reserve_layers(S.n_layers + n_new))) return rc;
+    HIP_TRY(grt::gbuffer_sub_append((const uint64_t*)local.p, nr, S.n_layers, (uint64_t*)S.layer_start.p + off, d_chunk,
+                                    mc, (uint32_t)S.n_pix, (uint32_t*)S.sub_block.p, (uint32_t*)S.sub_pixel.p, st));
+    grt::Workspace ws;
+    if ((rc = ensure_workspace(*dc, nr, &ws))) return rc;  // the carving of the trace above
+    ws.pool = dc->d_pool;
+    HIP_TRY(fill(tracer->desc.geometry, dc->d_scene, wo, ws, S.view(off, nr), st));
+    HIP_TRY(hipEventRecord(dc->ev1, st));
+    HIP_TRY(hipEventSynchronize(dc->ev1));
+    float f_ms = 0;
+    HIP_TRY(hipEventElapsedTime(&f_ms, dc->ev0, dc->ev1));
+    ms[1] += f_ms;
+    if ((rc = stream_done(*dc, st))) return rc;
+    for (uint64_t j = 0; j < mc; ++j) S.h_block[px[base + j]] = (uint32_t)(S.n_pix + j);
+    S.n_pix += mc;
+    S.n_layers += n_new;
+  }
+  return 0;
+}
+
+static void stats_from(const unsigned long long acc[8], double kernel_ms, grt_stats* stats) {
+  std::memset(stats, 0, sizeof(*stats));
+  stats->accepted_steps = acc[0];
+  stats->attempts = acc[1];
+  stats->rays = acc[2];
+  stats->hit_overflows = acc[3];
+  stats->kernel_ms = (float)kernel_ms;
+  stats->march_jobs = acc[4];
+  stats->march_samples = acc[5];
+  stats->march_noise_samples = acc[6];
+  stats->march_emit_samples = acc[7];
+}
+
+extern "C" {
+
+int grt_gbuffer_supersample(grt_scene* tracer, grt_gbuffer* gb, uint32_t spa, uint64_t n, const uint32_t* pixels,
+                            grt_stats* stats) {
+  if (!tracer || !gb || (n && !pixels)) return fail(-EINVAL, "null argument");
+  int rc;
+  if ((rc = check_spa(gb, spa)) || (rc = check_tracer(gb, tracer))) return rc;
+  if (stats) std::memset(stats, 0, sizeof(*stats));
+  std::vector<uint32_t> px;
+  px.reserve(n);
+  for (uint64_t k = 0; k < n; ++k) {
+    if (pixels[k] >= gb->info.n_pixels)
+      return fail(-EINVAL, "g-buffer: pixel " + std::to_string(pixels[k]) + " is outside the " +
+                               std::to_string(gb->info.n_pixels) + " pixels of the buffer");
+    if (gb->sub.h_block.empty() || gb->sub.h_block[pixels[k]] == grt::GBUFFER_NIL) px.push_back(pixels[k]);
+  }
+  // ascending pixel index: two runs append the same bytes
+  std::sort(px.begin(), px.end());
+  px.erase(std::unique(px.begin(), px.end()), px.end());
+  unsigned long long acc[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+  double ms[2] = {0.0, 0.0};
+  if ((rc = sub_fill(tracer, gb, spa, px, acc, ms))) return rc;
+  if (stats) stats_from(acc, ms[0], stats);
+  return 0;
+}
+
+int grt_gbuffer_shade_section(grt_scene* s, grt_gbuffer* gb, const grt_adaptive_config* cfg, const double* mask_xyza,
+                              grt_scene* tracer, double* xyza_out, uint8_t* class_out, uint8_t* status_out,
+                              uint64_t* n_supersampled, grt_subsample_failures* failures,
+                              grt_gbuffer_section_report* report) {
+  if (!s || !gb || !cfg || !xyza_out) return fail(-EINVAL, "null argument");
+  if (cfg->samples_per_axis == 0) return fail(-EINVAL, "adaptive_sampling.samples_per_axis must be greater than zero");
+  int rc = grt_gbuffer_shape_compatible(&gb->info.shape, &s->desc);
+  if (rc) return rc;
+  const bool supersampled = cfg->enabled || mask_xyza != nullptr;
+  const bool sub_pass = supersampled && !mask_xyza;
+  const uint32_t spa = cfg->samples_per_axis;
+  if (sub_pass && (rc = check_spa(gb, spa))) return rc;
+  if (sub_pass && tracer && (rc = check_tracer(gb, tracer))) return rc;
+  if (report) std::memset(report, 0, sizeof(*report));
+  if (n_supersampled) *n_supersampled = 0;
+  if (failures) failures->count = 0;
+  const int device = gb->info.device;
+  const uint32_t w = gb->info.cols, h = gb->info.rows;
+  const uint64_t n = gb->info.n_pixels, per = (uint64_t)spa * spa;
+  if (n > (uint64_t)INT_MAX) return fail(-EOVERFLOW, "section larger than INT_MAX pixels");
+  DeviceCopy* dc;
+  if ((rc = ensure_device(s, device, &dc))) return rc;
+  std::unique_lock<std::mutex> lk(dc->mu);
+  HIP_TRY(hipSetDevice(device));
+  GBufferSub& S = gb->sub;
+  if (sub_pass && (rc = S.ensure_map(n))) return rc;
+  const bool device_floor = supersampled && !cfg->has_minimum_luminance;
+  const uint64_t sub_chunk = g_sub_chunk.load(std::memory_order_relaxed);
+  size_t sort_bytes = 0, select_bytes = 0, split_bytes = 0;
+  if (device_floor) HIP_TRY(grt::luminance_floor_device(nullptr, 4, n, floor_index(n), nullptr, &sort_bytes, nullptr, 0));
+  if (supersampled) HIP_TRY(grt::compact_flags(nullptr, n, nullptr, nullptr, nullptr, &select_bytes, 0));
+  if (sub_pass)
+    HIP_TRY(grt::gbuffer_split(nullptr, nullptr, n, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr,
+                               &split_bytes, 0));
+  const uint64_t fail_cap = (failures && failures->pixel && failures->status) ? failures->capacity : 0;
+  const bool want_events = fail_cap && failures->stop;
+  grt::SubsampleFailures fails{nullptr, nullptr, nullptr, fail_cap};
+  // the section's buffers, then the selection's, then one chunk of sub-ray outputs
+  float *b_xyza = nullptr, *c_xyza = nullptr;
+  uint8_t *b_cls = nullptr, *b_status = nullptr, *b_flags = nullptr, *b_split = nullptr;
+  uint8_t *c_cls = nullptr, *c_status = nullptr, *c_stop = nullptr;
+  double *b_x64 = nullptr, *d_floor = nullptr, *c_x64 = nullptr;
+  uint32_t *b_sel = nullptr, *b_held = nullptr, *b_missing = nullptr, *c_steps = nullptr;
+  unsigned long long* d_cnt = nullptr;  // [0] selected, [1] failed sub-samples, [2] held, [3] missing
+  void *b_sort = nullptr, *b_select = nullptr, *b_split_tmp = nullptr;
+  const uint64_t chunk_pix = std::max<uint64_t>(1, std::min<uint64_t>(n, sub_chunk / per));
+  const uint32_t n_chunks = (uint32_t)((n + chunk_pix - 1) / chunk_pix);
+  const uint64_t cap = chunk_pix * per;
+  auto carve = [&](AdArena& A) {
+    b_xyza = (float*)A.take(n * 16);
+    b_cls = (uint8_t*)A.take(n);
+    b_status = (uint8_t*)A.take(n);
+    b_x64 = (double*)A.take(n * 32);
+    if (!supersampled) return;
+    b_flags = (uint8_t*)A.take(n);
+    b_sel = (uint32_t*)A.take(n * 4);
+    d_cnt = (unsigned long long*)A.take(32);
+    d_floor = (double*)A.take(8);
+    b_sort = A.take(sort_bytes);
+    b_select = A.take(select_bytes);
+    if (!sub_pass) return;
+    b_split = (uint8_t*)A.take(2 * n);
+    b_held = (uint32_t*)A.take(n * 4);
+    b_missing = (uint32_t*)A.take(n * 4);
+    b_split_tmp = A.take(split_bytes);
+    c_xyza = (float*)A.take(cap * 16);
+    c_cls = (uint8_t*)A.take(cap);
+    c_status = (uint8_t*)A.take(cap);
+    c_x64 = (double*)A.take(cap * 32);
+    c_stop = (uint8_t*)A.take(cap);
+    c_steps = (uint32_t*)A.take(cap * 4);
+    fails.key = (uint64_t*)A.take(fail_cap * 8);
+    fails.status = (uint8_t*)A.take(fail_cap);
+    if (want_events) {
+      fails.stop = (uint8_t*)A.take(fail_cap);
+      fails.steps = (uint32_t*)A.take(fail_cap * 4);
+    }
+  };
+  {
+    AdArena plan;
+    carve(plan);
+    if ((rc = ad_reserve(*dc, plan.off))) return rc;
+    AdArena A{(char*)dc->ad_mem, 0};
+    carve(A);
+  }
+  hipStream_t st = nullptr;
+  float shade_ms = 0;
+  unsigned long long cnt[4] = {0, 0, 0, 0};
+  // split the selection by what the set holds, shade the held sub-rays, average them
+  auto enqueue_sub_pass = [&]() -> int {
+    HIP_TRY(hipMemsetAsync(d_cnt + 1, 0, 24, st));
+    HIP_TRY(grt::gbuffer_split(b_sel, d_cnt, n, (const uint32_t*)S.sub_block.p, b_split, b_held, d_cnt + 2, b_missing,
+                               d_cnt + 3, b_split_tmp, &split_bytes, st));
+    if (S.n_pix == 0) return 0;  // nothing held: every selected pixel is missing
+    fails.count = d_cnt + 1;
+    fails.ray_stop = c_stop;
+    fails.ray_steps = c_steps;
+    const grt::Outputs so{c_xyza, c_cls, c_status, c_x64, c_steps, c_stop, nullptr};
+    const grt::GBufferArrays sv = S.view(0, S.n_rays());
+    for (uint32_t c = 0; c < n_chunks; ++c) {
+      const uint64_t base = (uint64_t)c * chunk_pix;
+      HIP_TRY(grt::launch_gbuffer_shade_sub(dc->d_scene, sv, (const uint32_t*)S.steps.p, (const uint32_t*)S.sub_block.p,
+                                            b_held + base, chunk_pix, d_cnt + 2, base, spa, so, st));
+      HIP_TRY(grt::launch_average(b_held + base, b_held + base, chunk_pix, d_cnt + 2, base, spa, c_x64, c_status, b_x64,
+                                  fails, st));
+    }
+    return 0;
+  };
+  auto finish_pass = [&]() -> int {
+    HIP_TRY(hipEventRecord(dc->ev1, st));
+    HIP_TRY(hipEventSynchronize(dc->ev1));
+    float t = 0;
+    HIP_TRY(hipEventElapsedTime(&t, dc->ev0, dc->ev1));
+    shade_ms += t;
+    if (supersampled) HIP_TRY(hipMemcpy(cnt, d_cnt, sizeof(cnt), hipMemcpyDeviceToHost));
+    return stream_done(*dc, st);
+  };
+  if ((rc = stream_order(*dc, st))) return rc;
+  if (supersampled) HIP_TRY(hipMemsetAsync(d_cnt, 0, 32, st));
+  HIP_TRY(hipEventRecord(dc->ev0, st));
+  {
+    const grt::Outputs o{b_xyza, b_cls, b_status, b_x64, nullptr, nullptr, nullptr};
+    HIP_TRY(grt::launch_gbuffer_shade(dc->d_scene, gb->view(), o, st));
+  }
+  if (supersampled) {
+    if (device_floor)
+      HIP_TRY(grt::luminance_floor_device(b_x64 + 1, 4, n, floor_index(n), b_sort, &sort_bytes, d_floor, st));
+    grt::AdaptiveParams ap;
+    ap.w = w;
+    ap.h = h;
+    ap.exclude_background_contrast = cfg->exclude_background_contrast;
+    ap._pad = 0;
+    ap.min_lum = cfg->minimum_luminance;
+    ap.luminance_contrast_threshold = cfg->luminance_contrast_threshold;
+    ap.opacity_contrast_threshold = cfg->opacity_contrast_threshold;
+    HIP_TRY(grt::launch_select(b_x64, b_cls, ap, device_floor ? d_floor : nullptr, b_flags, st));
+    HIP_TRY(grt::compact_flags(b_flags, n, b_sel, d_cnt, b_select, &select_bytes, st));
+    if (mask_xyza) HIP_TRY(grt::launch_paint(b_sel, n, d_cnt, mask_xyza, b_x64, st));
+    else if ((rc = enqueue_sub_pass())) return rc;
+  }
+  if ((rc = finish_pass())) return rc;
+  unsigned long long acc[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+  double trace_ms[2] = {0.0, 0.0};
+  const uint64_t n_held = cnt[2], n_missing = sub_pass ? cnt[3] : 0;
+  if (report) {
+    report->n_selected = cnt[0];
+    report->n_held = n_held;
+    report->shade_ms = shade_ms;
+  }
+  if (n_missing) {
+    if (!tracer) {
+      if (report) report->n_missing = n_missing;
+      return fail(-ENODATA, "g-buffer: the sub-sample set misses " + std::to_string(n_missing) + " of the " +
+                                std::to_string(cnt[0]) + " selected pixels and the call has no tracer");
+    }
+    // top-up: trace the missing pixels once, append them, then the sub-ray pass again over
+    // the whole selection, which the set now holds
+    std::vector<uint32_t> px(n_missing);
+    HIP_TRY(hipMemcpy(px.data(), b_missing, 4 * n_missing, hipMemcpyDeviceToHost));
+    lk.unlock();  // the tracer may be this scene: sub_fill takes its device's lock
+    rc = sub_fill(tracer, gb, spa, px, acc, trace_ms);
+    lk.lock();
+    if (rc) return rc;
+    HIP_TRY(hipSetDevice(device));
+    if ((rc = stream_order(*dc, st))) return rc;
+    HIP_TRY(hipEventRecord(dc->ev0, st));
+    if ((rc = enqueue_sub_pass()) || (rc = finish_pass())) return rc;
+    if (cnt[3] != 0) return fail(-EIO, "g-buffer: the top-up left selected pixels without sub-rays");
+    if (report) {
+      report->n_traced = n_missing;
+      report->shade_ms = shade_ms;
+      report->trace_ms = trace_ms[0] + trace_ms[1];
+      stats_from(acc, trace_ms[0], &report->top_up);
+    }
+  }
+  HIP_TRY(hipMemcpy(xyza_out, b_x64, n * 32, hipMemcpyDeviceToHost));
+  if (class_out) HIP_TRY(hipMemcpy(class_out, b_cls, n, hipMemcpyDeviceToHost));
+  if (status_out) HIP_TRY(hipMemcpy(status_out, b_status, n, hipMemcpyDeviceToHost));
+  if (supersampled) {
+    if (n_supersampled) *n_supersampled = cnt[0];
+    if (failures && sub_pass) {
+      failures->count = cnt[1];
+      if (int frc = copy_failures(fails, cnt[1], spa, failures)) return frc;
+    }
+  }
+  return 0;
+}
+
+int grt_gbuffer_sub_info_get(const grt_gbuffer* gb, grt_gbuffer_sub_info* out) {
+  if (!gb || !out) return fail(-EINVAL, "null argument");
+  std::memset(out, 0, sizeof(*out));
+  out->samples_per_axis = gb->sub.spa;
+  out->n_sub_pixels = gb->sub.n_pix;
+  out->n_sub_rays = gb->sub.n_rays();
+  out->n_sub_layers = gb->sub.n_layers;
+  return 0;
+}
+
+int grt_gbuffer_sub_download(const grt_gbuffer* gb, uint32_t* sub_pixel, const grt_gbuffer_arrays* h) {
+  if (!gb) return fail(-EINVAL, "null argument");
+  const GBufferSub& S = gb->sub;
+  const uint64_t m = S.n_pix, n = S.n_rays(), l = S.n_layers;
+  if (S.spa == 0 || m == 0) return 0;  // nothing to copy
+  if (!sub_pixel || !h || !h->status || !h->stop || !h->steps || !h->sky_u || !h->sky_v || !h->sky_redshift ||
+      !h->layer_start)
+    return fail(-EINVAL, "null argument");
+  if (l && (!h->object || !h->u || !h->v || !h->redshift || !h->radius)) return fail(-EINVAL, "null layer array");
+  HIP_TRY(hipSetDevice(gb->info.device));
+  HIP_TRY(hipMemcpy(sub_pixel, S.sub_pixel.p, 4 * m, hipMemcpyDeviceToHost));
+  HIP_TRY(hipMemcpy(h->status, S.status.p, n, hipMemcpyDeviceToHost));
+  HIP_TRY(hipMemcpy(h->stop, S.stop.p, n, hipMemcpyDeviceToHost));
+  HIP_TRY(hipMemcpy(h->steps, S.steps.p, 4 * n, hipMemcpyDeviceToHost));
+  HIP_TRY(hipMemcpy(h->sky_u, S.sky_u.p, 8 * n, hipMemcpyDeviceToHost));
+  HIP_TRY(hipMemcpy(h->sky_v, S.sky_v.p, 8 * n, hipMemcpyDeviceToHost));
+  HIP_TRY(hipMemcpy(h->sky_redshift, S.sky_z.p, 8 * n, hipMemcpyDeviceToHost));
+  HIP_TRY(hipMemcpy(h->layer_start, S.layer_start.p, 8 * (n + 1), hipMemcpyDeviceToHost));
+  if (l) {
+    HIP_TRY(hipMemcpy(h->object, S.object.p, l, hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(h->u, S.u.p, 8 * l, hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(h->v, S.v.p, 8 * l, hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(h->redshift, S.z.p, 8 * l, hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(h->radius, S.radius.p, 8 * l, hipMemcpyDeviceToHost));
+  }
+  return 0;
+}
+
+int grt_gbuffer_sub_upload(grt_gbuffer* gb, const grt_gbuffer_sub_info* sub, const uint32_t* sub_pixel,
+                           const grt_gbuffer_arrays* h) {
+  if (!gb || !sub) return fail(-EINVAL, "null argument");
+  static const grt_gbuffer_arrays none{};
+  // the shade kernel indexes by sub_pixel, layer_start and object: hold them to their ranges
+  int rc = grt_host::gbuffer_sub_check(&gb->info, sub, sub_pixel, sub->samples_per_axis ? h : &none);
+  if (rc) return rc;
+  if (sub->samples_per_axis && !h) return fail(-EINVAL, "g-buffer: null sub-ray array");
+  HIP_TRY(hipSetDevice(gb->info.device));
+  std::unique_ptr<GBufferSub> N(new GBufferSub());
+  if ((rc = N->ensure_map(gb->info.n_pixels))) return rc;
+  N->spa = sub->samples_per_axis;
+  const uint64_t m = sub->n_sub_pixels, n = sub->n_sub_rays, l = sub->n_sub_layers;
+  if (N->spa && m) {
+    if ((rc = N->reserve_pixels(m)) || (rc = N->reserve_layers(l))) return rc;
+    HIP_TRY(hipMemcpy(N->sub_pixel.p, sub_pixel, 4 * m, hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(N->status.p, h->status, n, hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(N->stop.p, h->stop, n, hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(N->steps.p, h->steps, 4 * n, hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(N->sky_u.p, h->sky_u, 8 * n, hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(N->sky_v.p, h->sky_v, 8 * n, hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(N->sky_z.p, h->sky_redshift, 8 * n, hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(N->layer_start.p, h->layer_start, 8 * (n + 1), hipMemcpyHostToDevice));
+    if (l) {
+      HIP_TRY(hipMemcpy(N->object.p, h->object, l, hipMemcpyHostToDevice));
+      HIP_TRY(hipMemcpy(N->u.p, h->u, 8 * l, hipMemcpyHostToDevice));
+      HIP_TRY(hipMemcpy(N->v.p, h->v, 8 * l, hipMemcpyHostToDevice));
+      HIP_TRY(hipMemcpy(N->z.p, h->redshift, 8 * l, hipMemcpyHostToDevice));
+      HIP_TRY(hipMemcpy(N->radius.p, h->radius, 8 * l, hipMemcpyHostToDevice));
+    }
+    N->n_pix = m;
+    N->n_layers = l;
+    HIP_TRY(grt::gbuffer_sub_index((const uint32_t*)N->sub_pixel.p, m, gb->info.n_pixels, (uint32_t*)N->sub_block.p,
+                                   nullptr));
+    HIP_TRY(hipDeviceSynchronize());
+    for (uint64_t j = 0; j < m; ++j) N->h_block[sub_pixel[j]] = (uint32_t)j;
+  }
+  // the old set's arrays are freed with N
+  std::swap(gb->sub.spa, N->spa);
+  std::swap(gb->sub.n_pix, N->n_pix);
+  std::swap(gb->sub.cap_pix, N->cap_pix);
+  std::swap(gb->sub.n_layers, N->n_layers);
+  std::swap(gb->sub.cap_layers, N->cap_layers);
+  std::swap(gb->sub.h_block, N->h_block);
+  for (DevBuf GBufferSub::*f : {&GBufferSub::sub_pixel, &GBufferSub::sub_block, &GBufferSub::status, &GBufferSub::stop,
+                                &GBufferSub::steps, &GBufferSub::sky_u, &GBufferSub::sky_v, &GBufferSub::sky_z,
+                                &GBufferSub::layer_start, &GBufferSub::object, &GBufferSub::u, &GBufferSub::v,
+                                &GBufferSub::z, &GBufferSub::radius})
+    std::swap((gb->sub.*f).p, ((*N).*f).p);
   return 0;
 }
 

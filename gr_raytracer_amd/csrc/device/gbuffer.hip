@@ -1,4 +1,7 @@
-// gbuffer.hip — layer offsets of a geometry buffer (grt_gbuffer_trace).
+// gbuffer.hip — layer offsets of a geometry buffer (grt_gbuffer_trace), and the bookkeeping
+// of its sub-sample set (grt_gbuffer_supersample, grt_gbuffer_shade_section): the split of
+// a selection into held and missing pixels, the append of a traced chunk, the pixel -> block
+// map of an uploaded set.
 //
 // A pixel's layers are the window-nearest hits that enter its blend: the trace's own
 // `hits` output, and none for a pixel the trace aborted (status != 0).  The offsets are
@@ -31,6 +34,80 @@ hipError_t gbuffer_layer_scan(const uint8_t* d_status, const uint32_t* d_hits, u
   hipError_t e = hipGetLastError();
   if (e != hipSuccess) return e;
   return hipcub::DeviceScan::ExclusiveSum(d_temp, *temp_bytes, d_counts, d_layer_start, (int)(n + 1), stream);
+}
+
+// ---- the sub-sample set (grt_gbuffer_supersample, grt_gbuffer_shade_section) ----
+// held[j] / missing[j]: whether selected pixel j has a block; 0 past the selection's end.
+__global__ void __launch_bounds__(256) gbuffer_split_flags_kernel(const uint32_t* __restrict__ sel,
+                                                                  const unsigned long long* __restrict__ d_count,
+                                                                  uint64_t n_max, const uint32_t* __restrict__ sub_block,
+                                                                  uint8_t* __restrict__ held,
+                                                                  uint8_t* __restrict__ missing) {
+  const uint64_t j = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (j >= n_max) return;
+  const bool live = j < *d_count;
+  const bool has = live && sub_block[sel[j]] != GBUFFER_NIL;
+  held[j] = has ? 1 : 0;
+  missing[j] = (live && !has) ? 1 : 0;
+}
+
+// An ordered compaction of each flag array (DeviceSelect::Flagged, as compact_flags): the
+// lists keep the selection's ascending pixel order, so a top-up appends the same bytes
+// every time.
+hipError_t gbuffer_split(const uint32_t* d_sel, const unsigned long long* d_count, uint64_t n_max,
+                         const uint32_t* d_sub_block, uint8_t* d_flags, uint32_t* d_held,
+                         unsigned long long* d_n_held, uint32_t* d_missing, unsigned long long* d_n_missing,
+                         void* d_temp, size_t* temp_bytes, hipStream_t stream) {
+  if (n_max > (uint64_t)INT_MAX) return hipErrorInvalidValue;
+  if (d_temp == nullptr)
+    return hipcub::DeviceSelect::Flagged(nullptr, *temp_bytes, d_sel, d_flags, d_held, d_n_held, (int)n_max, stream);
+  if (n_max == 0) return hipSuccess;
+  hipLaunchKernelGGL(gbuffer_split_flags_kernel, dim3((unsigned)((n_max + 255) / 256)), dim3(256), 0, stream, d_sel,
+                     d_count, n_max, d_sub_block, d_flags, d_flags + n_max);
+  hipError_t e = hipGetLastError();
+  if (e != hipSuccess) return e;
+  e = hipcub::DeviceSelect::Flagged(d_temp, *temp_bytes, d_sel, d_flags, d_held, d_n_held, (int)n_max, stream);
+  if (e != hipSuccess) return e;
+  return hipcub::DeviceSelect::Flagged(d_temp, *temp_bytes, d_sel, d_flags + n_max, d_missing, d_n_missing, (int)n_max,
+                                       stream);
+}
+
+__global__ void __launch_bounds__(256) gbuffer_sub_append_kernel(const uint64_t* __restrict__ local, uint64_t n_rays,
+                                                                 uint64_t layer_base, uint64_t* __restrict__ layer_start,
+                                                                 const uint32_t* __restrict__ pixels, uint64_t n_pixels,
+                                                                 uint32_t first_block, uint32_t* __restrict__ sub_block,
+                                                                 uint32_t* __restrict__ sub_pixel) {
+  const uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i <= n_rays) layer_start[i] = local[i] + layer_base;
+  if (i < n_pixels) {
+    const uint32_t p = pixels[i];
+    sub_block[p] = first_block + (uint32_t)i;
+    sub_pixel[first_block + i] = p;
+  }
+}
+
+hipError_t gbuffer_sub_append(const uint64_t* d_local, uint64_t n_rays, uint64_t layer_base, uint64_t* d_layer_start,
+                              const uint32_t* d_pixels, uint64_t n_pixels, uint32_t first_block, uint32_t* d_sub_block,
+                              uint32_t* d_sub_pixel, hipStream_t stream) {
+  const uint64_t n = (n_rays + 1 > n_pixels) ? n_rays + 1 : n_pixels;
+  hipLaunchKernelGGL(gbuffer_sub_append_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, stream, d_local, n_rays,
+                     layer_base, d_layer_start, d_pixels, n_pixels, first_block, d_sub_block, d_sub_pixel);
+  return hipGetLastError();
+}
+
+__global__ void __launch_bounds__(256) gbuffer_sub_index_kernel(const uint32_t* __restrict__ sub_pixel, uint64_t n_sub,
+                                                                uint32_t* __restrict__ sub_block) {
+  const uint64_t j = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (j < n_sub) sub_block[sub_pixel[j]] = (uint32_t)j;
+}
+
+hipError_t gbuffer_sub_index(const uint32_t* d_sub_pixel, uint64_t n_sub_pixels, uint64_t n_pixels,
+                             uint32_t* d_sub_block, hipStream_t stream) {
+  hipError_t e = hipMemsetAsync(d_sub_block, 0xff, 4 * n_pixels, stream);  // GBUFFER_NIL
+  if (e != hipSuccess || n_sub_pixels == 0) return e;
+  hipLaunchKernelGGL(gbuffer_sub_index_kernel, dim3((unsigned)((n_sub_pixels + 255) / 256)), dim3(256), 0, stream,
+                     d_sub_pixel, n_sub_pixels, d_sub_block);
+  return hipGetLastError();
 }
 
 }  // namespace grt

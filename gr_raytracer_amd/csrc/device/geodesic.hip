@@ -3845,6 +3845,49 @@ GDEV int gbuffer_layer_color(const DevScene& S, const GBufferArrays& gb, uint64_
   return GRT_OK;
 }
 
+// One ray of a buffer (`src` in gb's arrays) shaded into output slot `dst`: the body of
+// gbuffer_shade_kernel below, for gbuffer_shade_sub_kernel.  That kernel keeps its own copy
+// of these lines: calling this function from it compiles to other code than the one its
+// times were measured on (tools/kernel_hashes.py), and its code is to stay as it is.
+GDEV void gbuffer_shade_ray(const DevScene& S, const GBufferArrays& gb, uint64_t src, const Outputs& out,
+                            uint64_t dst) {
+  const int status = gb.status[src];
+  const int stop = gb.stop[src];
+  const XYZA fail{0.0, 0.0, 0.0, 1.0};
+  if (status != GRT_OK) {
+    write_out(out, dst, fail, GRT_CLASS_ESCAPED, status, stop, 0u);
+    return;
+  }
+  const uint64_t l0 = gb.layer_start[src], l1 = gb.layer_start[src + 1];
+  double opacity = 0.0;
+  for (uint64_t k = l0; k < l1; ++k) {
+    XYZA col;
+    int e = gbuffer_layer_color(S, gb, k, &col);
+    if (e != GRT_OK) {  // a temperature error the traced scene did not have: the window error's pixel
+      write_out(out, dst, fail, GRT_CLASS_ESCAPED, e, stop, (uint32_t)(k - l0));
+      return;
+    }
+    double alpha = rclamp(col.a, 0.0, 1.0);
+    opacity = alpha + opacity * (1.0 - alpha);
+  }
+  XYZA result{0.0, 0.0, 0.0, 1.0};
+  int cls = GRT_CLASS_CAPTURED;
+  if (stop == GRT_STOP_HORIZON || stop == GRT_STOP_CLOSED_ORBIT) {
+    result = blend(result, XYZA{0.0, 0.0, 0.0, 1.0});
+  } else if (stop == GRT_STOP_CELESTIAL) {
+    result = blend(result, texture_color(S, S.celestial, gb.sky_u[src], gb.sky_v[src], gb.sky_redshift[src],
+                                         S.celestial_temperature));
+    cls = GRT_CLASS_ESCAPED;
+  }
+  for (uint64_t k = l1; k > l0; --k) {
+    XYZA col{0.0, 0.0, 0.0, 0.0};
+    (void)gbuffer_layer_color(S, gb, k - 1, &col);
+    result = blend(result, col);
+  }
+  if (opacity >= S.hit_threshold) cls = GRT_CLASS_HIT;
+  write_out(out, dst, result, cls, status, stop, (uint32_t)(l1 - l0));
+}
+
 __global__ void __launch_bounds__(256) gbuffer_shade_kernel(const DevScene* __restrict__ Sp, GBufferArrays gb,
                                                             Outputs out) {
   const DevScene& S = *Sp;
@@ -3888,10 +3931,45 @@ __global__ void __launch_bounds__(256) gbuffer_shade_kernel(const DevScene* __re
   write_out(out, idx, result, cls, status, stop, (uint32_t)(l1 - l0));
 }
 
+// The supersample pass of an adaptive re-shade (grt_gbuffer_shade_section): one lane per
+// (held selected pixel j, stratum s) of a chunk of the list `sel` (entries base + j <
+// *d_count).  Sub-ray sub_block[sel[j]] * per + s of the buffer's sub-sample set `sub` is
+// shaded as gbuffer_shade_kernel shades a pixel, into slot j * per + s: the layout
+// average_kernel reads, with the sub-ray's step count beside it.
+__global__ void __launch_bounds__(256) gbuffer_shade_sub_kernel(const DevScene* __restrict__ Sp, GBufferArrays sub,
+                                                                const uint32_t* __restrict__ sub_steps,
+                                                                const uint32_t* __restrict__ sub_block,
+                                                                const uint32_t* __restrict__ sel, uint64_t n_sel,
+                                                                const unsigned long long* __restrict__ d_count,
+                                                                uint64_t base, uint32_t per, Outputs out) {
+  const DevScene& S = *Sp;
+  // a block past the held pixels (the empty chunks of a pass) has nothing to do
+  if (base + (uint64_t)blockIdx.x * blockDim.x / per >= *d_count) return;
+  glibc::tables_to_lds();  // whole block, before the per-lane early return
+  const uint64_t k = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  const uint64_t j = k / per;
+  if (j >= n_sel || base + j >= *d_count) return;
+  const uint64_t src = (uint64_t)sub_block[sel[j]] * per + k % per;
+  if (src >= sub.n) return;  // a pixel the set does not hold: the split never lists one
+  if (out.steps) out.steps[k] = sub_steps[src];
+  gbuffer_shade_ray(S, sub, src, out, k);
+}
+
 hipError_t launch_gbuffer_shade(const DevScene* d_scene, const GBufferArrays& gb, const Outputs& out,
                                 hipStream_t stream) {
   if (gb.n == 0) return hipSuccess;
   hipLaunchKernelGGL(gbuffer_shade_kernel, dim3((unsigned)((gb.n + 255) / 256)), dim3(256), 0, stream, d_scene, gb, out);
+  return hipGetLastError();
+}
+
+hipError_t launch_gbuffer_shade_sub(const DevScene* d_scene, const GBufferArrays& sub, const uint32_t* d_sub_steps,
+                                    const uint32_t* d_sub_block, const uint32_t* d_sel, uint64_t n_sel,
+                                    const unsigned long long* d_count, uint64_t base, uint32_t spa, const Outputs& out,
+                                    hipStream_t stream) {
+  const uint64_t n = n_sel * spa * spa;
+  if (n == 0) return hipSuccess;
+  hipLaunchKernelGGL(gbuffer_shade_sub_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, stream, d_scene, sub,
+                     d_sub_steps, d_sub_block, d_sel, n_sel, d_count, base, spa * spa, out);
   return hipGetLastError();
 }
 #endif  // GRT_MAIN_TU

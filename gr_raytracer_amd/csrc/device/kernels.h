@@ -145,6 +145,33 @@ hipError_t launch_gbuffer_fill(int geometry, const DevScene* d_scene, const Work
 // Deferred shade of `gb` under the appearance scene (gbuffer_shade_kernel, geodesic.hip).
 hipError_t launch_gbuffer_shade(const DevScene* d_scene, const GBufferArrays& gb, const Outputs& out,
                                 hipStream_t stream);
+// The sub-sample set of a buffer (grt_gbuffer_supersample): for some pixels, the spa^2
+// jittered sub-rays, each reduced as a 1-spp ray is; sub-ray b * spa^2 + s is stratum s of
+// block b, and sub_block[pixel] is the pixel's block or GBUFFER_NIL.
+constexpr uint32_t GBUFFER_NIL = 0xffffffffu;
+// Supersample pass of the adaptive re-shade (gbuffer_shade_sub_kernel, geodesic.hip): a
+// chunk of n_sel entries at position `base` of the held list d_sel (*d_count entries),
+// shaded into out at j * spa^2 + s (out.steps takes the sub-rays' step counts).
+hipError_t launch_gbuffer_shade_sub(const DevScene* d_scene, const GBufferArrays& sub, const uint32_t* d_sub_steps,
+                                    const uint32_t* d_sub_block, const uint32_t* d_sel, uint64_t n_sel,
+                                    const unsigned long long* d_count, uint64_t base, uint32_t spa, const Outputs& out,
+                                    hipStream_t stream);
+// The selected pixels d_sel (*d_count of them, ascending) split by sub_block into the ones
+// the set holds and the ones it misses, each in ascending order, with their counts
+// (gbuffer.hip; n_max <= INT_MAX entries of room).  d_flags: 2 * n_max bytes of scratch.
+// Call with d_temp == NULL for *temp_bytes.
+hipError_t gbuffer_split(const uint32_t* d_sel, const unsigned long long* d_count, uint64_t n_max,
+                         const uint32_t* d_sub_block, uint8_t* d_flags, uint32_t* d_held,
+                         unsigned long long* d_n_held, uint32_t* d_missing, unsigned long long* d_n_missing,
+                         void* d_temp, size_t* temp_bytes, hipStream_t stream);
+// Appending a chunk to the set: d_layer_start[i] = d_local[i] + layer_base for i <= n_rays,
+// and sub_block[d_pixels[j]] = first_block + j, sub_pixel[first_block + j] = d_pixels[j].
+hipError_t gbuffer_sub_append(const uint64_t* d_local, uint64_t n_rays, uint64_t layer_base, uint64_t* d_layer_start,
+                              const uint32_t* d_pixels, uint64_t n_pixels, uint32_t first_block, uint32_t* d_sub_block,
+                              uint32_t* d_sub_pixel, hipStream_t stream);
+// sub_block of an uploaded set: GBUFFER_NIL everywhere, then block j at d_sub_pixel[j].
+hipError_t gbuffer_sub_index(const uint32_t* d_sub_pixel, uint64_t n_sub_pixels, uint64_t n_pixels,
+                             uint32_t* d_sub_block, hipStream_t stream);
 
 // Invariant monitors of the n = rows x cols rays of a rectangle (health_kernel):
 // d_out n x 5 doubles, d_status n bytes.

@@ -5,6 +5,7 @@
 #include <cstdio>
 #include <cstring>
 #include <string>
+#include <vector>
 
 #include "host_internal.h"
 
@@ -17,6 +18,8 @@ int fail(int code, const std::string& msg) {
 
 const char MAGIC[8] = {'G', 'R', 'T', 'G', 'B', 'U', 'F', '\0'};
 constexpr uint64_t HEADER_BYTES = 16 + sizeof(grt_gbuffer_info);
+const char SUB_MAGIC[8] = {'G', 'R', 'T', 'G', 'S', 'U', 'B', '\0'};
+constexpr uint64_t SUB_HEADER_BYTES = HEADER_BYTES + sizeof(grt_gbuffer_sub_info);
 // no frame comes near these; they keep the size arithmetic below far from overflow
 constexpr uint64_t MAX_PIXELS = (1ull << 31) - 2;
 constexpr uint64_t MAX_LAYERS = 1ull << 40;
@@ -64,6 +67,57 @@ int gbuffer_check_arrays(const grt_gbuffer_info* info, const grt_gbuffer_arrays*
     if (a->object[k] >= info->shape.n_objects)
       return fail(-EINVAL, "g-buffer: layer " + std::to_string(k) + " names object " + std::to_string(a->object[k]) +
                                " of " + std::to_string(info->shape.n_objects));
+  return 0;
+}
+
+int gbuffer_sub_check(const grt_gbuffer_info* info, const grt_gbuffer_sub_info* sub, const uint32_t* sub_pixel,
+                      const grt_gbuffer_arrays* a) {
+  if (int rc = gbuffer_check_info(info)) return rc;
+  if (!sub) return fail(-EINVAL, "g-buffer: null sub-sample info");
+  const uint64_t spa = sub->samples_per_axis;
+  if (spa == 0) {
+    if (sub->n_sub_pixels || sub->n_sub_rays || sub->n_sub_layers)
+      return fail(-EINVAL, "g-buffer: samples_per_axis is 0 but the sub-sample set is not empty");
+    return 0;
+  }
+  if (spa > 64) return fail(-EINVAL, "g-buffer: samples_per_axis " + std::to_string(spa) + " is more than 64");
+  if (sub->n_sub_pixels > info->n_pixels)
+    return fail(-EINVAL, "g-buffer: n_sub_pixels " + std::to_string(sub->n_sub_pixels) + " is more than n_pixels");
+  if (sub->n_sub_rays != sub->n_sub_pixels * spa * spa)
+    return fail(-EINVAL, "g-buffer: n_sub_rays is not n_sub_pixels * samples_per_axis^2");
+  if (sub->n_sub_rays > MAX_PIXELS) return fail(-EINVAL, "g-buffer: too many sub-rays");
+  if (sub->n_sub_layers > MAX_LAYERS) return fail(-EINVAL, "g-buffer: too many sub-ray layers");
+  if (!a) return 0;
+  const uint64_t m = sub->n_sub_pixels, n = sub->n_sub_rays, l = sub->n_sub_layers;
+  if (m && !sub_pixel) return fail(-EINVAL, "g-buffer: null sub_pixel");
+  if (!a->status || !a->stop || !a->steps || !a->sky_u || !a->sky_v || !a->sky_redshift || !a->layer_start)
+    return fail(-EINVAL, "g-buffer: null sub-ray array");
+  if (l && (!a->object || !a->u || !a->v || !a->redshift || !a->radius))
+    return fail(-EINVAL, "g-buffer: null sub-ray layer array");
+  {
+    std::vector<bool> seen(info->n_pixels, false);
+    for (uint64_t j = 0; j < m; ++j) {
+      const uint32_t p = sub_pixel[j];
+      if (p >= info->n_pixels)
+        return fail(-EINVAL, "g-buffer: sub_pixel[" + std::to_string(j) + "] = " + std::to_string(p) +
+                                 " is outside the " + std::to_string(info->n_pixels) + " pixels");
+      if (seen[p])
+        return fail(-EINVAL, "g-buffer: sub_pixel[" + std::to_string(j) + "] = " + std::to_string(p) + " is a duplicate");
+      seen[p] = true;
+    }
+  }
+  if (a->layer_start[0] != 0) return fail(-EINVAL, "g-buffer: sub-ray layer_start does not begin at 0");
+  for (uint64_t i = 0; i < n; ++i) {
+    if (a->layer_start[i + 1] < a->layer_start[i])
+      return fail(-EINVAL, "g-buffer: sub-ray layer_start decreases at sub-ray " + std::to_string(i));
+    if (a->status[i] & GRT_FLAG_HIT_OVERFLOW)
+      return fail(-EINVAL, "g-buffer: sub-ray " + std::to_string(i) + " has the status flag GRT_FLAG_HIT_OVERFLOW");
+  }
+  if (a->layer_start[n] != l) return fail(-EINVAL, "g-buffer: sub-ray layer_start does not end at n_sub_layers");
+  for (uint64_t k = 0; k < l; ++k)
+    if (a->object[k] >= info->shape.n_objects)
+      return fail(-EINVAL, "g-buffer: sub-ray layer " + std::to_string(k) + " names object " +
+                               std::to_string(a->object[k]) + " of " + std::to_string(info->shape.n_objects));
   return 0;
 }
 
@@ -212,6 +266,126 @@ int grt_gbuffer_read_file(const char* path, grt_gbuffer_info* info, const grt_gb
   if (!ok) return fail(-EIO, name + "cannot read the arrays");
   if (int rc = grt_host::gbuffer_check_arrays(&in, a)) return rc;
   *info = in;
+  return 0;
+}
+
+// ---- the sub-sample set's sidecar ----
+// The buffer's info with the fields a load changes (the device) zeroed: what binds a set to it.
+static grt_gbuffer_info bound_info(const grt_gbuffer_info* info) {
+  grt_gbuffer_info b = *info;
+  b.device = 0;
+  b._pad = 0;
+  return b;
+}
+
+int grt_gbuffer_sub_write_file(const char* path, const grt_gbuffer_info* info, const grt_gbuffer_sub_info* sub,
+                               const uint32_t* sub_pixel, const grt_gbuffer_arrays* a) {
+  if (!path) return fail(-EINVAL, "null path");
+  if (!a) return fail(-EINVAL, "g-buffer: null sub-ray array");
+  if (int rc = grt_host::gbuffer_sub_check(info, sub, sub_pixel, a)) return rc;
+  File file;
+  file.f = std::fopen(path, "wb");
+  if (!file.f) return fail(-EIO, std::string("cannot create ") + path);
+  const uint64_t m = sub->n_sub_pixels, n = sub->n_sub_rays, l = sub->n_sub_layers;
+  const uint32_t head[2] = {GRT_GBUFFER_SUB_FILE_VERSION, (uint32_t)sizeof(grt_gbuffer_info)};
+  const grt_gbuffer_info bound = bound_info(info);
+  grt_gbuffer_sub_info si = *sub;
+  si._pad = 0;
+  bool ok = true;
+  auto put = [&](const void* p, uint64_t bytes) {
+    if (ok && bytes) ok = std::fwrite(p, 1, bytes, file.f) == bytes;
+  };
+  put(SUB_MAGIC, 8);
+  put(head, 8);
+  put(&bound, sizeof(bound));
+  put(&si, sizeof(si));
+  put(sub_pixel, 4 * m);
+  if (si.samples_per_axis) {
+    put(a->layer_start, 8 * (n + 1));
+    put(a->sky_u, 8 * n);
+    put(a->sky_v, 8 * n);
+    put(a->sky_redshift, 8 * n);
+    put(a->u, 8 * l);
+    put(a->v, 8 * l);
+    put(a->redshift, 8 * l);
+    put(a->radius, 8 * l);
+    put(a->steps, 4 * n);
+    put(a->status, n);
+    put(a->stop, n);
+    put(a->object, l);
+  }
+  FILE* f = file.f;
+  file.f = nullptr;
+  if (std::fclose(f) != 0) ok = false;
+  if (!ok) return fail(-EIO, std::string("cannot write ") + path);
+  return 0;
+}
+
+int grt_gbuffer_sub_read_file(const char* path, const grt_gbuffer_info* info, grt_gbuffer_sub_info* sub,
+                              uint32_t* sub_pixel, const grt_gbuffer_arrays* a) {
+  if (!path || !info || !sub) return fail(-EINVAL, "null argument");
+  File file;
+  file.f = std::fopen(path, "rb");
+  if (!file.f) return fail(-EIO, std::string("cannot open ") + path);
+  const std::string name = std::string(path) + ": ";
+  if (std::fseek(file.f, 0, SEEK_END) != 0) return fail(-EIO, name + "cannot seek");
+  const long end = std::ftell(file.f);
+  if (end < 0 || std::fseek(file.f, 0, SEEK_SET) != 0) return fail(-EIO, name + "cannot seek");
+  const uint64_t length = (uint64_t)end;
+  if (length < SUB_HEADER_BYTES) return fail(-EINVAL, name + "too short for a sub-sample set header");
+  char magic[8];
+  uint32_t head[2];
+  grt_gbuffer_info in;
+  grt_gbuffer_sub_info si;
+  if (std::fread(magic, 1, 8, file.f) != 8 || std::fread(head, 1, 8, file.f) != 8)
+    return fail(-EIO, name + "cannot read the header");
+  if (std::memcmp(magic, SUB_MAGIC, 8) != 0) return fail(-EINVAL, name + "not a g-buffer sub-sample file (magic)");
+  if (head[0] != GRT_GBUFFER_SUB_FILE_VERSION)
+    return fail(-EINVAL, name + "sub-sample file version " + std::to_string(head[0]) + ", this library reads " +
+                             std::to_string(GRT_GBUFFER_SUB_FILE_VERSION));
+  if (head[1] != sizeof(grt_gbuffer_info)) return fail(-EINVAL, name + "info block of another size");
+  if (std::fread(&in, 1, sizeof(in), file.f) != sizeof(in) || std::fread(&si, 1, sizeof(si), file.f) != sizeof(si))
+    return fail(-EIO, name + "cannot read the info blocks");
+  const grt_gbuffer_info bound = bound_info(info);
+  if (std::memcmp(&in, &bound, sizeof(in)) != 0)
+    return fail(-EINVAL, name + "the sub-sample set belongs to another g-buffer (its info block differs)");
+  if (int rc = grt_host::gbuffer_sub_check(info, &si, nullptr, nullptr)) return rc;
+  const uint64_t m = si.n_sub_pixels, n = si.n_sub_rays, l = si.n_sub_layers;
+  const uint64_t expect = SUB_HEADER_BYTES + 4 * m + (si.samples_per_axis ? payload_bytes(n, l) : 0);
+  if (length != expect)
+    return fail(-EINVAL, name + "file length " + std::to_string(length) + " disagrees with its sizes (" +
+                             std::to_string(expect) + " expected)");
+  if (!a) {  // size query
+    *sub = si;
+    return 0;
+  }
+  if (si.samples_per_axis == 0) {
+    *sub = si;
+    return 0;
+  }
+  if ((m && !sub_pixel) || !a->status || !a->stop || !a->steps || !a->sky_u || !a->sky_v || !a->sky_redshift ||
+      !a->layer_start || (l && (!a->object || !a->u || !a->v || !a->redshift || !a->radius)))
+    return fail(-EINVAL, "g-buffer: null sub-ray array");
+  bool ok = true;
+  auto get = [&](void* p, uint64_t bytes) {
+    if (ok && bytes) ok = std::fread(p, 1, bytes, file.f) == bytes;
+  };
+  get(sub_pixel, 4 * m);
+  get(a->layer_start, 8 * (n + 1));
+  get(a->sky_u, 8 * n);
+  get(a->sky_v, 8 * n);
+  get(a->sky_redshift, 8 * n);
+  get(a->u, 8 * l);
+  get(a->v, 8 * l);
+  get(a->redshift, 8 * l);
+  get(a->radius, 8 * l);
+  get(a->steps, 4 * n);
+  get(a->status, n);
+  get(a->stop, n);
+  get(a->object, l);
+  if (!ok) return fail(-EIO, name + "cannot read the arrays");
+  if (int rc = grt_host::gbuffer_sub_check(info, &si, sub_pixel, a)) return rc;
+  *sub = si;
   return 0;
 }
 

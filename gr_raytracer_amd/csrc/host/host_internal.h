@@ -44,6 +44,10 @@ int supersample_shard(grt_scene* s, int device, void* stream, const grt_row_shar
 // reader or an upload must hold before a kernel indexes by them.  -EINVAL with a message.
 int gbuffer_check_info(const grt_gbuffer_info* info);
 int gbuffer_check_arrays(const grt_gbuffer_info* info, const grt_gbuffer_arrays* arrays);
+// a sub-sample set's sizes against its buffer (arrays == nullptr: the sizes only), then its
+// sub_pixel list and arrays
+int gbuffer_sub_check(const grt_gbuffer_info* info, const grt_gbuffer_sub_info* sub, const uint32_t* sub_pixel,
+                      const grt_gbuffer_arrays* arrays);
 double rclamp_pub(double v, double lo, double hi);
 int camera_build(int geometry, double radius, double a, const double position[4], const double velocity[4],
                  double alpha, int64_t rows, int64_t cols, double phi, double theta, double psi,

@@ -12,6 +12,7 @@ Every call runs the HIP kernels in libgrt.so; there is no CPU path here.
 from __future__ import annotations
 
 import ctypes as C
+import errno
 import math
 from dataclasses import dataclass, field
 from pathlib import Path
@@ -224,16 +225,21 @@ class Scene:
         return res
 
     def trace_gbuffer(self, row0: int = 0, col0: int = 0, rows: Optional[int] = None, cols: Optional[int] = None,
-                      device: int = 0) -> "GBuffer":
+                      device: int = 0, adaptive: Optional[L.AdaptiveConfig] = None) -> "GBuffer":
         """1-spp exact trace of a rectangle that keeps its geometry buffer (grt_gbuffer_trace):
-        shade it again under any scene with the same shape key without integrating."""
+        shade it again under any scene with the same shape key without integrating.  With
+        `adaptive`, one `shade_section` with the scene as its own tracer follows, so the
+        buffer also holds the sub-rays of the pixels this scene's adaptive frame selects."""
         rows = self.rows - row0 if rows is None else rows
         cols = self.cols - col0 if cols is None else cols
         h = C.c_void_p()
         st = L.Stats()
         L.check(L.lib().grt_gbuffer_trace(self._s, device, row0, col0, rows, cols, C.byref(h), C.byref(st)),
                 "grt_gbuffer_trace")
-        return GBuffer(h, _stats_dict(st))
+        gb = GBuffer(h, _stats_dict(st))
+        if adaptive is not None:
+            gb.shade_section(self, adaptive=adaptive, tracer=self)
+        return gb
 
     def render_shard(self, band_rows: int, shard: int, n_shards: int, device: int = 0,
                      aux: bool = True) -> RenderResult:
@@ -538,6 +544,30 @@ def _gbuffer_host_arrays(info: L.GBufferInfo, arrays: Optional[dict] = None):
     return out, c
 
 
+def _gbuffer_sub_host_arrays(sub: L.GBufferSubInfo, arrays: Optional[dict] = None):
+    """_gbuffer_host_arrays for a sub-sample set: the twelve arrays over its sub-rays and
+    layers, and sub_pixel; returns (dict, grt_gbuffer_arrays, sub_pixel pointer)."""
+    sized = L.GBufferInfo(n_pixels=int(sub.n_sub_rays), n_layers=int(sub.n_sub_layers))
+    out, c = _gbuffer_host_arrays(sized, arrays)
+    m = int(sub.n_sub_pixels)
+    if arrays is None:
+        out["sub_pixel"] = np.zeros(m, np.uint32)
+    else:
+        out["sub_pixel"] = np.ascontiguousarray(arrays["sub_pixel"], np.uint32)
+        if out["sub_pixel"].shape != (m,):
+            raise L.GrtError(f"g-buffer array sub_pixel: shape {out['sub_pixel'].shape}, expected ({m},)")
+    return out, c, L.ptr(out["sub_pixel"], C.c_uint32)
+
+
+class GBufferMissing(L.GrtError):
+    """shade_section without a tracer met selected pixels the sub-sample set does not hold
+    (-ENODATA); `report` is the call's report (n_missing)."""
+
+    def __init__(self, msg: str, report: dict):
+        super().__init__(msg)
+        self.report = report
+
+
 class GBuffer:
     """Device-resident geometry buffer of a traced rectangle (grt_gbuffer): per pixel the
     trace's status, stop reason, steps and the celestial sphere's texture arguments; per
@@ -583,6 +613,110 @@ class GBuffer:
                 "grt_gbuffer_shade")
         res.stats = {"kernel_ms": float(ms.value)}
         return res
+
+    @property
+    def sub_info(self) -> L.GBufferSubInfo:
+        """Sizes of the sub-sample set (samples_per_axis 0: the buffer holds none)."""
+        out = L.GBufferSubInfo()
+        L.check(L.lib().grt_gbuffer_sub_info_get(self._h, C.byref(out)), "grt_gbuffer_sub_info_get")
+        return out
+
+    def sub_arrays(self) -> dict:
+        """The sub-sample set, downloaded: sub_pixel (block -> pixel) and the arrays of
+        grt_gbuffer_arrays over the sub-rays (block b, stratum s at b * spa^2 + s)."""
+        out, c, px = _gbuffer_sub_host_arrays(self.sub_info)
+        L.check(L.lib().grt_gbuffer_sub_download(self._h, px, C.byref(c)), "grt_gbuffer_sub_download")
+        return out
+
+    def set_sub_arrays(self, sub: L.GBufferSubInfo, arrays: dict) -> None:
+        """Replace the sub-sample set by host arrays (grt_gbuffer_sub_upload; checked)."""
+        held, c, px = _gbuffer_sub_host_arrays(sub, arrays)
+        L.check(L.lib().grt_gbuffer_sub_upload(self._h, C.byref(sub), px, C.byref(c)), "grt_gbuffer_sub_upload")
+
+    def supersample(self, tracer: "Scene", pixels, samples_per_axis: int) -> dict:
+        """Trace the sub-rays of `pixels` (indices into the rectangle) under `tracer` and
+        append them to the set; pixels already held are skipped.  Returns the traces' stats."""
+        px = np.ascontiguousarray(pixels, np.uint32).reshape(-1)
+        st = L.Stats()
+        L.check(L.lib().grt_gbuffer_supersample(tracer._s, self._h, samples_per_axis, len(px), L.ptr(px, C.c_uint32),
+                                                C.byref(st)), "grt_gbuffer_supersample")
+        return _stats_dict(st)
+
+    def shade_section(self, scene: "Scene", adaptive: Optional[L.AdaptiveConfig] = None,
+                      tracer: Optional["Scene"] = None, sampling_mask_xyza=None, failure_capacity: int = 0,
+                      log_events: bool = False):
+        """The adaptive frame of the buffer under `scene`'s appearance
+        (grt_gbuffer_shade_section): bit-identical to `render_section_ex` of a scene with
+        this appearance and the traced geometry, camera and integration parameters.
+        Selected pixels whose sub-rays the buffer does not hold are traced under `tracer`
+        and appended; without a tracer they raise GBufferMissing.  Returns (SectionResult,
+        report dict); the result's stats are the top-up's."""
+        n = int(self.info.n_pixels)
+        out = np.zeros((n, 4), np.float64)
+        cls = np.zeros(n, np.uint8)
+        status = np.zeros(n, np.uint8)
+        nsel = C.c_uint64(0)
+        mask = None
+        if sampling_mask_xyza is not None:
+            mask = np.ascontiguousarray(sampling_mask_xyza, np.float64)
+        cap = max(failure_capacity, 1)
+        fp, fs, fn = np.zeros(cap, np.uint32), np.zeros(cap, np.uint32), np.zeros(cap, np.uint32)
+        fst, fsp = np.zeros(cap, np.uint8), np.zeros(cap, np.uint8)
+        fails = L.SubsampleFailures(failure_capacity, L.ptr(fp, C.c_uint32), L.ptr(fs, C.c_uint32),
+                                    L.ptr(fst, C.c_uint8), 0, L.ptr(fsp, C.c_uint8) if log_events else None,
+                                    L.ptr(fn, C.c_uint32) if log_events else None)
+        rep = L.GBufferSectionReport()
+        rc = L.lib().grt_gbuffer_shade_section(scene._s, self._h, C.byref(adaptive or scene.adaptive),
+                                               L.dptr(mask) if mask is not None else None,
+                                               tracer._s if tracer is not None else None, L.dptr(out),
+                                               L.ptr(cls, C.c_uint8), L.ptr(status, C.c_uint8), C.byref(nsel),
+                                               C.byref(fails), C.byref(rep))
+        report = {"n_selected": int(rep.n_selected), "n_held": int(rep.n_held), "n_traced": int(rep.n_traced),
+                  "n_missing": int(rep.n_missing), "shade_ms": float(rep.shade_ms), "trace_ms": float(rep.trace_ms),
+                  "top_up": _stats_dict(rep.top_up)}
+        if rc == -errno.ENODATA:
+            msg = L.lib().grt_last_error().decode(errors="replace")
+            raise GBufferMissing(f"grt_gbuffer_shade_section failed ({rc}): {msg}", report)
+        L.check(rc, "grt_gbuffer_shade_section")
+        m = min(int(fails.count), failure_capacity)
+        rows = np.stack([fp[:m], fs[:m], fst[:m].astype(np.uint32)], axis=1)
+        if not log_events:
+            return SectionResult(out, cls, status, int(nsel.value), report["top_up"], int(fails.count), rows), report
+        failed = fst[:m] != 0
+        events = np.stack([fp[:m], fs[:m], fsp[:m].astype(np.uint32), fn[:m]], axis=1)[~failed]
+        a = self.arrays()  # the 1-spp rays' stop reasons and steps are the buffer's
+        return SectionResult(out, cls, status, int(nsel.value), report["top_up"], int(fails.count) - len(events),
+                             rows[failed], a["stop"], a["steps"], events), report
+
+    def save_sub(self, path) -> None:
+        """Write the sub-sample set's sidecar (grt_gbuffer_sub_write_file)."""
+        info, sub = self.info, self.sub_info
+        out, c, px = _gbuffer_sub_host_arrays(sub)
+        L.check(L.lib().grt_gbuffer_sub_download(self._h, px, C.byref(c)), "grt_gbuffer_sub_download")
+        L.check(L.lib().grt_gbuffer_sub_write_file(str(path).encode(), C.byref(info), C.byref(sub), px, C.byref(c)),
+                "grt_gbuffer_sub_write_file")
+
+    @staticmethod
+    def read_sub_file(path, info: L.GBufferInfo):
+        """(sub info, dict of arrays) of a sidecar bound to the buffer `info`, on the host."""
+        sub = L.GBufferSubInfo()
+        L.check(L.lib().grt_gbuffer_sub_read_file(str(path).encode(), C.byref(info), C.byref(sub), None, None),
+                "grt_gbuffer_sub_read_file")
+        out, c, px = _gbuffer_sub_host_arrays(sub)
+        L.check(L.lib().grt_gbuffer_sub_read_file(str(path).encode(), C.byref(info), C.byref(sub), px, C.byref(c)),
+                "grt_gbuffer_sub_read_file")
+        return sub, out
+
+    @staticmethod
+    def write_sub_file(path, info: L.GBufferInfo, sub: L.GBufferSubInfo, arrays: dict) -> None:
+        held, c, px = _gbuffer_sub_host_arrays(sub, arrays)
+        L.check(L.lib().grt_gbuffer_sub_write_file(str(path).encode(), C.byref(info), C.byref(sub), px, C.byref(c)),
+                "grt_gbuffer_sub_write_file")
+
+    def load_sub(self, path) -> None:
+        """Read a sidecar written for this buffer and make it the buffer's set."""
+        sub, arrays = self.read_sub_file(path, self.info)
+        self.set_sub_arrays(sub, arrays)
 
     def save(self, path) -> None:
         info = self.info

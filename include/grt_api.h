@@ -611,8 +611,9 @@ int grt_set_sequence_group(uint64_t rays);
  * The g-buffer trace always runs the exact arithmetic, whatever grt_set_arithmetic says (as
  * Kerr-Schild and the camera sequences do): re-shading reproduces the exact frame.  Scenes
  * with a GRT_OBJ_VOLUMETRIC_DISC are refused (-ENOTSUP): its colour is raymarched, not a
- * function of (u, v, redshift, temperature).  One rectangle at 1 spp on one device: no
- * offset lists, supersampling, row shards, sequences or multi-GPU frames.
+ * function of (u, v, redshift, temperature).  One rectangle on one device, at 1 spp or with
+ * the adaptive pass's sub-rays (the sub-sample set below): no offset lists, row shards,
+ * sequences or multi-GPU frames.
  * A grt_gbuffer is not synchronised: one host thread at a time per buffer. */
 typedef struct grt_gbuffer grt_gbuffer; /* device-resident, owns its arrays */
 
@@ -639,7 +640,8 @@ typedef struct grt_gbuffer_info {
   int32_t device;                  /* where the buffer lives (the traced device in a file) */
   uint32_t _pad;
   grt_gbuffer_shape shape;
-  /* provenance only, never compared: what was traced */
+  /* what was traced: never compared with an appearance scene, compared byte for byte with
+   * the tracer of grt_gbuffer_supersample */
   grt_camera_desc camera;
   uint64_t max_steps;
   double max_radius, step_size, epsilon, horizon_epsilon;
@@ -710,6 +712,92 @@ int grt_gbuffer_shape_compatible(const grt_gbuffer_shape* traced, const grt_scen
 #define GRT_GBUFFER_FILE_VERSION 1
 int grt_gbuffer_write_file(const char* path, const grt_gbuffer_info* info, const grt_gbuffer_arrays* arrays);
 int grt_gbuffer_read_file(const char* path, grt_gbuffer_info* info, const grt_gbuffer_arrays* arrays);
+
+/* ---- Supersampled g-buffer: the adaptive frame, re-shaded bit for bit ----
+ * A buffer optionally holds a sub-sample set: for some of its pixels, the samples_per_axis^2
+ * jittered sub-rays of the adaptive pass (raytracer.rs:320-384), each reduced to exactly
+ * what a 1-spp ray is reduced to above.  The jitter of a sub-ray depends on (row, col,
+ * stratum, samples_per_axis) alone, so a held pixel's sub-rays serve every appearance; which
+ * pixels an adaptive frame supersamples depends on the appearance, so the set grows.
+ *   sub_pixel[n_sub_pixels]   pixel index in the buffer's rectangle, in append order (block b);
+ *   a second grt_gbuffer_arrays over n_sub_rays = n_sub_pixels * spa^2 rays and n_sub_layers
+ *   layers: sub-ray b * spa^2 + s is stratum s (row-major, spa columns) of block b.
+ * The set is append-only; it never holds a GRT_FLAG_HIT_OVERFLOW ray.  Still outside the
+ * buffer: sequences, row shards, the multi-GPU frame, VolumetricDisc scenes, the fused
+ * arithmetic. */
+typedef struct grt_gbuffer_sub_info {
+  uint32_t samples_per_axis; /* 0: the buffer holds no set */
+  uint32_t _pad;
+  uint64_t n_sub_pixels;
+  uint64_t n_sub_rays;       /* n_sub_pixels * samples_per_axis^2 */
+  uint64_t n_sub_layers;
+} grt_gbuffer_sub_info;
+
+typedef struct grt_gbuffer_section_report {
+  uint64_t n_selected; /* pixels the selection picked under this appearance */
+  uint64_t n_held;     /* of those, held by the set when the call began */
+  uint64_t n_traced;   /* of those, traced and appended by this call */
+  uint64_t n_missing;  /* of those, still missing when the call returned (-ENODATA) */
+  double shade_ms;     /* event time: 1-spp shade, floor, select, split, sub-ray shade, average */
+  double trace_ms;     /* event time of the top-up's traces, scan and fill */
+  grt_stats top_up;    /* the top-up's counters (rays = n_traced * spa^2) */
+} grt_gbuffer_section_report;
+
+/* Trace the sub-rays of `pixels` (n indices into the buffer's rectangle, any order,
+ * duplicates allowed) under `tracer` and append them to the set.  Pixels already held are
+ * skipped; the rest are appended in ascending pixel index, traced with the exact kernels
+ * in chunks of grt_set_sub_chunk sub-rays.  A chunk that loses hit candidates grows the pool
+ * and is traced again (at most 3 traces, else -ENOMEM).  -EINVAL when spa is 0 or differs
+ * from the set's, when a pixel is outside the rectangle, when the tracer's shape key
+ * differs from the buffer's, or when its camera, max_steps, max_radius, step_size, epsilon
+ * or horizon_epsilon differ byte for byte from the recorded ones (grt_last_error names the
+ * field): the sub-rays must belong to the frame the buffer holds.  stats (nullable): the
+ * counters of this call's traces. */
+int grt_gbuffer_supersample(grt_scene* tracer, grt_gbuffer* gb, uint32_t samples_per_axis, uint64_t n,
+                            const uint32_t* pixels, grt_stats* stats);
+/* The adaptive frame of the buffer under `appearance`: what grt_render_section_ex writes for
+ * the buffer's rectangle of a scene with this appearance and the traced geometry, camera
+ * and integration parameters, bit for bit (f64 xyza, class and status of the 1-spp pass,
+ * n_supersampled, the failed sub-sample list).  1-spp shade, luminance floor, selection,
+ * then the held sub-rays of the selected pixels shaded and averaged, all on the buffer's
+ * device.  Selected pixels the set does not hold: with `tracer` (nullable; may be
+ * `appearance`) they are traced once and appended (grt_gbuffer_supersample's rules), else
+ * the call returns -ENODATA with report->n_missing set and the outputs untouched.  With
+ * sampling_mask_xyza the selected pixels are painted and nothing is supersampled; with
+ * cfg->enabled == 0 and no mask the frame is the 1-spp one.  cfg->samples_per_axis must
+ * equal the set's when one exists.  class_out, status_out, n_supersampled, failures and
+ * report are nullable. */
+int grt_gbuffer_shade_section(grt_scene* appearance, grt_gbuffer* gb, const grt_adaptive_config* cfg,
+                              const double* sampling_mask_xyza, grt_scene* tracer, double* xyza_out,
+                              uint8_t* class_out, uint8_t* status_out, uint64_t* n_supersampled,
+                              grt_subsample_failures* failures, grt_gbuffer_section_report* report);
+int grt_gbuffer_sub_info_get(const grt_gbuffer* gb, grt_gbuffer_sub_info* out);
+/* Copy the set to the host: sub_pixel[n_sub_pixels] and the arrays sized by
+ * grt_gbuffer_sub_info_get (n_sub_rays for the per-pixel ones, n_sub_layers per layer). */
+int grt_gbuffer_sub_download(const grt_gbuffer* gb, uint32_t* sub_pixel, const grt_gbuffer_arrays* host);
+/* Replace the buffer's set by host arrays.  They are held to the checks a file gets, and
+ * sub_pixel must be < n_pixels and free of duplicates, the statuses free of
+ * GRT_FLAG_HIT_OVERFLOW: -EINVAL, never a crash. */
+int grt_gbuffer_sub_upload(grt_gbuffer* gb, const grt_gbuffer_sub_info* sub, const uint32_t* sub_pixel,
+                           const grt_gbuffer_arrays* host);
+
+/* Host only: the set's sidecar file (a .grtg file keeps its bytes and its version).
+ * Little-endian, no padding:
+ *   8 B   magic "GRTGSUB\0"
+ *   u32   version (GRT_GBUFFER_SUB_FILE_VERSION), u32 sizeof(grt_gbuffer_info)
+ *   grt_gbuffer_info          a copy of the buffer's, binding the set to it
+ *   grt_gbuffer_sub_info
+ *   sub_pixel u32[n_sub_pixels]
+ *   the twelve arrays in the .grtg order, over n_sub_rays and n_sub_layers
+ * Reading takes two calls, as grt_gbuffer_read_file: arrays == NULL checks the header and
+ * the length and fills *sub.  `info` is the buffer's: a sidecar whose copy differs from it
+ * (the device aside) is refused with -EINVAL, as are a wrong magic or version, sizes that
+ * disagree, and arrays that fail grt_gbuffer_sub_upload's checks. */
+#define GRT_GBUFFER_SUB_FILE_VERSION 1
+int grt_gbuffer_sub_write_file(const char* path, const grt_gbuffer_info* info, const grt_gbuffer_sub_info* sub,
+                               const uint32_t* sub_pixel, const grt_gbuffer_arrays* arrays);
+int grt_gbuffer_sub_read_file(const char* path, const grt_gbuffer_info* info, grt_gbuffer_sub_info* sub,
+                              uint32_t* sub_pixel, const grt_gbuffer_arrays* arrays);
 
 /* The device hit pool that keeps the window candidates past a ray's GRT_MAX_HITS slots
  * (no reference counterpart: the reference's per-ray Vec grows, scene.rs:139-152).
