@@ -12,7 +12,7 @@ from .scene import (  # noqa: F401
     build_camera, cartesian_to_boyer_lindquist, cartesian_to_spherical, default_adaptive, device_count,
     kerr_temperature_lut, load_scene, r_isco, srgb_to_xyza, stationary_velocity, xyz_to_srgb8, Trajectories, ray_at,
     write_trajectory_csv, format_f64, set_arithmetic, get_arithmetic, set_sequence_group, load_camera_path,
-    GBuffer, GBufferMissing, gbuffer_compatible,
+    GBuffer, GBufferMissing, gbuffer_compatible, GBufferSequence, shade_sequence,
 )
 
 __all__ = [
@@ -21,5 +21,5 @@ __all__ = [
     "default_adaptive", "device_count", "kerr_temperature_lut", "load_scene", "r_isco", "srgb_to_xyza",
     "stationary_velocity", "xyz_to_srgb8", "Trajectories", "ray_at", "write_trajectory_csv", "format_f64",
     "set_arithmetic", "get_arithmetic", "set_sequence_group", "load_camera_path",
-    "GBuffer", "GBufferMissing", "gbuffer_compatible",
+    "GBuffer", "GBufferMissing", "gbuffer_compatible", "GBufferSequence", "shade_sequence",
 ]

@@ -184,6 +184,12 @@ class GBufferSectionReport(C.Structure):
                 ("n_missing", C.c_uint64), ("shade_ms", _d), ("trace_ms", _d), ("top_up", Stats)]
 
 
+class GBufferSequenceReport(C.Structure):
+    """grt_gbuffer_sequence_report: launch groups, traces and times of grt_gbuffer_trace_sequence."""
+    _fields_ = [("n_frames", C.c_uint32), ("n_launches", C.c_uint32), ("frames_per_launch", C.c_uint32),
+                ("n_traces", C.c_uint32), ("wall_ms", _d), ("trace_ms", _d), ("fill_ms", _d)]
+
+
 class Health(C.Structure):
     _fields_ = [
         ("rays", C.c_uint64), ("failed", C.c_uint64), ("null_violations", C.c_uint64), ("max_null", _d),
@@ -319,6 +325,9 @@ def lib() -> C.CDLL:
         "grt_gbuffer_shade": (C.c_int, [vp, vp, C.POINTER(C.c_float), C.POINTER(C.c_uint8), C.POINTER(C.c_uint8), _pd,
                                         C.POINTER(C.c_float)]),
         "grt_gbuffer_destroy": (C.c_int, [vp]),
+        "grt_gbuffer_trace_sequence": (C.c_int, [vp, C.c_int, u32, C.POINTER(CameraDesc), C.POINTER(vp),
+                                                 C.POINTER(Stats), C.POINTER(GBufferSequenceReport)]),
+        "grt_gbuffer_shade_sequence": (C.c_int, [vp, u32, C.POINTER(vp), C.POINTER(FrameOut), C.POINTER(C.c_float)]),
         "grt_gbuffer_shape_of": (None, [C.POINTER(SceneDesc), C.POINTER(GBufferShape)]),
         "grt_gbuffer_compatible": (C.c_int, [C.POINTER(SceneDesc), C.POINTER(SceneDesc)]),
         "grt_gbuffer_shape_compatible": (C.c_int, [C.POINTER(GBufferShape), C.POINTER(SceneDesc)]),
@@ -390,6 +399,7 @@ EXPORTED_SYMBOLS = [
     "grt_gbuffer_shape_compatible", "grt_gbuffer_write_file", "grt_gbuffer_read_file",
     "grt_gbuffer_supersample", "grt_gbuffer_shade_section", "grt_gbuffer_sub_info_get", "grt_gbuffer_sub_download",
     "grt_gbuffer_sub_upload", "grt_gbuffer_sub_write_file", "grt_gbuffer_sub_read_file",
+    "grt_gbuffer_trace_sequence", "grt_gbuffer_shade_sequence",
 ]
 
 

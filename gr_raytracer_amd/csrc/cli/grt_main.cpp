@@ -12,6 +12,9 @@
 //     | render-ray-at -p x,y,z -d x,y,z [--filename rendered-ray-at.csv]
 //     | gbuffer --filename a.grtg [--adaptive]
 //     | reshade --gbuffer a.grtg [--filename out.png|out.hdr] [--adaptive]
+//     | gbuffer-sequence --camera-path P --filename-pattern a-%04d.grtg [--first-index 0]
+//     | reshade-sequence --gbuffer-pattern a-%04d.grtg --frames K [--first-index 0]
+//                        [--filename-pattern frame-%04d.png]
 //     | blackbody -t T [-r Z]
 //     | blackbody-spectrum [--min-temperature T] [--max-temperature T] [--min-redshift Z]
 //                          [--max-redshift Z] [--width N] [--height N] [-f FILE]
@@ -44,6 +47,15 @@
 // the sidecar if there is one, traces the sub-rays of the pixels its appearance selects
 // and the set does not hold (with the file's camera and integration parameters), writes
 // what `render` of its config writes, and rewrites the sidecar when the set grew.
+// gbuffer-sequence / reshade-sequence (not in the reference): the two above for a camera
+// path.  `gbuffer-sequence` traces the path's frames stacked over one load of the scene
+// (grt_gbuffer_trace_sequence) and writes frame k to --filename-pattern at index
+// --first-index + k: the bytes `gbuffer` writes for that line's camera flags.
+// `reshade-sequence` loads the --frames files of --gbuffer-pattern from --first-index on,
+// shades them in stacked launches under its config's appearance (grt_gbuffer_shade_sequence)
+// and writes each frame, tone-mapped on its own, as `reshade` writes it.  Neither takes
+// --adaptive: a sequence's files are ordinary g-buffers, and the adaptive frame of one is
+// `reshade --adaptive` of that file.
 #include <algorithm>
 #include <charconv>
 #include <chrono>
@@ -78,6 +90,10 @@ static int usage(const char* msg) {
                "       grt [global options] --config-file FILE reshade --gbuffer F.grtg [--filename F] [--adaptive]\n"
                "           (--adaptive: the config's [adaptive_sampling]; the sub-rays live in F.grtg.sub)\n"
                "           (reshade: --width/--height must be the buffer's frame; camera flags are ignored)\n"
+               "       grt [global options] --config-file FILE gbuffer-sequence --camera-path P\n"
+               "           --filename-pattern F-%%04d.grtg [--first-index N]\n"
+               "       grt [global options] --config-file FILE reshade-sequence --gbuffer-pattern F-%%04d.grtg\n"
+               "           --frames K [--first-index N] [--filename-pattern frame-%%04d.png]\n"
                "       grt [global options] blackbody -t T [-r Z]\n"
                "       grt [global options] blackbody-spectrum [--min-temperature T] [--max-temperature T]\n"
                "           [--min-redshift Z] [--max-redshift Z] [--width N] [--height N] [-f FILE]\n",
@@ -443,6 +459,9 @@ int main(int argc, char** argv) {
   uint32_t band_rows = 16;
   std::string camera_path, filename_pattern = "frame-%04d.png";  // render-sequence
   std::string gbuffer_file;  // reshade
+  std::string gbuffer_pattern;  // reshade-sequence
+  long long n_frames = -1;      // reshade-sequence --frames
+  bool have_pattern = false;    // --filename-pattern given (gbuffer-sequence has no default)
   bool gbuffer_adaptive = false;  // gbuffer / reshade --adaptive: the config's [adaptive_sampling]
   long long first_index = 0;
   std::vector<std::string> args(argv + 1, argv + argc);
@@ -466,12 +485,16 @@ int main(int argc, char** argv) {
     };
     std::string v;
     if (action.empty() && (a == "render" || a == "render-sequence" || a == "render-ray" || a == "render-ray-at" ||
-                           a == "blackbody" || a == "blackbody-spectrum" || a == "gbuffer" || a == "reshade")) {
+                           a == "blackbody" || a == "blackbody-spectrum" || a == "gbuffer" || a == "reshade" ||
+                           a == "gbuffer-sequence" || a == "reshade-sequence")) {
       action = a;
       continue;
     }
     if (action.empty() && a == "--show-sampling-mask") { opts.show_sampling_mask = 1; continue; }
     if ((action == "gbuffer" || action == "reshade") && a == "--adaptive") { gbuffer_adaptive = true; continue; }
+    if ((action == "gbuffer-sequence" || action == "reshade-sequence") && a == "--adaptive")
+      return usage((action + " has no --adaptive: the stacked re-shade is 1 spp; for an adaptive frame run `gbuffer "
+                    "--adaptive` / `reshade --adaptive` per frame (a sequence's .grtg files are ordinary g-buffers)").c_str());
     if (!next(v)) return usage(("missing value for " + a).c_str());
     std::vector<double> nums;
     auto bad = [&]() { return usage(("invalid value '" + v + "' for '" + a + "'").c_str()); };
@@ -516,13 +539,22 @@ int main(int argc, char** argv) {
     if (a == "--resource-root") { resource_root = v; continue; }
     if (a == "--raw-out") { raw_out = v; continue; }
     if (!action.empty()) {  // subcommand options
-      if (a == "--filename" && action != "render-sequence") filename = v;
+      const bool seq_action = action == "render-sequence" || action == "gbuffer-sequence" || action == "reshade-sequence";
+      if (a == "--filename" && !seq_action) filename = v;
       else if (action == "reshade" && a == "--gbuffer") gbuffer_file = v;
-      else if (action == "render-sequence" && a == "--camera-path") camera_path = v;
-      else if (action == "render-sequence" && a == "--filename-pattern") filename_pattern = v;
-      else if (action == "render-sequence" && a == "--first-index") {
+      else if ((action == "render-sequence" || action == "gbuffer-sequence") && a == "--camera-path") camera_path = v;
+      else if (seq_action && a == "--filename-pattern") {
+        filename_pattern = v;
+        have_pattern = true;
+      }
+      else if (seq_action && a == "--first-index") {
         if (!int_in(0, 1000000000ull, &iv)) return bad();
         first_index = iv;
+      }
+      else if (action == "reshade-sequence" && a == "--gbuffer-pattern") gbuffer_pattern = v;
+      else if (action == "reshade-sequence" && a == "--frames") {
+        if (!int_in(0, 4294967295ull, &iv)) return bad();
+        n_frames = iv;
       }
       else if (action == "render" && (a == "--from-row" || a == "--from-col" || a == "--to-row" || a == "--to-col")) {
         if (!int_in(0, 4294967295ull, &iv)) return bad();  // Option<u32>
@@ -593,8 +625,8 @@ int main(int argc, char** argv) {
     else return usage(("unknown argument " + a).c_str());
   }
   if (action.empty())
-    return usage("missing subcommand (render, render-sequence, render-ray, render-ray-at, gbuffer, reshade, blackbody, "
-                 "blackbody-spectrum)");
+    return usage("missing subcommand (render, render-sequence, render-ray, render-ray-at, gbuffer, reshade, "
+                 "gbuffer-sequence, reshade-sequence, blackbody, blackbody-spectrum)");
   if (action == "blackbody") {  // run_blackbody (cli/blackbody.rs:7-25): no scene needed
     if (!have_temperature) return usage("blackbody needs --temperature");
     double xyz[3];
@@ -631,6 +663,23 @@ int main(int argc, char** argv) {
   if (action == "reshade" && gbuffer_file.empty()) return usage("reshade needs --gbuffer");
   if ((action == "gbuffer" || action == "reshade") && !multi_devices.empty())
     return usage("gbuffer and reshade run on one GPU (--device); --gpus / --devices do not apply");
+  if (action == "gbuffer-sequence" || action == "reshade-sequence") {  // every usage error before the GPU is touched
+    std::string probe;
+    if (!multi_devices.empty())
+      return usage((action + " runs on one GPU (--device); --gpus / --devices do not apply").c_str());
+    if (action == "gbuffer-sequence" && camera_path.empty()) return usage("gbuffer-sequence needs --camera-path");
+    if (action == "gbuffer-sequence" && !have_pattern)
+      return usage("gbuffer-sequence needs --filename-pattern (a-%04d.grtg)");
+    if (action == "reshade-sequence" && gbuffer_pattern.empty()) return usage("reshade-sequence needs --gbuffer-pattern");
+    if (action == "reshade-sequence" && n_frames < 0) return usage("reshade-sequence needs --frames");
+    if (action == "reshade-sequence" && n_frames == 0) return usage("--frames must be at least 1");
+    if (action == "reshade-sequence" && !expand_pattern(gbuffer_pattern, first_index, &probe))
+      return usage("--gbuffer-pattern needs one %d or %0Nd conversion for the frame index");
+    if (!expand_pattern(filename_pattern, first_index, &probe))
+      return usage("--filename-pattern needs one %d or %0Nd conversion for the frame index");
+    if (action == "reshade-sequence" && !raw_out.empty() && !expand_pattern(raw_out, first_index, &probe))
+      return usage("--raw-out of reshade-sequence is a pattern: it needs one %d or %0Nd conversion");
+  }
   if (filename.empty())
     filename = (action == "render" || action == "reshade") ? "render.png" : (action == "render-ray" ? "rendered-ray.csv" : "rendered-ray-at.csv");
   if (config_file.empty()) return usage("Config file is required for this action");
@@ -645,8 +694,31 @@ int main(int argc, char** argv) {
       return usage("--raw-out of render-sequence is a pattern: it needs one %d or %0Nd conversion");
     if (!load_camera_path(camera_path, path_cams, &perr)) return usage(perr.c_str());
   }
+  if (action == "gbuffer-sequence") {
+    std::string perr;
+    if (config_file.empty()) return usage("Config file is required for this action");
+    if (!load_camera_path(camera_path, path_cams, &perr)) return usage(perr.c_str());
+  }
 
   grt_gbuffer_info gb_info;
+  if (action == "reshade-sequence") {  // every file's header and length, before the GPU is touched
+    for (long long k = 0; k < n_frames; ++k) {
+      std::string name;
+      (void)expand_pattern(gbuffer_pattern, first_index + k, &name);
+      if (grt_gbuffer_read_file(name.c_str(), &gb_info, nullptr)) {
+        std::fprintf(stderr, "Error: %s\n", grt_last_error());
+        return 1;
+      }
+      if (gb_info.row0 != 0 || gb_info.col0 != 0 || (int64_t)gb_info.rows != gb_info.camera.rows ||
+          (int64_t)gb_info.cols != gb_info.camera.cols) {
+        std::fprintf(stderr, "Error: %s holds a rectangle, not a whole frame\n", name.c_str());
+        return 1;
+      }
+      if ((int64_t)gb_info.cols != opts.width || (int64_t)gb_info.rows != opts.height)
+        return usage(("--width / --height must be the frame of " + name + ", " + std::to_string(gb_info.cols) + " x " +
+                      std::to_string(gb_info.rows)).c_str());
+    }
+  }
   if (action == "reshade") {  // the file's header and length, before the GPU is touched
     if (config_file.empty()) return usage("Config file is required for this action");
     if (grt_gbuffer_read_file(gbuffer_file.c_str(), &gb_info, nullptr)) {
@@ -875,6 +947,111 @@ int main(int argc, char** argv) {
     elapsed();
     grt_gbuffer_destroy(gb);
     if (tracer) grt_scene_destroy(tracer);
+    grt_scene_destroy(scene);
+    grt_host_scene_destroy(hs);
+    return 0;
+  }
+  if (action == "gbuffer-sequence") {  // the camera path traced stacked, one .grtg per camera
+    const uint32_t K = (uint32_t)path_cams.size();
+    std::vector<grt_camera_desc> cams(K);
+    for (uint32_t k = 0; k < K; ++k) {
+      const std::vector<double>& c = path_cams[k];
+      if (grt_host_scene_camera(hs, c.data(), c[3], c[4], c[5], &cams[k])) {
+        std::fprintf(stderr, "Error: camera %u of %s: %s\n", k, camera_path.c_str(), grt_last_error());
+        return 1;
+      }
+    }
+    std::vector<grt_gbuffer*> gbs(K, nullptr);
+    grt_stats st;
+    grt_gbuffer_sequence_report rep;
+    t_phase = clk::now();
+    if (grt_gbuffer_trace_sequence(scene, device, K, cams.data(), gbs.data(), &st, &rep)) {
+      std::fprintf(stderr, "Error: %s\n", grt_last_error());
+      return 1;
+    }
+    ph_render = ms_since(t_phase);
+    t_phase = clk::now();
+    unsigned long long layers = 0;
+    for (uint32_t k = 0; k < K; ++k) {
+      std::string name;
+      (void)expand_pattern(filename_pattern, first_index + k, &name);
+      if (grt_gbuffer_info_get(gbs[k], &gb_info)) return 1;
+      GBufferHost host(gb_info.n_pixels, gb_info.n_layers);
+      const grt_gbuffer_arrays arr = host.arrays();
+      if (grt_gbuffer_download(gbs[k], &arr) || grt_gbuffer_write_file(name.c_str(), &gb_info, &arr)) {
+        std::fprintf(stderr, "Error: %s\n", grt_last_error());
+        return 1;
+      }
+      layers += gb_info.n_layers;
+      std::fprintf(stderr, "[grt] INFO saved g-buffer to %s\n", name.c_str());
+    }
+    ph_write = ms_since(t_phase);
+    std::fprintf(stderr, "[grt] %llu rays, %llu accepted steps, %llu attempts, kernel %.1f ms; g-buffers: %llu layers, "
+                 "scan + fill + split %.2f ms\n", (unsigned long long)st.rays, (unsigned long long)st.accepted_steps,
+                 (unsigned long long)st.attempts, st.kernel_ms, layers, rep.fill_ms);
+    std::fprintf(stderr, "[grt] sequence: %u frames in %u stacked launch(es) of up to %u, %u trace(s)\n", rep.n_frames,
+                 rep.n_launches, rep.frames_per_launch, rep.n_traces);
+    std::fprintf(stderr, "[grt] phases (ms): load %.1f, create %.1f, hip init %.1f, render %.1f, output %.1f, "
+                 "write %.1f, since start %.1f\n", ph_load, ph_create, ph_init, ph_render, ph_output, ph_write,
+                 ms_since(t_start));
+    elapsed();
+    for (grt_gbuffer* g : gbs) grt_gbuffer_destroy(g);
+    grt_scene_destroy(scene);
+    grt_host_scene_destroy(hs);
+    return 0;
+  }
+  if (action == "reshade-sequence") {  // K traced frames under this config's appearance, shaded stacked
+    const uint32_t K = (uint32_t)n_frames, w = (uint32_t)opts.width, h = (uint32_t)opts.height;
+    const size_t n = (size_t)w * h;
+    std::vector<grt_gbuffer*> gbs(K, nullptr);
+    unsigned long long layers = 0;
+    t_phase = clk::now();
+    for (uint32_t k = 0; k < K; ++k) {
+      std::string name;
+      (void)expand_pattern(gbuffer_pattern, first_index + k, &name);
+      if (grt_gbuffer_read_file(name.c_str(), &gb_info, nullptr)) {  // the sizes (checked before the load)
+        std::fprintf(stderr, "Error: %s\n", grt_last_error());
+        return 1;
+      }
+      GBufferHost host(gb_info.n_pixels, gb_info.n_layers);
+      const grt_gbuffer_arrays arr = host.arrays();
+      if (grt_gbuffer_read_file(name.c_str(), &gb_info, &arr) || grt_gbuffer_upload(&gb_info, &arr, device, &gbs[k])) {
+        std::fprintf(stderr, "Error: %s\n", grt_last_error());
+        return 1;
+      }
+      layers += gb_info.n_layers;
+    }
+    std::vector<double> xyza(n * 4 * K);
+    grt_frame_out fo{nullptr, xyza.data(), nullptr, nullptr, nullptr, nullptr};
+    float shade_ms = 0;
+    if (grt_gbuffer_shade_sequence(scene, K, gbs.data(), &fo, &shade_ms)) {
+      std::fprintf(stderr, "Error: %s\n", grt_last_error());
+      return 1;
+    }
+    ph_render = ms_since(t_phase);
+    std::fprintf(stderr, "[grt] re-shaded %u frames of %llu pixels, %llu layers, kernel %.2f ms\n", K,
+                 (unsigned long long)n, layers, shade_ms);
+    for (uint32_t k = 0; k < K; ++k) {  // each frame tone-mapped on its own, as `reshade` does
+      std::string name, raw;
+      (void)expand_pattern(filename_pattern, first_index + k, &name);
+      if (!raw_out.empty()) (void)expand_pattern(raw_out, first_index + k, &raw);
+      const bool hdr = name.size() >= 4 && name.compare(name.size() - 4, 4, ".hdr") == 0;
+      if (hdr) {
+        std::fprintf(stderr, "[grt] INFO Creating HDR image\n");
+      } else {
+        std::fprintf(stderr, "[grt] INFO Creating non-HDR image\n");
+        std::fprintf(stderr, "[grt] INFO Tone mapping method: %s\n",
+                     opts.tone_mapping == GRT_TONE_GLOBAL_LINEAR ? "GlobalLinear" : "Reinhard");
+      }
+      const std::vector<double> f_xyza(xyza.begin() + n * 4 * k, xyza.begin() + n * 4 * (k + 1));
+      if (int wrc = write_frame(name, raw, f_xyza, w, h, opts.tone_mapping, device, &ph_output, &ph_write)) return wrc;
+      std::fprintf(stderr, "[grt] INFO saved image to %s\n", name.c_str());
+    }
+    std::fprintf(stderr, "[grt] phases (ms): load %.1f, create %.1f, hip init %.1f, render %.1f, output %.1f, "
+                 "write %.1f, since start %.1f\n", ph_load, ph_create, ph_init, ph_render, ph_output, ph_write,
+                 ms_since(t_start));
+    elapsed();
+    for (grt_gbuffer* g : gbs) grt_gbuffer_destroy(g);
     grt_scene_destroy(scene);
     grt_host_scene_destroy(hs);
     return 0;

@@ -2704,6 +2704,267 @@ int grt_gbuffer_shade(grt_scene* s, const grt_gbuffer* gb, float* xyza_out, uint
 
 }  // extern "C"
 
+// ---- geometry buffers of a camera sequence (grt_api.h) ----
+namespace {
+struct GbSeqTimes {
+  unsigned long long acc[8] = {0, 0, 0, 0, 0, 0, 0, 0};  // as trace_sync's
+  double trace_ms = 0.0, fill_ms = 0.0;
+  uint32_t traces = 0;
+};
+
+// One launch group: the stacked 1-spp trace of the group's frames through the sequence unit,
+// the layer scan and the fill over the whole stack in slot order (frame after frame), then
+// the cut into one buffer per frame: device-to-device copies of the frame's slice of every
+// array, and its layer_start rebased to 0 at its first pixel.  Appends the buffers to `made`.
+int gbuffer_sequence_group(grt_scene* s, DeviceCopy& dc, int device, const grt::CamTable& ct,
+                           const grt_camera_desc* cameras, uint32_t rows, uint32_t cols,
+                           std::vector<std::unique_ptr<grt_gbuffer>>& made, GbSeqTimes* T) {
+  int rc;
+  const uint32_t kg = ct.n_cams;
+  const uint64_t per = (uint64_t)rows * cols, n = per * kg;
+  DevBuf status, stop, steps, sky_u, sky_v, sky_z, layer_start, xyza, cls, hits, counts, temp;
+  if ((rc = status.alloc(n)) || (rc = stop.alloc(n)) || (rc = steps.alloc(4 * n)) || (rc = sky_u.alloc(8 * n)) ||
+      (rc = sky_v.alloc(8 * n)) || (rc = sky_z.alloc(8 * n)) || (rc = layer_start.alloc(8 * (n + 1))) ||
+      (rc = xyza.alloc(16 * n)) || (rc = cls.alloc(n)) || (rc = hits.alloc(4 * n)) || (rc = counts.alloc(8 * (n + 1))))
+    return rc;
+  size_t temp_bytes = 0;
+  HIP_TRY(grt::gbuffer_layer_scan(nullptr, nullptr, n, nullptr, nullptr, nullptr, &temp_bytes, nullptr));
+  if ((rc = temp.alloc(temp_bytes))) return rc;
+  const grt::WorkList wl = rect_worklist(0, 0, kg * rows, cols);
+  const grt::Outputs o{(float*)xyza.p,     (uint8_t*)cls.p,  (uint8_t*)status.p, nullptr,
+                       (uint32_t*)steps.p, (uint8_t*)stop.p, (uint32_t*)hits.p};
+  unsigned long long acc[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+  float ms = 0;
+  // the whole group again while its trace loses candidates (grt_gbuffer_trace)
+  for (int traces = 1;; ++traces) {
+    unsigned long long need = 0;
+    acc[3] = 0;
+    ++T->traces;
+    if ((rc = trace_sync(s, dc, wl, o, acc, &ms, &need, &ct, true))) return rc;
+    if (acc[3] == 0) break;
+    if (traces == 3 || dc.pool_cap >= POOL_MAX)
+      return fail(-ENOMEM, "the hit pool still overflows after " + std::to_string(traces) + " traces");
+    if ((rc = ensure_pool(dc, need + need / 4))) return rc;
+  }
+  hipStream_t st = nullptr;
+  if ((rc = stream_order(dc, st))) return rc;
+  HIP_TRY(hipEventRecord(dc.ev0, st));
+  HIP_TRY(grt::gbuffer_layer_scan((const uint8_t*)status.p, (const uint32_t*)hits.p, n, (uint64_t*)counts.p,
+                                  (uint64_t*)layer_start.p, temp.p, &temp_bytes, st));
+  // where each frame's layers begin in the stack's, and the total
+  std::vector<uint64_t> base(kg + 1);
+  for (uint32_t f = 0; f <= kg; ++f)
+    HIP_TRY(hipMemcpy(&base[f], (const uint64_t*)layer_start.p + per * f, 8, hipMemcpyDeviceToHost));
+  const uint64_t total = base[kg];
+  DevBuf object, u, v, z, radius;
+  if ((rc = object.alloc(total)) || (rc = u.alloc(8 * total)) || (rc = v.alloc(8 * total)) ||
+      (rc = z.alloc(8 * total)) || (rc = radius.alloc(8 * total)))
+    return rc;
+  grt::Workspace ws;
+  if ((rc = ensure_workspace(dc, n, &ws))) return rc;  // the carving of the trace above
+  ws.pool = dc.d_pool;
+  const grt::GBufferArrays stack{n,
+                                 (const uint8_t*)status.p,
+                                 (const uint8_t*)stop.p,
+                                 (const uint64_t*)layer_start.p,
+                                 (double*)sky_u.p,
+                                 (double*)sky_v.p,
+                                 (double*)sky_z.p,
+                                 (uint8_t*)object.p,
+                                 (double*)u.p,
+                                 (double*)v.p,
+                                 (double*)z.p,
+                                 (double*)radius.p};
+  HIP_TRY(grt::seq::launch_gbuffer_fill(s->desc.geometry, dc.d_scene, wl, ws, stack, st, ct));
+  const size_t first = made.size();
+  for (uint32_t f = 0; f < kg; ++f) {
+    std::unique_ptr<grt_gbuffer> gb(new grt_gbuffer());
+    grt_gbuffer_info& info = gb->info;
+    info.row0 = 0;
+    info.col0 = 0;
+    info.rows = rows;
+    info.cols = cols;
+    info.n_pixels = per;
+    info.n_layers = base[f + 1] - base[f];
+    info.device = device;
+    grt_gbuffer_shape_of(&s->desc, &info.shape);
+    info.camera = cameras[f];
+    info.max_steps = s->desc.max_steps;
+    info.max_radius = s->desc.max_radius;
+    info.step_size = s->desc.step_size;
+    info.epsilon = s->desc.epsilon;
+    info.horizon_epsilon = s->desc.horizon_epsilon;
+    if ((rc = gb->alloc_pixels()) || (rc = gb->alloc_layers())) return rc;
+    const uint64_t p0 = per * f, l0 = base[f], nl = info.n_layers;
+    auto cut = [&](DevBuf& dst, const DevBuf& src, uint64_t at, uint64_t count, uint64_t size) {
+      return count ? hipMemcpyAsync(dst.p, (const char*)src.p + at * size, count * size, hipMemcpyDeviceToDevice, st)
+                   : hipSuccess;
+    };
+    HIP_TRY(cut(gb->status, status, p0, per, 1));
+    HIP_TRY(cut(gb->stop, stop, p0, per, 1));
+    HIP_TRY(cut(gb->steps, steps, p0, per, 4));
+    HIP_TRY(cut(gb->sky_u, sky_u, p0, per, 8));
+    HIP_TRY(cut(gb->sky_v, sky_v, p0, per, 8));
+    HIP_TRY(cut(gb->sky_z, sky_z, p0, per, 8));
+    HIP_TRY(cut(gb->object, object, l0, nl, 1));
+    HIP_TRY(cut(gb->u, u, l0, nl, 8));
+    HIP_TRY(cut(gb->v, v, l0, nl, 8));
+    HIP_TRY(cut(gb->z, z, l0, nl, 8));
+    HIP_TRY(cut(gb->radius, radius, l0, nl, 8));
+    HIP_TRY(grt::gbuffer_rebase((const uint64_t*)layer_start.p + p0, per, (uint64_t*)gb->layer_start.p, st));
+    made.push_back(std::move(gb));
+  }
+  HIP_TRY(hipEventRecord(dc.ev1, st));
+  HIP_TRY(hipEventSynchronize(dc.ev1));  // the stacked arrays are freed on return
+  float fill_ms = 0;
+  HIP_TRY(hipEventElapsedTime(&fill_ms, dc.ev0, dc.ev1));
+  if ((rc = stream_done(dc, st))) return rc;
+  for (size_t k = first; k < made.size(); ++k) {
+    made[k]->times[0] = ms;
+    made[k]->times[1] = fill_ms;
+  }
+  for (int k = 0; k < 8; ++k) T->acc[k] += acc[k];
+  T->trace_ms += ms;
+  T->fill_ms += fill_ms;
+  return 0;
+}
+}  // namespace
+
+extern "C" {
+
+int grt_gbuffer_trace_sequence(grt_scene* s, int device, uint32_t n_cameras, const grt_camera_desc* cameras,
+                               grt_gbuffer** out, grt_stats* stats, grt_gbuffer_sequence_report* report) {
+  const auto wall0 = std::chrono::steady_clock::now();
+  if (out)
+    for (uint32_t f = 0; f < n_cameras; ++f) out[f] = nullptr;
+  if (!s || !cameras || !out) return fail(-EINVAL, "null argument");
+  if (n_cameras == 0) return fail(-EINVAL, "a sequence needs at least one camera");
+  const int64_t rows64 = s->desc.camera.rows, cols64 = s->desc.camera.cols;
+  for (uint32_t f = 0; f < n_cameras; ++f)
+    if (cameras[f].rows != rows64 || cameras[f].cols != cols64)
+      return fail(-EINVAL, "camera " + std::to_string(f) + " of the sequence has " + std::to_string(cameras[f].rows) +
+                               " x " + std::to_string(cameras[f].cols) + " pixels, the scene's frame " +
+                               std::to_string(rows64) + " x " + std::to_string(cols64));
+  for (uint32_t k = 0; k < s->desc.n_objects; ++k)
+    if (s->desc.objects[k].kind == GRT_OBJ_VOLUMETRIC_DISC)
+      return fail(-ENOTSUP, "a VolumetricDisc's colour is raymarched: the scene has no geometry buffer");
+  const uint32_t rows = (uint32_t)rows64, cols = (uint32_t)cols64;
+  const uint64_t per = (uint64_t)rows * cols;
+  if (per == 0) return fail(-EINVAL, "empty frame");
+  if (per + 1 > (uint64_t)INT_MAX) return fail(-EOVERFLOW, "more than INT_MAX - 1 pixels");
+  // frames per launch group: grt_render_sequence's arithmetic; the scan runs over n + 1 entries
+  uint64_t g = std::max<uint64_t>(1, g_seq_group.load(std::memory_order_relaxed) / per);
+  g = std::min<uint64_t>(g, n_cameras);
+  g = std::min<uint64_t>(g, std::max<uint64_t>(1, ((uint64_t)INT_MAX - 1) / per));
+  g = std::min<uint64_t>(g, std::max<uint64_t>(1, 0xffffffffull / rows));
+  DeviceCopy* dc;
+  int rc = ensure_device(s, device, &dc);
+  if (rc) return rc;
+  std::lock_guard<std::mutex> lk(dc->mu);
+  HIP_TRY(hipSetDevice(device));
+  std::vector<grt::DevCamera> cams(n_cameras);
+  for (uint32_t f = 0; f < n_cameras; ++f) fill_dev_camera(cameras[f], cams[f]);
+  DevBuf b_cams;
+  if ((rc = b_cams.alloc(n_cameras * sizeof(grt::DevCamera)))) return rc;
+  HIP_TRY(hipMemcpy(b_cams.p, cams.data(), n_cameras * sizeof(grt::DevCamera), hipMemcpyHostToDevice));
+  // the buffers die with `made` on any failure below
+  std::vector<std::unique_ptr<grt_gbuffer>> made;
+  made.reserve(n_cameras);
+  GbSeqTimes T;
+  uint32_t launches = 0;
+  for (uint32_t f0 = 0; f0 < n_cameras; f0 += (uint32_t)g, ++launches) {
+    const uint32_t kg = (uint32_t)std::min<uint64_t>(g, n_cameras - f0);
+    const grt::CamTable ct{(const grt::DevCamera*)b_cams.p + f0, rows, kg};
+    if ((rc = gbuffer_sequence_group(s, *dc, device, ct, cameras + f0, rows, cols, made, &T))) return rc;
+  }
+  if (stats) {
+    std::memset(stats, 0, sizeof(*stats));
+    stats->accepted_steps = T.acc[0];
+    stats->attempts = T.acc[1];
+    stats->rays = T.acc[2];
+    stats->kernel_ms = T.trace_ms;
+  }
+  if (report) {
+    std::memset(report, 0, sizeof(*report));
+    report->n_frames = n_cameras;
+    report->n_launches = launches;
+    report->frames_per_launch = (uint32_t)g;
+    report->n_traces = T.traces;
+    report->trace_ms = T.trace_ms;
+    report->fill_ms = T.fill_ms;
+    report->wall_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - wall0).count();
+  }
+  for (uint32_t f = 0; f < n_cameras; ++f) out[f] = made[f].release();
+  return 0;
+}
+
+int grt_gbuffer_shade_sequence(grt_scene* s, uint32_t n_buffers, grt_gbuffer* const* buffers, const grt_frame_out* out,
+                               float* kernel_ms) {
+  if (!s || !buffers || !out) return fail(-EINVAL, "null argument");
+  if (n_buffers == 0) return fail(-EINVAL, "a sequence needs at least one buffer");
+  if (!out->xyza && !out->xyza64) return fail(-EINVAL, "grt_frame_out needs xyza or xyza64");
+  for (uint32_t f = 0; f < n_buffers; ++f)
+    if (!buffers[f]) return fail(-EINVAL, "frame " + std::to_string(f) + ": null buffer");
+  const grt_gbuffer_info& i0 = buffers[0]->info;
+  const int device = i0.device;
+  for (uint32_t f = 0; f < n_buffers; ++f) {
+    const grt_gbuffer_info& i = buffers[f]->info;
+    if (i.device != device)
+      return fail(-EINVAL, "frame " + std::to_string(f) + ": the g-buffer is on device " + std::to_string(i.device) +
+                               ", frame 0's on device " + std::to_string(device));
+    if (i.rows != i0.rows || i.cols != i0.cols)
+      return fail(-EINVAL, "frame " + std::to_string(f) + ": the g-buffer has " + std::to_string(i.rows) + " x " +
+                               std::to_string(i.cols) + " pixels, frame 0's " + std::to_string(i0.rows) + " x " +
+                               std::to_string(i0.cols));
+    if (int rc = grt_gbuffer_shape_compatible(&i.shape, &s->desc))
+      return fail(rc, "frame " + std::to_string(f) + ": " + grt_last_error());
+  }
+  const uint64_t per = i0.n_pixels;
+  if (per == 0 || per > (uint64_t)INT_MAX) return fail(-EINVAL, "frames of 0 or more than INT_MAX pixels");
+  uint64_t g = std::max<uint64_t>(1, g_seq_group.load(std::memory_order_relaxed) / per);
+  g = std::min<uint64_t>(g, n_buffers);
+  DeviceCopy* dc;
+  int rc = ensure_device(s, device, &dc);
+  if (rc) return rc;
+  std::lock_guard<std::mutex> lk(dc->mu);
+  HIP_TRY(hipSetDevice(device));
+  const uint64_t ng = per * g;  // slots of a full group
+  DevBuf xyza, cls, status, x64, stop, steps, table;
+  if ((rc = xyza.alloc(16 * ng)) || (rc = cls.alloc(ng)) || (rc = status.alloc(ng))) return rc;
+  if (out->xyza64 && (rc = x64.alloc(32 * ng))) return rc;
+  if (out->stop && (rc = stop.alloc(ng))) return rc;
+  if (out->steps && (rc = steps.alloc(4 * ng))) return rc;
+  std::vector<grt::GBufferFrame> frames(n_buffers);
+  for (uint32_t f = 0; f < n_buffers; ++f) frames[f] = grt::GBufferFrame{buffers[f]->view(), (const uint32_t*)buffers[f]->steps.p};
+  if ((rc = table.alloc(n_buffers * sizeof(grt::GBufferFrame)))) return rc;
+  HIP_TRY(hipMemcpy(table.p, frames.data(), n_buffers * sizeof(grt::GBufferFrame), hipMemcpyHostToDevice));
+  const grt::Outputs o{(float*)xyza.p,     (uint8_t*)cls.p,  (uint8_t*)status.p, (double*)x64.p,
+                       (uint32_t*)steps.p, (uint8_t*)stop.p, nullptr};
+  hipStream_t st = nullptr;
+  float total_ms = 0;
+  for (uint32_t f0 = 0; f0 < n_buffers; f0 += (uint32_t)g) {
+    const uint32_t kg = (uint32_t)std::min<uint64_t>(g, n_buffers - f0);
+    const uint64_t n = per * kg, at = per * f0;
+    HIP_TRY(hipEventRecord(dc->ev0, st));
+    HIP_TRY(grt::launch_gbuffer_shade_stack(dc->d_scene, (const grt::GBufferFrame*)table.p + f0, kg, per, o, st));
+    HIP_TRY(hipEventRecord(dc->ev1, st));
+    HIP_TRY(hipEventSynchronize(dc->ev1));
+    float t = 0;
+    HIP_TRY(hipEventElapsedTime(&t, dc->ev0, dc->ev1));
+    total_ms += t;
+    if (out->xyza) HIP_TRY(hipMemcpy(out->xyza + 4 * at, xyza.p, 16 * n, hipMemcpyDeviceToHost));
+    if (out->xyza64) HIP_TRY(hipMemcpy(out->xyza64 + 4 * at, x64.p, 32 * n, hipMemcpyDeviceToHost));
+    if (out->ray_class) HIP_TRY(hipMemcpy(out->ray_class + at, cls.p, n, hipMemcpyDeviceToHost));
+    if (out->status) HIP_TRY(hipMemcpy(out->status + at, status.p, n, hipMemcpyDeviceToHost));
+    if (out->stop) HIP_TRY(hipMemcpy(out->stop + at, stop.p, n, hipMemcpyDeviceToHost));
+    if (out->steps) HIP_TRY(hipMemcpy(out->steps + at, steps.p, 4 * n, hipMemcpyDeviceToHost));
+  }
+  if (kernel_ms) *kernel_ms = total_ms;
+  return 0;
+}
+
+}  // extern "C"
+
 // ---- the sub-sample set and the adaptive re-shade (grt_api.h) ----
 // The sub-rays of a buffer belong to the frame it holds: the tracer's geometry (shape key),
 // camera and integration parameters must be the recorded ones.

@@ -36,6 +36,21 @@ hipError_t gbuffer_layer_scan(const uint8_t* d_status, const uint32_t* d_hits, u
   return hipcub::DeviceScan::ExclusiveSum(d_temp, *temp_bytes, d_counts, d_layer_start, (int)(n + 1), stream);
 }
 
+// ---- a stacked buffer cut into its frames (grt_gbuffer_trace_sequence) ----
+// The scan above runs over the whole stack; a frame's own offsets start at 0 at its first
+// pixel.
+__global__ void __launch_bounds__(256) gbuffer_rebase_kernel(const uint64_t* __restrict__ stack_start, uint64_t n,
+                                                             uint64_t* __restrict__ frame_start) {
+  const uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i <= n) frame_start[i] = stack_start[i] - stack_start[0];
+}
+
+hipError_t gbuffer_rebase(const uint64_t* d_stack_start, uint64_t n, uint64_t* d_frame_start, hipStream_t stream) {
+  hipLaunchKernelGGL(gbuffer_rebase_kernel, dim3((unsigned)((n + 1 + 255) / 256)), dim3(256), 0, stream, d_stack_start,
+                     n, d_frame_start);
+  return hipGetLastError();
+}
+
 // ---- the sub-sample set (grt_gbuffer_supersample, grt_gbuffer_shade_section) ----
 // held[j] / missing[j]: whether selected pixel j has a block; 0 past the selection's end.
 __global__ void __launch_bounds__(256) gbuffer_split_flags_kernel(const uint32_t* __restrict__ sel,

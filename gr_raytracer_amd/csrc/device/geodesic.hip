@@ -3748,7 +3748,7 @@ __global__ void __launch_bounds__(256) shade_kernel(const DevScene* __restrict__
   write_out(out, idx, result, cls, status, stop, nh + n_pool_hits);
 }
 
-#if GRT_MAIN_TU || GRT_KERR_BL_TU  // the geometry buffer: the exact units only
+#if GRT_MAIN_TU || GRT_KERR_BL_TU || GRT_SEQ  // the geometry buffer: the exact units only
 // ============================================================ geometry buffer =====
 // After a 1-spp trace of a rectangle whose outputs (status, stop) are gb's: the numbers
 // shade_kernel<G, 0> reduces each ray to before any texture or temperature is applied --
@@ -3756,10 +3756,12 @@ __global__ void __launch_bounds__(256) shade_kernel(const DevScene* __restrict__
 // redshift, radius), at layer_start[idx] + k; per ray that ended on the celestial sphere
 // celestial_args' (1 - u, v, redshift).  The same record walk as shade_kernel; one lane per
 // ray.  A ray whose status is not 0 has no layers (layer_start is the scan of the trace's
-// own hit counts, zeroed for those rays).
+// own hit counts, zeroed for those rays).  The sequence unit's (grt_gbuffer_trace_sequence)
+// fills the buffer of a whole stack: slot idx is a ray of frame idx / (rows * cols), and its
+// camera is that frame's (observer_energy).
 template <int G>
 __global__ void __launch_bounds__(256) gbuffer_fill_kernel(const DevScene* __restrict__ Sp, WorkList wl, Workspace ws,
-                                                           GBufferArrays gb) {
+                                                           GBufferArrays gb CAMS_PARAM) {
   const DevScene& S = *Sp;
   glibc::tables_to_lds();  // whole block, before the early return
   const uint64_t idx = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
@@ -3769,7 +3771,7 @@ __global__ void __launch_bounds__(256) gbuffer_fill_kernel(const DevScene* __res
     RayConst rc;
     double y[8];
     const RayMeta mt = fin_get<G>(ws, idx, y, rc);
-    if constexpr (G != GRT_GEOM_KERR_BL) rc.obs = observer_energy<G>(S, wl, idx);
+    if constexpr (G != GRT_GEOM_KERR_BL) rc.obs = observer_energy<G>(S, wl, idx CAMS_ARG);
     bool lost;
     const uint32_t nr = rec_count(ws, idx, mt.nrec, &lost);
     uint64_t at = gb.layer_start[idx];
@@ -3801,29 +3803,35 @@ __global__ void __launch_bounds__(256) gbuffer_fill_kernel(const DevScene* __res
 
 template <int G>
 static hipError_t gbuffer_fill_g(const DevScene* d_scene, const WorkList& wl, const Workspace& ws,
-                                 const GBufferArrays& gb, hipStream_t stream) {
+                                 const GBufferArrays& gb, hipStream_t stream CAMS_PARAM) {
   hipLaunchKernelGGL((gbuffer_fill_kernel<G>), dim3((unsigned)((gb.n + 255) / 256)), dim3(256), 0, stream, d_scene, wl,
-                     ws, gb);
+                     ws, gb CAMS_ARG);
   return hipGetLastError();
 }
 
 hipError_t launch_gbuffer_fill(int geometry, const DevScene* d_scene, const WorkList& wl, const Workspace& ws,
-                               const GBufferArrays& gb, hipStream_t stream) {
+                               const GBufferArrays& gb, hipStream_t stream CAMS_PARAM) {
   if (gb.n == 0) return hipSuccess;
+#if GRT_SEQ  // the stack's slots are whole frames, one camera each
+  if (!ct.cams || ct.cam_rows == 0 || ct.n_cams == 0 || wl.pixel_index || wl.row0 != 0 || wl.col0 != 0 ||
+      (uint64_t)wl.rows != (uint64_t)ct.cam_rows * ct.n_cams || gb.n != (uint64_t)wl.rows * wl.cols)
+    return hipErrorInvalidValue;
+#endif
   switch (geometry) {
-#if GRT_MAIN_TU
-    case GRT_GEOM_EUCLIDEAN: return gbuffer_fill_g<GRT_GEOM_EUCLIDEAN>(d_scene, wl, ws, gb, stream);
-    case GRT_GEOM_SCHWARZSCHILD: return gbuffer_fill_g<GRT_GEOM_SCHWARZSCHILD>(d_scene, wl, ws, gb, stream);
-    case GRT_GEOM_KERR: return gbuffer_fill_g<GRT_GEOM_KERR>(d_scene, wl, ws, gb, stream);
+#if GRT_MAIN_TU || GRT_SEQ
+    case GRT_GEOM_EUCLIDEAN: return gbuffer_fill_g<GRT_GEOM_EUCLIDEAN>(d_scene, wl, ws, gb, stream CAMS_ARG);
+    case GRT_GEOM_SCHWARZSCHILD: return gbuffer_fill_g<GRT_GEOM_SCHWARZSCHILD>(d_scene, wl, ws, gb, stream CAMS_ARG);
+    case GRT_GEOM_KERR: return gbuffer_fill_g<GRT_GEOM_KERR>(d_scene, wl, ws, gb, stream CAMS_ARG);
     case GRT_GEOM_EUCLIDEAN_SPHERICAL:
-      return gbuffer_fill_g<GRT_GEOM_EUCLIDEAN_SPHERICAL>(d_scene, wl, ws, gb, stream);
-#else
-    case GRT_GEOM_KERR_BL: return gbuffer_fill_g<GRT_GEOM_KERR_BL>(d_scene, wl, ws, gb, stream);
+      return gbuffer_fill_g<GRT_GEOM_EUCLIDEAN_SPHERICAL>(d_scene, wl, ws, gb, stream CAMS_ARG);
+#endif
+#if GRT_KERR_BL_TU || GRT_SEQ
+    case GRT_GEOM_KERR_BL: return gbuffer_fill_g<GRT_GEOM_KERR_BL>(d_scene, wl, ws, gb, stream CAMS_ARG);
 #endif
     default: return hipErrorInvalidValue;
   }
 }
-#endif  // GRT_MAIN_TU || GRT_KERR_BL_TU
+#endif  // GRT_MAIN_TU || GRT_KERR_BL_TU || GRT_SEQ
 
 #if GRT_MAIN_TU
 // Deferred shade: shade_kernel's window colours, terminal colour and composite from a
@@ -3953,6 +3961,34 @@ __global__ void __launch_bounds__(256) gbuffer_shade_sub_kernel(const DevScene* 
   if (src >= sub.n) return;  // a pixel the set does not hold: the split never lists one
   if (out.steps) out.steps[k] = sub_steps[src];
   gbuffer_shade_ray(S, sub, src, out, k);
+}
+
+// The deferred shade of a stack of equally sized buffers (grt_gbuffer_shade_sequence): one
+// lane per (frame, pixel) of a launch group, the frame's arrays from a device table, the
+// pixel shaded as gbuffer_shade_kernel shades it into slot frame * per + pixel of the
+// stacked outputs, with the recorded step count beside it when asked for.
+__global__ void __launch_bounds__(256) gbuffer_shade_stack_kernel(const DevScene* __restrict__ Sp,
+                                                                  const GBufferFrame* __restrict__ frames,
+                                                                  uint32_t n_frames, uint64_t per, Outputs out) {
+  const DevScene& S = *Sp;
+  glibc::tables_to_lds();  // whole block, before the early return
+  const uint64_t idx = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (idx >= (uint64_t)n_frames * per) return;
+  const uint64_t f = idx / per, src = idx - f * per;
+  const GBufferFrame fr = frames[f];
+  if (src >= fr.gb.n) return;  // a frame of another size: the host refuses such a stack
+  if (out.steps) out.steps[idx] = fr.steps[src];
+  gbuffer_shade_ray(S, fr.gb, src, out, idx);
+}
+
+hipError_t launch_gbuffer_shade_stack(const DevScene* d_scene, const GBufferFrame* d_frames, uint32_t n_frames,
+                                      uint64_t per, const Outputs& out, hipStream_t stream) {
+  const uint64_t n = (uint64_t)n_frames * per;
+  if (n == 0) return hipSuccess;
+  if (n > 0xffffffffull * 256) return hipErrorInvalidValue;
+  hipLaunchKernelGGL(gbuffer_shade_stack_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, stream, d_scene,
+                     d_frames, n_frames, per, out);
+  return hipGetLastError();
 }
 
 hipError_t launch_gbuffer_shade(const DevScene* d_scene, const GBufferArrays& gb, const Outputs& out,

@@ -142,9 +142,29 @@ namespace kerr_bl {
 hipError_t launch_gbuffer_fill(int geometry, const DevScene* d_scene, const WorkList& wl, const Workspace& ws,
                                const GBufferArrays& gb, hipStream_t stream);
 }
+// The same after a stacked 1-spp trace of whole frames (seq::launch_trace; `wl` the stack's
+// rectangle from (0, 0), no offset list), every chart: `gb` spans the stack in slot order,
+// frame after frame, and a ray's camera is its frame's entry of the table
+// (grt_gbuffer_trace_sequence; hipErrorInvalidValue for any other work list).
+namespace seq {
+hipError_t launch_gbuffer_fill(int geometry, const DevScene* d_scene, const WorkList& wl, const Workspace& ws,
+                               const GBufferArrays& gb, hipStream_t stream, CamTable ct);
+}
+// A stacked buffer cut into its frames (gbuffer.hip): frame_start[i] = stack_start[i] -
+// stack_start[0] for i <= n, where stack_start points at the frame's first pixel.
+hipError_t gbuffer_rebase(const uint64_t* d_stack_start, uint64_t n, uint64_t* d_frame_start, hipStream_t stream);
 // Deferred shade of `gb` under the appearance scene (gbuffer_shade_kernel, geodesic.hip).
 hipError_t launch_gbuffer_shade(const DevScene* d_scene, const GBufferArrays& gb, const Outputs& out,
                                 hipStream_t stream);
+// Deferred shade of n_frames buffers of `per` pixels each in one launch
+// (gbuffer_shade_stack_kernel, geodesic.hip): d_frames is a device table of the buffers'
+// views and recorded step counts; out spans n_frames * per slots, frame-major.
+struct GBufferFrame {
+  GBufferArrays gb;
+  const uint32_t* steps;
+};
+hipError_t launch_gbuffer_shade_stack(const DevScene* d_scene, const GBufferFrame* d_frames, uint32_t n_frames,
+                                      uint64_t per, const Outputs& out, hipStream_t stream);
 // The sub-sample set of a buffer (grt_gbuffer_supersample): for some pixels, the spa^2
 // jittered sub-rays, each reduced as a 1-spp ray is; sub-ray b * spa^2 + s is stratum s of
 // block b, and sub_block[pixel] is the pixel's block or GBUFFER_NIL.

@@ -241,6 +241,25 @@ class Scene:
             gb.shade_section(self, adaptive=adaptive, tracer=self)
         return gb
 
+    def trace_gbuffer_sequence(self, cameras, device: int = 0) -> "GBufferSequence":
+        """K cameras (CameraDesc, each with the scene's rows and cols) over this scene, traced
+        stacked at 1 spp with the exact kernels, one geometry buffer per frame
+        (grt_gbuffer_trace_sequence).  Buffer k is the ordinary GBuffer of a scene with camera
+        k, byte for byte.  Returns a list of GBuffer with the call's `stats` and `report`
+        (GBufferSequenceReport) as attributes."""
+        cams = list(cameras)
+        k = len(cams)
+        table = (L.CameraDesc * max(k, 1))(*cams)
+        handles = (C.c_void_p * max(k, 1))()
+        st = L.Stats()
+        rep = L.GBufferSequenceReport()
+        L.check(L.lib().grt_gbuffer_trace_sequence(self._s, device, k, table, handles, C.byref(st), C.byref(rep)),
+                "grt_gbuffer_trace_sequence")
+        stats = _stats_dict(st)
+        out = GBufferSequence(GBuffer(C.c_void_p(handles[f]), stats) for f in range(k))
+        out.stats, out.report = stats, rep
+        return out
+
     def render_shard(self, band_rows: int, shard: int, n_shards: int, device: int = 0,
                      aux: bool = True) -> RenderResult:
         """The local rows of one cyclic row-band shard (grt_render_shard), full width."""
@@ -760,6 +779,43 @@ class GBuffer:
             self.close()
         except Exception:
             pass
+
+
+class GBufferSequence(list):
+    """The buffers of Scene.trace_gbuffer_sequence, frame by frame: a list of GBuffer with
+    the call's `stats` (dict) and `report` (GBufferSequenceReport)."""
+    stats: dict = {}
+    report = None
+
+
+def shade_sequence(buffers, scene: "Scene", fields=("xyza", "xyza64", "class", "status", "stop", "steps")) -> dict:
+    """Shade the buffers (equal rows x cols, one device) under `scene`'s appearance in
+    stacked launches (grt_gbuffer_shade_sequence): frame k is `buffers[k].shade(scene)` bit
+    for bit.  Returns a dict of the `fields` as arrays with a leading frame axis, as
+    Scene.render_sequence returns them at 1 spp ("stop" and "steps" are the buffers'
+    recorded ones), plus "stats" ({"kernel_ms"})."""
+    bufs = list(buffers)
+    k = len(bufs)
+    n = int(bufs[0].info.n_pixels) if k else 0
+    want = set(fields)
+    arrays = {}
+    for name, shape, dt in (("xyza", (k, n, 4), np.float32), ("xyza64", (k, n, 4), np.float64),
+                            ("class", (k, n), np.uint8), ("status", (k, n), np.uint8), ("stop", (k, n), np.uint8),
+                            ("steps", (k, n), np.uint32)):
+        if name in want:
+            arrays[name] = np.zeros(shape, dt)
+    out = L.FrameOut(L.ptr(arrays["xyza"], C.c_float) if "xyza" in arrays else None,
+                     L.dptr(arrays["xyza64"]) if "xyza64" in arrays else None,
+                     L.ptr(arrays["class"], C.c_uint8) if "class" in arrays else None,
+                     L.ptr(arrays["status"], C.c_uint8) if "status" in arrays else None,
+                     L.ptr(arrays["stop"], C.c_uint8) if "stop" in arrays else None,
+                     L.ptr(arrays["steps"], C.c_uint32) if "steps" in arrays else None)
+    handles = (C.c_void_p * max(k, 1))(*[b._h for b in bufs])
+    ms = C.c_float()
+    L.check(L.lib().grt_gbuffer_shade_sequence(scene._s, k, handles, C.byref(out), C.byref(ms)),
+            "grt_gbuffer_shade_sequence")
+    arrays["stats"] = {"kernel_ms": float(ms.value)}
+    return arrays
 
 
 def gbuffer_compatible(traced: L.SceneDesc, appearance: L.SceneDesc) -> None:

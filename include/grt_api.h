@@ -612,8 +612,9 @@ int grt_set_sequence_group(uint64_t rays);
  * Kerr-Schild and the camera sequences do): re-shading reproduces the exact frame.  Scenes
  * with a GRT_OBJ_VOLUMETRIC_DISC are refused (-ENOTSUP): its colour is raymarched, not a
  * function of (u, v, redshift, temperature).  One rectangle on one device, at 1 spp or with
- * the adaptive pass's sub-rays (the sub-sample set below): no offset lists, row shards,
- * sequences or multi-GPU frames.
+ * the adaptive pass's sub-rays (the sub-sample set below), or the whole frames of a camera
+ * sequence, one buffer each (grt_gbuffer_trace_sequence below): no offset lists, row shards
+ * or multi-GPU frames.
  * A grt_gbuffer is not synchronised: one host thread at a time per buffer. */
 typedef struct grt_gbuffer grt_gbuffer; /* device-resident, owns its arrays */
 
@@ -723,8 +724,9 @@ int grt_gbuffer_read_file(const char* path, grt_gbuffer_info* info, const grt_gb
  *   a second grt_gbuffer_arrays over n_sub_rays = n_sub_pixels * spa^2 rays and n_sub_layers
  *   layers: sub-ray b * spa^2 + s is stratum s (row-major, spa columns) of block b.
  * The set is append-only; it never holds a GRT_FLAG_HIT_OVERFLOW ray.  Still outside the
- * buffer: sequences, row shards, the multi-GPU frame, VolumetricDisc scenes, the fused
- * arithmetic. */
+ * buffer: row shards, the multi-GPU frame, VolumetricDisc scenes, the fused arithmetic.  A
+ * camera sequence's buffers (grt_gbuffer_trace_sequence) start without a set; each takes one
+ * as any buffer does, per frame, with a tracer that has the frame's camera. */
 typedef struct grt_gbuffer_sub_info {
   uint32_t samples_per_axis; /* 0: the buffer holds no set */
   uint32_t _pad;
@@ -798,6 +800,42 @@ int grt_gbuffer_sub_write_file(const char* path, const grt_gbuffer_info* info, c
                                const uint32_t* sub_pixel, const grt_gbuffer_arrays* arrays);
 int grt_gbuffer_sub_read_file(const char* path, const grt_gbuffer_info* info, grt_gbuffer_sub_info* sub,
                               uint32_t* sub_pixel, const grt_gbuffer_arrays* arrays);
+
+/* ---- geometry buffers of a camera sequence: trace the animation once, re-shade it ----
+ * K cameras over one resident scene, traced stacked as grt_render_sequence traces them (one
+ * 1-spp trace of the sequence unit per launch group of grt_set_sequence_group, the group
+ * arithmetic that call uses, always the exact arithmetic), each frame kept as a g-buffer. */
+typedef struct grt_gbuffer_sequence_report {
+  uint32_t n_frames, n_launches, frames_per_launch, n_traces; /* n_traces counts re-traces after a pool overflow */
+  double wall_ms, trace_ms, fill_ms;                          /* host clock; summed event times */
+} grt_gbuffer_sequence_report;
+
+/* Trace n_cameras whole frames of `scene` on `device` and keep one g-buffer per frame.  Every
+ * camera must have the scene's rows and cols, else -EINVAL (n_cameras = 0 too); -ENOTSUP for
+ * a scene with a VolumetricDisc.  out[k] is an ordinary grt_gbuffer: its info holds
+ * cameras[k], the rectangle (0, 0, rows, cols), the scene's shape key and integration
+ * parameters, and info and arrays are byte for byte what grt_gbuffer_trace returns for a scene
+ * created with that camera, so every grt_gbuffer_* call takes it.  A launch group whose trace
+ * loses hit candidates grows the pool to its need and is traced again as a whole (at most 3
+ * traces, else -ENOMEM): no buffer holds a GRT_FLAG_HIT_OVERFLOW ray.  On any failure every
+ * buffer the call made is destroyed and out[0 .. n_cameras) is NULL.  stats (nullable): the
+ * counters of all traces, kernel_ms their event time.  grt_gbuffer_trace_times of such a
+ * buffer reports the times of its whole launch group (the stacked trace(s); the scan, the
+ * fill and the split into frames), not a share of them.  report is nullable. */
+int grt_gbuffer_trace_sequence(grt_scene* scene, int device, uint32_t n_cameras, const grt_camera_desc* cameras,
+                               grt_gbuffer** out /* [n_cameras] */, grt_stats* stats,
+                               grt_gbuffer_sequence_report* report);
+/* Shade n buffers of equal rows x cols on one device under `appearance` in stacked launches:
+ * one kernel launch and one set of device-to-host copies per group of grt_set_sequence_group
+ * rays (whole buffers, at least one), not one per buffer.  out: host arrays, frame-major
+ * [n][rows][cols]; xyza, xyza64, ray_class and status are written where non-null (at least
+ * one of xyza and xyza64 is required); stop and steps, where non-null, are copies of the
+ * buffers' recorded ones.  Frame k equals grt_gbuffer_shade(appearance, buffers[k]) bit for
+ * bit.  -EINVAL for n = 0, a buffer on another device than buffers[0], another rows x cols,
+ * or a shape key that differs from the appearance's (grt_last_error names the frame index
+ * and the field).  kernel_ms (nullable): summed event time of the shade launches. */
+int grt_gbuffer_shade_sequence(grt_scene* appearance, uint32_t n, grt_gbuffer* const* buffers,
+                               const grt_frame_out* out, float* kernel_ms);
 
 /* The device hit pool that keeps the window candidates past a ray's GRT_MAX_HITS slots
  * (no reference counterpart: the reference's per-ray Vec grows, scene.rs:139-152).
