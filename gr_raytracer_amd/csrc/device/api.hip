@@ -389,6 +389,15 @@ int init_device_copy(grt_scene* s, int device, DeviceCopy& dc) {
     // Schwarzschild quotients drop their multiplies by it (rcp_seed.h unit_radius_quotients)
     ds.unit_radius = (d.radius == 1.0 && ds.div_fast) ? 1 : 0;
     ds.rkf_short = g_rkf_short.load(std::memory_order_relaxed);
+    // schw_div_ok_render's lower edge: radius (1 + 2^-40), moved up until schw_div_ok's own
+    // test |r - radius| > 2^-40 radius holds at the edge itself; r - radius is monotone in r,
+    // so it then holds for every r above the edge
+    ds.div_r_lo = INFINITY;
+    if (ds.div_fast) {
+      double lo = d.radius * (1.0 + 0x1p-40);
+      while (!(lo - d.radius > d.radius * 0x1p-40)) lo = std::nextafter(lo, INFINITY);
+      ds.div_r_lo = lo;
+    }
     // ks_fd_ok's coordinate bound: 2^ceil(log2(2 max_radius)) covers every state of a ray
     // (it stops one step beyond max_radius), within the proven 2^10 .. 2^32
     int em = 0;
@@ -1044,7 +1053,7 @@ int grt_debug_rhs_check(grt_scene* s, int device, uint64_t n, const double* stat
 
 #if GRT_PATH_COUNT
 // Diagnostic builds only (not in grt_api.h): the integrate kernels' path counters since the
-// last reset (geodesic.hip path_count): out[24], [k] wave-level, [12 + k] lane-level.
+// last reset (geodesic.hip path_count): out[28], [k] wave-level, [14 + k] lane-level.
 int grt_debug_path_counts(uint64_t* out, int reset) {
   if (!out) return fail(-EINVAL, "null argument");
   HIP_TRY(grt::path_read((unsigned long long*)out, reset != 0));

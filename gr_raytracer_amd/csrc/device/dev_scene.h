@@ -104,6 +104,7 @@ struct DevScene {
   int32_t rkf_short;       // Schwarzschild integrate kernels: attempts without the zero-weight k2 terms
                            // (geodesic.hip rkf_short_ok); grt_debug_rkf_short: 0 = every attempt in the full
                            // form, 2 = short attempts with the full-form fallback forced on the general path
+  double div_r_lo;         // Schwarzschild: radius (1 + 2^-40), the lower edge of schw_div_ok_render
   DevObject obj[8];
   uint8_t perm[8][256];    // Perlin permutation tables (noise 0.9.0 PermutationTable), per object
 };

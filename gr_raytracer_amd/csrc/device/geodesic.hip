@@ -117,6 +117,9 @@ namespace seq {
 #ifndef GRT_UNIT_RADIUS
 #define GRT_UNIT_RADIUS 1  // Schwarzschild region-B RHS: the quotients of radius == 1.0 without their multiplies (rcp_seed.h)
 #endif
+#ifndef GRT_DIV_OK_CHEAP
+#define GRT_DIV_OK_CHEAP 1  // Schwarzschild RHS: the render's division predicate as two compares (schw_div_ok_render)
+#endif
 #ifndef GRT_RKF_SHORT
 #define GRT_RKF_SHORT 1  // Schwarzschild integrate kernels: attempts without the zero-weight CH2 / CT2 terms (rkf_short_ok)
 #endif
@@ -589,8 +592,10 @@ GDEV void metric_bl(double r_s, double a, double r, double sin_t, double cos_t, 
 // pass, 5 accepted step, 6 attempt, 7 attempt taken again in the full form (rkf_short_ok
 // missed).  What the waves of path 3 hold: 8 every lane in glibc's region A
 // (2^-27 <= |x| < 0.855469) on do_sin's table path, 9 every lane in region A otherwise,
-// 10 every lane in region C (|x| >= 2.426265) with quadrant n = 2, 11 mixed.
-constexpr int NPATH = 12;
+// 10 every lane in region C (|x| >= 2.426265) with quadrant n = 2, 11 mixed.  Counted besides
+// those four: 12 every lane in region B (its table and Taylor cases mixed) with div_ok, 13 every
+// lane in region B with div_ok missed on some lane.
+constexpr int NPATH = 14;
 __shared__ unsigned long long path_lds[2 * NPATH];
 __device__ unsigned long long g_path[2 * NPATH];
 GDEV void path_count(int k) {
@@ -675,6 +680,9 @@ GDEV void with_sincos(double theta, bool fast_ok, F&& body, bool div_ok = false,
     const bool ra = k >= 0x3e400000u && k < 0x3feb6000u, ra_tab = ra && !(fabs(theta) < glibc::TAYLOR_MAX);
     double ca, cda;
     const bool rc2 = k >= 0x400368fdu && k < 0x419921fbu && glibc::reduce_sincos_nf(theta, &ca, &cda) == 2;
+    const bool rb = k >= 0x3feb6000u && k < 0x400368fdu;
+    if (fast_ok && __ballot(!(rb & div_ok)) == 0) PATH_COUNT(12);
+    else if (fast_ok && __ballot(!rb) == 0) PATH_COUNT(13);
     if (__ballot(!ra_tab) == 0) PATH_COUNT(8);
     else if (__ballot(!ra) == 0) PATH_COUNT(9);
     else if (__ballot(!rc2) == 0) PATH_COUNT(10);
@@ -717,6 +725,20 @@ GDEV bool ks_fd_ok(double a, double x, double y, double z, double cap) {
 // Region-B division predicates of the Schwarzschild and KerrBL RHS (see there)
 GDEV bool schw_div_ok(const DevScene& S, double r) {
   return S.div_fast && (fabs(r) > 0x1p-100) & (fabs(r) < 0x1p100) & (fabs(r - S.radius) > S.radius * 0x1p-40);
+}
+// What the render asks at each RHS: r > S.div_r_lo and r < 2^100, where the host (api.hip)
+// sets div_r_lo to radius (1 + 2^-40), moved up until schw_div_ok's third test holds at
+// div_r_lo itself.  With S.div_fast (0 < radius within 2^+-50) this implies schw_div_ok:
+// r > div_r_lo > radius > 2^-50 gives |r| > 2^-100, and the rounded r - radius is monotone
+// in r, so it is >= div_r_lo - radius > 2^-40 radius.  So the proofs at rhs<SCHWARZSCHILD>
+// hold unchanged on this subset, in two compares instead of a subtraction and three.  A ray
+// inside the horizon or at a negative r takes the IEEE divisions, as every r may.
+GDEV bool schw_div_ok_render(const DevScene& S, double r) {
+#if GRT_DIV_OK_CHEAP
+  return S.div_fast && (r > S.div_r_lo) & (r < 0x1p100);
+#else
+  return schw_div_ok(S, r);
+#endif
 }
 GDEV bool bl_div_ok(const DevScene& S, double r, double del, double l_z) {
   return S.div_fast && (fabs(r) < 0x1p100) & in_div_range(del) & (fabs(l_z) > 0x1p-200) & (fabs(l_z) < 0x1p100);
@@ -810,7 +832,8 @@ GDEV void rhs(const DevScene& S, const RayConst& rc, const double* y, double* o)
       } else body(st, ct, true, std::false_type{});
       return;
     }
-    with_sincos<GRT_FAST_DIV, GRT_UNIT_RADIUS>(theta, S.div_share, body, schw_div_ok(S, r), S.unit_radius != 0);
+    with_sincos<GRT_FAST_DIV, GRT_UNIT_RADIUS>(theta, S.div_share, body, schw_div_ok_render(S, r),
+                                               S.unit_radius != 0);
   } else if constexpr (G == GRT_GEOM_EUCLIDEAN_SPHERICAL) {  // euclidean_spherical.rs:48-70
     double r = y[1], theta = y[2];
     double v_t = y[4], v_r = y[5], v_theta = y[6], v_phi = y[7];

@@ -69,7 +69,7 @@ hipError_t launch_rhs_check(int geometry, const DevScene* d_scene, const double*
 hipError_t launch_rkf_check(const DevScene* d_scene, const double* d_states, const double* d_h, uint64_t n,
                             double* d_short, double* d_full, uint8_t* d_guard, hipStream_t stream);
 #if GRT_PATH_COUNT
-hipError_t path_read(unsigned long long* out, bool reset);  // 16 words
+hipError_t path_read(unsigned long long* out, bool reset);  // 2 * 14 words
 #endif
 // The same trace compiled with FMA contraction (geodesic_fused.hip, grt_set_arithmetic(1)):
 // every geometry but Kerr-Schild (hipErrorInvalidValue for it).

@@ -7,7 +7,8 @@ with range-free divisions, 1 region-B Taylor with them, 2 region B with IEEE div
 8 every lane in glibc's region A on the table path, 9 every lane in region A otherwise,
 10 every lane in region C with n = 2, 11 mixed.  All: 4 near-field window pass,
 5 accepted step, 6 attempt, 7 Schwarzschild attempt taken again with the full RKF sums
-(rkf_short_ok missed).
+(rkf_short_ok missed).  Also among the waves of 3: 12 every lane in region B (the table and
+Taylor cases mixed) with the division predicate, 13 every lane in region B without it.
 usage: tools/path_count.py c2|c3|c4 (c4: row-band shard 2 of 8)"""
 import ctypes as C
 import hashlib
@@ -37,7 +38,7 @@ sc = g.Scene(hs.desc_ptr(), keepalive=hs)
 fn = L.lib().grt_debug_path_counts
 fn.restype = C.c_int
 fn.argtypes = [C.POINTER(C.c_uint64), C.c_int]
-NPATH = 12
+NPATH = 14
 cnt = (C.c_uint64 * (2 * NPATH))()
 L.check(fn(cnt, 1), "grt_debug_path_counts")  # reset
 t = time.time()
@@ -50,8 +51,9 @@ keys = [0, 1] if which == "c4" else [0, 1, 2, 3]
 keys += [4, 5, 6]
 if which != "c4":
     names += ["rkf_full_form_recompute", "rhs_general_uniform_a_table", "rhs_general_uniform_a_other",
-              "rhs_general_uniform_c_n2", "rhs_general_mixed"]
-    keys += [7, 8, 9, 10, 11]
+              "rhs_general_uniform_c_n2", "rhs_general_mixed", "rhs_general_all_b_div_ok",
+              "rhs_general_all_b_div_missed"]
+    keys += [7, 8, 9, 10, 11, 12, 13]
 out = {"workload": which, "kernel_ms": r.stats["kernel_ms"], "wall_s": round(time.time() - t, 3),
        "accepted_steps": r.stats["accepted_steps"], "attempts_total": r.stats["attempts"],
        "md5": hashlib.md5(r.xyza.tobytes() + r.ray_class.tobytes()).hexdigest()[:12]}
