@@ -265,6 +265,8 @@ def lib() -> C.CDLL:
                                          C.POINTER(C.c_uint8)]),
         "grt_set_launch_config": (C.c_int, [C.c_int, C.c_int]),
         "grt_set_schedule": (C.c_int, [C.c_int]),
+        "grt_set_class_order": (C.c_int, [C.c_int]),
+        "grt_get_class_order": (C.c_int, []),
         "grt_set_two_ended": (C.c_int, [C.c_int]),
         "grt_set_tail": (C.c_int, [C.c_longlong]),
         "grt_health_pixels": (C.c_int, [C.c_void_p, C.c_int, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32,
@@ -386,7 +388,7 @@ EXPORTED_SYMBOLS = [
     "grt_camera_build", "grt_stationary_velocity", "grt_zamo_velocity", "grt_cartesian_to_spherical",
     "grt_cartesian_to_boyer_lindquist", "grt_kerr_temperature_lut", "grt_r_isco", "grt_blackbody_lut",
     "grt_blackbody_xyz", "grt_srgb_to_xyza", "grt_perlin_permutation", "grt_volumetric_frame", "grt_xyz_to_srgb8", "grt_xyz_to_srgb", "grt_blackbody_spectrum", "grt_linear_max", "grt_tonemap", "grt_scene_create", "grt_scene_destroy",
-    "grt_render_pixels", "grt_render_pixels_async", "grt_render_section", "grt_set_launch_config", "grt_set_schedule", "grt_set_two_ended", "grt_set_tail", "grt_tail_handoffs", "grt_health_pixels", "grt_tail_report",
+    "grt_render_pixels", "grt_render_pixels_async", "grt_render_section", "grt_set_launch_config", "grt_set_schedule", "grt_set_class_order", "grt_get_class_order", "grt_set_two_ended", "grt_set_tail", "grt_tail_handoffs", "grt_health_pixels", "grt_tail_report",
     "grt_shard_row_count", "grt_shard_frame_row", "grt_render_shard", "grt_render_shard_async", "grt_hit_pool_reserve", "grt_set_hit_pool_min", "grt_set_sub_chunk",
     "grt_linear_max_async", "grt_tonemap_async", "grt_xyz_to_srgb8_device", "grt_trace_pixels", "grt_trace_rays",
     "grt_ray_at", "grt_write_trajectory_csv", "grt_format_f64", "grt_adaptive_min_luminance", "grt_adaptive_min_luminance_device", "grt_supersample_shard",

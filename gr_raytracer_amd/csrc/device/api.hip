@@ -33,6 +33,7 @@ namespace {
 std::atomic<long long> g_launch{256};  // grt_set_launch_config: blocks per CU << 16 | threads per block
 std::atomic<int> g_rkf_short{1};       // grt_debug_rkf_short: 0 = every Schwarzschild attempt with the full RKF sums, 2 = the fallback forced (tests)
 std::atomic<int> g_range_free{1};      // grt_debug_range_free: 0 = every division and sqrt in its IEEE form (tests)
+std::atomic<int> g_class_order{-1};    // grt_set_class_order: -1 auto, 0 off, 1 / 2 forced (tiles by sincos class)
 std::atomic<int> g_schedule{-1};       // grt_set_schedule: -1 auto, 0 row-major tiles, 1 probe-ordered tiles
 std::atomic<int> g_two_ended{1};       // grt_set_two_ended: probe-ordered traces take the queue from both ends
 std::atomic<long long> g_tail{-1};     // grt_set_tail: -1 auto, 0 off, > 0 hand-off threshold (live rays)
@@ -42,12 +43,12 @@ constexpr uint32_t PROBE_CAP = 32768;  // upper bound of the probe's step cap
 struct Knobs {
   int blocks_per_cu, threads, schedule, two_ended;
   long long tail;
-  int arith;
+  int arith, class_order;
   static Knobs now() {
     const long long l = g_launch.load(std::memory_order_relaxed);
     return Knobs{(int)(l >> 16), (int)(l & 0xffff), g_schedule.load(std::memory_order_relaxed),
                  g_two_ended.load(std::memory_order_relaxed), g_tail.load(std::memory_order_relaxed),
-                 g_arith.load(std::memory_order_relaxed)};
+                 g_arith.load(std::memory_order_relaxed), g_class_order.load(std::memory_order_relaxed)};
   }
 };
 
@@ -586,17 +587,32 @@ bool impact_wanted(const grt_scene* s, const grt::WorkList& wl, const Knobs& k) 
          wl.n_items / 64 >= 1024 && !schedule_wanted(s, wl, k);
 }
 
+// The impact-parameter order with the tiles grouped by the sincos case of their rays
+// (schedule.hip tile_class; grt_set_class_order): automatic mode where impact_wanted
+// holds; forced (1, 2) for any Schwarzschild rectangle of more than one tile that is not
+// probe-ordered, whatever grt_set_schedule says.
+bool class_order_wanted(const grt_scene* s, const grt::WorkList& wl, const Knobs& k) {
+  if (k.class_order == 0 || wl.pixel_index || s->desc.geometry != GRT_GEOM_SCHWARZSCHILD) return false;
+  if (k.class_order < 0) return impact_wanted(s, wl, k);
+  return wl.n_items / 64 > 1 && !schedule_wanted(s, wl, k);
+}
+
 // Enqueue the probe pass and the sort; returns the device tile order in *order.
 // quad: the Kerr-Schild probe on quads, -1 automatic, 0 never, 1 always (grt_debug_probe_keys).
+// cls (with impact): the composite key, length bucket then sincos class; cls_out / corner_out
+// (nullable) receive the device arrays of the tiles' classes and the corner predictions.
 int enqueue_tile_order(grt_scene* s, DeviceCopy& dc, const grt::WorkList& wl, hipStream_t stream,
                        const uint32_t** order, int quad_mode = -1, bool impact = false,
-                       const grt::CamTable* ct = nullptr) {
+                       const grt::CamTable* ct = nullptr, bool cls = false, const uint8_t** cls_out = nullptr,
+                       const float** corner_out = nullptr) {
   const uint32_t tiles_x = wl.tiles_x, tiles_y = (uint32_t)(wl.n_items / 64 / wl.tiles_x);
   const uint64_t n = (uint64_t)tiles_x * tiles_y;
   size_t temp_bytes = 0;
   HIP_TRY(grt::launch_tile_order(nullptr, tiles_x, tiles_y, 0, nullptr, nullptr, nullptr, nullptr, nullptr,
                                  &temp_bytes, stream));
-  const uint64_t need = 5 * ((n * 4 + 255) & ~255ull) + temp_bytes + 256;
+  // the corner grid has (tiles_x + 1)(tiles_y + 1) <= 2 n + 2 entries whatever the frame's shape
+  const uint64_t need = 5 * ((n * 4 + 255) & ~255ull) + temp_bytes + 256 + (((2 * n + 2) * 4 + 255) & ~255ull) +
+                        ((n + 255) & ~255ull);
   if (n > dc.sched_tiles || !dc.sched_mem) {
     if (dc.sched_mem) {
       (void)hipDeviceSynchronize();
@@ -620,11 +636,20 @@ int enqueue_tile_order(grt_scene* s, DeviceCopy& dc, const grt::WorkList& wl, hi
   uint32_t* idx = (uint32_t*)take(n * 4);
   uint32_t* ord = (uint32_t*)take(n * 4);
   void* temp = take(temp_bytes);
+  float* corner_a = (float*)take((2 * n + 2) * 4);
+  uint8_t* tile_cls = (uint8_t*)take(n);
   if (impact) {  // predicted lengths, no probe rays; no key counts as capped
     HIP_TRY(ct ? grt::seq::launch_impact_keys(dc.d_scene, wl, (uint32_t)n, probe, stream, *ct)
                : grt::launch_impact_keys(dc.d_scene, wl, (uint32_t)n, probe, stream));
+    if (cls) {
+      const uint32_t n_corners = (tiles_x + 1) * (tiles_y + 1);
+      HIP_TRY(ct ? grt::seq::launch_class_keys(dc.d_scene, wl, tiles_x + 1, n_corners, corner_a, stream, *ct)
+                 : grt::launch_class_keys(dc.d_scene, wl, tiles_x + 1, n_corners, corner_a, stream));
+    }
     HIP_TRY(grt::launch_tile_order(probe, tiles_x, tiles_y, 0xffffffffu, keys, keys_sorted, idx, ord, temp, &temp_bytes,
-                                   stream));
+                                   stream, cls ? corner_a : nullptr, cls ? tile_cls : nullptr));
+    if (cls_out) *cls_out = tile_cls;
+    if (corner_out) *corner_out = corner_a;
     *order = ord;
     return 0;
   }
@@ -716,8 +741,8 @@ int enqueue_trace(grt_scene* s, DeviceCopy& dc, const grt::WorkList& wl_in, cons
     if (rc0) return rc0;
     // longest tiles to the priority wave of each SIMD, shortest to the others (WorkList)
     wl.two_ended = (k.two_ended != 0 && wl.n_items < (1ull << 31)) ? 1u : 0u;
-  } else if (impact_wanted(s, wl, k)) {
-    int rc0 = enqueue_tile_order(s, dc, wl, stream, &wl.tile_order, -1, true, ct);
+  } else if (impact_wanted(s, wl, k) || class_order_wanted(s, wl, k)) {
+    int rc0 = enqueue_tile_order(s, dc, wl, stream, &wl.tile_order, -1, true, ct, class_order_wanted(s, wl, k));
     if (rc0) return rc0;
   }
   HIP_TRY(hipMemsetAsync(dc.d_counter, 0, sizeof(unsigned long long), stream));
@@ -953,6 +978,38 @@ int grt_debug_probe_keys(grt_scene* s, int device, const grt_row_shard* sh, int 
   return 0;
 }
 
+// Test hook (not in grt_api.h): the class-ordered tile queue of a row-band shard as a trace
+// with grt_set_class_order(1) builds it, without the trace: the queue order (n_tiles), the
+// tiles' sincos classes (n_tiles) and the predictor's pi/2 - theta_f at the corners of the
+// tile grid (n_corners = (tiles_x + 1) * (tiles_y + 1)); any output nullable.
+int grt_debug_class_order(grt_scene* s, int device, const grt_row_shard* sh, uint32_t* order_out, uint8_t* class_out,
+                          float* corner_out, uint64_t n_tiles, uint64_t n_corners) {
+  if (!s || !sh) return fail(-EINVAL, "class order: null argument");
+  if (s->desc.geometry != GRT_GEOM_SCHWARZSCHILD) return fail(-EINVAL, "class order: Schwarzschild only");
+  DeviceCopy* dc;
+  int rc;
+  if ((rc = ensure_device(s, device, &dc))) return rc;
+  std::lock_guard<std::mutex> lk(dc->mu);
+  HIP_TRY(hipSetDevice(device));
+  grt::WorkList wl = rect_worklist(0, 0, grt_shard_row_count((uint32_t)s->desc.camera.rows, sh),
+                                   (uint32_t)s->desc.camera.cols);
+  wl.band_rows = sh->band_rows;
+  wl.shard = sh->shard;
+  wl.n_shards = sh->n_shards;
+  const uint64_t tiles_y = wl.n_items / 64 / wl.tiles_x;
+  if (wl.n_items / 64 != n_tiles || (wl.tiles_x + 1ull) * (tiles_y + 1) != n_corners)
+    return fail(-EINVAL, "class order: tile or corner count differs");
+  const uint32_t* order = nullptr;
+  const uint8_t* cls = nullptr;
+  const float* corner = nullptr;
+  if ((rc = enqueue_tile_order(s, *dc, wl, nullptr, &order, -1, true, nullptr, true, &cls, &corner))) return rc;
+  HIP_TRY(hipDeviceSynchronize());
+  if (order_out) HIP_TRY(hipMemcpy(order_out, order, n_tiles * 4, hipMemcpyDeviceToHost));
+  if (class_out) HIP_TRY(hipMemcpy(class_out, cls, n_tiles, hipMemcpyDeviceToHost));
+  if (corner_out) HIP_TRY(hipMemcpy(corner_out, corner, n_corners * 4, hipMemcpyDeviceToHost));
+  return 0;
+}
+
 // Test hook (not in grt_api.h): the range-free divisions and square root (geodesic.hip
 // div_inrange, div2_inrange, div_fx, sqrt_fx) against the compiler's over the exponent
 // plane (arith_map_kernel): map[2047 * 2047], zmap[2047], smap[2047] flag bytes.
@@ -1122,6 +1179,14 @@ int grt_set_two_ended(int on) {
   g_two_ended.store(on);
   return 0;
 }
+
+int grt_set_class_order(int mode) {
+  if (mode < -1 || mode > 2) return fail(-EINVAL, "class order mode must be -1 (auto), 0, 1 or 2");
+  g_class_order.store(mode);
+  return 0;
+}
+
+int grt_get_class_order(void) { return g_class_order.load(); }
 
 int grt_set_schedule(int mode) {
   if (mode < -1 || mode > 1) return fail(-EINVAL, "schedule mode must be -1 (auto), 0 or 1");

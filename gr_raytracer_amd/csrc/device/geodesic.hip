@@ -3322,6 +3322,86 @@ hipError_t launch_impact_keys(const DevScene* d_scene, const WorkList& wl, uint3
   return hipGetLastError();
 }
 
+// Where a Schwarzschild camera ray ends up, without the chart integration: pi/2 - theta_f
+// of its asymptotic direction, for the corner pixels (8i, 8j) of the tile grid (clamped to
+// the frame).  In the far field a ray's theta is constant to O(b / r), so for nearly all
+// of its steps the RHS's sincos takes the case theta_f falls in (glibc_math.h: Taylor
+// within TAYLOR_MAX of pi/2, table elsewhere in region B), and a wave whose lanes agree
+// on the case runs one straight-line form (rhs path 12 / 13) instead of the general one.
+// schedule.hip groups the tiles by it.  The ray moves in the plane of its position and
+// its tangential momentum; with psi the angle swept in that plane, u = 1 / r obeys
+// u'' = -u + 1.5 r_s u^2 (fixed-step RK4 here), u(0) = 1 / r_0, u'(0) = -(dr/dl) / L with
+// L = r^2 dpsi/dl.  The direction after psi is cos(psi) n_0 + sin(psi) t_0 (n_0 the
+// camera's position direction, t_0 the tangential momentum's), hence theta_f.
+// Out: pi/2 - theta_f; CLASS_CAPTURED for a ray that reaches the horizon; NaN for one
+// still winding after CLASS_STEPS steps.  Only the queue order depends on it, never a result.
+constexpr float CLASS_CAPTURED = 1.0e30f;
+constexpr int CLASS_STEPS = 400;
+constexpr double CLASS_DPSI = 0.03125;  // 400 steps: 12.5 rad, two turns round the hole
+__global__ void __launch_bounds__(64) class_key_kernel(const DevScene* __restrict__ Sp, WorkList wl,
+                                                       uint32_t corners_x, uint32_t n_corners,
+                                                       float* __restrict__ a_out CAMS_PARAM) {
+  const DevScene& S = *Sp;
+  glibc::tables_to_lds();
+  const uint32_t t = blockIdx.x * blockDim.x + threadIdx.x;
+  if (t >= n_corners) return;
+  const uint32_t r = min((t / corners_x) * 8, wl.rows - 1), c = min((t % corners_x) * 8, wl.cols - 1);
+  double y[8];
+  RayConst rc;
+#if GRT_SEQ
+  uint32_t ri = wl.row0 + shard_frame_row(wl.band_rows, wl.shard, wl.n_shards, r);
+  const DevCamera& cam = stacked_camera(ct, &ri);
+  init_ray<GRT_GEOM_SCHWARZSCHILD>(S, (double)ri, (double)(wl.col0 + c), y, rc, cam);
+#else
+  init_ray<GRT_GEOM_SCHWARZSCHILD>(S, (double)(wl.row0 + shard_frame_row(wl.band_rows, wl.shard, wl.n_shards, r)),
+                                   (double)(wl.col0 + c), y, rc);
+#endif
+  const double rs = S.radius, st0 = sin(y[2]), ct0 = cos(y[2]);
+  const double tang = sqrt(y[6] * y[6] + st0 * st0 * y[7] * y[7]);  // dpsi/dl
+  const double l = y[1] * y[1] * tang;
+  const double u_hor = 1.0 / rs;
+  double u = 1.0 / y[1], v = -y[5] / l, psi = 0.0;
+  float a = __builtin_nanf("");
+  if (!(l > 0.0) || !isfinite(v)) {  // a radial ray keeps its direction, or falls in
+    a_out[t] = y[5] > 0.0 ? (float)(1.5707963267948966 - y[2]) : CLASS_CAPTURED;
+    return;
+  }
+  auto acc = [rs](double uu) { return -uu + 1.5 * rs * uu * uu; };
+  for (int k = 0; k < CLASS_STEPS; ++k) {
+    const double h = CLASS_DPSI;
+    const double k1u = v, k1v = acc(u);
+    const double k2u = v + 0.5 * h * k1v, k2v = acc(u + 0.5 * h * k1u);
+    const double k3u = v + 0.5 * h * k2v, k3v = acc(u + 0.5 * h * k2u);
+    const double k4u = v + h * k3v, k4v = acc(u + h * k3u);
+    const double un = u + h / 6.0 * (k1u + 2.0 * k2u + 2.0 * k3u + k4u);
+    const double vn = v + h / 6.0 * (k1v + 2.0 * k2v + 2.0 * k3v + k4v);
+    if (!(un > 0.0)) {  // escaped within this step: psi where u crosses 0
+      psi += h * u / (u - un);
+      // t_0's z component: the theta part of the tangential momentum, e_theta . z = -sin(theta)
+      const double tz = -st0 * (y[6] / tang);
+      const double nz = fmin(1.0, fmax(-1.0, cos(psi) * ct0 + sin(psi) * tz));
+      a = (float)(1.5707963267948966 - acos(nz));
+      break;
+    }
+    if (un >= u_hor) {
+      a = CLASS_CAPTURED;
+      break;
+    }
+    u = un;
+    v = vn;
+    psi += h;
+  }
+  a_out[t] = a;
+}
+
+hipError_t launch_class_keys(const DevScene* d_scene, const WorkList& wl, uint32_t corners_x, uint32_t n_corners,
+                             float* d_a, hipStream_t stream CAMS_PARAM) {
+  if (n_corners == 0) return hipSuccess;
+  hipLaunchKernelGGL(class_key_kernel, dim3((n_corners + 63) / 64), dim3(64), 0, stream, d_scene, wl, corners_x,
+                     n_corners, d_a CAMS_ARG);
+  return hipGetLastError();
+}
+
 // probe_kernel<KERR> with each probe ray on the 4 lanes of a quad (rhs_ks_quad, as in
 // tail_kernel): the same operations on the same values, so the same keys (GPU test
 // tests/test_gpu_schedule.py).  For a pass of few probe rays (a 1/8 row-band shard of

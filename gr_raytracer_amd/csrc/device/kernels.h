@@ -31,12 +31,22 @@ hipError_t launch_probe(int geometry, const DevScene* d_scene, const WorkList& w
 // `wl` from the impact parameter of the tile's probe pixel (impact_key_kernel).
 hipError_t launch_impact_keys(const DevScene* d_scene, const WorkList& wl, uint32_t n_tiles, uint32_t* d_keys,
                               hipStream_t stream);
+// Schwarzschild sincos-case predictor (class_key_kernel): pi/2 - theta_f of the asymptotic
+// direction of the ray through pixel (8i, 8j) of `wl`, clamped to the frame, for the
+// corners_x x (n_corners / corners_x) corners of the tile grid; CLASS_CAPTURED-large for
+// a captured ray, NaN for an undecided one.
+hipError_t launch_class_keys(const DevScene* d_scene, const WorkList& wl, uint32_t corners_x, uint32_t n_corners,
+                             float* d_a, hipStream_t stream);
 // Tile queue order from the probe keys (schedule.hip): 3x3-dilated keys (edge tiles of a
 // region of probes that reached `cap` boosted), sorted descending (stable).  `temp` /
 // `temp_bytes`: scratch, query with temp == NULL.
+// d_corner_a (launch_class_keys' output, NULL = none): the composite key, the predicted
+// length in LEN_BUCKET steps as the major part and the tile's sincos class as the minor
+// one (schedule.hip tile_class); d_class (nullable) receives the classes.
 hipError_t launch_tile_order(const uint32_t* d_probe, uint32_t tiles_x, uint32_t tiles_y, uint32_t cap, uint32_t* d_keys,
                              uint32_t* d_keys_sorted, uint32_t* d_idx, uint32_t* d_order, void* temp,
-                             size_t* temp_bytes, hipStream_t stream);
+                             size_t* temp_bytes, hipStream_t stream, const float* d_corner_a = nullptr,
+                             uint8_t* d_class = nullptr);
 
 // Whole trajectories (render-ray / render-ray-at): camera pixels (row, col) or explicit
 // native-chart (position, momentum) pairs; record layout in trajectory_kernel.
@@ -112,6 +122,8 @@ hipError_t launch_probe(int geometry, const DevScene* d_scene, const WorkList& w
                         uint32_t* d_steps, bool quad, hipStream_t stream, CamTable ct);
 hipError_t launch_impact_keys(const DevScene* d_scene, const WorkList& wl, uint32_t n_tiles, uint32_t* d_keys,
                               hipStream_t stream, CamTable ct);
+hipError_t launch_class_keys(const DevScene* d_scene, const WorkList& wl, uint32_t corners_x, uint32_t n_corners,
+                             float* d_a, hipStream_t stream, CamTable ct);
 }  // namespace seq
 hipError_t launch_trajectories(int geometry, const DevScene* d_scene, const TrajectoryList& tl, hipStream_t stream);
 

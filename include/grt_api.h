@@ -1012,6 +1012,19 @@ int grt_set_launch_config(int blocks_per_cu, int threads_per_block);
  * max_steps >= 262144 over >= 1024 tiles; KerrBL's Mino-time rays are all short).
  * Scheduling only: every pixel's result is identical in all modes. */
 int grt_set_schedule(int mode);
+/* Schwarzschild tile queue grouped by sincos case.  In the far field a ray's theta hardly
+ * moves, so the right-hand side's sincos stays in one of its cases (Taylor near the
+ * equator, table elsewhere) for nearly every step, and a wave whose 64 rays agree on it
+ * runs a straight-line form.  A small predictor kernel finds each tile's case from the
+ * asymptotic direction of its corner rays, and the impact-parameter order (above) takes it
+ * as the minor part of its sort key.  -1 = automatic (default: wherever the
+ * impact-parameter order applies); 0 = off; 1 = forced for any Schwarzschild rectangle of
+ * more than one tile, whatever grt_set_schedule says (probe-ordered traces excepted);
+ * 2 = the same as 1 (it selected a pixel-level regrouping of the tiles that straddle a
+ * border, which was measured, did not pay for itself and is not built).
+ * Scheduling only: every pixel's result is identical in all modes. */
+int grt_set_class_order(int mode);
+int grt_get_class_order(void);
 /* Probe-ordered traces (above) hand the queue out from both ends: on every SIMD the wave
  * in an even hardware slot takes the tiles with the longest predicted rays, at raised
  * issue priority, the others take the shortest (1 = default); 0 = one end, longest

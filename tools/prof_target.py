@@ -10,6 +10,8 @@ import gr_raytracer_amd as g
 import os
 if "GRT_SCHEDULE" in os.environ:  # -1 auto, 0 row-major tiles, 1 probe-ordered
     g.lib().grt_set_schedule(int(os.environ["GRT_SCHEDULE"]))
+if "GRT_CLASS_ORDER" in os.environ:  # -1 auto, 0 off, 1 tiles by sincos class (forced)
+    g.lib().grt_set_class_order(int(os.environ["GRT_CLASS_ORDER"]))
 which = sys.argv[1] if len(sys.argv) > 1 else "c2"
 if which == "c2":
     opts = g.GlobalOpts(width=1500, height=1500, camera_position=(-16.0, 0.0, 3.5), theta=-3.142, max_steps=100000)
