@@ -1,0 +1,946 @@
+// api_gbuffer.hip — geometry buffers of the C ABI (include/grt_api.h): the exact trace and
+// fill of a frame or of a camera sequence, the sub-sample set, and the re-shades, the
+// adaptive one through the pass of api_adaptive.hip (AdaptivePlan, api_internal.h).
+#include <hip/hip_runtime.h>
+
+#include <algorithm>
+#include <atomic>
+#include <chrono>
+#include <cerrno>
+#include <climits>
+#include <cstring>
+#include <memory>
+#include <mutex>
+#include <string>
+#include <vector>
+
+#include "grt_api.h"
+#include "../host/host_internal.h"
+#include "dev_scene.h"
+#include "kernels.h"
+#include "api_internal.h"
+
+using namespace grt_api;
+
+// ---- geometry buffer (grt_api.h): trace once, re-shade many times -------------------------
+// The device-resident buffer: its arrays belong to it, not to a scene's scratch, so later
+// traces on the device leave it alone.
+// Grow a device array to `want` bytes, keeping its first `keep` bytes.
+static int grow_buf(DevBuf& b, size_t keep, size_t want) {
+  void* p = nullptr;
+  if (hipMalloc(&p, want ? want : 16) != hipSuccess) {
+    (void)hipGetLastError();
+    return fail(-ENOMEM, "cannot grow the g-buffer's sub-sample set");
+  }
+  if (keep && b.p) {
+    hipError_t e = hipMemcpy(p, b.p, keep, hipMemcpyDeviceToDevice);
+    if (e != hipSuccess) {
+      (void)hipFree(p);
+      return fail(-EIO, std::string("HIP error: ") + hipGetErrorString(e));
+    }
+  }
+  if (b.p) (void)hipFree(b.p);
+  b.p = p;
+  return 0;
+}
+
+// The sub-sample set of a buffer (grt_api.h): append-only, capacities grow geometrically.
+// Block b holds the per sub-rays of pixel sub_pixel[b] at rays [b * per, (b + 1) * per).
+struct GBufferSub {
+  uint32_t spa = 0;  // 0: no set
+  uint64_t n_pix = 0, cap_pix = 0, n_layers = 0, cap_layers = 0;
+  DevBuf sub_pixel;  // u32[cap_pix]
+  DevBuf sub_block;  // u32[n_pixels], GBUFFER_NIL where a pixel has no block (derived, never stored)
+  std::vector<uint32_t> h_block;  // host copy of sub_block
+  DevBuf status, stop, steps, sky_u, sky_v, sky_z, layer_start, object, u, v, z, radius;
+  uint64_t per() const { return (uint64_t)spa * spa; }
+  uint64_t n_rays() const { return n_pix * per(); }
+  // the pixel -> block map, all NIL, before any block exists
+  int ensure_map(uint64_t n_pixels) {
+    if (sub_block.p) return 0;
+    if (int rc = sub_block.alloc(4 * n_pixels)) return rc;
+    HIP_TRY(hipMemset(sub_block.p, 0xff, 4 * n_pixels));
+    h_block.assign(n_pixels, grt::GBUFFER_NIL);
+    return 0;
+  }
+  int reserve_pixels(uint64_t want) {
+    if (want <= cap_pix) return 0;
+    const uint64_t cap = std::max<uint64_t>({want, 2 * cap_pix, 1024}), p = per(), r0 = n_rays(), r1 = cap * p;
+    int rc;
+    if ((rc = grow_buf(sub_pixel, 4 * n_pix, 4 * cap)) || (rc = grow_buf(status, r0, r1)) ||
+        (rc = grow_buf(stop, r0, r1)) || (rc = grow_buf(steps, 4 * r0, 4 * r1)) ||
+        (rc = grow_buf(sky_u, 8 * r0, 8 * r1)) || (rc = grow_buf(sky_v, 8 * r0, 8 * r1)) ||
+        (rc = grow_buf(sky_z, 8 * r0, 8 * r1)))
+      return rc;
+    const bool first = layer_start.p == nullptr;
+    if ((rc = grow_buf(layer_start, first ? 0 : 8 * (r0 + 1), 8 * (r1 + 1)))) return rc;
+    if (first) HIP_TRY(hipMemset(layer_start.p, 0, 8));
+    cap_pix = cap;
+    return 0;
+  }
+  int reserve_layers(uint64_t want) {
+    if (want <= cap_layers && object.p) return 0;
+    const uint64_t cap = std::max<uint64_t>({want, 2 * cap_layers, 4096}), l = n_layers;
+    int rc;
+    if ((rc = grow_buf(object, l, cap)) || (rc = grow_buf(u, 8 * l, 8 * cap)) || (rc = grow_buf(v, 8 * l, 8 * cap)) ||
+        (rc = grow_buf(z, 8 * l, 8 * cap)) || (rc = grow_buf(radius, 8 * l, 8 * cap)))
+      return rc;
+    cap_layers = cap;
+    return 0;
+  }
+  // the rays from `first_ray` on (layer offsets stay the set's own)
+  grt::GBufferArrays view(uint64_t first_ray, uint64_t n) const {
+    return grt::GBufferArrays{n,
+                              (const uint8_t*)status.p + first_ray,
+                              (const uint8_t*)stop.p + first_ray,
+                              (const uint64_t*)layer_start.p + first_ray,
+                              (double*)sky_u.p + first_ray,
+                              (double*)sky_v.p + first_ray,
+                              (double*)sky_z.p + first_ray,
+                              (uint8_t*)object.p,
+                              (double*)u.p,
+                              (double*)v.p,
+                              (double*)z.p,
+                              (double*)radius.p};
+  }
+};
+
+struct grt_gbuffer {
+  grt_gbuffer_info info;
+  double times[2] = {0.0, 0.0};  // trace, scan + fill (ms)
+  DevBuf status, stop, steps, sky_u, sky_v, sky_z, layer_start, object, u, v, z, radius;
+  GBufferSub sub;
+  grt_gbuffer() { std::memset(&info, 0, sizeof(info)); }
+  int alloc_pixels() {
+    const uint64_t n = info.n_pixels;
+    int rc;
+    if ((rc = status.alloc(n)) || (rc = stop.alloc(n)) || (rc = steps.alloc(4 * n)) || (rc = sky_u.alloc(8 * n)) ||
+        (rc = sky_v.alloc(8 * n)) || (rc = sky_z.alloc(8 * n)) || (rc = layer_start.alloc(8 * (n + 1))))
+      return rc;
+    return 0;
+  }
+  int alloc_layers() {
+    const uint64_t l = info.n_layers;
+    int rc;
+    if ((rc = object.alloc(l)) || (rc = u.alloc(8 * l)) || (rc = v.alloc(8 * l)) || (rc = z.alloc(8 * l)) ||
+        (rc = radius.alloc(8 * l)))
+      return rc;
+    return 0;
+  }
+  grt::GBufferArrays view() const {
+    return grt::GBufferArrays{info.n_pixels,      (const uint8_t*)status.p, (const uint8_t*)stop.p,
+                              (const uint64_t*)layer_start.p, (double*)sky_u.p, (double*)sky_v.p,
+                              (double*)sky_z.p,   (uint8_t*)object.p,       (double*)u.p,
+                              (double*)v.p,       (double*)z.p,             (double*)radius.p};
+  }
+};
+
+// What a buffer records of the scene it was traced with, beside the camera: written by
+// info_from_scene, held to the tracer of the sub-rays by check_tracer, byte for byte.
+#define GRT_GBUFFER_RECORDED(X) X(max_steps) X(max_radius) X(step_size) X(epsilon) X(horizon_epsilon)
+
+static void info_from_scene(const grt_scene_desc& d, const grt_camera_desc& camera, grt_gbuffer_info* info) {
+  grt_gbuffer_shape_of(&d, &info->shape);
+  info->camera = camera;
+#define X(field) info->field = d.field;
+  GRT_GBUFFER_RECORDED(X)
+#undef X
+}
+
+// The sub-rays of a buffer belong to the frame it holds: the tracer's geometry (shape key),
+// camera and integration parameters must be the recorded ones.
+static int check_tracer(const grt_gbuffer* gb, const grt_scene* t) {
+  if (int rc = grt_gbuffer_shape_compatible(&gb->info.shape, &t->desc)) return rc;
+  auto differs = [](const char* field) {
+    return fail(-EINVAL, std::string("g-buffer: the tracer differs from the traced scene in ") + field);
+  };
+  const grt_gbuffer_info& i = gb->info;
+  if (std::memcmp(&i.camera, &t->desc.camera, sizeof(i.camera)) != 0) return differs("camera");
+#define X(field) \
+  if (std::memcmp(&i.field, &t->desc.field, sizeof(i.field)) != 0) return differs(#field);
+  GRT_GBUFFER_RECORDED(X)
+#undef X
+  return 0;
+}
+
+// Trace `wl` with the exact kernels, waited for (trace_sync), the whole list again with a
+// larger pool while a trace loses candidates: the workspace and pool a fill reads must be
+// one complete trace's.  acc[3] is 0 on success; *n_traces (nullable) counts the traces.
+static int trace_exact(grt_scene* s, DeviceCopy& dc, const grt::WorkList& wl, const grt::Outputs& o,
+                       unsigned long long acc[8], float* ms, const grt::CamTable* ct = nullptr,
+                       uint32_t* n_traces = nullptr) {
+  for (int traces = 1;; ++traces) {
+    unsigned long long need = 0;
+    acc[3] = 0;
+    if (n_traces) ++*n_traces;
+    if (int rc = trace_sync(s, dc, wl, o, acc, ms, &need, ct, true)) return rc;
+    if (acc[3] == 0) return 0;
+    if (traces == 3 || dc.pool_cap >= POOL_MAX)
+      return fail(-ENOMEM, "the hit pool still overflows after " + std::to_string(traces) + " traces");
+    if (int rc = ensure_pool(dc, need + need / 4)) return rc;
+  }
+}
+
+extern "C" {
+
+int grt_gbuffer_trace(grt_scene* s, int device, uint32_t row0, uint32_t col0, uint32_t rows, uint32_t cols,
+                      grt_gbuffer** out, grt_stats* stats) {
+  if (!s || !out) return fail(-EINVAL, "null argument");
+  *out = nullptr;
+  if (rows == 0 || cols == 0) return fail(-EINVAL, "empty rectangle");
+  int rc = check_rect(s, row0, col0, rows, cols);
+  if (rc) return rc;
+  for (uint32_t k = 0; k < s->desc.n_objects; ++k)
+    if (s->desc.objects[k].kind == GRT_OBJ_VOLUMETRIC_DISC)
+      return fail(-ENOTSUP, "a VolumetricDisc's colour is raymarched: the scene has no geometry buffer");
+  const uint64_t n = (uint64_t)rows * cols;
+  if (n + 1 > (uint64_t)INT_MAX) return fail(-EOVERFLOW, "more than INT_MAX - 1 pixels");
+  DeviceCopy* dc;
+  if ((rc = ensure_device(s, device, &dc))) return rc;
+  std::lock_guard<std::mutex> lk(dc->mu);
+  HIP_TRY(hipSetDevice(device));
+  std::unique_ptr<grt_gbuffer> gb(new grt_gbuffer());
+  grt_gbuffer_info& info = gb->info;
+  info.row0 = row0;
+  info.col0 = col0;
+  info.rows = rows;
+  info.cols = cols;
+  info.n_pixels = n;
+  info.device = device;
+  info_from_scene(s->desc, s->desc.camera, &info);
+  if ((rc = gb->alloc_pixels())) return rc;
+  // the trace's other outputs, and the scan's scratch
+  DevBuf xyza, cls, hits, counts, temp;
+  if ((rc = xyza.alloc(16 * n)) || (rc = cls.alloc(n)) || (rc = hits.alloc(4 * n)) || (rc = counts.alloc(8 * (n + 1))))
+    return rc;
+  size_t temp_bytes = 0;
+  HIP_TRY(grt::gbuffer_layer_scan(nullptr, nullptr, n, nullptr, nullptr, nullptr, &temp_bytes, nullptr));
+  if ((rc = temp.alloc(temp_bytes))) return rc;
+  const grt::WorkList wl = rect_worklist(row0, col0, rows, cols);
+  const grt::Outputs o{(float*)xyza.p,          (uint8_t*)cls.p,         (uint8_t*)gb->status.p, nullptr,
+                       (uint32_t*)gb->steps.p,  (uint8_t*)gb->stop.p,    (uint32_t*)hits.p};
+  unsigned long long acc[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+  float ms = 0;
+  if ((rc = trace_exact(s, *dc, wl, o, acc, &ms))) return rc;
+  hipStream_t st = nullptr;
+  if ((rc = stream_order(*dc, st))) return rc;
+  HIP_TRY(hipEventRecord(dc->ev0, st));
+  HIP_TRY(grt::gbuffer_layer_scan((const uint8_t*)gb->status.p, (const uint32_t*)hits.p, n, (uint64_t*)counts.p,
+                                  (uint64_t*)gb->layer_start.p, temp.p, &temp_bytes, st));
+  uint64_t n_layers = 0;
+  HIP_TRY(hipMemcpy(&n_layers, (const uint64_t*)gb->layer_start.p + n, 8, hipMemcpyDeviceToHost));
+  info.n_layers = n_layers;
+  if ((rc = gb->alloc_layers())) return rc;
+  grt::Workspace ws;
+  if ((rc = ensure_workspace(*dc, n, &ws))) return rc;  // the carving of the trace above
+  ws.pool = dc->d_pool;
+  const auto fill = s->desc.geometry == GRT_GEOM_KERR_BL ? grt::kerr_bl::launch_gbuffer_fill : grt::launch_gbuffer_fill;
+  HIP_TRY(fill(s->desc.geometry, dc->d_scene, wl, ws, gb->view(), st));
+  HIP_TRY(hipEventRecord(dc->ev1, st));
+  HIP_TRY(hipEventSynchronize(dc->ev1));
+  float fill_ms = 0;
+  HIP_TRY(hipEventElapsedTime(&fill_ms, dc->ev0, dc->ev1));
+  if ((rc = stream_done(*dc, st))) return rc;
+  gb->times[0] = ms;
+  gb->times[1] = fill_ms;
+  // the overflows are 0 (trace_exact) and so are the march counters: only march_kernel
+  // (volumetric.h) adds to them, and scenes with a VolumetricDisc are refused above
+  if (stats) stats_from(acc, ms, stats);
+  *out = gb.release();
+  return 0;
+}
+
+int grt_gbuffer_trace_times(const grt_gbuffer* gb, double ms[2]) {
+  if (!gb || !ms) return fail(-EINVAL, "null argument");
+  ms[0] = gb->times[0];
+  ms[1] = gb->times[1];
+  return 0;
+}
+
+int grt_gbuffer_info_get(const grt_gbuffer* gb, grt_gbuffer_info* out) {
+  if (!gb || !out) return fail(-EINVAL, "null argument");
+  *out = gb->info;
+  return 0;
+}
+
+int grt_gbuffer_download(const grt_gbuffer* gb, const grt_gbuffer_arrays* h) {
+  if (!gb || !h || !h->status || !h->stop || !h->steps || !h->sky_u || !h->sky_v || !h->sky_redshift ||
+      !h->layer_start)
+    return fail(-EINVAL, "null argument");
+  const uint64_t n = gb->info.n_pixels, l = gb->info.n_layers;
+  if (l && (!h->object || !h->u || !h->v || !h->redshift || !h->radius)) return fail(-EINVAL, "null layer array");
+  HIP_TRY(hipSetDevice(gb->info.device));
+  HIP_TRY(hipMemcpy(h->status, gb->status.p, n, hipMemcpyDeviceToHost));
+  HIP_TRY(hipMemcpy(h->stop, gb->stop.p, n, hipMemcpyDeviceToHost));
+  HIP_TRY(hipMemcpy(h->steps, gb->steps.p, 4 * n, hipMemcpyDeviceToHost));
+  HIP_TRY(hipMemcpy(h->sky_u, gb->sky_u.p, 8 * n, hipMemcpyDeviceToHost));
+  HIP_TRY(hipMemcpy(h->sky_v, gb->sky_v.p, 8 * n, hipMemcpyDeviceToHost));
+  HIP_TRY(hipMemcpy(h->sky_redshift, gb->sky_z.p, 8 * n, hipMemcpyDeviceToHost));
+  HIP_TRY(hipMemcpy(h->layer_start, gb->layer_start.p, 8 * (n + 1), hipMemcpyDeviceToHost));
+  if (l) {
+    HIP_TRY(hipMemcpy(h->object, gb->object.p, l, hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(h->u, gb->u.p, 8 * l, hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(h->v, gb->v.p, 8 * l, hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(h->redshift, gb->z.p, 8 * l, hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(h->radius, gb->radius.p, 8 * l, hipMemcpyDeviceToHost));
+  }
+  return 0;
+}
+
+int grt_gbuffer_upload(const grt_gbuffer_info* info, const grt_gbuffer_arrays* h, int device, grt_gbuffer** out) {
+  if (!out) return fail(-EINVAL, "null argument");
+  *out = nullptr;
+  // the shade kernel indexes by layer_start and object: hold them to their ranges first
+  int rc = grt_host::gbuffer_check_arrays(info, h);
+  if (rc) return rc;
+  int ndev = 0;
+  HIP_TRY(hipGetDeviceCount(&ndev));
+  if (device < 0 || device >= ndev) return fail(-ENODEV, "invalid device ordinal");
+  HIP_TRY(hipSetDevice(device));
+  std::unique_ptr<grt_gbuffer> gb(new grt_gbuffer());
+  gb->info = *info;
+  gb->info.device = device;
+  gb->info._pad = 0;
+  const uint64_t n = info->n_pixels, l = info->n_layers;
+  if ((rc = gb->alloc_pixels()) || (rc = gb->alloc_layers())) return rc;
+  HIP_TRY(hipMemcpy(gb->status.p, h->status, n, hipMemcpyHostToDevice));
+  HIP_TRY(hipMemcpy(gb->stop.p, h->stop, n, hipMemcpyHostToDevice));
+  HIP_TRY(hipMemcpy(gb->steps.p, h->steps, 4 * n, hipMemcpyHostToDevice));
+  HIP_TRY(hipMemcpy(gb->sky_u.p, h->sky_u, 8 * n, hipMemcpyHostToDevice));
+  HIP_TRY(hipMemcpy(gb->sky_v.p, h->sky_v, 8 * n, hipMemcpyHostToDevice));
+  HIP_TRY(hipMemcpy(gb->sky_z.p, h->sky_redshift, 8 * n, hipMemcpyHostToDevice));
+  HIP_TRY(hipMemcpy(gb->layer_start.p, h->layer_start, 8 * (n + 1), hipMemcpyHostToDevice));
+  if (l) {
+    HIP_TRY(hipMemcpy(gb->object.p, h->object, l, hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(gb->u.p, h->u, 8 * l, hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(gb->v.p, h->v, 8 * l, hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(gb->z.p, h->redshift, 8 * l, hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(gb->radius.p, h->radius, 8 * l, hipMemcpyHostToDevice));
+  }
+  *out = gb.release();
+  return 0;
+}
+
+int grt_gbuffer_shade(grt_scene* s, const grt_gbuffer* gb, float* xyza_out, uint8_t* class_out, uint8_t* status_out,
+                      double* xyza64_out, float* kernel_ms) {
+  if (!s || !gb || !xyza_out || !class_out || !status_out) return fail(-EINVAL, "null argument");
+  int rc = grt_gbuffer_shape_compatible(&gb->info.shape, &s->desc);
+  if (rc) return rc;
+  const int device = gb->info.device;
+  DeviceCopy* dc;
+  if ((rc = ensure_device(s, device, &dc))) return rc;
+  std::lock_guard<std::mutex> lk(dc->mu);
+  HIP_TRY(hipSetDevice(device));
+  const uint64_t n = gb->info.n_pixels;
+  DevBuf xyza, cls, status, x64;
+  if ((rc = xyza.alloc(16 * n)) || (rc = cls.alloc(n)) || (rc = status.alloc(n))) return rc;
+  if (xyza64_out && (rc = x64.alloc(32 * n))) return rc;
+  const grt::Outputs o{(float*)xyza.p, (uint8_t*)cls.p, (uint8_t*)status.p, (double*)x64.p, nullptr, nullptr, nullptr};
+  hipStream_t st = nullptr;
+  HIP_TRY(hipEventRecord(dc->ev0, st));
+  HIP_TRY(grt::launch_gbuffer_shade(dc->d_scene, gb->view(), o, st));
+  HIP_TRY(hipEventRecord(dc->ev1, st));
+  HIP_TRY(hipEventSynchronize(dc->ev1));
+  float t = 0;
+  HIP_TRY(hipEventElapsedTime(&t, dc->ev0, dc->ev1));
+  if (kernel_ms) *kernel_ms = t;
+  HIP_TRY(hipMemcpy(xyza_out, xyza.p, 16 * n, hipMemcpyDeviceToHost));
+  HIP_TRY(hipMemcpy(class_out, cls.p, n, hipMemcpyDeviceToHost));
+  HIP_TRY(hipMemcpy(status_out, status.p, n, hipMemcpyDeviceToHost));
+  if (xyza64_out) HIP_TRY(hipMemcpy(xyza64_out, x64.p, 32 * n, hipMemcpyDeviceToHost));
+  return 0;
+}
+
+}  // extern "C"
+
+// ---- geometry buffers of a camera sequence (grt_api.h) ----
+namespace {
+struct GbSeqTimes {
+  unsigned long long acc[8] = {0, 0, 0, 0, 0, 0, 0, 0};  // as trace_sync's
+  double trace_ms = 0.0, fill_ms = 0.0;
+  uint32_t traces = 0;
+};
+
+// One launch group: the stacked 1-spp trace of the group's frames through the sequence unit,
+// the layer scan and the fill over the whole stack in slot order (frame after frame), then
+// the cut into one buffer per frame: device-to-device copies of the frame's slice of every
+// array, and its layer_start rebased to 0 at its first pixel.  Appends the buffers to `made`.
+int gbuffer_sequence_group(grt_scene* s, DeviceCopy& dc, int device, const grt::CamTable& ct,
+                           const grt_camera_desc* cameras, uint32_t rows, uint32_t cols,
+                           std::vector<std::unique_ptr<grt_gbuffer>>& made, GbSeqTimes* T) {
+  int rc;
+  const uint32_t kg = ct.n_cams;
+  const uint64_t per = (uint64_t)rows * cols, n = per * kg;
+  DevBuf status, stop, steps, sky_u, sky_v, sky_z, layer_start, xyza, cls, hits, counts, temp;
+  if ((rc = status.alloc(n)) || (rc = stop.alloc(n)) || (rc = steps.alloc(4 * n)) || (rc = sky_u.alloc(8 * n)) ||
+      (rc = sky_v.alloc(8 * n)) || (rc = sky_z.alloc(8 * n)) || (rc = layer_start.alloc(8 * (n + 1))) ||
+      (rc = xyza.alloc(16 * n)) || (rc = cls.alloc(n)) || (rc = hits.alloc(4 * n)) || (rc = counts.alloc(8 * (n + 1))))
+    return rc;
+  size_t temp_bytes = 0;
+  HIP_TRY(grt::gbuffer_layer_scan(nullptr, nullptr, n, nullptr, nullptr, nullptr, &temp_bytes, nullptr));
+  if ((rc = temp.alloc(temp_bytes))) return rc;
+  const grt::WorkList wl = rect_worklist(0, 0, kg * rows, cols);
+  const grt::Outputs o{(float*)xyza.p,     (uint8_t*)cls.p,  (uint8_t*)status.p, nullptr,
+                       (uint32_t*)steps.p, (uint8_t*)stop.p, (uint32_t*)hits.p};
+  unsigned long long acc[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+  float ms = 0;
+  if ((rc = trace_exact(s, dc, wl, o, acc, &ms, &ct, &T->traces))) return rc;
+  hipStream_t st = nullptr;
+  if ((rc = stream_order(dc, st))) return rc;
+  HIP_TRY(hipEventRecord(dc.ev0, st));
+  HIP_TRY(grt::gbuffer_layer_scan((const uint8_t*)status.p, (const uint32_t*)hits.p, n, (uint64_t*)counts.p,
+                                  (uint64_t*)layer_start.p, temp.p, &temp_bytes, st));
+  // where each frame's layers begin in the stack's, and the total
+  std::vector<uint64_t> base(kg + 1);
+  for (uint32_t f = 0; f <= kg; ++f)
+    HIP_TRY(hipMemcpy(&base[f], (const uint64_t*)layer_start.p + per * f, 8, hipMemcpyDeviceToHost));
+  const uint64_t total = base[kg];
+  DevBuf object, u, v, z, radius;
+  if ((rc = object.alloc(total)) || (rc = u.alloc(8 * total)) || (rc = v.alloc(8 * total)) ||
+      (rc = z.alloc(8 * total)) || (rc = radius.alloc(8 * total)))
+    return rc;
+  grt::Workspace ws;
+  if ((rc = ensure_workspace(dc, n, &ws))) return rc;  // the carving of the trace above
+  ws.pool = dc.d_pool;
+  const grt::GBufferArrays stack{n,
+                                 (const uint8_t*)status.p,
+                                 (const uint8_t*)stop.p,
+                                 (const uint64_t*)layer_start.p,
+                                 (double*)sky_u.p,
+                                 (double*)sky_v.p,
+                                 (double*)sky_z.p,
+                                 (uint8_t*)object.p,
+                                 (double*)u.p,
+                                 (double*)v.p,
+                                 (double*)z.p,
+                                 (double*)radius.p};
+  HIP_TRY(grt::seq::launch_gbuffer_fill(s->desc.geometry, dc.d_scene, wl, ws, stack, st, ct));
+  const size_t first = made.size();
+  for (uint32_t f = 0; f < kg; ++f) {
+    std::unique_ptr<grt_gbuffer> gb(new grt_gbuffer());
+    grt_gbuffer_info& info = gb->info;
+    info.row0 = 0;
+    info.col0 = 0;
+    info.rows = rows;
+    info.cols = cols;
+    info.n_pixels = per;
+    info.n_layers = base[f + 1] - base[f];
+    info.device = device;
+    info_from_scene(s->desc, cameras[f], &info);
+    if ((rc = gb->alloc_pixels()) || (rc = gb->alloc_layers())) return rc;
+    const uint64_t p0 = per * f, l0 = base[f], nl = info.n_layers;
+    auto cut = [&](DevBuf& dst, const DevBuf& src, uint64_t at, uint64_t count, uint64_t size) {
+      return count ? hipMemcpyAsync(dst.p, (const char*)src.p + at * size, count * size, hipMemcpyDeviceToDevice, st)
+                   : hipSuccess;
+    };
+    HIP_TRY(cut(gb->status, status, p0, per, 1));
+    HIP_TRY(cut(gb->stop, stop, p0, per, 1));
+    HIP_TRY(cut(gb->steps, steps, p0, per, 4));
+    HIP_TRY(cut(gb->sky_u, sky_u, p0, per, 8));
+    HIP_TRY(cut(gb->sky_v, sky_v, p0, per, 8));
+    HIP_TRY(cut(gb->sky_z, sky_z, p0, per, 8));
+    HIP_TRY(cut(gb->object, object, l0, nl, 1));
+    HIP_TRY(cut(gb->u, u, l0, nl, 8));
+    HIP_TRY(cut(gb->v, v, l0, nl, 8));
+    HIP_TRY(cut(gb->z, z, l0, nl, 8));
+    HIP_TRY(cut(gb->radius, radius, l0, nl, 8));
+    HIP_TRY(grt::gbuffer_rebase((const uint64_t*)layer_start.p + p0, per, (uint64_t*)gb->layer_start.p, st));
+    made.push_back(std::move(gb));
+  }
+  HIP_TRY(hipEventRecord(dc.ev1, st));
+  HIP_TRY(hipEventSynchronize(dc.ev1));  // the stacked arrays are freed on return
+  float fill_ms = 0;
+  HIP_TRY(hipEventElapsedTime(&fill_ms, dc.ev0, dc.ev1));
+  if ((rc = stream_done(dc, st))) return rc;
+  for (size_t k = first; k < made.size(); ++k) {
+    made[k]->times[0] = ms;
+    made[k]->times[1] = fill_ms;
+  }
+  for (int k = 0; k < 8; ++k) T->acc[k] += acc[k];
+  T->trace_ms += ms;
+  T->fill_ms += fill_ms;
+  return 0;
+}
+}  // namespace
+
+extern "C" {
+
+int grt_gbuffer_trace_sequence(grt_scene* s, int device, uint32_t n_cameras, const grt_camera_desc* cameras,
+                               grt_gbuffer** out, grt_stats* stats, grt_gbuffer_sequence_report* report) {
+  const auto wall0 = std::chrono::steady_clock::now();
+  if (out)
+    for (uint32_t f = 0; f < n_cameras; ++f) out[f] = nullptr;
+  if (!s || !cameras || !out) return fail(-EINVAL, "null argument");
+  if (n_cameras == 0) return fail(-EINVAL, "a sequence needs at least one camera");
+  const int64_t rows64 = s->desc.camera.rows, cols64 = s->desc.camera.cols;
+  for (uint32_t f = 0; f < n_cameras; ++f)
+    if (cameras[f].rows != rows64 || cameras[f].cols != cols64)
+      return fail(-EINVAL, "camera " + std::to_string(f) + " of the sequence has " + std::to_string(cameras[f].rows) +
+                               " x " + std::to_string(cameras[f].cols) + " pixels, the scene's frame " +
+                               std::to_string(rows64) + " x " + std::to_string(cols64));
+  for (uint32_t k = 0; k < s->desc.n_objects; ++k)
+    if (s->desc.objects[k].kind == GRT_OBJ_VOLUMETRIC_DISC)
+      return fail(-ENOTSUP, "a VolumetricDisc's colour is raymarched: the scene has no geometry buffer");
+  const uint32_t rows = (uint32_t)rows64, cols = (uint32_t)cols64;
+  const uint64_t per = (uint64_t)rows * cols;
+  if (per == 0) return fail(-EINVAL, "empty frame");
+  if (per + 1 > (uint64_t)INT_MAX) return fail(-EOVERFLOW, "more than INT_MAX - 1 pixels");
+  // frames per launch group: grt_render_sequence's arithmetic; the scan runs over n + 1 entries
+  uint64_t g = std::max<uint64_t>(1, g_seq_group.load(std::memory_order_relaxed) / per);
+  g = std::min<uint64_t>(g, n_cameras);
+  g = std::min<uint64_t>(g, std::max<uint64_t>(1, ((uint64_t)INT_MAX - 1) / per));
+  g = std::min<uint64_t>(g, std::max<uint64_t>(1, 0xffffffffull / rows));
+  DeviceCopy* dc;
+  int rc = ensure_device(s, device, &dc);
+  if (rc) return rc;
+  std::lock_guard<std::mutex> lk(dc->mu);
+  HIP_TRY(hipSetDevice(device));
+  std::vector<grt::DevCamera> cams(n_cameras);
+  for (uint32_t f = 0; f < n_cameras; ++f) fill_dev_camera(cameras[f], cams[f]);
+  DevBuf b_cams;
+  if ((rc = b_cams.alloc(n_cameras * sizeof(grt::DevCamera)))) return rc;
+  HIP_TRY(hipMemcpy(b_cams.p, cams.data(), n_cameras * sizeof(grt::DevCamera), hipMemcpyHostToDevice));
+  // the buffers die with `made` on any failure below
+  std::vector<std::unique_ptr<grt_gbuffer>> made;
+  made.reserve(n_cameras);
+  GbSeqTimes T;
+  uint32_t launches = 0;
+  for (uint32_t f0 = 0; f0 < n_cameras; f0 += (uint32_t)g, ++launches) {
+    const uint32_t kg = (uint32_t)std::min<uint64_t>(g, n_cameras - f0);
+    const grt::CamTable ct{(const grt::DevCamera*)b_cams.p + f0, rows, kg};
+    if ((rc = gbuffer_sequence_group(s, *dc, device, ct, cameras + f0, rows, cols, made, &T))) return rc;
+  }
+  if (stats) stats_from(T.acc, T.trace_ms, stats);  // as grt_gbuffer_trace: no overflows, no raymarch
+  if (report) {
+    std::memset(report, 0, sizeof(*report));
+    report->n_frames = n_cameras;
+    report->n_launches = launches;
+    report->frames_per_launch = (uint32_t)g;
+    report->n_traces = T.traces;
+    report->trace_ms = T.trace_ms;
+    report->fill_ms = T.fill_ms;
+    report->wall_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - wall0).count();
+  }
+  for (uint32_t f = 0; f < n_cameras; ++f) out[f] = made[f].release();
+  return 0;
+}
+
+int grt_gbuffer_shade_sequence(grt_scene* s, uint32_t n_buffers, grt_gbuffer* const* buffers, const grt_frame_out* out,
+                               float* kernel_ms) {
+  if (!s || !buffers || !out) return fail(-EINVAL, "null argument");
+  if (n_buffers == 0) return fail(-EINVAL, "a sequence needs at least one buffer");
+  if (!out->xyza && !out->xyza64) return fail(-EINVAL, "grt_frame_out needs xyza or xyza64");
+  for (uint32_t f = 0; f < n_buffers; ++f)
+    if (!buffers[f]) return fail(-EINVAL, "frame " + std::to_string(f) + ": null buffer");
+  const grt_gbuffer_info& i0 = buffers[0]->info;
+  const int device = i0.device;
+  for (uint32_t f = 0; f < n_buffers; ++f) {
+    const grt_gbuffer_info& i = buffers[f]->info;
+    if (i.device != device)
+      return fail(-EINVAL, "frame " + std::to_string(f) + ": the g-buffer is on device " + std::to_string(i.device) +
+                               ", frame 0's on device " + std::to_string(device));
+    if (i.rows != i0.rows || i.cols != i0.cols)
+      return fail(-EINVAL, "frame " + std::to_string(f) + ": the g-buffer has " + std::to_string(i.rows) + " x " +
+                               std::to_string(i.cols) + " pixels, frame 0's " + std::to_string(i0.rows) + " x " +
+                               std::to_string(i0.cols));
+    if (int rc = grt_gbuffer_shape_compatible(&i.shape, &s->desc))
+      return fail(rc, "frame " + std::to_string(f) + ": " + grt_last_error());
+  }
+  const uint64_t per = i0.n_pixels;
+  if (per == 0 || per > (uint64_t)INT_MAX) return fail(-EINVAL, "frames of 0 or more than INT_MAX pixels");
+  uint64_t g = std::max<uint64_t>(1, g_seq_group.load(std::memory_order_relaxed) / per);
+  g = std::min<uint64_t>(g, n_buffers);
+  DeviceCopy* dc;
+  int rc = ensure_device(s, device, &dc);
+  if (rc) return rc;
+  std::lock_guard<std::mutex> lk(dc->mu);
+  HIP_TRY(hipSetDevice(device));
+  const uint64_t ng = per * g;  // slots of a full group
+  DevBuf xyza, cls, status, x64, stop, steps, table;
+  if ((rc = xyza.alloc(16 * ng)) || (rc = cls.alloc(ng)) || (rc = status.alloc(ng))) return rc;
+  if (out->xyza64 && (rc = x64.alloc(32 * ng))) return rc;
+  if (out->stop && (rc = stop.alloc(ng))) return rc;
+  if (out->steps && (rc = steps.alloc(4 * ng))) return rc;
+  std::vector<grt::GBufferFrame> frames(n_buffers);
+  for (uint32_t f = 0; f < n_buffers; ++f) frames[f] = grt::GBufferFrame{buffers[f]->view(), (const uint32_t*)buffers[f]->steps.p};
+  if ((rc = table.alloc(n_buffers * sizeof(grt::GBufferFrame)))) return rc;
+  HIP_TRY(hipMemcpy(table.p, frames.data(), n_buffers * sizeof(grt::GBufferFrame), hipMemcpyHostToDevice));
+  const grt::Outputs o{(float*)xyza.p,     (uint8_t*)cls.p,  (uint8_t*)status.p, (double*)x64.p,
+                       (uint32_t*)steps.p, (uint8_t*)stop.p, nullptr};
+  hipStream_t st = nullptr;
+  float total_ms = 0;
+  for (uint32_t f0 = 0; f0 < n_buffers; f0 += (uint32_t)g) {
+    const uint32_t kg = (uint32_t)std::min<uint64_t>(g, n_buffers - f0);
+    const uint64_t n = per * kg, at = per * f0;
+    HIP_TRY(hipEventRecord(dc->ev0, st));
+    HIP_TRY(grt::launch_gbuffer_shade_stack(dc->d_scene, (const grt::GBufferFrame*)table.p + f0, kg, per, o, st));
+    HIP_TRY(hipEventRecord(dc->ev1, st));
+    HIP_TRY(hipEventSynchronize(dc->ev1));
+    float t = 0;
+    HIP_TRY(hipEventElapsedTime(&t, dc->ev0, dc->ev1));
+    total_ms += t;
+    if (out->xyza) HIP_TRY(hipMemcpy(out->xyza + 4 * at, xyza.p, 16 * n, hipMemcpyDeviceToHost));
+    if (out->xyza64) HIP_TRY(hipMemcpy(out->xyza64 + 4 * at, x64.p, 32 * n, hipMemcpyDeviceToHost));
+    if (out->ray_class) HIP_TRY(hipMemcpy(out->ray_class + at, cls.p, n, hipMemcpyDeviceToHost));
+    if (out->status) HIP_TRY(hipMemcpy(out->status + at, status.p, n, hipMemcpyDeviceToHost));
+    if (out->stop) HIP_TRY(hipMemcpy(out->stop + at, stop.p, n, hipMemcpyDeviceToHost));
+    if (out->steps) HIP_TRY(hipMemcpy(out->steps + at, steps.p, 4 * n, hipMemcpyDeviceToHost));
+  }
+  if (kernel_ms) *kernel_ms = total_ms;
+  return 0;
+}
+
+}  // extern "C"
+
+// ---- the sub-sample set and the adaptive re-shade (grt_api.h) ----
+static int check_spa(const grt_gbuffer* gb, uint32_t spa) {
+  if (spa == 0) return fail(-EINVAL, "adaptive_sampling.samples_per_axis must be greater than zero");
+  if (spa > 64) return fail(-EINVAL, "samples_per_axis is more than 64");
+  if (gb->sub.spa && gb->sub.spa != spa)
+    return fail(-EINVAL, "g-buffer: samples_per_axis " + std::to_string(spa) + " differs from the sub-sample set's " +
+                             std::to_string(gb->sub.spa));
+  return 0;
+}
+
+// Trace the sub-rays of `px` (ascending, unique, none held) and append them to the set:
+// enqueue_supersample's machinery -- jitter offsets, the offset-list trace, in chunks of
+// grt_set_sub_chunk -- with the exact kernels and the `hits` output, then per chunk the
+// layer scan (one host sync for the layer total), the growth of the arrays and the fill.
+// The fill is gbuffer_fill_kernel over the chunk's own work list, its arrays pointing at
+// the chunk's place in the set; a chunk launches exactly its rays, so no live count.
+// acc / ms[2]: counters and event times (trace; scan + fill), added to.
+static int sub_fill(grt_scene* tracer, grt_gbuffer* gb, uint32_t spa, const std::vector<uint32_t>& px,
+                    unsigned long long acc[8], double ms[2]) {
+  const uint64_t m = px.size();
+  if (m == 0) return 0;
+  const grt_gbuffer_info& info = gb->info;
+  GBufferSub& S = gb->sub;
+  DeviceCopy* dc;
+  int rc;
+  if ((rc = ensure_device(tracer, info.device, &dc))) return rc;
+  std::lock_guard<std::mutex> lk(dc->mu);
+  HIP_TRY(hipSetDevice(info.device));
+  if ((rc = S.ensure_map(info.n_pixels))) return rc;
+  S.spa = spa;
+  const uint64_t per = S.per();
+  if ((S.n_pix + m) * per + 1 > (uint64_t)INT_MAX) return fail(-EOVERFLOW, "more than INT_MAX - 1 sub-rays");
+  SuperBufs C;  // the chunking of enqueue_supersample; the buffers are this call's own
+  C.plan(m, spa);
+  const uint64_t chunk_pix = C.chunk_pix, cap = C.cap;
+  DevBuf d_px, pix, dx, dy, xyza, cls, hits, counts, local, temp;
+  if ((rc = d_px.alloc(4 * m)) || (rc = pix.alloc(4 * cap)) || (rc = dx.alloc(8 * cap)) || (rc = dy.alloc(8 * cap)) ||
+      (rc = xyza.alloc(16 * cap)) || (rc = cls.alloc(cap)) || (rc = hits.alloc(4 * cap)) ||
+      (rc = counts.alloc(8 * (cap + 1))) || (rc = local.alloc(8 * (cap + 1))))
+    return rc;
+  size_t temp_bytes = 0;
+  HIP_TRY(grt::gbuffer_layer_scan(nullptr, nullptr, cap, nullptr, nullptr, nullptr, &temp_bytes, nullptr));
+  if ((rc = temp.alloc(temp_bytes))) return rc;
+  HIP_TRY(hipMemcpy(d_px.p, px.data(), 4 * m, hipMemcpyHostToDevice));
+  hipStream_t st = nullptr;
+  const auto fill =
+      tracer->desc.geometry == GRT_GEOM_KERR_BL ? grt::kerr_bl::launch_gbuffer_fill : grt::launch_gbuffer_fill;
+  for (uint64_t base = 0; base < m; base += chunk_pix) {
+    const uint64_t mc = std::min(chunk_pix, m - base), nr = mc * per;
+    if ((rc = S.reserve_pixels(S.n_pix + mc))) return rc;
+    const uint64_t off = S.n_rays();
+    const uint32_t* d_chunk = (const uint32_t*)d_px.p + base;
+    HIP_TRY(grt::launch_make_offsets(d_chunk, mc, nullptr, 0, spa, info.row0, info.col0, info.cols, (uint32_t*)pix.p,
+                                     (double*)dx.p, (double*)dy.p, st));
+    grt::WorkList wo;
+    std::memset(&wo, 0, sizeof(wo));
+    wo.row0 = info.row0;
+    wo.col0 = info.col0;
+    wo.rows = info.rows;
+    wo.cols = info.cols;
+    wo.n_items = nr;
+    wo.pixel_index = (const uint32_t*)pix.p;
+    wo.dx = (const double*)dx.p;
+    wo.dy = (const double*)dy.p;
+    const grt::Outputs o{(float*)xyza.p,
+                         (uint8_t*)cls.p,
+                         (uint8_t*)S.status.p + off,
+                         nullptr,
+                         (uint32_t*)S.steps.p + off,
+                         (uint8_t*)S.stop.p + off,
+                         (uint32_t*)hits.p};
+    float t_ms = 0;
+    if ((rc = trace_exact(tracer, *dc, wo, o, acc, &t_ms))) return rc;
+    ms[0] += t_ms;
+    if ((rc = stream_order(*dc, st))) return rc;
+    HIP_TRY(hipEventRecord(dc->ev0, st));
+    HIP_TRY(grt::gbuffer_layer_scan((const uint8_t*)S.status.p + off, (const uint32_t*)hits.p, nr, (uint64_t*)counts.p,
+                                    (uint64_t*)local.p, temp.p, &temp_bytes, st));
+    uint64_t n_new = 0;
+    HIP_TRY(hipMemcpy(&n_new, (const uint64_t*)local.p + nr, 8, hipMemcpyDeviceToHost));
+    if ((rc = S.reserve_layers(S.n_layers + n_new))) return rc;
+    HIP_TRY(grt::gbuffer_sub_append((const uint64_t*)local.p, nr, S.n_layers, (uint64_t*)S.layer_start.p + off, d_chunk,
+                                    mc, (uint32_t)S.n_pix, (uint32_t*)S.sub_block.p, (uint32_t*)S.sub_pixel.p, st));
+    grt::Workspace ws;
+    if ((rc = ensure_workspace(*dc, nr, &ws))) return rc;  // the carving of the trace above
+    ws.pool = dc->d_pool;
+    HIP_TRY(fill(tracer->desc.geometry, dc->d_scene, wo, ws, S.view(off, nr), st));
+    HIP_TRY(hipEventRecord(dc->ev1, st));
+    HIP_TRY(hipEventSynchronize(dc->ev1));
+    float f_ms = 0;
+    HIP_TRY(hipEventElapsedTime(&f_ms, dc->ev0, dc->ev1));
+    ms[1] += f_ms;
+    if ((rc = stream_done(*dc, st))) return rc;
+    for (uint64_t j = 0; j < mc; ++j) S.h_block[px[base + j]] = (uint32_t)(S.n_pix + j);
+    S.n_pix += mc;
+    S.n_layers += n_new;
+  }
+  return 0;
+}
+
+extern "C" {
+
+int grt_gbuffer_supersample(grt_scene* tracer, grt_gbuffer* gb, uint32_t spa, uint64_t n, const uint32_t* pixels,
+                            grt_stats* stats) {
+  if (!tracer || !gb || (n && !pixels)) return fail(-EINVAL, "null argument");
+  int rc;
+  if ((rc = check_spa(gb, spa)) || (rc = check_tracer(gb, tracer))) return rc;
+  if (stats) std::memset(stats, 0, sizeof(*stats));
+  std::vector<uint32_t> px;
+  px.reserve(n);
+  for (uint64_t k = 0; k < n; ++k) {
+    if (pixels[k] >= gb->info.n_pixels)
+      return fail(-EINVAL, "g-buffer: pixel " + std::to_string(pixels[k]) + " is outside the " +
+                               std::to_string(gb->info.n_pixels) + " pixels of the buffer");
+    if (gb->sub.h_block.empty() || gb->sub.h_block[pixels[k]] == grt::GBUFFER_NIL) px.push_back(pixels[k]);
+  }
+  // ascending pixel index: two runs append the same bytes
+  std::sort(px.begin(), px.end());
+  px.erase(std::unique(px.begin(), px.end()), px.end());
+  unsigned long long acc[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+  double ms[2] = {0.0, 0.0};
+  if ((rc = sub_fill(tracer, gb, spa, px, acc, ms))) return rc;
+  if (stats) stats_from(acc, (float)ms[0], stats);
+  return 0;
+}
+
+int grt_gbuffer_shade_section(grt_scene* s, grt_gbuffer* gb, const grt_adaptive_config* cfg, const double* mask_xyza,
+                              grt_scene* tracer, double* xyza_out, uint8_t* class_out, uint8_t* status_out,
+                              uint64_t* n_supersampled, grt_subsample_failures* failures,
+                              grt_gbuffer_section_report* report) {
+  if (!s || !gb || !cfg || !xyza_out) return fail(-EINVAL, "null argument");
+  if (cfg->samples_per_axis == 0) return fail(-EINVAL, "adaptive_sampling.samples_per_axis must be greater than zero");
+  int rc = grt_gbuffer_shape_compatible(&gb->info.shape, &s->desc);
+  if (rc) return rc;
+  const bool supersampled = cfg->enabled || mask_xyza != nullptr;
+  const bool sub_pass = supersampled && !mask_xyza;
+  const uint32_t spa = cfg->samples_per_axis;
+  if (sub_pass && (rc = check_spa(gb, spa))) return rc;
+  if (sub_pass && tracer && (rc = check_tracer(gb, tracer))) return rc;
+  if (report) std::memset(report, 0, sizeof(*report));
+  if (n_supersampled) *n_supersampled = 0;
+  if (failures) failures->count = 0;
+  const int device = gb->info.device;
+  const uint32_t w = gb->info.cols, h = gb->info.rows;
+  const uint64_t n = gb->info.n_pixels;
+  if (n > (uint64_t)INT_MAX) return fail(-EOVERFLOW, "section larger than INT_MAX pixels");
+  DeviceCopy* dc;
+  if ((rc = ensure_device(s, device, &dc))) return rc;
+  std::unique_lock<std::mutex> lk(dc->mu);
+  HIP_TRY(hipSetDevice(device));
+  GBufferSub& S = gb->sub;
+  if (sub_pass && (rc = S.ensure_map(n))) return rc;
+  // the section's buffers, then the selection's, then one chunk of sub-ray outputs; the
+  // counts: [0] selected, [1] failed sub-samples, [2] held, [3] missing
+  AdaptivePlan P;
+  P.n = n;
+  P.w = w;
+  P.h = h;
+  P.spa = spa;
+  P.held = true;
+  P.supersampled = supersampled;
+  P.device_floor = supersampled && !cfg->has_minimum_luminance;
+  P.sub_rays = sub_pass;
+  if ((rc = P.plan(*dc, sub_pass ? failures : nullptr))) return rc;  // the mask records no failures
+  const SectionBufs& b = P.sec;
+  const SuperBufs& B = P.B;
+  unsigned long long* const d_cnt = P.d_cnt;
+  hipStream_t st = nullptr;
+  float shade_ms = 0;
+  unsigned long long cnt[4] = {0, 0, 0, 0};
+  // split the selection by what the set holds, shade the held sub-rays, average them
+  auto enqueue_sub_pass = [&]() -> int {
+    HIP_TRY(hipMemsetAsync(d_cnt + 1, 0, 24, st));
+    HIP_TRY(grt::gbuffer_split(P.sel, d_cnt, n, (const uint32_t*)S.sub_block.p, P.split, P.held_px, d_cnt + 2,
+                               P.missing_px, d_cnt + 3, P.split_tmp, &P.split_bytes, st));
+    if (S.n_pix == 0) return 0;  // nothing held: every selected pixel is missing
+    grt::SubsampleFailures fails = P.fails[0].f;
+    fails.count = d_cnt + 1;
+    fails.ray_stop = B.stop;
+    fails.ray_steps = B.steps;
+    const grt::Outputs so{B.xyza, B.cls, B.status, B.x64, B.steps, B.stop, nullptr};
+    const grt::GBufferArrays sv = S.view(0, S.n_rays());
+    for (uint32_t c = 0; c < B.n_chunks; ++c) {
+      const uint64_t base = (uint64_t)c * B.chunk_pix;
+      HIP_TRY(grt::launch_gbuffer_shade_sub(dc->d_scene, sv, (const uint32_t*)S.steps.p, (const uint32_t*)S.sub_block.p,
+                                            P.held_px + base, B.chunk_pix, d_cnt + 2, base, spa, so, st));
+      HIP_TRY(grt::launch_average(P.held_px + base, P.held_px + base, B.chunk_pix, d_cnt + 2, base, spa, B.x64, B.status,
+                                  b.x64, fails, st));
+    }
+    return 0;
+  };
+  auto finish_pass = [&]() -> int {
+    HIP_TRY(hipEventRecord(dc->ev1, st));
+    HIP_TRY(hipEventSynchronize(dc->ev1));
+    float t = 0;
+    HIP_TRY(hipEventElapsedTime(&t, dc->ev0, dc->ev1));
+    shade_ms += t;
+    if (supersampled) HIP_TRY(hipMemcpy(cnt, d_cnt, sizeof(cnt), hipMemcpyDeviceToHost));
+    return stream_done(*dc, st);
+  };
+  if ((rc = stream_order(*dc, st))) return rc;
+  if (supersampled) HIP_TRY(hipMemsetAsync(d_cnt, 0, 32, st));
+  HIP_TRY(hipEventRecord(dc->ev0, st));
+  HIP_TRY(grt::launch_gbuffer_shade(dc->d_scene, gb->view(), b.outputs(), st));
+  if (supersampled) {
+    if ((rc = P.enqueue_select(st, b.x64, b.cls, adaptive_params(cfg, w, h, cfg->minimum_luminance), d_cnt))) return rc;
+    if (mask_xyza) HIP_TRY(grt::launch_paint(P.sel, n, d_cnt, mask_xyza, b.x64, st));
+    else if ((rc = enqueue_sub_pass())) return rc;
+  }
+  if ((rc = finish_pass())) return rc;
+  unsigned long long acc[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+  double trace_ms[2] = {0.0, 0.0};
+  const uint64_t n_held = cnt[2], n_missing = sub_pass ? cnt[3] : 0;
+  if (report) {
+    report->n_selected = cnt[0];
+    report->n_held = n_held;
+    report->shade_ms = shade_ms;
+  }
+  if (n_missing) {
+    if (!tracer) {
+      if (report) report->n_missing = n_missing;
+      return fail(-ENODATA, "g-buffer: the sub-sample set misses " + std::to_string(n_missing) + " of the " +
+                                std::to_string(cnt[0]) + " selected pixels and the call has no tracer");
+    }
+    // top-up: trace the missing pixels once, append them, then the sub-ray pass again over
+    // the whole selection, which the set now holds
+    std::vector<uint32_t> px(n_missing);
+    HIP_TRY(hipMemcpy(px.data(), P.missing_px, 4 * n_missing, hipMemcpyDeviceToHost));
+    lk.unlock();  // the tracer may be this scene: sub_fill takes its device's lock
+    rc = sub_fill(tracer, gb, spa, px, acc, trace_ms);
+    lk.lock();
+    if (rc) return rc;
+    HIP_TRY(hipSetDevice(device));
+    if ((rc = stream_order(*dc, st))) return rc;
+    HIP_TRY(hipEventRecord(dc->ev0, st));
+    if ((rc = enqueue_sub_pass()) || (rc = finish_pass())) return rc;
+    if (cnt[3] != 0) return fail(-EIO, "g-buffer: the top-up left selected pixels without sub-rays");
+    if (report) {
+      report->n_traced = n_missing;
+      report->shade_ms = shade_ms;
+      report->trace_ms = trace_ms[0] + trace_ms[1];
+      stats_from(acc, (float)trace_ms[0], &report->top_up);
+    }
+  }
+  HIP_TRY(hipMemcpy(xyza_out, b.x64, n * 32, hipMemcpyDeviceToHost));
+  if (class_out) HIP_TRY(hipMemcpy(class_out, b.cls, n, hipMemcpyDeviceToHost));
+  if (status_out) HIP_TRY(hipMemcpy(status_out, b.status, n, hipMemcpyDeviceToHost));
+  if (supersampled) {
+    if (n_supersampled) *n_supersampled = cnt[0];
+    if ((rc = P.fails[0].read(cnt[1], spa, sub_pass ? failures : nullptr))) return rc;
+  }
+  return 0;
+}
+
+int grt_gbuffer_sub_info_get(const grt_gbuffer* gb, grt_gbuffer_sub_info* out) {
+  if (!gb || !out) return fail(-EINVAL, "null argument");
+  std::memset(out, 0, sizeof(*out));
+  out->samples_per_axis = gb->sub.spa;
+  out->n_sub_pixels = gb->sub.n_pix;
+  out->n_sub_rays = gb->sub.n_rays();
+  out->n_sub_layers = gb->sub.n_layers;
+  return 0;
+}
+
+int grt_gbuffer_sub_download(const grt_gbuffer* gb, uint32_t* sub_pixel, const grt_gbuffer_arrays* h) {
+  if (!gb) return fail(-EINVAL, "null argument");
+  const GBufferSub& S = gb->sub;
+  const uint64_t m = S.n_pix, n = S.n_rays(), l = S.n_layers;
+  if (S.spa == 0 || m == 0) return 0;  // nothing to copy
+  if (!sub_pixel || !h || !h->status || !h->stop || !h->steps || !h->sky_u || !h->sky_v || !h->sky_redshift ||
+      !h->layer_start)
+    return fail(-EINVAL, "null argument");
+  if (l && (!h->object || !h->u || !h->v || !h->redshift || !h->radius)) return fail(-EINVAL, "null layer array");
+  HIP_TRY(hipSetDevice(gb->info.device));
+  HIP_TRY(hipMemcpy(sub_pixel, S.sub_pixel.p, 4 * m, hipMemcpyDeviceToHost));
+  HIP_TRY(hipMemcpy(h->status, S.status.p, n, hipMemcpyDeviceToHost));
+  HIP_TRY(hipMemcpy(h->stop, S.stop.p, n, hipMemcpyDeviceToHost));
+  HIP_TRY(hipMemcpy(h->steps, S.steps.p, 4 * n, hipMemcpyDeviceToHost));
+  HIP_TRY(hipMemcpy(h->sky_u, S.sky_u.p, 8 * n, hipMemcpyDeviceToHost));
+  HIP_TRY(hipMemcpy(h->sky_v, S.sky_v.p, 8 * n, hipMemcpyDeviceToHost));
+  HIP_TRY(hipMemcpy(h->sky_redshift, S.sky_z.p, 8 * n, hipMemcpyDeviceToHost));
+  HIP_TRY(hipMemcpy(h->layer_start, S.layer_start.p, 8 * (n + 1), hipMemcpyDeviceToHost));
+  if (l) {
+    HIP_TRY(hipMemcpy(h->object, S.object.p, l, hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(h->u, S.u.p, 8 * l, hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(h->v, S.v.p, 8 * l, hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(h->redshift, S.z.p, 8 * l, hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(h->radius, S.radius.p, 8 * l, hipMemcpyDeviceToHost));
+  }
+  return 0;
+}
+
+int grt_gbuffer_sub_upload(grt_gbuffer* gb, const grt_gbuffer_sub_info* sub, const uint32_t* sub_pixel,
+                           const grt_gbuffer_arrays* h) {
+  if (!gb || !sub) return fail(-EINVAL, "null argument");
+  static const grt_gbuffer_arrays none{};
+  // the shade kernel indexes by sub_pixel, layer_start and object: hold them to their ranges
+  int rc = grt_host::gbuffer_sub_check(&gb->info, sub, sub_pixel, sub->samples_per_axis ? h : &none);
+  if (rc) return rc;
+  if (sub->samples_per_axis && !h) return fail(-EINVAL, "g-buffer: null sub-ray array");
+  HIP_TRY(hipSetDevice(gb->info.device));
+  std::unique_ptr<GBufferSub> N(new GBufferSub());
+  if ((rc = N->ensure_map(gb->info.n_pixels))) return rc;
+  N->spa = sub->samples_per_axis;
+  const uint64_t m = sub->n_sub_pixels, n = sub->n_sub_rays, l = sub->n_sub_layers;
+  if (N->spa && m) {
+    if ((rc = N->reserve_pixels(m)) || (rc = N->reserve_layers(l))) return rc;
+    HIP_TRY(hipMemcpy(N->sub_pixel.p, sub_pixel, 4 * m, hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(N->status.p, h->status, n, hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(N->stop.p, h->stop, n, hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(N->steps.p, h->steps, 4 * n, hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(N->sky_u.p, h->sky_u, 8 * n, hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(N->sky_v.p, h->sky_v, 8 * n, hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(N->sky_z.p, h->sky_redshift, 8 * n, hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(N->layer_start.p, h->layer_start, 8 * (n + 1), hipMemcpyHostToDevice));
+    if (l) {
+      HIP_TRY(hipMemcpy(N->object.p, h->object, l, hipMemcpyHostToDevice));
+      HIP_TRY(hipMemcpy(N->u.p, h->u, 8 * l, hipMemcpyHostToDevice));
+      HIP_TRY(hipMemcpy(N->v.p, h->v, 8 * l, hipMemcpyHostToDevice));
+      HIP_TRY(hipMemcpy(N->z.p, h->redshift, 8 * l, hipMemcpyHostToDevice));
+      HIP_TRY(hipMemcpy(N->radius.p, h->radius, 8 * l, hipMemcpyHostToDevice));
+    }
+    N->n_pix = m;
+    N->n_layers = l;
+    HIP_TRY(grt::gbuffer_sub_index((const uint32_t*)N->sub_pixel.p, m, gb->info.n_pixels, (uint32_t*)N->sub_block.p,
+                                   nullptr));
+    HIP_TRY(hipDeviceSynchronize());
+    for (uint64_t j = 0; j < m; ++j) N->h_block[sub_pixel[j]] = (uint32_t)j;
+  }
+  // the old set's arrays are freed with N
+  std::swap(gb->sub.spa, N->spa);
+  std::swap(gb->sub.n_pix, N->n_pix);
+  std::swap(gb->sub.cap_pix, N->cap_pix);
+  std::swap(gb->sub.n_layers, N->n_layers);
+  std::swap(gb->sub.cap_layers, N->cap_layers);
+  std::swap(gb->sub.h_block, N->h_block);
+  for (DevBuf GBufferSub::*f : {&GBufferSub::sub_pixel, &GBufferSub::sub_block, &GBufferSub::status, &GBufferSub::stop,
+                                &GBufferSub::steps, &GBufferSub::sky_u, &GBufferSub::sky_v, &GBufferSub::sky_z,
+                                &GBufferSub::layer_start, &GBufferSub::object, &GBufferSub::u, &GBufferSub::v,
+                                &GBufferSub::z, &GBufferSub::radius})
+    std::swap((gb->sub.*f).p, ((*N).*f).p);
+  return 0;
+}
+
+int grt_gbuffer_destroy(grt_gbuffer* gb) {
+  if (!gb) return 0;
+  (void)hipSetDevice(gb->info.device);
+  delete gb;
+  return 0;
+}
+
+}  // extern "C"

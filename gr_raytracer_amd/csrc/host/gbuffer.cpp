@@ -1,6 +1,6 @@
 // gbuffer.cpp — host side of the geometry buffer (grt_api.h, grt_gbuffer_*): the shape key
 // of a scene, its comparison, the consistency checks of a buffer's arrays, and the file.
-// No device code: api.hip owns the device-resident buffer.
+// No device code: api_gbuffer.hip owns the device-resident buffer.
 #include <cerrno>
 #include <cstdio>
 #include <cstring>

@@ -146,9 +146,10 @@ def _frame_adaptive(grt, width=72, height=64, spa=4):
     return hs, ad
 
 
-def _supersample_in_process(grt, sc, ad, n_shards, band_rows, mask=None):
+def _supersample_in_process(grt, sc, ad, n_shards, band_rows, mask=None, device_entry=False):
     """Every rank's steps of render_frame_adaptive, one after another in this process,
-    with the allgather done by array assembly."""
+    with the allgather done by array assembly.  device_entry: through
+    grt_supersample_shard_device (the count stays on the device) instead of its host wrapper."""
     import torch
 
     from gr_raytracer_amd import _lib as L
@@ -175,9 +176,17 @@ def _supersample_in_process(grt, sc, ad, n_shards, band_rows, mask=None):
         cnt = C.c_uint64(0)
         sh = L.RowShard(band_rows, s, n_shards)
         m = None if mask is None else (C.c_double * 4)(*mask)
-        L.check(L.lib().grt_supersample_shard(sc._s, 0, None, C.byref(sh), C.byref(ad), min_lum, d_ya.data_ptr(),
-                                              d_cls.data_ptr(), m, d_x.data_ptr(), C.byref(cnt), stats.data_ptr()),
-                "grt_supersample_shard")
+        if device_entry:
+            d_cnt = torch.zeros(1, dtype=torch.int64, device=dev)
+            L.check(L.lib().grt_supersample_shard_device(sc._s, 0, None, C.byref(sh), C.byref(ad), min_lum, None,
+                                                         d_ya.data_ptr(), d_cls.data_ptr(), m, d_x.data_ptr(),
+                                                         d_cnt.data_ptr(), stats.data_ptr(), None),
+                    "grt_supersample_shard_device")
+            cnt.value = int(d_cnt.cpu()[0])
+        else:
+            L.check(L.lib().grt_supersample_shard(sc._s, 0, None, C.byref(sh), C.byref(ad), min_lum, d_ya.data_ptr(),
+                                                  d_cls.data_ptr(), m, d_x.data_ptr(), C.byref(cnt), stats.data_ptr()),
+                    "grt_supersample_shard")
         n_sel += cnt.value
         r = shard_frame_rows(rows, band_rows, s, n_shards)
         out[r] = d_x.cpu().numpy().reshape(len(r), cols, 4)
@@ -194,6 +203,27 @@ def test_shard_supersampling_equals_render_section(grt, gpu, n_shards, band_rows
     assert want_sel > 0 and got_sel == want_sel
     assert np.array_equal(got_cls, want_cls)
     assert np.array_equal(got, want)  # bit for bit
+
+
+@pytest.mark.gpu
+def test_shard_supersampling_in_chunks_equals_unchunked(grt, gpu):
+    """grt_supersample_shard_device with the sub-rays forced into chunks of 7 pixels
+    (grt_set_sub_chunk, 4 x 4 samples each) gives the bits of the pass in one chunk: the
+    two-shard case of test_shard_supersampling_equals_render_section."""
+    from gr_raytracer_amd import _lib as L
+
+    hs, ad = _frame_adaptive(grt)
+    sc = grt.Scene(hs.desc_ptr(), keepalive=hs, adaptive=ad)
+    want, want_cls, want_sel = _supersample_in_process(grt, sc, ad, 2, 8, device_entry=True)
+    assert want_sel > 2 * 7  # either shard or both: more than one chunk
+    try:
+        L.check(L.lib().grt_set_sub_chunk(7 * 16), "grt_set_sub_chunk")
+        got, got_cls, got_sel = _supersample_in_process(grt, sc, ad, 2, 8, device_entry=True)
+    finally:
+        L.check(L.lib().grt_set_sub_chunk(0), "grt_set_sub_chunk")
+    assert got_sel == want_sel
+    assert np.array_equal(got_cls, want_cls)
+    assert np.array_equal(got.view(np.uint64), want.view(np.uint64))  # bit for bit
 
 
 @pytest.mark.gpu

@@ -287,11 +287,22 @@ def test_tail_hand_off_changes_nothing(grt, gpu):
 MASK = (0.25, 0.5, 0.125, 1.0)
 
 
+_ADAPTIVE_REFS = []
+
+
+def adaptive_reference(grt):
+    """(case, stock adaptive configuration, each camera's render_section_ex alone at the
+    default sub-ray chunk), computed once and shared (never modified)."""
+    if not _ADAPTIVE_REFS:
+        case, _ = reference(grt, "schwarzschild")
+        ad = grt.default_adaptive()  # the stock configuration: enabled, 4 x 4 samples
+        assert ad.enabled == 1 and ad.samples_per_axis == 4
+        _ADAPTIVE_REFS.append((case, ad, [case.scene(k).render_section_ex(adaptive=ad) for k in range(K)]))
+    return _ADAPTIVE_REFS[0]
+
+
 def test_adaptive_frames_equal_render_section_ex(grt, gpu):
-    case, _ = reference(grt, "schwarzschild")
-    ad = grt.default_adaptive()  # the stock configuration: enabled, 4 x 4 samples
-    assert ad.enabled == 1 and ad.samples_per_axis == 4
-    refs = [case.scene(k).render_section_ex(adaptive=ad) for k in range(K)]
+    case, ad, refs = adaptive_reference(grt)
     masks = [case.scene(k).render_section_ex(adaptive=ad, sampling_mask_xyza=MASK) for k in range(K)]
     # every frame selects pixels, and not the same ones
     selected = [np.all(m.xyza64 == np.array(MASK), axis=1) for m in masks]
@@ -318,6 +329,32 @@ def test_adaptive_frames_equal_render_section_ex(grt, gpu):
         for key in ("accepted_steps", "attempts", "rays"):
             assert seq["stats"][key] == sum(r.stats[key] for r in refs), key
         assert seq["report"].supersample_ms > 0 and seq["report"].n_launches == (1 if group == 0 else K)
+
+
+def test_adaptive_frames_in_chunks_equal_render_section_ex(grt, gpu):
+    """The stacked supersample pass with its sub-rays forced into chunks of 7 pixels
+    (grt_set_sub_chunk, 4 x 4 samples each), as one stacked launch and as one frame per
+    launch: the bits of render_section_ex per frame at the default chunk."""
+    L = grt._lib
+    case, ad, refs = adaptive_reference(grt)
+    assert max(r.n_supersampled for r in refs) > 7, [r.n_supersampled for r in refs]  # a second chunk runs
+    sc, cams = sequence_scene(case)
+    try:
+        L.check(L.lib().grt_set_sub_chunk(7 * 16), "grt_set_sub_chunk")
+        for group in (0, N):
+            grt.set_sequence_group(group)
+            seq = sc.render_sequence(cams, adaptive=ad, supersample=True)
+            assert seq["report"].n_launches == (1 if group == 0 else K)
+            for k in range(K):
+                assert np.array_equal(seq["xyza64"][k].view(np.uint64), refs[k].xyza64.view(np.uint64)), (group, k)
+                assert np.array_equal(seq["class"][k], refs[k].ray_class), (group, k)
+                assert np.array_equal(seq["status"][k], refs[k].status), (group, k)
+                assert int(seq["n_supersampled"][k]) == refs[k].n_supersampled, (group, k)
+                assert seq["n_failed"][k] == refs[k].n_failed_subsamples, (group, k)
+                assert np.array_equal(seq["failures"][k], refs[k].failed_subsamples), (group, k)
+    finally:
+        grt.set_sequence_group(0)
+        L.check(L.lib().grt_set_sub_chunk(0), "grt_set_sub_chunk")
 
 
 # ------------------------------------------------------------ 5. hit-pool overflow --

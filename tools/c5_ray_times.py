@@ -27,7 +27,7 @@ L.check(only(2), "grt_debug_ray_times_only")  # trace 1: the 1-spp frame, trace 
 _, _, n_sel, st = sc.render_section()
 f = L.lib().grt_debug_ray_times
 f.argtypes = [C.c_void_p, C.c_int, C.POINTER(C.c_uint64), C.c_uint64, C.POINTER(C.c_uint64)]
-n = 1 << 21  # the supersample chunk (api.hip SUB_CHUNK): the last trace's slots
+n = 1 << 21  # the supersample chunk (api_internal.h SUB_CHUNK): the last trace's slots
 buf = np.zeros(6 * n, np.uint64)
 t0 = C.c_uint64()
 L.check(f(sc._s, 0, buf.ctypes.data_as(C.POINTER(C.c_uint64)), n, C.byref(t0)), "grt_debug_ray_times")

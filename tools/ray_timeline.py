@@ -35,7 +35,7 @@ if mode == "c5":
     sc = g.Scene(hs.desc_ptr(), keepalive=hs, adaptive=ad)
     L.check(only(2), "grt_debug_ray_times_only")  # trace 1: the 1-spp frame, trace 2: the sub-ray chunk
     sc.render_section()
-    n = 1 << 21  # the supersample chunk's slots (api.hip SUB_CHUNK)
+    n = 1 << 21  # the supersample chunk's slots (api_internal.h SUB_CHUNK)
 else:
     sc = g.Scene(hs.desc_ptr(), keepalive=hs)
     L.check(only(0), "grt_debug_ray_times_only")
