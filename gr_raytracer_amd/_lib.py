@@ -190,6 +190,13 @@ class GBufferSequenceReport(C.Structure):
                 ("n_traces", C.c_uint32), ("wall_ms", _d), ("trace_ms", _d), ("fill_ms", _d)]
 
 
+class GBufferSectionSequenceReport(C.Structure):
+    """grt_gbuffer_section_sequence_report: launch groups, totals and times of the stacked adaptive re-shade."""
+    _fields_ = [("n_frames", C.c_uint32), ("n_launches", C.c_uint32), ("n_selected", C.c_uint64),
+                ("n_held", C.c_uint64), ("n_traced", C.c_uint64), ("n_missing", C.c_uint64), ("wall_ms", _d),
+                ("shade_ms", _d), ("trace_ms", _d), ("top_up", Stats)]
+
+
 class Health(C.Structure):
     _fields_ = [
         ("rays", C.c_uint64), ("failed", C.c_uint64), ("null_violations", C.c_uint64), ("max_null", _d),
@@ -330,6 +337,13 @@ def lib() -> C.CDLL:
         "grt_gbuffer_trace_sequence": (C.c_int, [vp, C.c_int, u32, C.POINTER(CameraDesc), C.POINTER(vp),
                                                  C.POINTER(Stats), C.POINTER(GBufferSequenceReport)]),
         "grt_gbuffer_shade_sequence": (C.c_int, [vp, u32, C.POINTER(vp), C.POINTER(FrameOut), C.POINTER(C.c_float)]),
+        "grt_gbuffer_supersample_sequence": (C.c_int, [vp, u32, C.POINTER(vp), u32, C.POINTER(u64),
+                                                       C.POINTER(C.POINTER(C.c_uint32)), C.POINTER(Stats),
+                                                       C.POINTER(GBufferSequenceReport)]),
+        "grt_gbuffer_shade_section_sequence": (C.c_int, [vp, u32, C.POINTER(vp), C.POINTER(AdaptiveConfig), _pd, vp,
+                                                         C.POINTER(FrameOut), C.POINTER(u64),
+                                                         C.POINTER(SubsampleFailures), C.POINTER(u64),
+                                                         C.POINTER(GBufferSectionSequenceReport)]),
         "grt_gbuffer_shape_of": (None, [C.POINTER(SceneDesc), C.POINTER(GBufferShape)]),
         "grt_gbuffer_compatible": (C.c_int, [C.POINTER(SceneDesc), C.POINTER(SceneDesc)]),
         "grt_gbuffer_shape_compatible": (C.c_int, [C.POINTER(GBufferShape), C.POINTER(SceneDesc)]),
@@ -401,7 +415,8 @@ EXPORTED_SYMBOLS = [
     "grt_gbuffer_shape_compatible", "grt_gbuffer_write_file", "grt_gbuffer_read_file",
     "grt_gbuffer_supersample", "grt_gbuffer_shade_section", "grt_gbuffer_sub_info_get", "grt_gbuffer_sub_download",
     "grt_gbuffer_sub_upload", "grt_gbuffer_sub_write_file", "grt_gbuffer_sub_read_file",
-    "grt_gbuffer_trace_sequence", "grt_gbuffer_shade_sequence",
+    "grt_gbuffer_trace_sequence", "grt_gbuffer_shade_sequence", "grt_gbuffer_supersample_sequence",
+    "grt_gbuffer_shade_section_sequence",
 ]
 
 

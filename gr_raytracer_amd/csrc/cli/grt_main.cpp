@@ -13,8 +13,9 @@
 //     | gbuffer --filename a.grtg [--adaptive]
 //     | reshade --gbuffer a.grtg [--filename out.png|out.hdr] [--adaptive]
 //     | gbuffer-sequence --camera-path P --filename-pattern a-%04d.grtg [--first-index 0]
+//                        [--adaptive-stacked]
 //     | reshade-sequence --gbuffer-pattern a-%04d.grtg --frames K [--first-index 0]
-//                        [--filename-pattern frame-%04d.png]
+//                        [--filename-pattern frame-%04d.png] [--adaptive-stacked]
 //     | blackbody -t T [-r Z]
 //     | blackbody-spectrum [--min-temperature T] [--max-temperature T] [--min-redshift Z]
 //                          [--max-redshift Z] [--width N] [--height N] [-f FILE]
@@ -55,7 +56,15 @@
 // shades them in stacked launches under its config's appearance (grt_gbuffer_shade_sequence)
 // and writes each frame, tone-mapped on its own, as `reshade` writes it.  Neither takes
 // --adaptive: a sequence's files are ordinary g-buffers, and the adaptive frame of one is
-// `reshade --adaptive` of that file.
+// `reshade --adaptive` of that file.  The adaptive frames of the whole path are
+// --adaptive-stacked on both (grt_gbuffer_shade_section_sequence): `gbuffer-sequence` then
+// also traces, in one stacked top-up, the sub-rays each frame's own adaptive frame selects
+// and writes every `<file>.sub`, the bytes `gbuffer --adaptive` writes for that line's
+// camera; `reshade-sequence` builds one scene from its config with the files' recorded
+// integration parameters (they must agree, as must the frame sizes: usage errors) as
+// appearance and tracer, loads the sidecars that exist, tops the sets up in one stacked call,
+// writes each frame as `render` of its config writes it (--show-sampling-mask included) and
+// rewrites the sidecars that grew.
 #include <algorithm>
 #include <charconv>
 #include <chrono>
@@ -91,9 +100,10 @@ static int usage(const char* msg) {
                "           (--adaptive: the config's [adaptive_sampling]; the sub-rays live in F.grtg.sub)\n"
                "           (reshade: --width/--height must be the buffer's frame; camera flags are ignored)\n"
                "       grt [global options] --config-file FILE gbuffer-sequence --camera-path P\n"
-               "           --filename-pattern F-%%04d.grtg [--first-index N]\n"
+               "           --filename-pattern F-%%04d.grtg [--first-index N] [--adaptive-stacked]\n"
                "       grt [global options] --config-file FILE reshade-sequence --gbuffer-pattern F-%%04d.grtg\n"
-               "           --frames K [--first-index N] [--filename-pattern frame-%%04d.png]\n"
+               "           --frames K [--first-index N] [--filename-pattern frame-%%04d.png] [--adaptive-stacked]\n"
+               "           (--adaptive-stacked: the adaptive frames of the sequence, the sub-rays in F-%%04d.grtg.sub)\n"
                "       grt [global options] blackbody -t T [-r Z]\n"
                "       grt [global options] blackbody-spectrum [--min-temperature T] [--max-temperature T]\n"
                "           [--min-redshift Z] [--max-redshift Z] [--width N] [--height N] [-f FILE]\n",
@@ -463,6 +473,7 @@ int main(int argc, char** argv) {
   long long n_frames = -1;      // reshade-sequence --frames
   bool have_pattern = false;    // --filename-pattern given (gbuffer-sequence has no default)
   bool gbuffer_adaptive = false;  // gbuffer / reshade --adaptive: the config's [adaptive_sampling]
+  bool seq_adaptive = false;      // gbuffer-sequence / reshade-sequence --adaptive-stacked: the same, stacked
   long long first_index = 0;
   std::vector<std::string> args(argv + 1, argv + argc);
   for (size_t i = 0; i < args.size(); ++i) {
@@ -492,9 +503,14 @@ int main(int argc, char** argv) {
     }
     if (action.empty() && a == "--show-sampling-mask") { opts.show_sampling_mask = 1; continue; }
     if ((action == "gbuffer" || action == "reshade") && a == "--adaptive") { gbuffer_adaptive = true; continue; }
+    if ((action == "gbuffer-sequence" || action == "reshade-sequence") && a == "--adaptive-stacked") {
+      seq_adaptive = true;
+      continue;
+    }
     if ((action == "gbuffer-sequence" || action == "reshade-sequence") && a == "--adaptive")
-      return usage((action + " has no --adaptive: the stacked re-shade is 1 spp; for an adaptive frame run `gbuffer "
-                    "--adaptive` / `reshade --adaptive` per frame (a sequence's .grtg files are ordinary g-buffers)").c_str());
+      return usage((action + " has no --adaptive: the stacked adaptive frames are --adaptive-stacked; for one frame "
+                    "run `gbuffer --adaptive` / `reshade --adaptive` (a sequence's .grtg files are ordinary "
+                    "g-buffers)").c_str());
     if (!next(v)) return usage(("missing value for " + a).c_str());
     std::vector<double> nums;
     auto bad = [&]() { return usage(("invalid value '" + v + "' for '" + a + "'").c_str()); };
@@ -700,7 +716,8 @@ int main(int argc, char** argv) {
     if (!load_camera_path(camera_path, path_cams, &perr)) return usage(perr.c_str());
   }
 
-  grt_gbuffer_info gb_info;
+  grt_gbuffer_info gb_info, gb_first;
+  std::memset(&gb_first, 0, sizeof(gb_first));
   if (action == "reshade-sequence") {  // every file's header and length, before the GPU is touched
     for (long long k = 0; k < n_frames; ++k) {
       std::string name;
@@ -717,6 +734,13 @@ int main(int argc, char** argv) {
       if ((int64_t)gb_info.cols != opts.width || (int64_t)gb_info.rows != opts.height)
         return usage(("--width / --height must be the frame of " + name + ", " + std::to_string(gb_info.cols) + " x " +
                       std::to_string(gb_info.rows)).c_str());
+      if (k == 0) gb_first = gb_info;
+      // --adaptive-stacked: one tracer serves every frame, so the files' recorded integration parameters agree
+#define GRT_SAME(field)                                                                                         \
+  if (seq_adaptive && std::memcmp(&gb_info.field, &gb_first.field, sizeof(gb_info.field)) != 0)                 \
+    return usage(("--adaptive-stacked: " + name + " differs from the first file in " #field).c_str());
+      GRT_SAME(max_steps) GRT_SAME(max_radius) GRT_SAME(step_size) GRT_SAME(epsilon) GRT_SAME(horizon_epsilon)
+#undef GRT_SAME
     }
   }
   if (action == "reshade") {  // the file's header and length, before the GPU is touched
@@ -969,6 +993,17 @@ int main(int argc, char** argv) {
       std::fprintf(stderr, "Error: %s\n", grt_last_error());
       return 1;
     }
+    grt_gbuffer_section_sequence_report srep;
+    std::vector<uint64_t> per_frame(4 * (size_t)K, 0);
+    if (seq_adaptive) {  // this scene's own adaptive frames: each buffer then holds its selection's sub-rays
+      std::vector<double> frames(4 * (size_t)opts.width * opts.height * K);
+      grt_frame_out fo{nullptr, frames.data(), nullptr, nullptr, nullptr, nullptr};
+      if (grt_gbuffer_shade_section_sequence(scene, K, gbs.data(), &ac, nullptr, scene, &fo, nullptr, nullptr,
+                                             per_frame.data(), &srep)) {
+        std::fprintf(stderr, "Error: %s\n", grt_last_error());
+        return 1;
+      }
+    }
     ph_render = ms_since(t_phase);
     t_phase = clk::now();
     unsigned long long layers = 0;
@@ -978,13 +1013,21 @@ int main(int argc, char** argv) {
       if (grt_gbuffer_info_get(gbs[k], &gb_info)) return 1;
       GBufferHost host(gb_info.n_pixels, gb_info.n_layers);
       const grt_gbuffer_arrays arr = host.arrays();
-      if (grt_gbuffer_download(gbs[k], &arr) || grt_gbuffer_write_file(name.c_str(), &gb_info, &arr)) {
+      if (grt_gbuffer_download(gbs[k], &arr) || grt_gbuffer_write_file(name.c_str(), &gb_info, &arr) ||
+          (seq_adaptive && save_sub_sidecar(gbs[k], gb_info, name + ".sub"))) {
         std::fprintf(stderr, "Error: %s\n", grt_last_error());
         return 1;
       }
       layers += gb_info.n_layers;
+      if (seq_adaptive)
+        std::fprintf(stderr, "[grt] sub-sample set: %llu selected pixels traced, saved to %s.sub\n",
+                     (unsigned long long)per_frame[4 * k + 2], name.c_str());
       std::fprintf(stderr, "[grt] INFO saved g-buffer to %s\n", name.c_str());
     }
+    if (seq_adaptive)
+      std::fprintf(stderr, "[grt] sub-sample sets: %llu selected pixels of %u frames traced in one stacked top-up "
+                   "(%llu sub-rays, %.1f ms)\n", (unsigned long long)srep.n_traced, K,
+                   (unsigned long long)srep.top_up.rays, srep.trace_ms);
     ph_write = ms_since(t_phase);
     std::fprintf(stderr, "[grt] %llu rays, %llu accepted steps, %llu attempts, kernel %.1f ms; g-buffers: %llu layers, "
                  "scan + fill + split %.2f ms\n", (unsigned long long)st.rays, (unsigned long long)st.accepted_steps,
@@ -1024,7 +1067,96 @@ int main(int argc, char** argv) {
     std::vector<double> xyza(n * 4 * K);
     grt_frame_out fo{nullptr, xyza.data(), nullptr, nullptr, nullptr, nullptr};
     float shade_ms = 0;
-    if (grt_gbuffer_shade_sequence(scene, K, gbs.data(), &fo, &shade_ms)) {
+    // --adaptive-stacked: the adaptive frames, as `render` writes them
+    grt_scene* tracer = nullptr;
+    std::vector<uint8_t> status, stop;
+    std::vector<uint32_t> steps;
+    std::vector<uint64_t> nsel(K, 0), per_frame(4 * (size_t)K, 0);
+    const uint64_t fail_cap = seq_adaptive ? 1u << 16 : 0;  // failed sub-rays logged per frame, as render-sequence
+    std::vector<uint32_t> fail_pix(fail_cap * K), fail_sample(fail_cap * K), fail_steps(fail_cap * K);
+    std::vector<uint8_t> fail_status(fail_cap * K), fail_stop(fail_cap * K);
+    std::vector<grt_subsample_failures> fails(K);
+    double mask[4];
+    const double* maskp = nullptr;
+    if (seq_adaptive) {
+      // this config's scene with the files' recorded integration parameters (equal in every
+      // file, checked above): it traces the sub-rays the sets do not hold yet, each with its
+      // file's camera, and its appearance is the one applied
+      grt_scene_desc td = *d;
+      td.camera = gb_first.camera;
+      td.max_steps = gb_first.max_steps;
+      td.max_radius = gb_first.max_radius;
+      td.step_size = gb_first.step_size;
+      td.epsilon = gb_first.epsilon;
+      td.horizon_epsilon = gb_first.horizon_epsilon;
+      if (grt_scene_create(&td, &tracer)) {
+        std::fprintf(stderr, "Error: %s\n", grt_last_error());
+        return 1;
+      }
+      std::vector<uint64_t> before(K, 0);
+      for (uint32_t k = 0; k < K; ++k) {  // the sidecars that exist
+        std::string name;
+        (void)expand_pattern(gbuffer_pattern, first_index + k, &name);
+        const std::string sidecar = name + ".sub";
+        FILE* f = std::fopen(sidecar.c_str(), "rb");
+        if (!f) continue;
+        std::fclose(f);
+        grt_gbuffer_sub_info sub;
+        if (grt_gbuffer_info_get(gbs[k], &gb_info) ||
+            grt_gbuffer_sub_read_file(sidecar.c_str(), &gb_info, &sub, nullptr, nullptr)) {
+          std::fprintf(stderr, "Error: %s\n", grt_last_error());
+          return 1;
+        }
+        GBufferSubHost sh(sub);
+        const grt_gbuffer_arrays sarr = sh.rays.arrays();
+        if (grt_gbuffer_sub_read_file(sidecar.c_str(), &gb_info, &sub, sh.sub_pixel.data(), &sarr) ||
+            grt_gbuffer_sub_upload(gbs[k], &sub, sh.sub_pixel.data(), &sarr)) {
+          std::fprintf(stderr, "Error: %s\n", grt_last_error());
+          return 1;
+        }
+        before[k] = sub.n_sub_pixels;
+      }
+      if (opts.show_sampling_mask) {
+        grt_srgb_to_xyza(opts.sampling_mask_color[0], opts.sampling_mask_color[1], opts.sampling_mask_color[2], 255, mask);
+        maskp = mask;
+      }
+      status.resize(n * K);
+      stop.resize(n * K);
+      steps.resize(n * K);
+      for (uint32_t k = 0; k < K; ++k)
+        fails[k] = grt_subsample_failures{fail_cap, fail_pix.data() + fail_cap * k, fail_sample.data() + fail_cap * k,
+                                          fail_status.data() + fail_cap * k, 0, fail_stop.data() + fail_cap * k,
+                                          fail_steps.data() + fail_cap * k};
+      fo.status = status.data();
+      fo.stop = stop.data();
+      fo.steps = steps.data();
+      grt_gbuffer_section_sequence_report srep;
+      if (grt_gbuffer_shade_section_sequence(tracer, K, gbs.data(), &ac, maskp, tracer, &fo, nsel.data(), fails.data(),
+                                             per_frame.data(), &srep)) {
+        std::fprintf(stderr, "Error: %s\n", grt_last_error());
+        return 1;
+      }
+      shade_ms = (float)srep.shade_ms;
+      for (uint32_t k = 0; k < K; ++k)
+        std::fprintf(stderr, "[grt] adaptive re-shade, frame %u: %llu selected pixels, %llu held, %llu traced\n", k,
+                     (unsigned long long)per_frame[4 * k], (unsigned long long)per_frame[4 * k + 1],
+                     (unsigned long long)per_frame[4 * k + 2]);
+      std::fprintf(stderr, "[grt] adaptive re-shade: %llu selected pixels, %llu held, %llu traced in one stacked top-up "
+                   "(%llu sub-rays, %.1f ms)\n", (unsigned long long)srep.n_selected, (unsigned long long)srep.n_held,
+                   (unsigned long long)srep.n_traced, (unsigned long long)srep.top_up.rays, srep.trace_ms);
+      for (uint32_t k = 0; k < K; ++k) {  // the sets that grew: the next re-shade finds them
+        grt_gbuffer_sub_info after;
+        if (grt_gbuffer_sub_info_get(gbs[k], &after)) return 1;
+        if (after.n_sub_pixels <= before[k]) continue;
+        std::string name;
+        (void)expand_pattern(gbuffer_pattern, first_index + k, &name);
+        if (grt_gbuffer_info_get(gbs[k], &gb_info) || save_sub_sidecar(gbs[k], gb_info, name + ".sub")) {
+          std::fprintf(stderr, "Error: %s\n", grt_last_error());
+          return 1;
+        }
+        std::fprintf(stderr, "[grt] INFO saved sub-sample set to %s.sub\n", name.c_str());
+      }
+    } else if (grt_gbuffer_shade_sequence(scene, K, gbs.data(), &fo, &shade_ms)) {
       std::fprintf(stderr, "Error: %s\n", grt_last_error());
       return 1;
     }
@@ -1043,6 +1175,12 @@ int main(int argc, char** argv) {
         std::fprintf(stderr, "[grt] INFO Tone mapping method: %s\n",
                      opts.tone_mapping == GRT_TONE_GLOBAL_LINEAR ? "GlobalLinear" : "Reinhard");
       }
+      if (seq_adaptive) {  // the frame's ray log, as `reshade --adaptive` writes it
+        const std::vector<uint8_t> f_status(status.begin() + n * k, status.begin() + n * (k + 1));
+        const std::vector<uint8_t> f_stop(stop.begin() + n * k, stop.begin() + n * (k + 1));
+        const std::vector<uint32_t> f_steps(steps.begin() + n * k, steps.begin() + n * (k + 1));
+        log_frame_rays(0, 0, w, f_status, f_stop, f_steps, ac.enabled && !maskp, nsel[k], fails[k]);
+      }
       const std::vector<double> f_xyza(xyza.begin() + n * 4 * k, xyza.begin() + n * 4 * (k + 1));
       if (int wrc = write_frame(name, raw, f_xyza, w, h, opts.tone_mapping, device, &ph_output, &ph_write)) return wrc;
       std::fprintf(stderr, "[grt] INFO saved image to %s\n", name.c_str());
@@ -1052,6 +1190,7 @@ int main(int argc, char** argv) {
                  ms_since(t_start));
     elapsed();
     for (grt_gbuffer* g : gbs) grt_gbuffer_destroy(g);
+    if (tracer) grt_scene_destroy(tracer);
     grt_scene_destroy(scene);
     grt_host_scene_destroy(hs);
     return 0;

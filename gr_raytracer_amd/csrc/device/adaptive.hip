@@ -10,6 +10,8 @@
 //    mix64 :132-143), samples_per_axis^2 samples per selected pixel, stratum order.
 //  * average_kernel: the ordered sum of the valid sub-samples and the 1/valid scale
 //    (supersample :334-380).
+//  * offsets_stack_kernel, failures_stack_kernel: the jitter and the failure records of
+//    sub-rays whose pixels belong to several stacked frames (g-buffer sequences).
 #include <hip/hip_runtime.h>
 #include <hipcub/hipcub.hpp>
 #include <stdint.h>
@@ -115,6 +117,27 @@ __global__ void offsets_kernel(const uint32_t* __restrict__ sel, uint64_t n_sel,
   dy[k] = ((double)sr + hash_pixel_samples(row, col, 2 * idx + 1)) / (double)spa;
 }
 
+// The same over a stack of frames of rows x w pixels (grt_gbuffer_supersample_sequence):
+// sel holds stacked indices P = frame * rows * w + pixel, n_sel of them, all live.  The
+// jitter hashes the frame's own (row, col), never the stacked row, so a sub-ray has the
+// offsets it has when its frame is supersampled alone; pix takes P, from which the trace
+// finds the frame's camera.
+__global__ void offsets_stack_kernel(const uint32_t* __restrict__ sel, uint64_t n_sel, uint32_t spa, uint32_t rows,
+                                     uint32_t w, uint32_t* __restrict__ pix, double* __restrict__ dx,
+                                     double* __restrict__ dy) {
+  uint64_t k = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  uint64_t per = (uint64_t)spa * spa;
+  if (k >= n_sel * per) return;
+  uint64_t j = k / per, s = k % per;
+  uint32_t p = sel[j];
+  int64_t row = (p / w) % rows, col = p % w;
+  uint64_t sr = s / spa, sc = s % spa;
+  uint64_t idx = sr * spa + sc;
+  pix[k] = p;
+  dx[k] = ((double)sc + hash_pixel_samples(row, col, 2 * idx)) / (double)spa;
+  dy[k] = ((double)sr + hash_pixel_samples(row, col, 2 * idx + 1)) / (double)spa;
+}
+
 // sel_out: output index per selected pixel; sel_px: its pixel index in the traced rect
 // (for the failure records).  A failed sub-sample (supersample's Err arm, :357-362) is
 // appended to f.key (pixel * spa^2 + stratum) / f.status when f.cap allows; f.count
@@ -161,6 +184,38 @@ __global__ void average_kernel(const uint32_t* __restrict__ sel_out, const uint3
     o[1] = y * inv;
     o[2] = z * inv;
     o[3] = a * inv;
+  }
+}
+
+// average_kernel's failure records when the chunk's pixels belong to several frames
+// (grt_gbuffer_shade_section_sequence, which runs average_kernel without a list): one lane
+// per sub-ray k = j * per + s of the chunk; sel[j] is a stacked index P = frame * npix +
+// pixel, and the record goes to the frame's own list frames[P / npix] under average_kernel's
+// conditions, with the key (P % npix) * per + s the frame alone would give it.
+__global__ void failures_stack_kernel(const uint32_t* __restrict__ sel, uint64_t n_sel, const unsigned long long* d_count,
+                                      uint64_t base, uint32_t spa, uint64_t npix, uint32_t n_frames,
+                                      const uint8_t* __restrict__ status,
+                                      const SubsampleFailures* __restrict__ frames) {
+  const uint64_t k = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  const uint64_t per = (uint64_t)spa * spa;
+  const uint64_t j = k / per, s = k % per;
+  if (j >= n_sel || (d_count && base + j >= *d_count)) return;
+  const int st = status[k] & 0x7f;
+  const uint64_t p = sel[j], fr = p / npix;
+  if (fr >= n_frames) return;
+  const SubsampleFailures f = frames[fr];
+  const int stop = f.ray_stop ? f.ray_stop[k] : GRT_STOP_CELESTIAL;
+  const bool event = f.stop && st == GRT_OK && (stop == GRT_STOP_NAN || stop == GRT_STOP_NONE);
+  if ((st != GRT_OK || event) && f.count) {
+    const unsigned long long slot = atomicAdd(f.count, 1ull);
+    if (slot < f.cap) {
+      f.key[slot] = (p - fr * npix) * per + s;
+      f.status[slot] = (uint8_t)st;
+      if (f.stop) {
+        f.stop[slot] = (uint8_t)stop;
+        f.steps[slot] = f.ray_steps ? f.ray_steps[k] : 0u;
+      }
+    }
   }
 }
 
@@ -358,12 +413,31 @@ hipError_t launch_make_offsets(const uint32_t* d_sel, uint64_t n_sel, const unsi
                      row0, col0, w, d_pix, d_dx, d_dy);
   return hipGetLastError();
 }
+hipError_t launch_make_offsets_stack(const uint32_t* d_sel, uint64_t n_sel, uint32_t spa, uint32_t rows, uint32_t w,
+                                     uint32_t* d_pix, double* d_dx, double* d_dy, hipStream_t stream) {
+  uint64_t n = n_sel * spa * spa;
+  if (n == 0) return hipSuccess;
+  if (rows == 0 || w == 0) return hipErrorInvalidValue;
+  hipLaunchKernelGGL(offsets_stack_kernel, dim3(nblocks(n, 256)), dim3(256), 0, stream, d_sel, n_sel, spa, rows, w,
+                     d_pix, d_dx, d_dy);
+  return hipGetLastError();
+}
 hipError_t launch_average(const uint32_t* d_sel_out, const uint32_t* d_sel_px, uint64_t n_sel,
                           const unsigned long long* d_count, uint64_t base, uint32_t spa, const double* d_samples,
                           const uint8_t* d_status, double* d_out, const SubsampleFailures& f, hipStream_t stream) {
   if (n_sel == 0) return hipSuccess;
   hipLaunchKernelGGL(average_kernel, dim3(nblocks(n_sel, 256)), dim3(256), 0, stream, d_sel_out, d_sel_px, n_sel,
                      d_count, base, spa, d_samples, d_status, d_out, f);
+  return hipGetLastError();
+}
+hipError_t launch_failures_stack(const uint32_t* d_sel, uint64_t n_sel, const unsigned long long* d_count, uint64_t base,
+                                 uint32_t spa, uint64_t npix, uint32_t n_frames, const uint8_t* d_status,
+                                 const SubsampleFailures* d_frames, hipStream_t stream) {
+  const uint64_t n = n_sel * spa * spa;
+  if (n == 0) return hipSuccess;
+  if (npix == 0 || n_frames == 0) return hipErrorInvalidValue;
+  hipLaunchKernelGGL(failures_stack_kernel, dim3(nblocks(n, 256)), dim3(256), 0, stream, d_sel, n_sel, d_count, base,
+                     spa, npix, n_frames, d_status, d_frames);
   return hipGetLastError();
 }
 hipError_t launch_paint(const uint32_t* d_sel, uint64_t n_sel, const unsigned long long* d_count, const double* mask,

@@ -1,6 +1,7 @@
 // api_gbuffer.hip — geometry buffers of the C ABI (include/grt_api.h): the exact trace and
-// fill of a frame or of a camera sequence, the sub-sample set, and the re-shades, the
-// adaptive one through the pass of api_adaptive.hip (AdaptivePlan, api_internal.h).
+// fill of a frame or of a camera sequence, the sub-sample set (of one buffer, or of a stack
+// of buffers filled by stacked traces), and the re-shades, the adaptive ones through the
+// pass of api_adaptive.hip (AdaptivePlan, api_internal.h).
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -148,14 +149,18 @@ static void info_from_scene(const grt_scene_desc& d, const grt_camera_desc& came
 }
 
 // The sub-rays of a buffer belong to the frame it holds: the tracer's geometry (shape key),
-// camera and integration parameters must be the recorded ones.
-static int check_tracer(const grt_gbuffer* gb, const grt_scene* t) {
+// camera and integration parameters must be the recorded ones.  A stacked trace takes each
+// frame's camera from the buffer's record (`camera` false): the tracer's own is then held
+// to the frame size only.
+static int check_tracer(const grt_gbuffer* gb, const grt_scene* t, bool camera = true) {
   if (int rc = grt_gbuffer_shape_compatible(&gb->info.shape, &t->desc)) return rc;
   auto differs = [](const char* field) {
     return fail(-EINVAL, std::string("g-buffer: the tracer differs from the traced scene in ") + field);
   };
   const grt_gbuffer_info& i = gb->info;
-  if (std::memcmp(&i.camera, &t->desc.camera, sizeof(i.camera)) != 0) return differs("camera");
+  if (camera && std::memcmp(&i.camera, &t->desc.camera, sizeof(i.camera)) != 0) return differs("camera");
+  if (!camera && (t->desc.camera.rows != i.camera.rows || t->desc.camera.cols != i.camera.cols))
+    return differs("camera.rows x camera.cols");
 #define X(field) \
   if (std::memcmp(&i.field, &t->desc.field, sizeof(i.field)) != 0) return differs(#field);
   GRT_GBUFFER_RECORDED(X)
@@ -692,6 +697,242 @@ static int sub_fill(grt_scene* tracer, grt_gbuffer* gb, uint32_t spa, const std:
   return 0;
 }
 
+// ---- the sub-sample sets of a stack of buffers (grt_gbuffer_supersample_sequence) ----
+// What a stacked call asks of its buffers: distinct whole frames of one size on one device,
+// and, for the sub-ray pass, a samples_per_axis every existing set agrees with and a tracer
+// (nullable) that check_tracer accepts for every frame, the camera aside.  Every refusal
+// names the frame.
+static int check_sequence_buffers(uint32_t n, grt_gbuffer* const* buffers, bool sub_pass, uint32_t spa,
+                                  const grt_scene* tracer) {
+  if (!buffers) return fail(-EINVAL, "null argument");
+  if (n == 0) return fail(-EINVAL, "a sequence needs at least one buffer");
+  for (uint32_t f = 0; f < n; ++f)
+    if (!buffers[f]) return fail(-EINVAL, "frame " + std::to_string(f) + ": null buffer");
+  const grt_gbuffer_info& i0 = buffers[0]->info;
+  for (uint32_t f = 0; f < n; ++f) {
+    const std::string frame = "frame " + std::to_string(f) + ": ";
+    const grt_gbuffer_info& i = buffers[f]->info;
+    for (uint32_t g = 0; g < f; ++g)
+      if (buffers[g] == buffers[f]) return fail(-EINVAL, frame + "the g-buffer is frame " + std::to_string(g) + "'s too");
+    if (i.device != i0.device)
+      return fail(-EINVAL, frame + "the g-buffer is on device " + std::to_string(i.device) + ", frame 0's on device " +
+                               std::to_string(i0.device));
+    if (i.rows != i0.rows || i.cols != i0.cols)
+      return fail(-EINVAL, frame + "the g-buffer has " + std::to_string(i.rows) + " x " + std::to_string(i.cols) +
+                               " pixels, frame 0's " + std::to_string(i0.rows) + " x " + std::to_string(i0.cols));
+    if (i.row0 != 0 || i.col0 != 0 || (int64_t)i.rows != i.camera.rows || (int64_t)i.cols != i.camera.cols)
+      return fail(-EINVAL, frame + "the g-buffer holds the rectangle (" + std::to_string(i.row0) + ", " +
+                               std::to_string(i.col0) + ", " + std::to_string(i.rows) + ", " + std::to_string(i.cols) +
+                               ") of a frame of " + std::to_string(i.camera.rows) + " x " +
+                               std::to_string(i.camera.cols) + " pixels, not the whole frame");
+    if (sub_pass && check_spa(buffers[f], spa)) return fail(-EINVAL, frame + grt_last_error());
+    if (tracer)
+      if (int rc = check_tracer(buffers[f], tracer, false)) return fail(rc, frame + grt_last_error());
+  }
+  if (i0.n_pixels == 0 || (uint64_t)n * i0.n_pixels > 0xffffffffull || (uint64_t)n * i0.rows > 0xffffffffull)
+    return fail(-EINVAL, "the stack of " + std::to_string(n) + " frames has 0 or more than 2^32 - 1 pixels");
+  return 0;
+}
+
+// The pixels of `pixels` that buffer f does not hold yet, ascending and unique
+// (grt_gbuffer_supersample's rules).
+static int missing_of(uint32_t f, const grt_gbuffer* gb, uint64_t n, const uint32_t* pixels, std::vector<uint32_t>* px) {
+  px->clear();
+  px->reserve(n);
+  for (uint64_t k = 0; k < n; ++k) {
+    if (pixels[k] >= gb->info.n_pixels)
+      return fail(-EINVAL, "frame " + std::to_string(f) + ": g-buffer: pixel " + std::to_string(pixels[k]) +
+                               " is outside the " + std::to_string(gb->info.n_pixels) + " pixels of the buffer");
+    if (gb->sub.h_block.empty() || gb->sub.h_block[pixels[k]] == grt::GBUFFER_NIL) px->push_back(pixels[k]);
+  }
+  std::sort(px->begin(), px->end());
+  px->erase(std::unique(px->begin(), px->end()), px->end());
+  return 0;
+}
+
+struct SubSeqTimes {
+  unsigned long long acc[8] = {0, 0, 0, 0, 0, 0, 0, 0};  // as trace_sync's
+  double trace_ms = 0.0, fill_ms = 0.0;
+  uint32_t traces = 0, chunks = 0;
+};
+
+// sub_fill for K buffers at once (check_sequence_buffers holds): px[k] are buffer k's new
+// pixels (ascending, unique, none held).  The lists are concatenated frame-major as stacked
+// indices P = k * rows * cols + p and cut into chunks of grt_set_sub_chunk sub-rays, so a
+// chunk may span frames.  Per chunk: the stacked jitter offsets, one offset-list trace
+// through the sequence unit over the stack of K * rows rows with the buffers' recorded
+// cameras as the table (trace_exact: a chunk that loses candidates is traced again), one
+// layer scan and one gbuffer_fill_kernel launch of that unit into a transient stacked set,
+// then the cut: per frame of the chunk, device-to-device copies of its slice of every array
+// to the end of its own set, and gbuffer_sub_append with the layer offsets rebased from the
+// chunk's to the set's.  The sets' counts move only after a chunk is complete.
+static int sub_fill_sequence(grt_scene* tracer, uint32_t K, grt_gbuffer* const* buffers, uint32_t spa,
+                             const std::vector<std::vector<uint32_t>>& px, SubSeqTimes* T) {
+  const grt_gbuffer_info& i0 = buffers[0]->info;
+  const uint32_t rows = i0.rows, cols = i0.cols;
+  const uint64_t npix = i0.n_pixels, per = (uint64_t)spa * spa;
+  std::vector<uint64_t> start(K + 1, 0);
+  for (uint32_t k = 0; k < K; ++k) start[k + 1] = start[k] + px[k].size();
+  const uint64_t m = start[K];
+  if (m == 0) return 0;
+  if (m * per + 1 > (uint64_t)INT_MAX)
+    return fail(-EINVAL, "g-buffer: more than INT_MAX - 1 stacked sub-rays (" + std::to_string(m) + " pixels x " +
+                             std::to_string(per) + ")");
+  for (uint32_t k = 0; k < K; ++k)
+    if ((buffers[k]->sub.n_pix + px[k].size()) * per + 1 > (uint64_t)INT_MAX)
+      return fail(-EOVERFLOW, "frame " + std::to_string(k) + ": more than INT_MAX - 1 sub-rays");
+  DeviceCopy* dc;
+  int rc;
+  if ((rc = ensure_device(tracer, i0.device, &dc))) return rc;
+  std::lock_guard<std::mutex> lk(dc->mu);
+  HIP_TRY(hipSetDevice(i0.device));
+  std::vector<uint32_t> h_local(m), h_stack(m);
+  for (uint32_t k = 0; k < K; ++k)
+    for (uint64_t j = 0; j < px[k].size(); ++j) {
+      h_local[start[k] + j] = px[k][j];
+      h_stack[start[k] + j] = (uint32_t)(k * npix + px[k][j]);
+    }
+  std::vector<grt::DevCamera> cams(K);
+  for (uint32_t k = 0; k < K; ++k) fill_dev_camera(buffers[k]->info.camera, cams[k]);
+  DevBuf b_cams;
+  if ((rc = b_cams.alloc(K * sizeof(grt::DevCamera)))) return rc;
+  HIP_TRY(hipMemcpy(b_cams.p, cams.data(), K * sizeof(grt::DevCamera), hipMemcpyHostToDevice));
+  const grt::CamTable ct{(const grt::DevCamera*)b_cams.p, rows, K};
+  for (uint32_t k = 0; k < K; ++k) {
+    if (px[k].empty()) continue;
+    if ((rc = buffers[k]->sub.ensure_map(npix))) return rc;
+    buffers[k]->sub.spa = spa;
+  }
+  SuperBufs C;  // the chunking of enqueue_supersample, over the concatenation
+  C.plan(m, spa);
+  const uint64_t chunk_pix = C.chunk_pix, cap = C.cap;
+  DevBuf d_local, d_stack, pix, dx, dy, xyza, cls, hits, counts, local, temp;
+  DevBuf status, stop, steps, sky_u, sky_v, sky_z, object, u, v, z, radius;  // the transient stacked set
+  if ((rc = d_local.alloc(4 * m)) || (rc = d_stack.alloc(4 * m)) || (rc = pix.alloc(4 * cap)) ||
+      (rc = dx.alloc(8 * cap)) || (rc = dy.alloc(8 * cap)) || (rc = xyza.alloc(16 * cap)) || (rc = cls.alloc(cap)) ||
+      (rc = hits.alloc(4 * cap)) || (rc = counts.alloc(8 * (cap + 1))) || (rc = local.alloc(8 * (cap + 1))) ||
+      (rc = status.alloc(cap)) || (rc = stop.alloc(cap)) || (rc = steps.alloc(4 * cap)) || (rc = sky_u.alloc(8 * cap)) ||
+      (rc = sky_v.alloc(8 * cap)) || (rc = sky_z.alloc(8 * cap)))
+    return rc;
+  uint64_t cap_layers = 0;
+  size_t temp_bytes = 0;
+  HIP_TRY(grt::gbuffer_layer_scan(nullptr, nullptr, cap, nullptr, nullptr, nullptr, &temp_bytes, nullptr));
+  if ((rc = temp.alloc(temp_bytes))) return rc;
+  HIP_TRY(hipMemcpy(d_local.p, h_local.data(), 4 * m, hipMemcpyHostToDevice));
+  HIP_TRY(hipMemcpy(d_stack.p, h_stack.data(), 4 * m, hipMemcpyHostToDevice));
+  hipStream_t st = nullptr;
+  struct Seg {
+    uint32_t frame;
+    uint64_t a, b;  // the frame's pixels of the chunk, [a, b) of its mc
+  };
+  std::vector<Seg> segs;
+  std::vector<uint64_t> lb;  // the chunk's layer offset at each segment's first ray, then the total
+  uint32_t k0 = 0;           // first frame that may have pixels in the chunk
+  for (uint64_t base = 0; base < m; base += chunk_pix) {
+    const uint64_t mc = std::min(chunk_pix, m - base), nr = mc * per;
+    segs.clear();
+    while (start[k0 + 1] <= base) ++k0;
+    for (uint32_t k = k0; k < K && start[k] < base + mc; ++k) {
+      const uint64_t a = std::max(start[k], base), b = std::min(start[k + 1], base + mc);
+      if (a < b) segs.push_back(Seg{k, a - base, b - base});
+    }
+    HIP_TRY(grt::launch_make_offsets_stack((const uint32_t*)d_stack.p + base, mc, spa, rows, cols, (uint32_t*)pix.p,
+                                           (double*)dx.p, (double*)dy.p, st));
+    grt::WorkList wo;
+    std::memset(&wo, 0, sizeof(wo));
+    wo.rows = K * rows;
+    wo.cols = cols;
+    wo.n_items = nr;
+    wo.pixel_index = (const uint32_t*)pix.p;
+    wo.dx = (const double*)dx.p;
+    wo.dy = (const double*)dy.p;
+    const grt::Outputs o{(float*)xyza.p,     (uint8_t*)cls.p,  (uint8_t*)status.p, nullptr,
+                         (uint32_t*)steps.p, (uint8_t*)stop.p, (uint32_t*)hits.p};
+    float t_ms = 0;
+    ++T->chunks;
+    if ((rc = trace_exact(tracer, *dc, wo, o, T->acc, &t_ms, &ct, &T->traces))) return rc;
+    T->trace_ms += t_ms;
+    if ((rc = stream_order(*dc, st))) return rc;
+    HIP_TRY(hipEventRecord(dc->ev0, st));
+    HIP_TRY(grt::gbuffer_layer_scan((const uint8_t*)status.p, (const uint32_t*)hits.p, nr, (uint64_t*)counts.p,
+                                    (uint64_t*)local.p, temp.p, &temp_bytes, st));
+    lb.assign(segs.size() + 1, 0);
+    for (size_t q = 0; q <= segs.size(); ++q) {
+      const uint64_t at = (q < segs.size() ? segs[q].a : mc) * per;
+      HIP_TRY(hipMemcpy(&lb[q], (const uint64_t*)local.p + at, 8, hipMemcpyDeviceToHost));
+    }
+    const uint64_t total = lb.back();
+    if (total > cap_layers || !object.p) {
+      const uint64_t want = std::max<uint64_t>({total, 2 * cap_layers, 4096});
+      for (DevBuf* b : {&object, &u, &v, &z, &radius}) {
+        if (b->p) (void)hipFree(b->p);
+        b->p = nullptr;
+      }
+      if ((rc = object.alloc(want)) || (rc = u.alloc(8 * want)) || (rc = v.alloc(8 * want)) ||
+          (rc = z.alloc(8 * want)) || (rc = radius.alloc(8 * want)))
+        return rc;
+      cap_layers = want;
+    }
+    grt::Workspace ws;
+    if ((rc = ensure_workspace(*dc, nr, &ws))) return rc;  // the carving of the trace above
+    ws.pool = dc->d_pool;
+    const grt::GBufferArrays stack{nr,
+                                   (const uint8_t*)status.p,
+                                   (const uint8_t*)stop.p,
+                                   (const uint64_t*)local.p,
+                                   (double*)sky_u.p,
+                                   (double*)sky_v.p,
+                                   (double*)sky_z.p,
+                                   (uint8_t*)object.p,
+                                   (double*)u.p,
+                                   (double*)v.p,
+                                   (double*)z.p,
+                                   (double*)radius.p};
+    HIP_TRY(grt::seq::launch_gbuffer_fill(tracer->desc.geometry, dc->d_scene, wo, ws, stack, st, ct));
+    for (size_t q = 0; q < segs.size(); ++q) {
+      GBufferSub& S = buffers[segs[q].frame]->sub;
+      const uint64_t mk = segs[q].b - segs[q].a, nk = mk * per, r0 = segs[q].a * per;
+      const uint64_t l0 = lb[q], nl = lb[q + 1] - lb[q];
+      if ((rc = S.reserve_pixels(S.n_pix + mk)) || (rc = S.reserve_layers(S.n_layers + nl))) return rc;
+      const uint64_t off = S.n_rays(), loff = S.n_layers;
+      auto cut = [&](DevBuf& dst, uint64_t to, const DevBuf& src, uint64_t from, uint64_t count, uint64_t size) {
+        return count ? hipMemcpyAsync((char*)dst.p + to * size, (const char*)src.p + from * size, count * size,
+                                      hipMemcpyDeviceToDevice, st)
+                     : hipSuccess;
+      };
+      HIP_TRY(cut(S.status, off, status, r0, nk, 1));
+      HIP_TRY(cut(S.stop, off, stop, r0, nk, 1));
+      HIP_TRY(cut(S.steps, off, steps, r0, nk, 4));
+      HIP_TRY(cut(S.sky_u, off, sky_u, r0, nk, 8));
+      HIP_TRY(cut(S.sky_v, off, sky_v, r0, nk, 8));
+      HIP_TRY(cut(S.sky_z, off, sky_z, r0, nk, 8));
+      HIP_TRY(cut(S.object, loff, object, l0, nl, 1));
+      HIP_TRY(cut(S.u, loff, u, l0, nl, 8));
+      HIP_TRY(cut(S.v, loff, v, l0, nl, 8));
+      HIP_TRY(cut(S.z, loff, z, l0, nl, 8));
+      HIP_TRY(cut(S.radius, loff, radius, l0, nl, 8));
+      // layer_start[off + i] = local[r0 + i] - l0 + loff: the rebase, in wrapping u64 arithmetic
+      HIP_TRY(grt::gbuffer_sub_append((const uint64_t*)local.p + r0, nk, loff - l0, (uint64_t*)S.layer_start.p + off,
+                                      (const uint32_t*)d_local.p + base + segs[q].a, mk, (uint32_t)S.n_pix,
+                                      (uint32_t*)S.sub_block.p, (uint32_t*)S.sub_pixel.p, st));
+    }
+    HIP_TRY(hipEventRecord(dc->ev1, st));
+    HIP_TRY(hipEventSynchronize(dc->ev1));
+    float f_ms = 0;
+    HIP_TRY(hipEventElapsedTime(&f_ms, dc->ev0, dc->ev1));
+    T->fill_ms += f_ms;
+    if ((rc = stream_done(*dc, st))) return rc;
+    for (size_t q = 0; q < segs.size(); ++q) {
+      GBufferSub& S = buffers[segs[q].frame]->sub;
+      const uint64_t mk = segs[q].b - segs[q].a;
+      for (uint64_t j = 0; j < mk; ++j) S.h_block[h_local[base + segs[q].a + j]] = (uint32_t)(S.n_pix + j);
+      S.n_pix += mk;
+      S.n_layers += lb[q + 1] - lb[q];
+    }
+  }
+  return 0;
+}
+
 extern "C" {
 
 int grt_gbuffer_supersample(grt_scene* tracer, grt_gbuffer* gb, uint32_t spa, uint64_t n, const uint32_t* pixels,
@@ -843,6 +1084,263 @@ int grt_gbuffer_shade_section(grt_scene* s, grt_gbuffer* gb, const grt_adaptive_
     if (n_supersampled) *n_supersampled = cnt[0];
     if ((rc = P.fails[0].read(cnt[1], spa, sub_pass ? failures : nullptr))) return rc;
   }
+  return 0;
+}
+
+int grt_gbuffer_supersample_sequence(grt_scene* tracer, uint32_t n, grt_gbuffer* const* buffers, uint32_t spa,
+                                     const uint64_t* n_pixels, const uint32_t* const* pixels, grt_stats* stats,
+                                     grt_gbuffer_sequence_report* report) {
+  const auto wall0 = std::chrono::steady_clock::now();
+  if (!tracer || !buffers || !n_pixels || !pixels) return fail(-EINVAL, "null argument");
+  int rc;
+  if ((rc = check_sequence_buffers(n, buffers, true, spa, tracer))) return rc;
+  if (stats) std::memset(stats, 0, sizeof(*stats));
+  if (report) std::memset(report, 0, sizeof(*report));
+  std::vector<std::vector<uint32_t>> px(n);
+  for (uint32_t f = 0; f < n; ++f) {
+    if (n_pixels[f] && !pixels[f]) return fail(-EINVAL, "frame " + std::to_string(f) + ": null pixel list");
+    if ((rc = missing_of(f, buffers[f], n_pixels[f], pixels[f], &px[f]))) return rc;
+  }
+  SubSeqTimes T;
+  rc = sub_fill_sequence(tracer, n, buffers, spa, px, &T);
+  if (stats) stats_from(T.acc, T.trace_ms, stats);
+  if (report) {
+    report->n_frames = n;
+    report->n_launches = T.chunks;
+    report->n_traces = T.traces;
+    report->trace_ms = T.trace_ms;
+    report->fill_ms = T.fill_ms;
+    report->wall_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - wall0).count();
+  }
+  return rc;
+}
+
+int grt_gbuffer_shade_section_sequence(grt_scene* s, uint32_t n, grt_gbuffer* const* buffers,
+                                       const grt_adaptive_config* cfg, const double* mask_xyza, grt_scene* tracer,
+                                       const grt_frame_out* out, uint64_t* n_supersampled,
+                                       grt_subsample_failures* failures, uint64_t* per_frame,
+                                       grt_gbuffer_section_sequence_report* report) {
+  const auto wall0 = std::chrono::steady_clock::now();
+  if (!s || !buffers || !cfg || !out) return fail(-EINVAL, "null argument");
+  if (!out->xyza64) return fail(-EINVAL, "grt_frame_out needs xyza64");
+  if (cfg->samples_per_axis == 0) return fail(-EINVAL, "adaptive_sampling.samples_per_axis must be greater than zero");
+  const bool supersampled = cfg->enabled || mask_xyza != nullptr;
+  const bool sub_pass = supersampled && !mask_xyza;
+  const uint32_t spa = cfg->samples_per_axis;
+  int rc;
+  if ((rc = check_sequence_buffers(n, buffers, sub_pass, spa, sub_pass ? tracer : nullptr))) return rc;
+  for (uint32_t f = 0; f < n; ++f)
+    if ((rc = grt_gbuffer_shape_compatible(&buffers[f]->info.shape, &s->desc)))
+      return fail(rc, "frame " + std::to_string(f) + ": " + grt_last_error());
+  if (report) std::memset(report, 0, sizeof(*report));
+  for (uint32_t f = 0; f < n; ++f) {
+    if (n_supersampled) n_supersampled[f] = 0;
+    if (failures) failures[f].count = 0;
+  }
+  if (per_frame) std::memset(per_frame, 0, 32ull * n);
+  const grt_gbuffer_info& i0 = buffers[0]->info;
+  const int device = i0.device;
+  const uint32_t rows = i0.rows, cols = i0.cols;
+  const uint64_t per = i0.n_pixels;
+  if (per > (uint64_t)INT_MAX) return fail(-EOVERFLOW, "frame larger than INT_MAX pixels");
+  // frames per launch group: whole buffers within the group's rays, at least one; the
+  // split compacts the group's slots with 32-bit counts
+  uint64_t g = std::max<uint64_t>(1, g_seq_group.load(std::memory_order_relaxed) / per);
+  g = std::min<uint64_t>(g, n);
+  g = std::min<uint64_t>(g, std::max<uint64_t>(1, (uint64_t)INT_MAX / per));
+  const uint32_t n_groups = (uint32_t)((n + g - 1) / g);
+  DeviceCopy* dc;
+  if ((rc = ensure_device(s, device, &dc))) return rc;
+  std::unique_lock<std::mutex> lk(dc->mu);
+  HIP_TRY(hipSetDevice(device));
+  if (sub_pass)
+    for (uint32_t f = 0; f < n; ++f)
+      if ((rc = buffers[f]->sub.ensure_map(per))) return rc;
+  const grt::AdaptiveParams ap = adaptive_params(cfg, cols, rows, cfg->minimum_luminance);
+  hipStream_t st = nullptr;
+  double shade_ms = 0.0;
+  // One launch group, everything on `st`: the stacked 1-spp shade; per frame the floor, the
+  // selection and its compaction on the frame's slice (the mask: the paint); then, over all
+  // the group's selections, the split, and with `chunks` the sub-ray shade, the average and
+  // the failure records per chunk.  cnt: per frame selected, failed, held, missing; then the
+  // totals held, missing.
+  auto run_group = [&](AdaptivePlan& P, uint32_t f0, uint32_t kg, bool chunks,
+                       std::vector<unsigned long long>& cnt) -> int {
+    P.n = per;
+    P.w = cols;
+    P.h = rows;
+    P.frames = kg;
+    P.spa = spa;
+    P.held = P.stack = true;
+    P.supersampled = supersampled;
+    P.device_floor = supersampled && !cfg->has_minimum_luminance;
+    P.sub_rays = sub_pass;
+    P.sec_stop = out->stop != nullptr;
+    P.sec_steps = out->steps != nullptr;
+    if (int rc = P.plan(*dc, sub_pass && failures ? failures + f0 : nullptr)) return rc;
+    const SectionBufs& b = P.sec;
+    const SuperBufs& B = P.B;
+    std::vector<grt::GBufferFrame> frames(kg);
+    std::vector<grt::GBufferSubFrame> subs(kg);
+    std::vector<grt::SubsampleFailures> lists(kg);
+    for (uint32_t f = 0; f < kg; ++f) {
+      const grt_gbuffer* gb = buffers[f0 + f];
+      const GBufferSub& S = gb->sub;
+      frames[f] = grt::GBufferFrame{gb->view(), (const uint32_t*)gb->steps.p};
+      subs[f] = grt::GBufferSubFrame{S.view(0, S.n_rays()), (const uint32_t*)S.steps.p, (const uint32_t*)S.sub_block.p};
+      if (!supersampled) continue;
+      lists[f] = P.fails[f].f;
+      lists[f].count = P.d_cnt + 4 * f + 1;
+      lists[f].ray_stop = B.stop;
+      lists[f].ray_steps = B.steps;
+    }
+    HIP_TRY(hipMemcpy(P.frame_tab, frames.data(), kg * sizeof(frames[0]), hipMemcpyHostToDevice));
+    if (sub_pass) {
+      HIP_TRY(hipMemcpy(P.sub_tab, subs.data(), kg * sizeof(subs[0]), hipMemcpyHostToDevice));
+      HIP_TRY(hipMemcpy(P.fail_tab, lists.data(), kg * sizeof(lists[0]), hipMemcpyHostToDevice));
+    }
+    if (int rc = stream_order(*dc, st)) return rc;
+    if (supersampled) HIP_TRY(hipMemsetAsync(P.d_cnt, 0, P.cnt_bytes(), st));
+    HIP_TRY(hipEventRecord(dc->ev0, st));
+    HIP_TRY(grt::launch_gbuffer_shade_stack(dc->d_scene, P.frame_tab, kg, per, b.outputs(), st));
+    for (uint32_t f = 0; f < kg && supersampled; ++f) {  // the frame's slice, its own counts
+      double* x64 = b.x64 + 4 * per * f;
+      unsigned long long* c = P.d_cnt + 4 * f;
+      uint32_t* sel = sub_pass ? P.sel + per * f : P.sel;
+      if (int rc = P.enqueue_select(st, x64, b.cls + per * f, ap, c, nullptr, nullptr, 0, sel)) return rc;
+      if (mask_xyza) HIP_TRY(grt::launch_paint(sel, per, c, mask_xyza, x64, st));
+    }
+    if (sub_pass) {
+      unsigned long long* tot = P.d_totals();
+      HIP_TRY(grt::gbuffer_split_stack(P.sel, P.d_cnt, kg, per, P.sub_tab, P.split, P.stack_px, P.held_px, tot,
+                                       P.missing_px, tot + 1, P.split_tmp, &P.split_bytes, st));
+      const grt::Outputs so{B.xyza, B.cls, B.status, B.x64, B.steps, B.stop, nullptr};
+      const grt::SubsampleFailures none{};  // the records are failures_stack_kernel's
+      for (uint32_t c = 0; c < B.n_chunks && chunks; ++c) {
+        const uint64_t base = (uint64_t)c * B.chunk_pix;
+        const uint32_t* px = P.held_px + base;
+        HIP_TRY(grt::launch_gbuffer_shade_sub_stack(dc->d_scene, P.sub_tab, kg, per, px, B.chunk_pix, tot, base, spa, so,
+                                                    st));
+        HIP_TRY(grt::launch_average(px, px, B.chunk_pix, tot, base, spa, B.x64, B.status, b.x64, none, st));
+        HIP_TRY(grt::launch_failures_stack(px, B.chunk_pix, tot, base, spa, per, kg, B.status, P.fail_tab, st));
+      }
+    }
+    HIP_TRY(hipEventRecord(dc->ev1, st));
+    HIP_TRY(hipEventSynchronize(dc->ev1));
+    float t = 0;
+    HIP_TRY(hipEventElapsedTime(&t, dc->ev0, dc->ev1));
+    shade_ms += t;
+    cnt.assign(4 * (size_t)kg + 4, 0);
+    if (supersampled) HIP_TRY(hipMemcpy(cnt.data(), P.d_cnt, P.cnt_bytes(), hipMemcpyDeviceToHost));
+    return stream_done(*dc, st);
+  };
+  // the group's frames, counts and failure lists to the caller's arrays
+  auto finish_group = [&](const AdaptivePlan& P, uint32_t f0, uint32_t kg,
+                          const std::vector<unsigned long long>& cnt) -> int {
+    const SectionBufs& b = P.sec;
+    const uint64_t m = per * kg, at = per * f0;
+    HIP_TRY(hipMemcpy(out->xyza64 + 4 * at, b.x64, 32 * m, hipMemcpyDeviceToHost));
+    if (out->ray_class) HIP_TRY(hipMemcpy(out->ray_class + at, b.cls, m, hipMemcpyDeviceToHost));
+    if (out->status) HIP_TRY(hipMemcpy(out->status + at, b.status, m, hipMemcpyDeviceToHost));
+    if (out->stop) HIP_TRY(hipMemcpy(out->stop + at, b.stop, m, hipMemcpyDeviceToHost));
+    if (out->steps) HIP_TRY(hipMemcpy(out->steps + at, b.steps, 4 * m, hipMemcpyDeviceToHost));
+    for (uint32_t f = 0; f < kg && supersampled; ++f) {
+      if (n_supersampled) n_supersampled[f0 + f] = cnt[4 * f];
+      if (int rc = P.fails[f].read(cnt[4 * f + 1], spa, sub_pass && failures ? &failures[f0 + f] : nullptr)) return rc;
+    }
+    return 0;
+  };
+  // per frame: selected, held when the call began, missing then
+  std::vector<uint64_t> first(3ull * n, 0);
+  std::vector<std::vector<uint32_t>> missing(n);
+  std::vector<uint8_t> dirty(n_groups, 0);
+  uint64_t n_missing = 0;
+  std::vector<unsigned long long> cnt;
+  // without a tracer a later group may still refuse the call: count first, write nothing
+  const bool count_first = sub_pass && !tracer && n_groups > 1;
+  for (int pass = count_first ? 0 : 1; pass < 2; ++pass) {
+    for (uint32_t gi = 0; gi < n_groups; ++gi) {
+      const uint32_t f0 = (uint32_t)(gi * g), kg = (uint32_t)std::min<uint64_t>(g, n - f0);
+      AdaptivePlan P;
+      if ((rc = run_group(P, f0, kg, pass == 1, cnt))) return rc;
+      if (pass == 1 && count_first) {  // nothing is missing: the counts stand
+        if ((rc = finish_group(P, f0, kg, cnt))) return rc;
+        continue;
+      }
+      for (uint32_t f = 0; f < kg; ++f) {
+        first[3 * (f0 + f)] = cnt[4 * f];
+        first[3 * (f0 + f) + 1] = cnt[4 * f + 2];
+        first[3 * (f0 + f) + 2] = cnt[4 * f + 3];
+      }
+      const uint64_t gm = sub_pass ? cnt[4 * kg + 1] : 0;
+      if (gm) {
+        dirty[gi] = 1;
+        n_missing += gm;
+        std::vector<uint32_t> px(gm);
+        HIP_TRY(hipMemcpy(px.data(), P.missing_px, 4 * gm, hipMemcpyDeviceToHost));
+        for (uint32_t p : px) missing[f0 + p / per].push_back((uint32_t)(p % per));
+      } else if (pass == 1 && (rc = finish_group(P, f0, kg, cnt))) {
+        return rc;
+      }
+    }
+    if (pass == 0 && n_missing) break;
+  }
+  uint64_t n_selected = 0, n_held = 0;
+  for (uint32_t f = 0; f < n; ++f) {
+    n_selected += first[3 * f];
+    n_held += first[3 * f + 1];
+    if (per_frame) {
+      per_frame[4 * f] = first[3 * f];
+      per_frame[4 * f + 1] = first[3 * f + 1];
+      per_frame[4 * f + 3] = first[3 * f + 2];
+    }
+  }
+  auto fill_report = [&](uint64_t traced, uint64_t still_missing, const SubSeqTimes* T) {
+    if (!report) return;
+    report->n_frames = n;
+    report->n_launches = n_groups;
+    report->n_selected = n_selected;
+    report->n_held = n_held;
+    report->n_traced = traced;
+    report->n_missing = still_missing;
+    report->shade_ms = shade_ms;
+    if (T) {
+      report->trace_ms = T->trace_ms + T->fill_ms;
+      stats_from(T->acc, T->trace_ms, &report->top_up);
+    }
+    report->wall_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - wall0).count();
+  };
+  if (n_missing == 0) {
+    fill_report(0, 0, nullptr);
+    return 0;
+  }
+  if (!tracer) {
+    fill_report(0, n_missing, nullptr);
+    return fail(-ENODATA, "g-buffer: the sub-sample sets miss " + std::to_string(n_missing) + " of the " +
+                              std::to_string(n_selected) + " selected pixels of the " + std::to_string(n) +
+                              " frames and the call has no tracer");
+  }
+  // one stacked top-up of every frame's missing pixels, then the groups that missed some again
+  SubSeqTimes T;
+  lk.unlock();  // the tracer may be this scene: sub_fill_sequence takes its device's lock
+  rc = sub_fill_sequence(tracer, n, buffers, spa, missing, &T);
+  lk.lock();
+  if (rc) return rc;
+  HIP_TRY(hipSetDevice(device));
+  for (uint32_t gi = 0; gi < n_groups; ++gi) {
+    if (!dirty[gi]) continue;
+    const uint32_t f0 = (uint32_t)(gi * g), kg = (uint32_t)std::min<uint64_t>(g, n - f0);
+    AdaptivePlan P;
+    if ((rc = run_group(P, f0, kg, true, cnt))) return rc;
+    if (cnt[4 * kg + 1] != 0) return fail(-EIO, "g-buffer: the top-up left selected pixels without sub-rays");
+    if ((rc = finish_group(P, f0, kg, cnt))) return rc;
+  }
+  if (per_frame)
+    for (uint32_t f = 0; f < n; ++f) {
+      per_frame[4 * f + 2] = first[3 * f + 2];
+      per_frame[4 * f + 3] = 0;
+    }
+  fill_report(n_missing, 0, &T);
   return 0;
 }
 

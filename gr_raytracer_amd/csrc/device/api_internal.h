@@ -252,6 +252,10 @@ struct SectionBufs {
 //                           the frame indices of the selection beside the local ones
 //   grt_gbuffer_shade_section  `held`: no trace, so no sub-ray offsets; the held / missing
 //                           split of the selection, four counts
+//   grt_gbuffer_shade_section_sequence  `held` and `stack`: the stack's 1-spp buffers; the
+//                           selections of all `frames` kept side by side (frame f's at
+//                           sel + f * n), one split and one sub-ray pass over all of them,
+//                           four counts per frame and the two totals after them
 struct AdaptivePlan {
   // set by the caller before plan()
   uint64_t n = 0;          // pixels of one selection
@@ -260,19 +264,25 @@ struct AdaptivePlan {
   bool section = true;     // SectionBufs (with stop / steps as asked for)
   bool sec_stop = false, sec_steps = false;
   bool supersampled = true, device_floor = false, ordered = false, sub_rays = false;
-  bool shard = false, held = false;
+  bool shard = false, held = false, stack = false;
   std::vector<FailBufs> fails;  // one per frame
   // sizes (plan) and buffers (carve)
   size_t sort_bytes = 0, select_bytes = 0, order_bytes = 0, split_bytes = 0;
   SectionBufs sec;
   uint8_t *flags = nullptr, *split = nullptr;
   uint32_t *sel = nullptr, *sel_frame = nullptr, *order = nullptr, *held_px = nullptr, *missing_px = nullptr;
+  uint32_t* stack_px = nullptr;              // stack: the selections as stacked indices f * n + pixel
+  grt::GBufferFrame* frame_tab = nullptr;    // stack: device tables, one entry per frame
+  grt::GBufferSubFrame* sub_tab = nullptr;
+  grt::SubsampleFailures* fail_tab = nullptr;
   unsigned long long* d_cnt = nullptr;  // per frame: [0] selected pixels, [1] failed sub-samples (held: [2] held, [3] missing)
   double* d_floor = nullptr;
   void *sort = nullptr, *select = nullptr, *order_tmp = nullptr, *split_tmp = nullptr;
   SuperBufs B;
 
-  uint64_t cnt_bytes() const { return (held ? 32ull : 16ull) * frames; }
+  uint64_t cnt_bytes() const { return (held ? 32ull : 16ull) * frames + (stack ? 32ull : 0ull); }
+  uint64_t sel_n() const { return stack ? n * frames : n; }  // entries of the selection arrays
+  unsigned long long* d_totals() const { return d_cnt + 4ull * frames; }  // stack: [0] held, [1] missing
 
   // The scratch sizes, then the buffers from the device's arena, grown first if need be.
   int plan(DeviceCopy& dc, const grt_subsample_failures* failures) {
@@ -283,10 +293,13 @@ struct AdaptivePlan {
     if (supersampled) HIP_TRY(grt::compact_flags(nullptr, n, nullptr, nullptr, nullptr, &select_bytes, 0));
     // the supersample pass's work order (longest sub-rays first) reads the 1-spp step counts
     if (ordered) HIP_TRY(grt::order_selection(nullptr, nullptr, n, nullptr, w, h, nullptr, nullptr, &order_bytes, 0));
-    if (held && sub_rays)
+    if (held && sub_rays && !stack)
       HIP_TRY(grt::gbuffer_split(nullptr, nullptr, n, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr,
                                  &split_bytes, 0));
-    if (sub_rays) B.plan(n, spa);
+    if (held && sub_rays && stack)
+      HIP_TRY(grt::gbuffer_split_stack(nullptr, nullptr, frames, n, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr,
+                                       nullptr, nullptr, &split_bytes, 0));
+    if (sub_rays) B.plan(sel_n(), spa);
     AdArena sizes;
     carve(sizes);
     if (int rc = ad_reserve(dc, sizes.off)) return rc;
@@ -300,10 +313,11 @@ struct AdaptivePlan {
   // its order arrays after the compaction scratch, the others before the flags.
   void carve(AdArena& A) {
     if (section) sec.carve(A, n * frames, sec_stop, sec_steps);
+    if (stack) frame_tab = (grt::GBufferFrame*)A.take(frames * sizeof(grt::GBufferFrame));
     if (!supersampled) return;
     if (ordered && !shard) carve_order(A);
     flags = (uint8_t*)A.take(n);
-    sel = (uint32_t*)A.take(n * 4);
+    sel = (uint32_t*)A.take((sub_rays ? sel_n() : n) * 4);
     if (shard) sel_frame = (uint32_t*)A.take(n * 4);
     d_cnt = (unsigned long long*)A.take(cnt_bytes());
     if (!shard) {
@@ -313,10 +327,15 @@ struct AdaptivePlan {
     select = A.take(select_bytes);
     if (ordered && shard) carve_order(A);
     if (held && sub_rays) {
-      split = (uint8_t*)A.take(2 * n);
-      held_px = (uint32_t*)A.take(n * 4);
-      missing_px = (uint32_t*)A.take(n * 4);
+      split = (uint8_t*)A.take(2 * sel_n());
+      held_px = (uint32_t*)A.take(sel_n() * 4);
+      missing_px = (uint32_t*)A.take(sel_n() * 4);
       split_tmp = A.take(split_bytes);
+      if (stack) stack_px = (uint32_t*)A.take(sel_n() * 4);
+    }
+    if (stack) {
+      sub_tab = (grt::GBufferSubFrame*)A.take(frames * sizeof(grt::GBufferSubFrame));
+      fail_tab = (grt::SubsampleFailures*)A.take(frames * sizeof(grt::SubsampleFailures));
     }
     if (sub_rays && held) B.carve_outputs(A);
     else if (sub_rays) B.carve(A);
@@ -332,17 +351,18 @@ struct AdaptivePlan {
   // collect_pixels_to_supersample (:386-458): the stencil, and the selected pixels in order
   // by a device stream compaction, their count in cnt[0].  sh: a row-band shard's pixels
   // (local_rows of them) with the whole frame (ya, cls) as the neighbourhood and the
-  // caller's floor d_min_lum (nullable), else a section's x64 and class.
+  // caller's floor d_min_lum (nullable), else a section's x64 and class.  sel_to: where the
+  // selection goes (stack: frame f's place, sel + f * n), else `sel`.
   int enqueue_select(hipStream_t st, const double* x64, const uint8_t* cls, const grt::AdaptiveParams& ap,
                      unsigned long long* cnt, const grt_row_shard* sh = nullptr, const double* d_min_lum = nullptr,
-                     uint32_t local_rows = 0) {
+                     uint32_t local_rows = 0, uint32_t* sel_to = nullptr) {
     if (device_floor) HIP_TRY(grt::luminance_floor_device(x64 + 1, 4, n, floor_index(n), sort, &sort_bytes, d_floor, st));
     if (sh)
       HIP_TRY(grt::launch_select_shard(x64, cls, ap, d_min_lum, sh->band_rows, sh->shard, sh->n_shards, local_rows, flags,
                                        st));
     else
       HIP_TRY(grt::launch_select(x64, cls, ap, device_floor ? d_floor : nullptr, flags, st));
-    HIP_TRY(grt::compact_flags(flags, n, sel, cnt, select, &select_bytes, st));
+    HIP_TRY(grt::compact_flags(flags, n, sel_to ? sel_to : sel, cnt, select, &select_bytes, st));
     return 0;
   }
 
@@ -379,7 +399,7 @@ struct AdaptivePlan {
   int read(uint64_t* n_supersampled, grt_subsample_failures* failures) const {
     std::vector<unsigned long long> cnt(cnt_bytes() / 8);
     HIP_TRY(hipMemcpy(cnt.data(), d_cnt, cnt_bytes(), hipMemcpyDeviceToHost));
-    const size_t stride = cnt.size() / frames;
+    const size_t stride = held ? 4 : 2;
     for (uint32_t f = 0; f < frames; ++f) {
       if (n_supersampled) n_supersampled[f] = cnt[stride * f];
       if (int rc = fails[f].read(cnt[stride * f + 1], spa, failures ? &failures[f] : nullptr)) return rc;

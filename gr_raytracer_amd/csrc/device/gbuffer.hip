@@ -1,7 +1,8 @@
 // gbuffer.hip — layer offsets of a geometry buffer (grt_gbuffer_trace), and the bookkeeping
 // of its sub-sample set (grt_gbuffer_supersample, grt_gbuffer_shade_section): the split of
-// a selection into held and missing pixels, the append of a traced chunk, the pixel -> block
-// map of an uploaded set.
+// a selection into held and missing pixels (of one buffer, or of a stack of buffers at once:
+// grt_gbuffer_shade_section_sequence), the append of a traced chunk, the pixel -> block map
+// of an uploaded set.
 //
 // A pixel's layers are the window-nearest hits that enter its blend: the trace's own
 // `hits` output, and none for a pixel the trace aborted (status != 0).  The offsets are
@@ -84,6 +85,50 @@ hipError_t gbuffer_split(const uint32_t* d_sel, const unsigned long long* d_coun
   e = hipcub::DeviceSelect::Flagged(d_temp, *temp_bytes, d_sel, d_flags, d_held, d_n_held, (int)n_max, stream);
   if (e != hipSuccess) return e;
   return hipcub::DeviceSelect::Flagged(d_temp, *temp_bytes, d_sel, d_flags + n_max, d_missing, d_n_missing, (int)n_max,
+                                       stream);
+}
+
+// The same over the selections of a stack of buffers (grt_gbuffer_shade_section_sequence):
+// slot i = f * npix + j is entry j of frame f's selection, live while j < cnt[4 f], and is
+// looked up in that frame's own sub_block.  stack[i] is the entry as a stacked index
+// f * npix + pixel; cnt[4 f + 2] / cnt[4 f + 3] count the frame's held / missing pixels.
+__global__ void __launch_bounds__(256) gbuffer_split_stack_flags_kernel(const uint32_t* __restrict__ sel,
+                                                                        unsigned long long* __restrict__ cnt,
+                                                                        uint32_t n_frames, uint64_t npix,
+                                                                        const GBufferSubFrame* __restrict__ frames,
+                                                                        uint8_t* __restrict__ held,
+                                                                        uint8_t* __restrict__ missing,
+                                                                        uint32_t* __restrict__ stack) {
+  const uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n_frames * npix) return;
+  const uint64_t f = i / npix, j = i - f * npix;
+  const bool live = j < cnt[4 * f];
+  const uint32_t p = live ? sel[i] : 0u;
+  const bool has = live && p < npix && frames[f].sub_block[p] != GBUFFER_NIL;
+  held[i] = has ? 1 : 0;
+  missing[i] = (live && !has) ? 1 : 0;
+  stack[i] = (uint32_t)(f * npix + p);
+  if (live) atomicAdd(&cnt[4 * f + (has ? 2 : 3)], 1ull);
+}
+
+// Two ordered compactions, as gbuffer_split: slot order is frame-major and a frame's
+// selection ascends, so each list ascends in the stacked index.
+hipError_t gbuffer_split_stack(const uint32_t* d_sel, unsigned long long* d_cnt, uint32_t n_frames, uint64_t npix,
+                               const GBufferSubFrame* d_frames, uint8_t* d_flags, uint32_t* d_stack, uint32_t* d_held,
+                               unsigned long long* d_n_held, uint32_t* d_missing, unsigned long long* d_n_missing,
+                               void* d_temp, size_t* temp_bytes, hipStream_t stream) {
+  const uint64_t m = (uint64_t)n_frames * npix;
+  if (m > (uint64_t)INT_MAX) return hipErrorInvalidValue;
+  if (d_temp == nullptr)
+    return hipcub::DeviceSelect::Flagged(nullptr, *temp_bytes, d_stack, d_flags, d_held, d_n_held, (int)m, stream);
+  if (m == 0) return hipSuccess;
+  hipLaunchKernelGGL(gbuffer_split_stack_flags_kernel, dim3((unsigned)((m + 255) / 256)), dim3(256), 0, stream, d_sel,
+                     d_cnt, n_frames, npix, d_frames, d_flags, d_flags + m, d_stack);
+  hipError_t e = hipGetLastError();
+  if (e != hipSuccess) return e;
+  e = hipcub::DeviceSelect::Flagged(d_temp, *temp_bytes, d_stack, d_flags, d_held, d_n_held, (int)m, stream);
+  if (e != hipSuccess) return e;
+  return hipcub::DeviceSelect::Flagged(d_temp, *temp_bytes, d_stack, d_flags + m, d_missing, d_n_missing, (int)m,
                                        stream);
 }
 

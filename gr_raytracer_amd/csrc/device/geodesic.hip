@@ -3915,9 +3915,10 @@ static hipError_t gbuffer_fill_g(const DevScene* d_scene, const WorkList& wl, co
 hipError_t launch_gbuffer_fill(int geometry, const DevScene* d_scene, const WorkList& wl, const Workspace& ws,
                                const GBufferArrays& gb, hipStream_t stream CAMS_PARAM) {
   if (gb.n == 0) return hipSuccess;
-#if GRT_SEQ  // the stack's slots are whole frames, one camera each
-  if (!ct.cams || ct.cam_rows == 0 || ct.n_cams == 0 || wl.pixel_index || wl.row0 != 0 || wl.col0 != 0 ||
-      (uint64_t)wl.rows != (uint64_t)ct.cam_rows * ct.n_cams || gb.n != (uint64_t)wl.rows * wl.cols)
+#if GRT_SEQ  // the stack from (0, 0): whole frames, one camera each, or an offset list over them (a slot per entry)
+  if (!ct.cams || ct.cam_rows == 0 || ct.n_cams == 0 || wl.row0 != 0 || wl.col0 != 0 ||
+      (uint64_t)wl.rows != (uint64_t)ct.cam_rows * ct.n_cams || (wl.pixel_index && (!wl.dx || !wl.dy)) ||
+      gb.n != (wl.pixel_index ? wl.n_items : (uint64_t)wl.rows * wl.cols))
     return hipErrorInvalidValue;
 #endif
   switch (geometry) {
@@ -4066,6 +4067,34 @@ __global__ void __launch_bounds__(256) gbuffer_shade_sub_kernel(const DevScene* 
   gbuffer_shade_ray(S, sub, src, out, k);
 }
 
+// The supersample pass of an adaptive re-shade of a stack of buffers
+// (grt_gbuffer_shade_section_sequence): gbuffer_shade_sub_kernel with the set found per lane.
+// `sel` holds stacked indices P = frame * npix + pixel of held selected pixels (entries
+// base + j < *d_count); the frame's entry of the device table gives its set, the set's step
+// counts and its sub_block.  Sub-ray sub_block[pixel] * per + s of that set is shaded by
+// gbuffer_shade_ray into the chunk's slot j * per + s, the layout average_kernel reads.
+__global__ void __launch_bounds__(256) gbuffer_shade_sub_stack_kernel(const DevScene* __restrict__ Sp,
+                                                                      const GBufferSubFrame* __restrict__ frames,
+                                                                      uint32_t n_frames, uint64_t npix,
+                                                                      const uint32_t* __restrict__ sel, uint64_t n_sel,
+                                                                      const unsigned long long* __restrict__ d_count,
+                                                                      uint64_t base, uint32_t per, Outputs out) {
+  const DevScene& S = *Sp;
+  // a block past the held pixels (the empty chunks of a pass) has nothing to do
+  if (base + (uint64_t)blockIdx.x * blockDim.x / per >= *d_count) return;
+  glibc::tables_to_lds();  // whole block, before the per-lane early return
+  const uint64_t k = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  const uint64_t j = k / per;
+  if (j >= n_sel || base + j >= *d_count) return;
+  const uint64_t p = sel[j], f = p / npix;
+  if (f >= n_frames) return;  // an index past the stack: the split never lists one
+  const GBufferSubFrame fr = frames[f];
+  const uint64_t src = (uint64_t)fr.sub_block[p - f * npix] * per + k % per;
+  if (src >= fr.sub.n) return;  // a pixel the set does not hold: the split never lists one
+  if (out.steps) out.steps[k] = fr.steps[src];
+  gbuffer_shade_ray(S, fr.sub, src, out, k);
+}
+
 // The deferred shade of a stack of equally sized buffers (grt_gbuffer_shade_sequence): one
 // lane per (frame, pixel) of a launch group, the frame's arrays from a device table, the
 // pixel shaded as gbuffer_shade_kernel shades it into slot frame * per + pixel of the
@@ -4109,6 +4138,18 @@ hipError_t launch_gbuffer_shade_sub(const DevScene* d_scene, const GBufferArrays
   if (n == 0) return hipSuccess;
   hipLaunchKernelGGL(gbuffer_shade_sub_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, stream, d_scene, sub,
                      d_sub_steps, d_sub_block, d_sel, n_sel, d_count, base, spa * spa, out);
+  return hipGetLastError();
+}
+
+hipError_t launch_gbuffer_shade_sub_stack(const DevScene* d_scene, const GBufferSubFrame* d_frames, uint32_t n_frames,
+                                          uint64_t npix, const uint32_t* d_sel, uint64_t n_sel,
+                                          const unsigned long long* d_count, uint64_t base, uint32_t spa,
+                                          const Outputs& out, hipStream_t stream) {
+  const uint64_t n = n_sel * spa * spa;
+  if (n == 0) return hipSuccess;
+  if (npix == 0 || n_frames == 0 || n > 0xffffffffull * 256) return hipErrorInvalidValue;
+  hipLaunchKernelGGL(gbuffer_shade_sub_stack_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, stream, d_scene,
+                     d_frames, n_frames, npix, d_sel, n_sel, d_count, base, spa * spa, out);
   return hipGetLastError();
 }
 #endif  // GRT_MAIN_TU

@@ -154,10 +154,11 @@ namespace kerr_bl {
 hipError_t launch_gbuffer_fill(int geometry, const DevScene* d_scene, const WorkList& wl, const Workspace& ws,
                                const GBufferArrays& gb, hipStream_t stream);
 }
-// The same after a stacked 1-spp trace of whole frames (seq::launch_trace; `wl` the stack's
-// rectangle from (0, 0), no offset list), every chart: `gb` spans the stack in slot order,
-// frame after frame, and a ray's camera is its frame's entry of the table
-// (grt_gbuffer_trace_sequence; hipErrorInvalidValue for any other work list).
+// The same after a stacked trace (seq::launch_trace), every chart; `wl` is the stack from
+// (0, 0): its whole rectangle, `gb` spanning it in slot order, frame after frame
+// (grt_gbuffer_trace_sequence), or an offset list over it, `gb` spanning the list's
+// n_items slots (grt_gbuffer_supersample_sequence).  A ray's camera is its frame's entry
+// of the table, found from its stacked row; hipErrorInvalidValue for any other work list.
 namespace seq {
 hipError_t launch_gbuffer_fill(int geometry, const DevScene* d_scene, const WorkList& wl, const Workspace& ws,
                                const GBufferArrays& gb, hipStream_t stream, CamTable ct);
@@ -188,6 +189,18 @@ hipError_t launch_gbuffer_shade_sub(const DevScene* d_scene, const GBufferArrays
                                     const uint32_t* d_sub_block, const uint32_t* d_sel, uint64_t n_sel,
                                     const unsigned long long* d_count, uint64_t base, uint32_t spa, const Outputs& out,
                                     hipStream_t stream);
+// The same for the buffers of a stack (gbuffer_shade_sub_stack_kernel, geodesic.hip): d_sel
+// holds stacked indices P = frame * npix + pixel of held selected pixels, and entry P / npix
+// of the device table d_frames gives the frame's set, its step counts and its sub_block.
+struct GBufferSubFrame {
+  GBufferArrays sub;  // the set's rays, n = n_sub_rays (0: the buffer holds none)
+  const uint32_t* steps;
+  const uint32_t* sub_block;
+};
+hipError_t launch_gbuffer_shade_sub_stack(const DevScene* d_scene, const GBufferSubFrame* d_frames, uint32_t n_frames,
+                                          uint64_t npix, const uint32_t* d_sel, uint64_t n_sel,
+                                          const unsigned long long* d_count, uint64_t base, uint32_t spa,
+                                          const Outputs& out, hipStream_t stream);
 // The selected pixels d_sel (*d_count of them, ascending) split by sub_block into the ones
 // the set holds and the ones it misses, each in ascending order, with their counts
 // (gbuffer.hip; n_max <= INT_MAX entries of room).  d_flags: 2 * n_max bytes of scratch.
@@ -196,6 +209,16 @@ hipError_t gbuffer_split(const uint32_t* d_sel, const unsigned long long* d_coun
                          const uint32_t* d_sub_block, uint8_t* d_flags, uint32_t* d_held,
                          unsigned long long* d_n_held, uint32_t* d_missing, unsigned long long* d_n_missing,
                          void* d_temp, size_t* temp_bytes, hipStream_t stream);
+// gbuffer_split over the selections of n_frames buffers of npix pixels at once: frame f's
+// selection is d_sel[f * npix + j], j < d_cnt[4 f], looked up in its own buffer's sub_block
+// (d_frames[f]).  The lists hold stacked indices f * npix + pixel, ascending, so frame-major;
+// d_cnt[4 f + 2] and [4 f + 3] (zero on entry) take the frame's held and missing counts,
+// *d_n_held and *d_n_missing the totals.  d_flags: 2 * n_frames * npix bytes, d_stack:
+// n_frames * npix entries of scratch (n_frames * npix <= INT_MAX).
+hipError_t gbuffer_split_stack(const uint32_t* d_sel, unsigned long long* d_cnt, uint32_t n_frames, uint64_t npix,
+                               const GBufferSubFrame* d_frames, uint8_t* d_flags, uint32_t* d_stack, uint32_t* d_held,
+                               unsigned long long* d_n_held, uint32_t* d_missing, unsigned long long* d_n_missing,
+                               void* d_temp, size_t* temp_bytes, hipStream_t stream);
 // Appending a chunk to the set: d_layer_start[i] = d_local[i] + layer_base for i <= n_rays,
 // and sub_block[d_pixels[j]] = first_block + j, sub_pixel[first_block + j] = d_pixels[j].
 hipError_t gbuffer_sub_append(const uint64_t* d_local, uint64_t n_rays, uint64_t layer_base, uint64_t* d_layer_start,
@@ -242,6 +265,11 @@ hipError_t launch_select_shard(const double* d_ya, const uint8_t* d_cls, const A
 hipError_t launch_make_offsets(const uint32_t* d_sel, uint64_t n_sel, const unsigned long long* d_count, uint64_t base,
                                uint32_t spa, uint32_t row0, uint32_t col0, uint32_t w, uint32_t* d_pix, double* d_dx,
                                double* d_dy, hipStream_t stream);
+// The same for n_sel entries of a list over a stack of frames of `rows` x `w` pixels
+// (offsets_stack_kernel): entry P = frame * rows * w + pixel; the jitter hashes the frame's
+// own (row, col) = ((P / w) % rows, P % w), as the frame alone does, and d_pix takes P.
+hipError_t launch_make_offsets_stack(const uint32_t* d_sel, uint64_t n_sel, uint32_t spa, uint32_t rows, uint32_t w,
+                                     uint32_t* d_pix, double* d_dx, double* d_dy, hipStream_t stream);
 // Failed sub-samples of the supersample pass (device side; count NULL: not recorded).
 struct SubsampleFailures {
   unsigned long long* count;
@@ -258,6 +286,14 @@ struct SubsampleFailures {
 hipError_t launch_average(const uint32_t* d_sel_out, const uint32_t* d_sel_px, uint64_t n_sel,
                           const unsigned long long* d_count, uint64_t base, uint32_t spa, const double* d_samples,
                           const uint8_t* d_status, double* d_out, const SubsampleFailures& f, hipStream_t stream);
+// average_kernel's failure records for a chunk whose pixels belong to several frames
+// (failures_stack_kernel): d_sel holds stacked indices P = frame * npix + pixel, the chunk's
+// sub-ray j * spa^2 + s has status d_status[...], and a failed sub-sample (or, where the
+// frame's list has `stop`, an event) goes to list P / npix of the device table d_frames
+// with the key (P % npix) * spa^2 + s; each list's count counts them all.
+hipError_t launch_failures_stack(const uint32_t* d_sel, uint64_t n_sel, const unsigned long long* d_count, uint64_t base,
+                                 uint32_t spa, uint64_t npix, uint32_t n_frames, const uint8_t* d_status,
+                                 const SubsampleFailures* d_frames, hipStream_t stream);
 hipError_t launch_paint(const uint32_t* d_sel, uint64_t n_sel, const unsigned long long* d_count, const double* mask,
                         double* d_out, hipStream_t stream);
 // live[c] = sub-rays of chunk c (P selected pixels per chunk, `per` sub-rays each)

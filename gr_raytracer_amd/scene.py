@@ -241,12 +241,16 @@ class Scene:
             gb.shade_section(self, adaptive=adaptive, tracer=self)
         return gb
 
-    def trace_gbuffer_sequence(self, cameras, device: int = 0) -> "GBufferSequence":
+    def trace_gbuffer_sequence(self, cameras, device: int = 0,
+                               adaptive: Optional[L.AdaptiveConfig] = None) -> "GBufferSequence":
         """K cameras (CameraDesc, each with the scene's rows and cols) over this scene, traced
         stacked at 1 spp with the exact kernels, one geometry buffer per frame
         (grt_gbuffer_trace_sequence).  Buffer k is the ordinary GBuffer of a scene with camera
         k, byte for byte.  Returns a list of GBuffer with the call's `stats` and `report`
-        (GBufferSequenceReport) as attributes."""
+        (GBufferSequenceReport) as attributes.  With `adaptive`, one `shade_section_sequence`
+        with the scene as appearance and as tracer follows, so each buffer also holds the
+        sub-rays of the pixels this scene's adaptive frame of its camera selects (its report
+        dict: the attribute `adaptive_report`)."""
         cams = list(cameras)
         k = len(cams)
         table = (L.CameraDesc * max(k, 1))(*cams)
@@ -258,6 +262,8 @@ class Scene:
         stats = _stats_dict(st)
         out = GBufferSequence(GBuffer(C.c_void_p(handles[f]), stats) for f in range(k))
         out.stats, out.report = stats, rep
+        if adaptive is not None:
+            out.adaptive_report = shade_section_sequence(out, self, adaptive=adaptive, tracer=self)[1]
         return out
 
     def render_shard(self, band_rows: int, shard: int, n_shards: int, device: int = 0,
@@ -786,6 +792,7 @@ class GBufferSequence(list):
     the call's `stats` (dict) and `report` (GBufferSequenceReport)."""
     stats: dict = {}
     report = None
+    adaptive_report = None
 
 
 def shade_sequence(buffers, scene: "Scene", fields=("xyza", "xyza64", "class", "status", "stop", "steps")) -> dict:
@@ -816,6 +823,97 @@ def shade_sequence(buffers, scene: "Scene", fields=("xyza", "xyza64", "class", "
             "grt_gbuffer_shade_sequence")
     arrays["stats"] = {"kernel_ms": float(ms.value)}
     return arrays
+
+
+def supersample_sequence(buffers, tracer: "Scene", pixels_per_buffer, samples_per_axis: int) -> dict:
+    """GBuffer.supersample for several whole-frame buffers at once, the traces stacked
+    (grt_gbuffer_supersample_sequence): the sub-rays of `pixels_per_buffer[k]` are appended to
+    `buffers[k]`'s set, byte for byte what `buffers[k].supersample` leaves with a tracer that
+    has frame k's camera.  `tracer` needs the buffers' shape key, integration parameters and
+    frame size; its camera is not used (each ray takes the camera its buffer recorded).
+    Returns the traces' stats with the call's `report` (GBufferSequenceReport: n_launches
+    chunks, n_traces traces) under "report"."""
+    bufs = list(buffers)
+    k = len(bufs)
+    lists = [np.ascontiguousarray(p, np.uint32).reshape(-1) for p in pixels_per_buffer]
+    if len(lists) != k:
+        raise L.GrtError(f"grt_gbuffer_supersample_sequence failed (-22): {len(lists)} pixel lists for {k} buffers")
+    handles = (C.c_void_p * max(k, 1))(*[b._h for b in bufs])
+    counts = (C.c_uint64 * max(k, 1))(*[len(p) for p in lists])
+    ptrs = (C.POINTER(C.c_uint32) * max(k, 1))(*[L.ptr(p, C.c_uint32) for p in lists])
+    st = L.Stats()
+    rep = L.GBufferSequenceReport()
+    L.check(L.lib().grt_gbuffer_supersample_sequence(tracer._s, k, handles, samples_per_axis, counts, ptrs,
+                                                     C.byref(st), C.byref(rep)), "grt_gbuffer_supersample_sequence")
+    stats = _stats_dict(st)
+    stats["report"] = rep
+    return stats
+
+
+def shade_section_sequence(buffers, scene: "Scene", adaptive: Optional[L.AdaptiveConfig] = None, mask=None,
+                           tracer: Optional["Scene"] = None, failure_capacity: int = 0, log_events: bool = False):
+    """The adaptive frames of several whole-frame buffers under `scene`'s appearance in stacked
+    launches (grt_gbuffer_shade_section_sequence): frame k is `buffers[k].shade_section(scene,
+    ...)` with a tracer that has frame k's camera, bit for bit.  `mask` (XYZA) paints the
+    selected pixels instead.  Selected pixels the sets do not hold are traced in one stacked
+    top-up under `tracer` (its camera is not used; it may be `scene`); without a tracer they
+    raise GBufferMissing, whose report carries the per-frame counts.  Returns (dict, report):
+    the dict holds "xyza64", "class", "status", "stop" and "steps" with a leading frame axis,
+    "n_supersampled" [K], and per frame the failure lists "failed_subsamples" (rows pixel,
+    stratum, status), "n_failed_subsamples" and, with log_events, "subsample_events" (rows
+    pixel, stratum, stop, steps); the report dict has the totals, the times, "top_up" and
+    "per_frame" ([K, 4]: selected, held, traced, missing)."""
+    bufs = list(buffers)
+    k = len(bufs)
+    n = int(bufs[0].info.n_pixels) if k else 0
+    arrays = {"xyza64": np.zeros((k, n, 4), np.float64), "class": np.zeros((k, n), np.uint8),
+              "status": np.zeros((k, n), np.uint8), "stop": np.zeros((k, n), np.uint8),
+              "steps": np.zeros((k, n), np.uint32)}
+    out = L.FrameOut(None, L.dptr(arrays["xyza64"]), L.ptr(arrays["class"], C.c_uint8), L.ptr(arrays["status"], C.c_uint8),
+                     L.ptr(arrays["stop"], C.c_uint8), L.ptr(arrays["steps"], C.c_uint32))
+    handles = (C.c_void_p * max(k, 1))(*[b._h for b in bufs])
+    nsel = np.zeros(max(k, 1), np.uint64)
+    per_frame = np.zeros((max(k, 1), 4), np.uint64)
+    cap = max(failure_capacity, 1)
+    held = [[np.zeros(cap, np.uint32), np.zeros(cap, np.uint32), np.zeros(cap, np.uint8), np.zeros(cap, np.uint8),
+             np.zeros(cap, np.uint32)] for _ in range(max(k, 1))]
+    fails = (L.SubsampleFailures * max(k, 1))(*[
+        L.SubsampleFailures(failure_capacity, L.ptr(h[0], C.c_uint32), L.ptr(h[1], C.c_uint32), L.ptr(h[2], C.c_uint8), 0,
+                            L.ptr(h[3], C.c_uint8) if log_events else None,
+                            L.ptr(h[4], C.c_uint32) if log_events else None) for h in held])
+    m = None if mask is None else np.ascontiguousarray(mask, np.float64)
+    rep = L.GBufferSectionSequenceReport()
+    cfg = adaptive or scene.adaptive
+    rc = L.lib().grt_gbuffer_shade_section_sequence(scene._s, k, handles, C.byref(cfg),
+                                                    L.dptr(m) if m is not None else None,
+                                                    tracer._s if tracer is not None else None, C.byref(out),
+                                                    L.ptr(nsel, C.c_uint64), fails, L.ptr(per_frame, C.c_uint64),
+                                                    C.byref(rep))
+    report = {"n_frames": int(rep.n_frames), "n_launches": int(rep.n_launches), "n_selected": int(rep.n_selected),
+              "n_held": int(rep.n_held), "n_traced": int(rep.n_traced), "n_missing": int(rep.n_missing),
+              "wall_ms": float(rep.wall_ms), "shade_ms": float(rep.shade_ms), "trace_ms": float(rep.trace_ms),
+              "top_up": _stats_dict(rep.top_up), "per_frame": per_frame[:k].astype(np.int64)}
+    if rc == -errno.ENODATA:
+        msg = L.lib().grt_last_error().decode(errors="replace")
+        raise GBufferMissing(f"grt_gbuffer_shade_section_sequence failed ({rc}): {msg}", report)
+    L.check(rc, "grt_gbuffer_shade_section_sequence")
+    arrays["n_supersampled"] = nsel[:k].astype(np.int64)
+    arrays["failed_subsamples"], arrays["n_failed_subsamples"], arrays["subsample_events"] = [], [], []
+    for f in range(k):
+        fp, fs, fst, fsp, fn = held[f]
+        got = min(int(fails[f].count), failure_capacity)
+        rows = np.stack([fp[:got], fs[:got], fst[:got].astype(np.uint32)], axis=1)
+        if not log_events:
+            arrays["failed_subsamples"].append(rows)
+            arrays["n_failed_subsamples"].append(int(fails[f].count))
+            arrays["subsample_events"].append(None)
+            continue
+        failed = fst[:got] != 0
+        events = np.stack([fp[:got], fs[:got], fsp[:got].astype(np.uint32), fn[:got]], axis=1)[~failed]
+        arrays["failed_subsamples"].append(rows[failed])
+        arrays["n_failed_subsamples"].append(int(fails[f].count) - len(events))
+        arrays["subsample_events"].append(events)
+    return arrays, report
 
 
 def gbuffer_compatible(traced: L.SceneDesc, appearance: L.SceneDesc) -> None:

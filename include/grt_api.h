@@ -726,7 +726,8 @@ int grt_gbuffer_read_file(const char* path, grt_gbuffer_info* info, const grt_gb
  * The set is append-only; it never holds a GRT_FLAG_HIT_OVERFLOW ray.  Still outside the
  * buffer: row shards, the multi-GPU frame, VolumetricDisc scenes, the fused arithmetic.  A
  * camera sequence's buffers (grt_gbuffer_trace_sequence) start without a set; each takes one
- * as any buffer does, per frame, with a tracer that has the frame's camera. */
+ * as any buffer does, per frame, with a tracer that has the frame's camera, or all of them
+ * in stacked traces (grt_gbuffer_supersample_sequence). */
 typedef struct grt_gbuffer_sub_info {
   uint32_t samples_per_axis; /* 0: the buffer holds no set */
   uint32_t _pad;
@@ -836,6 +837,69 @@ int grt_gbuffer_trace_sequence(grt_scene* scene, int device, uint32_t n_cameras,
  * and the field).  kernel_ms (nullable): summed event time of the shade launches. */
 int grt_gbuffer_shade_sequence(grt_scene* appearance, uint32_t n, grt_gbuffer* const* buffers,
                                const grt_frame_out* out, float* kernel_ms);
+/* grt_gbuffer_supersample for n buffers at once, the traces stacked: the sub-rays of
+ * pixels[k] (n_pixels[k] indices into buffers[k], any order, duplicates allowed) are traced
+ * and appended to buffers[k]'s own set.  Per buffer the rules are grt_gbuffer_supersample's
+ * (held pixels skipped, the rest ascending and unique); the n lists are concatenated
+ * frame-major and cut into chunks of grt_set_sub_chunk sub-rays, so a chunk may span frames.
+ * A chunk is one offset-list trace of the sequence unit over the stack of n * rows rows, each
+ * ray with the camera its buffer recorded (info.camera) and the jitter of its frame's own
+ * (row, col); one layer scan and one fill, then the cut into the sets.  A chunk that loses
+ * hit candidates grows the pool and is traced again (at most 3 traces, else -ENOMEM).  Every
+ * set is byte for byte (grt_gbuffer_sub_info, sub_pixel, the twelve arrays) what
+ * grt_gbuffer_supersample leaves with a tracer created with that frame's camera.
+ * `tracer`: its shape key and max_steps, max_radius, step_size, epsilon and horizon_epsilon
+ * must equal every buffer's record byte for byte, its camera's rows and cols the buffers';
+ * its camera is otherwise not used.  -EINVAL, grt_last_error naming the frame index (and the
+ * field where grt_gbuffer_supersample names one): n = 0, a buffer listed twice, buffers on
+ * different devices or of different rows x cols, a buffer that is not a whole frame
+ * (rectangle (0, 0, camera.rows, camera.cols)), samples_per_axis 0, above 64 or different
+ * from an existing set's, a pixel outside its buffer, more than INT_MAX - 1 stacked sub-rays.
+ * After a failure every set is still a valid set: whole pixels only, grown by the chunks that
+ * were complete.  stats (nullable): the counters of all traces.  report (nullable):
+ * n_launches counts the chunks, n_traces the traces with the re-traces, frames_per_launch
+ * is 0 (a chunk is cut over sub-rays, not frames). */
+int grt_gbuffer_supersample_sequence(grt_scene* tracer, uint32_t n, grt_gbuffer* const* buffers,
+                                     uint32_t samples_per_axis, const uint64_t* n_pixels /* [n] */,
+                                     const uint32_t* const* pixels /* [n] */, grt_stats* stats,
+                                     grt_gbuffer_sequence_report* report);
+
+typedef struct grt_gbuffer_section_sequence_report {
+  uint32_t n_frames, n_launches;                    /* n_launches: launch groups of the shade */
+  uint64_t n_selected, n_held, n_traced, n_missing; /* grt_gbuffer_section_report's, summed over the frames */
+  double wall_ms, shade_ms, trace_ms;               /* host clock; summed event times, as grt_gbuffer_section_report */
+  grt_stats top_up;                                 /* the stacked top-up's counters */
+} grt_gbuffer_section_sequence_report;
+
+/* grt_gbuffer_shade_section for n whole-frame buffers of one size on one device, stacked:
+ * frame k of the outputs is what grt_gbuffer_shade_section(appearance, buffers[k], cfg, mask,
+ * tracer_k, ...) writes, bit for bit (xyza64, ray_class, status, n_supersampled[k],
+ * failures[k]), tracer_k being a scene with the frame's camera; hence grt_render_section_ex
+ * of the appearance with camera k.  out: host arrays, frame-major [n][rows][cols]; xyza64 is
+ * required, ray_class and status are written where non-null, stop and steps are copies of
+ * the recorded ones (as grt_gbuffer_shade_sequence), xyza is not written.
+ * Per launch group (whole buffers, grt_set_sequence_group rays), on one stream without a
+ * host round trip: one stacked 1-spp shade; per frame, on its slice, the luminance floor,
+ * the selection and its compaction (neither sees another frame); with the mask the paint;
+ * else one split of all the selections into held and missing, each pixel looked up in its
+ * own buffer's set, then per chunk of grt_set_sub_chunk sub-rays one stacked sub-ray shade
+ * and the average; one copy of the counters and one set of device-to-host copies.
+ * Selected pixels that the sets do not hold: without `tracer`, -ENODATA, per_frame and
+ * report->n_missing filled, the frame outputs untouched and no set changed; with `tracer`
+ * (may be `appearance`; grt_gbuffer_supersample_sequence's rules) all frames' missing pixels
+ * are traced in one stacked top-up and the groups that missed some are shaded again.
+ * -EINVAL: grt_gbuffer_supersample_sequence's refusals (the samples_per_axis and tracer ones
+ * only where sub-rays are shaded), no out->xyza64, a shape key that differs from the
+ * appearance's (frame index and field named).  With cfg->enabled == 0 and no mask the frames
+ * are the 1-spp ones.  failures[k].count is exact; the list holds the frame's first
+ * `capacity` records in (pixel, stratum) order of those the device kept.  per_frame
+ * (nullable) [n][4]: selected, held when the call began, traced by it, still missing.
+ * n_supersampled, failures, per_frame and report are nullable. */
+int grt_gbuffer_shade_section_sequence(grt_scene* appearance, uint32_t n, grt_gbuffer* const* buffers,
+                                       const grt_adaptive_config* cfg, const double* sampling_mask_xyza,
+                                       grt_scene* tracer /* nullable */, const grt_frame_out* out,
+                                       uint64_t* n_supersampled /* [n] */, grt_subsample_failures* failures /* [n] */,
+                                       uint64_t* per_frame /* [n][4] */, grt_gbuffer_section_sequence_report* report);
 
 /* The device hit pool that keeps the window candidates past a ray's GRT_MAX_HITS slots
  * (no reference counterpart: the reference's per-ray Vec grows, scene.rs:139-152).
