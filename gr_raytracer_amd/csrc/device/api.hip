@@ -484,6 +484,30 @@ grt::WorkList rect_worklist(uint32_t row0, uint32_t col0, uint32_t rows, uint32_
   return wl;
 }
 
+grt::WorkList offsets_worklist(uint32_t row0, uint32_t col0, uint32_t rows, uint32_t cols, uint64_t n_items,
+                               const uint32_t* pix, const double* dx, const double* dy) {
+  grt::WorkList wl;
+  std::memset(&wl, 0, sizeof(wl));
+  wl.row0 = row0;
+  wl.col0 = col0;
+  wl.rows = rows;
+  wl.cols = cols;
+  wl.n_items = n_items;
+  wl.pixel_index = pix;
+  wl.dx = dx;
+  wl.dy = dy;
+  return wl;
+}
+
+int upload_cam_table(const grt_camera_desc* cameras, uint32_t n, uint32_t rows, DevBuf& buf, grt::CamTable* ct) {
+  std::vector<grt::DevCamera> cams(n);
+  for (uint32_t f = 0; f < n; ++f) fill_dev_camera(cameras[f], cams[f]);
+  if (int rc = buf.alloc(n * sizeof(grt::DevCamera))) return rc;
+  HIP_TRY(hipMemcpy(buf.p, cams.data(), n * sizeof(grt::DevCamera), hipMemcpyHostToDevice));
+  *ct = grt::CamTable{(const grt::DevCamera*)buf.p, rows, n};
+  return 0;
+}
+
 // Step cap of the probe rays (scheduling only).  The pass lasts as long as its capped
 // probes (horizon creepers) take to run the cap.  An escaping ray needs about max_radius
 // accepted steps at H_MAX = 1 (C4: 15825-15900 for max_radius 15000), so the cap is
@@ -1303,29 +1327,21 @@ int trace_to_host(grt_scene* s, DeviceCopy& dc, const grt::WorkList& wl, uint64_
     const uint64_t m = lost.size();
     std::vector<uint32_t> pix(m);
     std::vector<double> dx(m, 0.5), dy(m, 0.5);
-    grt::WorkList wo;
-    std::memset(&wo, 0, sizeof(wo));
-    wo.col0 = wl.col0;
-    wo.cols = wl.cols;
-    wo.n_items = m;
+    uint32_t row0 = wl.row0, rows = wl.rows;
     if (offs) {  // an offsets trace: the same (pixel, dx, dy) items
-      wo.row0 = wl.row0;
-      wo.rows = wl.rows;
       for (uint64_t j = 0; j < m; ++j) {
         pix[j] = offs->pixel_index[lost[j]];
         dx[j] = offs->dx[lost[j]];
         dy[j] = offs->dy[lost[j]];
       }
     } else if (wl.n_shards > 1) {  // a row-band shard: frame rows of the local ones
-      wo.row0 = 0;
-      wo.rows = (uint32_t)s->desc.camera.rows;
+      row0 = 0;
+      rows = (uint32_t)s->desc.camera.rows;
       for (uint64_t j = 0; j < m; ++j) {
         const uint32_t lr = (uint32_t)(lost[j] / wl.cols), c = (uint32_t)(lost[j] % wl.cols);
         pix[j] = grt::shard_frame_row(wl.band_rows, wl.shard, wl.n_shards, lr) * wl.cols + c;
       }
     } else {
-      wo.row0 = wl.row0;
-      wo.rows = wl.rows;
       for (uint64_t j = 0; j < m; ++j) pix[j] = (uint32_t)lost[j];
     }
     DevBuf b_pix, b_dx, b_dy;
@@ -1333,9 +1349,8 @@ int trace_to_host(grt_scene* s, DeviceCopy& dc, const grt::WorkList& wl, uint64_
     HIP_TRY(hipMemcpy(b_pix.p, pix.data(), m * 4, hipMemcpyHostToDevice));
     HIP_TRY(hipMemcpy(b_dx.p, dx.data(), m * 8, hipMemcpyHostToDevice));
     HIP_TRY(hipMemcpy(b_dy.p, dy.data(), m * 8, hipMemcpyHostToDevice));
-    wo.pixel_index = (const uint32_t*)b_pix.p;
-    wo.dx = (const double*)b_dx.p;
-    wo.dy = (const double*)b_dy.p;
+    const grt::WorkList wo = offsets_worklist(row0, wl.col0, rows, wl.cols, m, (const uint32_t*)b_pix.p,
+                                              (const double*)b_dx.p, (const double*)b_dy.p);
     HostTrace T;
     acc[3] = 0;  // the overflows of the last round are the ones left
     if ((rc = T.alloc(m, aux)) || (rc = trace_sync(s, dc, wo, T.o, acc, &ms, &need, ct))) return rc;
@@ -1418,19 +1433,12 @@ int grt_render_pixels(grt_scene* s, int device, uint32_t row0, uint32_t col0, ui
     if (cols == 0) return fail(-EINVAL, "offsets need the rectangle width");
     for (uint64_t k = 0; k < n; ++k)
       if (offsets->pixel_index[k] >= (uint64_t)rows * cols) return fail(-EINVAL, "offset pixel outside rectangle");
-    std::memset(&wl, 0, sizeof(wl));
-    wl.row0 = row0;
-    wl.col0 = col0;
-    wl.rows = rows;
-    wl.cols = cols;
-    wl.n_items = n;
     if ((rc = b_pix.alloc(n * 4)) || (rc = b_dx.alloc(n * 8)) || (rc = b_dy.alloc(n * 8))) return rc;
     HIP_TRY(hipMemcpy(b_pix.p, offsets->pixel_index, n * 4, hipMemcpyHostToDevice));
     HIP_TRY(hipMemcpy(b_dx.p, offsets->dx, n * 8, hipMemcpyHostToDevice));
     HIP_TRY(hipMemcpy(b_dy.p, offsets->dy, n * 8, hipMemcpyHostToDevice));
-    wl.pixel_index = (const uint32_t*)b_pix.p;
-    wl.dx = (const double*)b_dx.p;
-    wl.dy = (const double*)b_dy.p;
+    wl = offsets_worklist(row0, col0, rows, cols, n, (const uint32_t*)b_pix.p, (const double*)b_dx.p,
+                          (const double*)b_dy.p);
   } else {
     wl = rect_worklist(row0, col0, rows, cols);
   }

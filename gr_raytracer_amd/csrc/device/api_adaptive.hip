@@ -47,6 +47,14 @@ std::atomic<uint64_t> g_sub_chunk{SUB_CHUNK};  // grt_set_sub_chunk (tests force
 constexpr uint64_t SEQ_GROUP = 1ull << 22;     // rays per launch group of a camera sequence
 std::atomic<uint64_t> g_seq_group{SEQ_GROUP};  // grt_set_sequence_group
 
+uint64_t frames_per_group(uint64_t per, uint64_t n, uint64_t max_slots, uint64_t rows) {
+  uint64_t g = std::max<uint64_t>(1, g_seq_group.load(std::memory_order_relaxed) / per);
+  g = std::min<uint64_t>(g, n);
+  if (max_slots) g = std::min<uint64_t>(g, std::max<uint64_t>(1, max_slots / per));
+  if (rows) g = std::min<uint64_t>(g, std::max<uint64_t>(1, 0xffffffffull / rows));
+  return g;
+}
+
 // supersample (raytracer.rs:320-384) over a selection that lives on the device: entries
 // j < *d_count <= n_max of sel_px (pixel index in the rect row0/col0/rows/cols: camera
 // ray and jitter hash) and sel_out (index into d_out64).  The sub-rays go through the
@@ -64,18 +72,9 @@ int enqueue_supersample(grt_scene* s, DeviceCopy& dc, hipStream_t st, const Supe
     const uint64_t base = (uint64_t)c * B.chunk_pix;
     HIP_TRY(grt::launch_make_offsets(sel_px + base, B.chunk_pix, d_count, base, spa, row0, col0, cols, B.pix, B.dx,
                                      B.dy, st));
-    grt::WorkList wo;
-    std::memset(&wo, 0, sizeof(wo));
     // a camera sequence: the rect is a frame of the stack, stack_row0 its first stacked row
     // (the jitter above hashes the frame's own pixel coordinates, as a frame alone does)
-    wo.row0 = row0 + stack_row0;
-    wo.col0 = col0;
-    wo.rows = rows;
-    wo.cols = cols;
-    wo.n_items = B.cap;
-    wo.pixel_index = B.pix;
-    wo.dx = B.dx;
-    wo.dy = B.dy;
+    grt::WorkList wo = offsets_worklist(row0 + stack_row0, col0, rows, cols, B.cap, B.pix, B.dx, B.dy);
     wo.n_live = B.live + c;
     grt::Outputs so{B.xyza, B.cls, B.status, B.x64, B.steps, B.stop};
     int rc = enqueue_trace(s, dc, wo, so, d_stats, st, ct);
@@ -364,10 +363,7 @@ int grt_render_sequence(grt_scene* s, int device, uint32_t n_cameras, const grt_
   if (per > (uint64_t)INT_MAX) return fail(-EOVERFLOW, "frame larger than INT_MAX pixels");
   // frames per launch group: whole frames within the group's rays, at least one; the
   // stack's slots and rows are 32-bit indices
-  uint64_t g = std::max<uint64_t>(1, g_seq_group.load(std::memory_order_relaxed) / per);
-  g = std::min<uint64_t>(g, n_cameras);
-  g = std::min<uint64_t>(g, std::max<uint64_t>(1, (uint64_t)INT_MAX / per));
-  g = std::min<uint64_t>(g, std::max<uint64_t>(1, 0xffffffffull / rows));
+  const uint64_t g = frames_per_group(per, n_cameras, INT_MAX, rows);
   DeviceCopy* dc;
   int rc = ensure_device(s, device, &dc);
   if (rc) return rc;
@@ -379,11 +375,9 @@ int grt_render_sequence(grt_scene* s, int device, uint32_t n_cameras, const grt_
     if (failures) failures[f].count = 0;
   }
   // the camera table, in device form
-  std::vector<grt::DevCamera> cams(n_cameras);
-  for (uint32_t f = 0; f < n_cameras; ++f) fill_dev_camera(cameras[f], cams[f]);
   DevBuf b_cams;
-  if ((rc = b_cams.alloc(n_cameras * sizeof(grt::DevCamera)))) return rc;
-  HIP_TRY(hipMemcpy(b_cams.p, cams.data(), n_cameras * sizeof(grt::DevCamera), hipMemcpyHostToDevice));
+  grt::CamTable all;
+  if ((rc = upload_cam_table(cameras, n_cameras, rows, b_cams, &all))) return rc;
   SeqTimes T;
   uint32_t launches = 0;
   // 1 spp: run_to_host needs the f32 colour, class and status on the host even when the
@@ -393,7 +387,7 @@ int grt_render_sequence(grt_scene* s, int device, uint32_t n_cameras, const grt_
   for (uint32_t f0 = 0; f0 < n_cameras; f0 += (uint32_t)g, ++launches) {
     const uint32_t kg = (uint32_t)std::min<uint64_t>(g, n_cameras - f0);
     const uint64_t n = per * kg, at = per * f0;
-    const grt::CamTable ct{(const grt::DevCamera*)b_cams.p + f0, rows, kg};
+    const grt::CamTable ct{all.cams + f0, rows, kg};
     if (supersampled) {
       grt_frame_out go{nullptr, out->xyza64 + 4 * at, out->ray_class ? out->ray_class + at : nullptr,
                        out->status ? out->status + at : nullptr, out->stop ? out->stop + at : nullptr,

@@ -40,10 +40,77 @@ static int grow_buf(DevBuf& b, size_t keep, size_t want) {
       return fail(-EIO, std::string("HIP error: ") + hipGetErrorString(e));
     }
   }
-  if (b.p) (void)hipFree(b.p);
+  b.reset();
   b.p = p;
   return 0;
 }
+
+using namespace grt_host;  // the field table: GRT_GBUFFER_FIELDS, GBUFFER_FIELDS, GB_*
+
+// The twelve device arrays of a buffer, of a sub-sample set or of a transient stack, by the
+// table.  Counts and capacities are the owner's: every size is an argument.
+struct GBufferDev {
+  DevBuf a[GB_N_FIELDS];
+  uint8_t* status() const { return (uint8_t*)a[GB_status].p; }
+  uint8_t* stop() const { return (uint8_t*)a[GB_stop].p; }
+  uint32_t* steps() const { return (uint32_t*)a[GB_steps].p; }
+  uint64_t* layer_start() const { return (uint64_t*)a[GB_layer_start].p; }
+  // fresh per-ray (`layer`: per-layer) arrays of `count` elements; what they held is freed
+  int alloc(bool layer, uint64_t count) {
+    for (int k = 0; k < GB_N_FIELDS; ++k) {
+      const GBufferField& f = GBUFFER_FIELDS[k];
+      if (f.layer != layer) continue;
+      a[k].reset();
+      if (int rc = a[k].alloc(f.size * (count + f.extra))) return rc;
+    }
+    return 0;
+  }
+  // those arrays grown to `count` elements, the first `keep` kept; a new layer_start begins at 0
+  int grow(bool layer, uint64_t keep, uint64_t count) {
+    for (int k = 0; k < GB_N_FIELDS; ++k) {
+      const GBufferField& f = GBUFFER_FIELDS[k];
+      if (f.layer != layer) continue;
+      const bool first = a[k].p == nullptr;
+      if (int rc = grow_buf(a[k], f.size * (keep + f.extra), f.size * (count + f.extra))) return rc;
+      if (first && f.extra) HIP_TRY(hipMemset(a[k].p, 0, f.size * f.extra));
+    }
+    return 0;
+  }
+  // the n rays from `first_ray` on, over all the layers (layer offsets stay the owner's)
+  grt::GBufferArrays view(uint64_t first_ray, uint64_t n) const {
+    auto f64 = [&](int k, uint64_t at) { return (double*)a[k].p + at; };
+    const uint64_t r = first_ray;
+    return grt::GBufferArrays{n, status() + r, stop() + r, layer_start() + r, f64(GB_sky_u, r), f64(GB_sky_v, r),
+                              f64(GB_sky_redshift, r), (uint8_t*)a[GB_object].p, f64(GB_u, 0), f64(GB_v, 0),
+                              f64(GB_redshift, 0), f64(GB_radius, 0)};
+  }
+  // n rays and l layers to the host's arrays (hipMemcpyDeviceToHost) or from them
+  int copy(const grt_gbuffer_arrays& h, uint64_t n, uint64_t l, hipMemcpyKind kind) const {
+    const GBufferPtrs H(h);
+    for (int k = 0; k < GB_N_FIELDS; ++k) {
+      const uint64_t bytes = GBUFFER_FIELDS[k].bytes(n, l);
+      if (!bytes) continue;
+      const bool down = kind == hipMemcpyDeviceToHost;
+      HIP_TRY(hipMemcpy(down ? H.p[k] : a[k].p, down ? a[k].p : H.p[k], bytes, kind));
+    }
+    return 0;
+  }
+  // n_rays rays and n_layers layers from (src_ray, src_layer) to (dst_ray, dst_layer) of `dst`
+  // on `st`, empty copies skipped; not layer_start, which gbuffer_rebase / gbuffer_sub_append
+  // write rebased
+  int copy_slice(GBufferDev& dst, uint64_t dst_ray, uint64_t dst_layer, uint64_t src_ray, uint64_t src_layer,
+                 uint64_t n_rays, uint64_t n_layers, hipStream_t st) const {
+    for (int k = 0; k < GB_N_FIELDS; ++k) {
+      const GBufferField& f = GBUFFER_FIELDS[k];
+      const uint64_t to = f.layer ? dst_layer : dst_ray, from = f.layer ? src_layer : src_ray;
+      const uint64_t bytes = f.size * (f.layer ? n_layers : n_rays);
+      if (k == GB_layer_start || !bytes) continue;
+      HIP_TRY(hipMemcpyAsync((char*)dst.a[k].p + to * f.size, (const char*)a[k].p + from * f.size, bytes,
+                             hipMemcpyDeviceToDevice, st));
+    }
+    return 0;
+  }
+};
 
 // The sub-sample set of a buffer (grt_api.h): append-only, capacities grow geometrically.
 // Block b holds the per sub-rays of pixel sub_pixel[b] at rays [b * per, (b + 1) * per).
@@ -53,7 +120,7 @@ struct GBufferSub {
   DevBuf sub_pixel;  // u32[cap_pix]
   DevBuf sub_block;  // u32[n_pixels], GBUFFER_NIL where a pixel has no block (derived, never stored)
   std::vector<uint32_t> h_block;  // host copy of sub_block
-  DevBuf status, stop, steps, sky_u, sky_v, sky_z, layer_start, object, u, v, z, radius;
+  GBufferDev arr;
   uint64_t per() const { return (uint64_t)spa * spa; }
   uint64_t n_rays() const { return n_pix * per(); }
   // the pixel -> block map, all NIL, before any block exists
@@ -66,74 +133,29 @@ struct GBufferSub {
   }
   int reserve_pixels(uint64_t want) {
     if (want <= cap_pix) return 0;
-    const uint64_t cap = std::max<uint64_t>({want, 2 * cap_pix, 1024}), p = per(), r0 = n_rays(), r1 = cap * p;
+    const uint64_t cap = std::max<uint64_t>({want, 2 * cap_pix, 1024});
     int rc;
-    if ((rc = grow_buf(sub_pixel, 4 * n_pix, 4 * cap)) || (rc = grow_buf(status, r0, r1)) ||
-        (rc = grow_buf(stop, r0, r1)) || (rc = grow_buf(steps, 4 * r0, 4 * r1)) ||
-        (rc = grow_buf(sky_u, 8 * r0, 8 * r1)) || (rc = grow_buf(sky_v, 8 * r0, 8 * r1)) ||
-        (rc = grow_buf(sky_z, 8 * r0, 8 * r1)))
-      return rc;
-    const bool first = layer_start.p == nullptr;
-    if ((rc = grow_buf(layer_start, first ? 0 : 8 * (r0 + 1), 8 * (r1 + 1)))) return rc;
-    if (first) HIP_TRY(hipMemset(layer_start.p, 0, 8));
+    if ((rc = grow_buf(sub_pixel, 4 * n_pix, 4 * cap)) || (rc = arr.grow(false, n_rays(), cap * per()))) return rc;
     cap_pix = cap;
     return 0;
   }
   int reserve_layers(uint64_t want) {
-    if (want <= cap_layers && object.p) return 0;
-    const uint64_t cap = std::max<uint64_t>({want, 2 * cap_layers, 4096}), l = n_layers;
-    int rc;
-    if ((rc = grow_buf(object, l, cap)) || (rc = grow_buf(u, 8 * l, 8 * cap)) || (rc = grow_buf(v, 8 * l, 8 * cap)) ||
-        (rc = grow_buf(z, 8 * l, 8 * cap)) || (rc = grow_buf(radius, 8 * l, 8 * cap)))
-      return rc;
+    if (want <= cap_layers && arr.a[GB_object].p) return 0;
+    const uint64_t cap = std::max<uint64_t>({want, 2 * cap_layers, 4096});
+    if (int rc = arr.grow(true, n_layers, cap)) return rc;
     cap_layers = cap;
     return 0;
   }
-  // the rays from `first_ray` on (layer offsets stay the set's own)
-  grt::GBufferArrays view(uint64_t first_ray, uint64_t n) const {
-    return grt::GBufferArrays{n,
-                              (const uint8_t*)status.p + first_ray,
-                              (const uint8_t*)stop.p + first_ray,
-                              (const uint64_t*)layer_start.p + first_ray,
-                              (double*)sky_u.p + first_ray,
-                              (double*)sky_v.p + first_ray,
-                              (double*)sky_z.p + first_ray,
-                              (uint8_t*)object.p,
-                              (double*)u.p,
-                              (double*)v.p,
-                              (double*)z.p,
-                              (double*)radius.p};
-  }
+  grt::GBufferArrays view() const { return arr.view(0, n_rays()); }
 };
 
 struct grt_gbuffer {
   grt_gbuffer_info info;
   double times[2] = {0.0, 0.0};  // trace, scan + fill (ms)
-  DevBuf status, stop, steps, sky_u, sky_v, sky_z, layer_start, object, u, v, z, radius;
+  GBufferDev arr;
   GBufferSub sub;
   grt_gbuffer() { std::memset(&info, 0, sizeof(info)); }
-  int alloc_pixels() {
-    const uint64_t n = info.n_pixels;
-    int rc;
-    if ((rc = status.alloc(n)) || (rc = stop.alloc(n)) || (rc = steps.alloc(4 * n)) || (rc = sky_u.alloc(8 * n)) ||
-        (rc = sky_v.alloc(8 * n)) || (rc = sky_z.alloc(8 * n)) || (rc = layer_start.alloc(8 * (n + 1))))
-      return rc;
-    return 0;
-  }
-  int alloc_layers() {
-    const uint64_t l = info.n_layers;
-    int rc;
-    if ((rc = object.alloc(l)) || (rc = u.alloc(8 * l)) || (rc = v.alloc(8 * l)) || (rc = z.alloc(8 * l)) ||
-        (rc = radius.alloc(8 * l)))
-      return rc;
-    return 0;
-  }
-  grt::GBufferArrays view() const {
-    return grt::GBufferArrays{info.n_pixels,      (const uint8_t*)status.p, (const uint8_t*)stop.p,
-                              (const uint64_t*)layer_start.p, (double*)sky_u.p, (double*)sky_v.p,
-                              (double*)sky_z.p,   (uint8_t*)object.p,       (double*)u.p,
-                              (double*)v.p,       (double*)z.p,             (double*)radius.p};
-  }
+  grt::GBufferArrays view() const { return arr.view(0, info.n_pixels); }
 };
 
 // What a buffer records of the scene it was traced with, beside the camera: written by
@@ -186,6 +208,42 @@ static int trace_exact(grt_scene* s, DeviceCopy& dc, const grt::WorkList& wl, co
   }
 }
 
+// The layer scan's scratch, sized once per call for scans of at most `cap` rays.
+struct LayerScan {
+  DevBuf counts, temp;
+  size_t temp_bytes = 0;
+  int alloc(uint64_t cap) {
+    if (int rc = counts.alloc(8 * (cap + 1))) return rc;
+    HIP_TRY(grt::gbuffer_layer_scan(nullptr, nullptr, cap, nullptr, nullptr, nullptr, &temp_bytes, nullptr));
+    return temp.alloc(temp_bytes);
+  }
+  // The scan of a trace's n rays on `st` into layer_start (n + 1 entries), then the entries
+  // at the ray positions `at`, read back in order: one 8-byte copy each, the first waits.
+  int run(const uint8_t* status, const uint32_t* hits, uint64_t n, uint64_t* layer_start, hipStream_t st,
+          const std::vector<uint64_t>& at, std::vector<uint64_t>* starts) {
+    HIP_TRY(grt::gbuffer_layer_scan(status, hits, n, (uint64_t*)counts.p, layer_start, temp.p, &temp_bytes, st));
+    starts->assign(at.size(), 0);
+    for (size_t q = 0; q < at.size(); ++q)
+      HIP_TRY(hipMemcpy(&(*starts)[q], layer_start + at[q], 8, hipMemcpyDeviceToHost));
+    return 0;
+  }
+};
+
+// The fill of `gb` on `st` after a complete trace of the n rays of `wl`: the workspace as
+// that trace carved it, its hit pool, and the fill kernel of the unit that traced -- the
+// sequence unit's with a camera table, else KerrBL's own or the default.
+static int enqueue_fill(const grt_scene* s, DeviceCopy& dc, const grt::WorkList& wl, uint64_t n,
+                        const grt::GBufferArrays& gb, hipStream_t st, const grt::CamTable* ct = nullptr) {
+  grt::Workspace ws;
+  if (int rc = ensure_workspace(dc, n, &ws)) return rc;
+  ws.pool = dc.d_pool;
+  const int geom = s->desc.geometry;
+  if (ct) HIP_TRY(grt::seq::launch_gbuffer_fill(geom, dc.d_scene, wl, ws, gb, st, *ct));
+  else if (geom == GRT_GEOM_KERR_BL) HIP_TRY(grt::kerr_bl::launch_gbuffer_fill(geom, dc.d_scene, wl, ws, gb, st));
+  else HIP_TRY(grt::launch_gbuffer_fill(geom, dc.d_scene, wl, ws, gb, st));
+  return 0;
+}
+
 extern "C" {
 
 int grt_gbuffer_trace(grt_scene* s, int device, uint32_t row0, uint32_t col0, uint32_t rows, uint32_t cols,
@@ -213,34 +271,25 @@ int grt_gbuffer_trace(grt_scene* s, int device, uint32_t row0, uint32_t col0, ui
   info.n_pixels = n;
   info.device = device;
   info_from_scene(s->desc, s->desc.camera, &info);
-  if ((rc = gb->alloc_pixels())) return rc;
+  GBufferDev& A = gb->arr;
   // the trace's other outputs, and the scan's scratch
-  DevBuf xyza, cls, hits, counts, temp;
-  if ((rc = xyza.alloc(16 * n)) || (rc = cls.alloc(n)) || (rc = hits.alloc(4 * n)) || (rc = counts.alloc(8 * (n + 1))))
+  DevBuf xyza, cls, hits;
+  LayerScan scan;
+  if ((rc = A.alloc(false, n)) || (rc = xyza.alloc(16 * n)) || (rc = cls.alloc(n)) || (rc = hits.alloc(4 * n)) ||
+      (rc = scan.alloc(n)))
     return rc;
-  size_t temp_bytes = 0;
-  HIP_TRY(grt::gbuffer_layer_scan(nullptr, nullptr, n, nullptr, nullptr, nullptr, &temp_bytes, nullptr));
-  if ((rc = temp.alloc(temp_bytes))) return rc;
   const grt::WorkList wl = rect_worklist(row0, col0, rows, cols);
-  const grt::Outputs o{(float*)xyza.p,          (uint8_t*)cls.p,         (uint8_t*)gb->status.p, nullptr,
-                       (uint32_t*)gb->steps.p,  (uint8_t*)gb->stop.p,    (uint32_t*)hits.p};
+  const grt::Outputs o{(float*)xyza.p, (uint8_t*)cls.p, A.status(), nullptr, A.steps(), A.stop(), (uint32_t*)hits.p};
   unsigned long long acc[8] = {0, 0, 0, 0, 0, 0, 0, 0};
   float ms = 0;
   if ((rc = trace_exact(s, *dc, wl, o, acc, &ms))) return rc;
   hipStream_t st = nullptr;
   if ((rc = stream_order(*dc, st))) return rc;
   HIP_TRY(hipEventRecord(dc->ev0, st));
-  HIP_TRY(grt::gbuffer_layer_scan((const uint8_t*)gb->status.p, (const uint32_t*)hits.p, n, (uint64_t*)counts.p,
-                                  (uint64_t*)gb->layer_start.p, temp.p, &temp_bytes, st));
-  uint64_t n_layers = 0;
-  HIP_TRY(hipMemcpy(&n_layers, (const uint64_t*)gb->layer_start.p + n, 8, hipMemcpyDeviceToHost));
-  info.n_layers = n_layers;
-  if ((rc = gb->alloc_layers())) return rc;
-  grt::Workspace ws;
-  if ((rc = ensure_workspace(*dc, n, &ws))) return rc;  // the carving of the trace above
-  ws.pool = dc->d_pool;
-  const auto fill = s->desc.geometry == GRT_GEOM_KERR_BL ? grt::kerr_bl::launch_gbuffer_fill : grt::launch_gbuffer_fill;
-  HIP_TRY(fill(s->desc.geometry, dc->d_scene, wl, ws, gb->view(), st));
+  std::vector<uint64_t> total;  // the layers of the rectangle
+  if ((rc = scan.run(A.status(), (const uint32_t*)hits.p, n, A.layer_start(), st, {n}, &total))) return rc;
+  info.n_layers = total[0];
+  if ((rc = A.alloc(true, info.n_layers)) || (rc = enqueue_fill(s, *dc, wl, n, gb->view(), st))) return rc;
   HIP_TRY(hipEventRecord(dc->ev1, st));
   HIP_TRY(hipEventSynchronize(dc->ev1));
   float fill_ms = 0;
@@ -269,27 +318,11 @@ int grt_gbuffer_info_get(const grt_gbuffer* gb, grt_gbuffer_info* out) {
 }
 
 int grt_gbuffer_download(const grt_gbuffer* gb, const grt_gbuffer_arrays* h) {
-  if (!gb || !h || !h->status || !h->stop || !h->steps || !h->sky_u || !h->sky_v || !h->sky_redshift ||
-      !h->layer_start)
-    return fail(-EINVAL, "null argument");
+  if (!gb || !h || GBufferPtrs(*h).missing(false)) return fail(-EINVAL, "null argument");
   const uint64_t n = gb->info.n_pixels, l = gb->info.n_layers;
-  if (l && (!h->object || !h->u || !h->v || !h->redshift || !h->radius)) return fail(-EINVAL, "null layer array");
+  if (l && GBufferPtrs(*h).missing(true)) return fail(-EINVAL, "null layer array");
   HIP_TRY(hipSetDevice(gb->info.device));
-  HIP_TRY(hipMemcpy(h->status, gb->status.p, n, hipMemcpyDeviceToHost));
-  HIP_TRY(hipMemcpy(h->stop, gb->stop.p, n, hipMemcpyDeviceToHost));
-  HIP_TRY(hipMemcpy(h->steps, gb->steps.p, 4 * n, hipMemcpyDeviceToHost));
-  HIP_TRY(hipMemcpy(h->sky_u, gb->sky_u.p, 8 * n, hipMemcpyDeviceToHost));
-  HIP_TRY(hipMemcpy(h->sky_v, gb->sky_v.p, 8 * n, hipMemcpyDeviceToHost));
-  HIP_TRY(hipMemcpy(h->sky_redshift, gb->sky_z.p, 8 * n, hipMemcpyDeviceToHost));
-  HIP_TRY(hipMemcpy(h->layer_start, gb->layer_start.p, 8 * (n + 1), hipMemcpyDeviceToHost));
-  if (l) {
-    HIP_TRY(hipMemcpy(h->object, gb->object.p, l, hipMemcpyDeviceToHost));
-    HIP_TRY(hipMemcpy(h->u, gb->u.p, 8 * l, hipMemcpyDeviceToHost));
-    HIP_TRY(hipMemcpy(h->v, gb->v.p, 8 * l, hipMemcpyDeviceToHost));
-    HIP_TRY(hipMemcpy(h->redshift, gb->z.p, 8 * l, hipMemcpyDeviceToHost));
-    HIP_TRY(hipMemcpy(h->radius, gb->radius.p, 8 * l, hipMemcpyDeviceToHost));
-  }
-  return 0;
+  return gb->arr.copy(*h, n, l, hipMemcpyDeviceToHost);
 }
 
 int grt_gbuffer_upload(const grt_gbuffer_info* info, const grt_gbuffer_arrays* h, int device, grt_gbuffer** out) {
@@ -307,21 +340,9 @@ int grt_gbuffer_upload(const grt_gbuffer_info* info, const grt_gbuffer_arrays* h
   gb->info.device = device;
   gb->info._pad = 0;
   const uint64_t n = info->n_pixels, l = info->n_layers;
-  if ((rc = gb->alloc_pixels()) || (rc = gb->alloc_layers())) return rc;
-  HIP_TRY(hipMemcpy(gb->status.p, h->status, n, hipMemcpyHostToDevice));
-  HIP_TRY(hipMemcpy(gb->stop.p, h->stop, n, hipMemcpyHostToDevice));
-  HIP_TRY(hipMemcpy(gb->steps.p, h->steps, 4 * n, hipMemcpyHostToDevice));
-  HIP_TRY(hipMemcpy(gb->sky_u.p, h->sky_u, 8 * n, hipMemcpyHostToDevice));
-  HIP_TRY(hipMemcpy(gb->sky_v.p, h->sky_v, 8 * n, hipMemcpyHostToDevice));
-  HIP_TRY(hipMemcpy(gb->sky_z.p, h->sky_redshift, 8 * n, hipMemcpyHostToDevice));
-  HIP_TRY(hipMemcpy(gb->layer_start.p, h->layer_start, 8 * (n + 1), hipMemcpyHostToDevice));
-  if (l) {
-    HIP_TRY(hipMemcpy(gb->object.p, h->object, l, hipMemcpyHostToDevice));
-    HIP_TRY(hipMemcpy(gb->u.p, h->u, 8 * l, hipMemcpyHostToDevice));
-    HIP_TRY(hipMemcpy(gb->v.p, h->v, 8 * l, hipMemcpyHostToDevice));
-    HIP_TRY(hipMemcpy(gb->z.p, h->redshift, 8 * l, hipMemcpyHostToDevice));
-    HIP_TRY(hipMemcpy(gb->radius.p, h->radius, 8 * l, hipMemcpyHostToDevice));
-  }
+  if ((rc = gb->arr.alloc(false, n)) || (rc = gb->arr.alloc(true, l)) ||
+      (rc = gb->arr.copy(*h, n, l, hipMemcpyHostToDevice)))
+    return rc;
   *out = gb.release();
   return 0;
 }
@@ -370,56 +391,34 @@ struct GbSeqTimes {
 // the layer scan and the fill over the whole stack in slot order (frame after frame), then
 // the cut into one buffer per frame: device-to-device copies of the frame's slice of every
 // array, and its layer_start rebased to 0 at its first pixel.  Appends the buffers to `made`.
+// Not grt_gbuffer_trace's body: that one fills the buffer in place from a rectangle through
+// the default / KerrBL unit; the two share LayerScan and enqueue_fill.
 int gbuffer_sequence_group(grt_scene* s, DeviceCopy& dc, int device, const grt::CamTable& ct,
                            const grt_camera_desc* cameras, uint32_t rows, uint32_t cols,
                            std::vector<std::unique_ptr<grt_gbuffer>>& made, GbSeqTimes* T) {
   int rc;
   const uint32_t kg = ct.n_cams;
   const uint64_t per = (uint64_t)rows * cols, n = per * kg;
-  DevBuf status, stop, steps, sky_u, sky_v, sky_z, layer_start, xyza, cls, hits, counts, temp;
-  if ((rc = status.alloc(n)) || (rc = stop.alloc(n)) || (rc = steps.alloc(4 * n)) || (rc = sky_u.alloc(8 * n)) ||
-      (rc = sky_v.alloc(8 * n)) || (rc = sky_z.alloc(8 * n)) || (rc = layer_start.alloc(8 * (n + 1))) ||
-      (rc = xyza.alloc(16 * n)) || (rc = cls.alloc(n)) || (rc = hits.alloc(4 * n)) || (rc = counts.alloc(8 * (n + 1))))
+  GBufferDev stack;
+  DevBuf xyza, cls, hits;
+  LayerScan scan;
+  if ((rc = stack.alloc(false, n)) || (rc = xyza.alloc(16 * n)) || (rc = cls.alloc(n)) || (rc = hits.alloc(4 * n)) ||
+      (rc = scan.alloc(n)))
     return rc;
-  size_t temp_bytes = 0;
-  HIP_TRY(grt::gbuffer_layer_scan(nullptr, nullptr, n, nullptr, nullptr, nullptr, &temp_bytes, nullptr));
-  if ((rc = temp.alloc(temp_bytes))) return rc;
   const grt::WorkList wl = rect_worklist(0, 0, kg * rows, cols);
-  const grt::Outputs o{(float*)xyza.p,     (uint8_t*)cls.p,  (uint8_t*)status.p, nullptr,
-                       (uint32_t*)steps.p, (uint8_t*)stop.p, (uint32_t*)hits.p};
+  const grt::Outputs o{(float*)xyza.p, (uint8_t*)cls.p,   stack.status(), nullptr,
+                       stack.steps(),  stack.stop(),      (uint32_t*)hits.p};
   unsigned long long acc[8] = {0, 0, 0, 0, 0, 0, 0, 0};
   float ms = 0;
   if ((rc = trace_exact(s, dc, wl, o, acc, &ms, &ct, &T->traces))) return rc;
   hipStream_t st = nullptr;
   if ((rc = stream_order(dc, st))) return rc;
   HIP_TRY(hipEventRecord(dc.ev0, st));
-  HIP_TRY(grt::gbuffer_layer_scan((const uint8_t*)status.p, (const uint32_t*)hits.p, n, (uint64_t*)counts.p,
-                                  (uint64_t*)layer_start.p, temp.p, &temp_bytes, st));
   // where each frame's layers begin in the stack's, and the total
-  std::vector<uint64_t> base(kg + 1);
-  for (uint32_t f = 0; f <= kg; ++f)
-    HIP_TRY(hipMemcpy(&base[f], (const uint64_t*)layer_start.p + per * f, 8, hipMemcpyDeviceToHost));
-  const uint64_t total = base[kg];
-  DevBuf object, u, v, z, radius;
-  if ((rc = object.alloc(total)) || (rc = u.alloc(8 * total)) || (rc = v.alloc(8 * total)) ||
-      (rc = z.alloc(8 * total)) || (rc = radius.alloc(8 * total)))
-    return rc;
-  grt::Workspace ws;
-  if ((rc = ensure_workspace(dc, n, &ws))) return rc;  // the carving of the trace above
-  ws.pool = dc.d_pool;
-  const grt::GBufferArrays stack{n,
-                                 (const uint8_t*)status.p,
-                                 (const uint8_t*)stop.p,
-                                 (const uint64_t*)layer_start.p,
-                                 (double*)sky_u.p,
-                                 (double*)sky_v.p,
-                                 (double*)sky_z.p,
-                                 (uint8_t*)object.p,
-                                 (double*)u.p,
-                                 (double*)v.p,
-                                 (double*)z.p,
-                                 (double*)radius.p};
-  HIP_TRY(grt::seq::launch_gbuffer_fill(s->desc.geometry, dc.d_scene, wl, ws, stack, st, ct));
+  std::vector<uint64_t> at(kg + 1), base;
+  for (uint32_t f = 0; f <= kg; ++f) at[f] = per * f;
+  if ((rc = scan.run(stack.status(), (const uint32_t*)hits.p, n, stack.layer_start(), st, at, &base))) return rc;
+  if ((rc = stack.alloc(true, base[kg])) || (rc = enqueue_fill(s, dc, wl, n, stack.view(0, n), st, &ct))) return rc;
   const size_t first = made.size();
   for (uint32_t f = 0; f < kg; ++f) {
     std::unique_ptr<grt_gbuffer> gb(new grt_gbuffer());
@@ -432,24 +431,10 @@ int gbuffer_sequence_group(grt_scene* s, DeviceCopy& dc, int device, const grt::
     info.n_layers = base[f + 1] - base[f];
     info.device = device;
     info_from_scene(s->desc, cameras[f], &info);
-    if ((rc = gb->alloc_pixels()) || (rc = gb->alloc_layers())) return rc;
-    const uint64_t p0 = per * f, l0 = base[f], nl = info.n_layers;
-    auto cut = [&](DevBuf& dst, const DevBuf& src, uint64_t at, uint64_t count, uint64_t size) {
-      return count ? hipMemcpyAsync(dst.p, (const char*)src.p + at * size, count * size, hipMemcpyDeviceToDevice, st)
-                   : hipSuccess;
-    };
-    HIP_TRY(cut(gb->status, status, p0, per, 1));
-    HIP_TRY(cut(gb->stop, stop, p0, per, 1));
-    HIP_TRY(cut(gb->steps, steps, p0, per, 4));
-    HIP_TRY(cut(gb->sky_u, sky_u, p0, per, 8));
-    HIP_TRY(cut(gb->sky_v, sky_v, p0, per, 8));
-    HIP_TRY(cut(gb->sky_z, sky_z, p0, per, 8));
-    HIP_TRY(cut(gb->object, object, l0, nl, 1));
-    HIP_TRY(cut(gb->u, u, l0, nl, 8));
-    HIP_TRY(cut(gb->v, v, l0, nl, 8));
-    HIP_TRY(cut(gb->z, z, l0, nl, 8));
-    HIP_TRY(cut(gb->radius, radius, l0, nl, 8));
-    HIP_TRY(grt::gbuffer_rebase((const uint64_t*)layer_start.p + p0, per, (uint64_t*)gb->layer_start.p, st));
+    if ((rc = gb->arr.alloc(false, per)) || (rc = gb->arr.alloc(true, info.n_layers)) ||
+        (rc = stack.copy_slice(gb->arr, 0, 0, per * f, base[f], per, info.n_layers, st)))
+      return rc;
+    HIP_TRY(grt::gbuffer_rebase(stack.layer_start() + per * f, per, gb->arr.layer_start(), st));
     made.push_back(std::move(gb));
   }
   HIP_TRY(hipEventRecord(dc.ev1, st));
@@ -464,6 +449,26 @@ int gbuffer_sequence_group(grt_scene* s, DeviceCopy& dc, int device, const grt::
   for (int k = 0; k < 8; ++k) T->acc[k] += acc[k];
   T->trace_ms += ms;
   T->fill_ms += fill_ms;
+  return 0;
+}
+
+// What every stacked call asks of its buffers: none null, and (check_frame) frame f on frame
+// 0's device and of its size.  Per frame, because each caller has further checks of a frame
+// and a refusal names the first frame with any fault.
+int check_no_null_buffer(uint32_t n, grt_gbuffer* const* buffers) {
+  for (uint32_t f = 0; f < n; ++f)
+    if (!buffers[f]) return fail(-EINVAL, "frame " + std::to_string(f) + ": null buffer");
+  return 0;
+}
+int check_frame(grt_gbuffer* const* buffers, uint32_t f) {
+  const std::string frame = "frame " + std::to_string(f) + ": ";
+  const grt_gbuffer_info &i = buffers[f]->info, &i0 = buffers[0]->info;
+  if (i.device != i0.device)
+    return fail(-EINVAL, frame + "the g-buffer is on device " + std::to_string(i.device) + ", frame 0's on device " +
+                             std::to_string(i0.device));
+  if (i.rows != i0.rows || i.cols != i0.cols)
+    return fail(-EINVAL, frame + "the g-buffer has " + std::to_string(i.rows) + " x " + std::to_string(i.cols) +
+                             " pixels, frame 0's " + std::to_string(i0.rows) + " x " + std::to_string(i0.cols));
   return 0;
 }
 }  // namespace
@@ -491,20 +496,15 @@ int grt_gbuffer_trace_sequence(grt_scene* s, int device, uint32_t n_cameras, con
   if (per == 0) return fail(-EINVAL, "empty frame");
   if (per + 1 > (uint64_t)INT_MAX) return fail(-EOVERFLOW, "more than INT_MAX - 1 pixels");
   // frames per launch group: grt_render_sequence's arithmetic; the scan runs over n + 1 entries
-  uint64_t g = std::max<uint64_t>(1, g_seq_group.load(std::memory_order_relaxed) / per);
-  g = std::min<uint64_t>(g, n_cameras);
-  g = std::min<uint64_t>(g, std::max<uint64_t>(1, ((uint64_t)INT_MAX - 1) / per));
-  g = std::min<uint64_t>(g, std::max<uint64_t>(1, 0xffffffffull / rows));
+  const uint64_t g = frames_per_group(per, n_cameras, (uint64_t)INT_MAX - 1, rows);
   DeviceCopy* dc;
   int rc = ensure_device(s, device, &dc);
   if (rc) return rc;
   std::lock_guard<std::mutex> lk(dc->mu);
   HIP_TRY(hipSetDevice(device));
-  std::vector<grt::DevCamera> cams(n_cameras);
-  for (uint32_t f = 0; f < n_cameras; ++f) fill_dev_camera(cameras[f], cams[f]);
   DevBuf b_cams;
-  if ((rc = b_cams.alloc(n_cameras * sizeof(grt::DevCamera)))) return rc;
-  HIP_TRY(hipMemcpy(b_cams.p, cams.data(), n_cameras * sizeof(grt::DevCamera), hipMemcpyHostToDevice));
+  grt::CamTable all;
+  if ((rc = upload_cam_table(cameras, n_cameras, rows, b_cams, &all))) return rc;
   // the buffers die with `made` on any failure below
   std::vector<std::unique_ptr<grt_gbuffer>> made;
   made.reserve(n_cameras);
@@ -512,7 +512,7 @@ int grt_gbuffer_trace_sequence(grt_scene* s, int device, uint32_t n_cameras, con
   uint32_t launches = 0;
   for (uint32_t f0 = 0; f0 < n_cameras; f0 += (uint32_t)g, ++launches) {
     const uint32_t kg = (uint32_t)std::min<uint64_t>(g, n_cameras - f0);
-    const grt::CamTable ct{(const grt::DevCamera*)b_cams.p + f0, rows, kg};
+    const grt::CamTable ct{all.cams + f0, rows, kg};
     if ((rc = gbuffer_sequence_group(s, *dc, device, ct, cameras + f0, rows, cols, made, &T))) return rc;
   }
   if (stats) stats_from(T.acc, T.trace_ms, stats);  // as grt_gbuffer_trace: no overflows, no raymarch
@@ -535,29 +535,20 @@ int grt_gbuffer_shade_sequence(grt_scene* s, uint32_t n_buffers, grt_gbuffer* co
   if (!s || !buffers || !out) return fail(-EINVAL, "null argument");
   if (n_buffers == 0) return fail(-EINVAL, "a sequence needs at least one buffer");
   if (!out->xyza && !out->xyza64) return fail(-EINVAL, "grt_frame_out needs xyza or xyza64");
-  for (uint32_t f = 0; f < n_buffers; ++f)
-    if (!buffers[f]) return fail(-EINVAL, "frame " + std::to_string(f) + ": null buffer");
-  const grt_gbuffer_info& i0 = buffers[0]->info;
-  const int device = i0.device;
+  int rc;
+  if ((rc = check_no_null_buffer(n_buffers, buffers))) return rc;
+  // no more than that: a re-shade takes rectangles, and the same buffer twice
   for (uint32_t f = 0; f < n_buffers; ++f) {
-    const grt_gbuffer_info& i = buffers[f]->info;
-    if (i.device != device)
-      return fail(-EINVAL, "frame " + std::to_string(f) + ": the g-buffer is on device " + std::to_string(i.device) +
-                               ", frame 0's on device " + std::to_string(device));
-    if (i.rows != i0.rows || i.cols != i0.cols)
-      return fail(-EINVAL, "frame " + std::to_string(f) + ": the g-buffer has " + std::to_string(i.rows) + " x " +
-                               std::to_string(i.cols) + " pixels, frame 0's " + std::to_string(i0.rows) + " x " +
-                               std::to_string(i0.cols));
-    if (int rc = grt_gbuffer_shape_compatible(&i.shape, &s->desc))
+    if ((rc = check_frame(buffers, f))) return rc;
+    if ((rc = grt_gbuffer_shape_compatible(&buffers[f]->info.shape, &s->desc)))
       return fail(rc, "frame " + std::to_string(f) + ": " + grt_last_error());
   }
-  const uint64_t per = i0.n_pixels;
+  const int device = buffers[0]->info.device;
+  const uint64_t per = buffers[0]->info.n_pixels;
   if (per == 0 || per > (uint64_t)INT_MAX) return fail(-EINVAL, "frames of 0 or more than INT_MAX pixels");
-  uint64_t g = std::max<uint64_t>(1, g_seq_group.load(std::memory_order_relaxed) / per);
-  g = std::min<uint64_t>(g, n_buffers);
+  const uint64_t g = frames_per_group(per, n_buffers);
   DeviceCopy* dc;
-  int rc = ensure_device(s, device, &dc);
-  if (rc) return rc;
+  if ((rc = ensure_device(s, device, &dc))) return rc;
   std::lock_guard<std::mutex> lk(dc->mu);
   HIP_TRY(hipSetDevice(device));
   const uint64_t ng = per * g;  // slots of a full group
@@ -567,7 +558,7 @@ int grt_gbuffer_shade_sequence(grt_scene* s, uint32_t n_buffers, grt_gbuffer* co
   if (out->stop && (rc = stop.alloc(ng))) return rc;
   if (out->steps && (rc = steps.alloc(4 * ng))) return rc;
   std::vector<grt::GBufferFrame> frames(n_buffers);
-  for (uint32_t f = 0; f < n_buffers; ++f) frames[f] = grt::GBufferFrame{buffers[f]->view(), (const uint32_t*)buffers[f]->steps.p};
+  for (uint32_t f = 0; f < n_buffers; ++f) frames[f] = grt::GBufferFrame{buffers[f]->view(), buffers[f]->arr.steps()};
   if ((rc = table.alloc(n_buffers * sizeof(grt::GBufferFrame)))) return rc;
   HIP_TRY(hipMemcpy(table.p, frames.data(), n_buffers * sizeof(grt::GBufferFrame), hipMemcpyHostToDevice));
   const grt::Outputs o{(float*)xyza.p,     (uint8_t*)cls.p,  (uint8_t*)status.p, (double*)x64.p,
@@ -632,18 +623,15 @@ static int sub_fill(grt_scene* tracer, grt_gbuffer* gb, uint32_t spa, const std:
   SuperBufs C;  // the chunking of enqueue_supersample; the buffers are this call's own
   C.plan(m, spa);
   const uint64_t chunk_pix = C.chunk_pix, cap = C.cap;
-  DevBuf d_px, pix, dx, dy, xyza, cls, hits, counts, local, temp;
+  DevBuf d_px, pix, dx, dy, xyza, cls, hits, local;
+  LayerScan scan;
   if ((rc = d_px.alloc(4 * m)) || (rc = pix.alloc(4 * cap)) || (rc = dx.alloc(8 * cap)) || (rc = dy.alloc(8 * cap)) ||
       (rc = xyza.alloc(16 * cap)) || (rc = cls.alloc(cap)) || (rc = hits.alloc(4 * cap)) ||
-      (rc = counts.alloc(8 * (cap + 1))) || (rc = local.alloc(8 * (cap + 1))))
+      (rc = local.alloc(8 * (cap + 1))) || (rc = scan.alloc(cap)))
     return rc;
-  size_t temp_bytes = 0;
-  HIP_TRY(grt::gbuffer_layer_scan(nullptr, nullptr, cap, nullptr, nullptr, nullptr, &temp_bytes, nullptr));
-  if ((rc = temp.alloc(temp_bytes))) return rc;
   HIP_TRY(hipMemcpy(d_px.p, px.data(), 4 * m, hipMemcpyHostToDevice));
   hipStream_t st = nullptr;
-  const auto fill =
-      tracer->desc.geometry == GRT_GEOM_KERR_BL ? grt::kerr_bl::launch_gbuffer_fill : grt::launch_gbuffer_fill;
+  std::vector<uint64_t> total;  // the chunk's layers
   for (uint64_t base = 0; base < m; base += chunk_pix) {
     const uint64_t mc = std::min(chunk_pix, m - base), nr = mc * per;
     if ((rc = S.reserve_pixels(S.n_pix + mc))) return rc;
@@ -651,39 +639,22 @@ static int sub_fill(grt_scene* tracer, grt_gbuffer* gb, uint32_t spa, const std:
     const uint32_t* d_chunk = (const uint32_t*)d_px.p + base;
     HIP_TRY(grt::launch_make_offsets(d_chunk, mc, nullptr, 0, spa, info.row0, info.col0, info.cols, (uint32_t*)pix.p,
                                      (double*)dx.p, (double*)dy.p, st));
-    grt::WorkList wo;
-    std::memset(&wo, 0, sizeof(wo));
-    wo.row0 = info.row0;
-    wo.col0 = info.col0;
-    wo.rows = info.rows;
-    wo.cols = info.cols;
-    wo.n_items = nr;
-    wo.pixel_index = (const uint32_t*)pix.p;
-    wo.dx = (const double*)dx.p;
-    wo.dy = (const double*)dy.p;
-    const grt::Outputs o{(float*)xyza.p,
-                         (uint8_t*)cls.p,
-                         (uint8_t*)S.status.p + off,
-                         nullptr,
-                         (uint32_t*)S.steps.p + off,
-                         (uint8_t*)S.stop.p + off,
-                         (uint32_t*)hits.p};
+    const grt::WorkList wo = offsets_worklist(info.row0, info.col0, info.rows, info.cols, nr, (const uint32_t*)pix.p,
+                                              (const double*)dx.p, (const double*)dy.p);
+    const grt::Outputs o{(float*)xyza.p,         (uint8_t*)cls.p,       S.arr.status() + off, nullptr,
+                         S.arr.steps() + off,    S.arr.stop() + off,    (uint32_t*)hits.p};
     float t_ms = 0;
     if ((rc = trace_exact(tracer, *dc, wo, o, acc, &t_ms))) return rc;
     ms[0] += t_ms;
     if ((rc = stream_order(*dc, st))) return rc;
     HIP_TRY(hipEventRecord(dc->ev0, st));
-    HIP_TRY(grt::gbuffer_layer_scan((const uint8_t*)S.status.p + off, (const uint32_t*)hits.p, nr, (uint64_t*)counts.p,
-                                    (uint64_t*)local.p, temp.p, &temp_bytes, st));
-    uint64_t n_new = 0;
-    HIP_TRY(hipMemcpy(&n_new, (const uint64_t*)local.p + nr, 8, hipMemcpyDeviceToHost));
+    if ((rc = scan.run(S.arr.status() + off, (const uint32_t*)hits.p, nr, (uint64_t*)local.p, st, {nr}, &total)))
+      return rc;
+    const uint64_t n_new = total[0];
     if ((rc = S.reserve_layers(S.n_layers + n_new))) return rc;
-    HIP_TRY(grt::gbuffer_sub_append((const uint64_t*)local.p, nr, S.n_layers, (uint64_t*)S.layer_start.p + off, d_chunk,
-                                    mc, (uint32_t)S.n_pix, (uint32_t*)S.sub_block.p, (uint32_t*)S.sub_pixel.p, st));
-    grt::Workspace ws;
-    if ((rc = ensure_workspace(*dc, nr, &ws))) return rc;  // the carving of the trace above
-    ws.pool = dc->d_pool;
-    HIP_TRY(fill(tracer->desc.geometry, dc->d_scene, wo, ws, S.view(off, nr), st));
+    HIP_TRY(grt::gbuffer_sub_append((const uint64_t*)local.p, nr, S.n_layers, S.arr.layer_start() + off, d_chunk, mc,
+                                    (uint32_t)S.n_pix, (uint32_t*)S.sub_block.p, (uint32_t*)S.sub_pixel.p, st));
+    if ((rc = enqueue_fill(tracer, *dc, wo, nr, S.arr.view(off, nr), st))) return rc;
     HIP_TRY(hipEventRecord(dc->ev1, st));
     HIP_TRY(hipEventSynchronize(dc->ev1));
     float f_ms = 0;
@@ -706,20 +677,14 @@ static int check_sequence_buffers(uint32_t n, grt_gbuffer* const* buffers, bool 
                                   const grt_scene* tracer) {
   if (!buffers) return fail(-EINVAL, "null argument");
   if (n == 0) return fail(-EINVAL, "a sequence needs at least one buffer");
-  for (uint32_t f = 0; f < n; ++f)
-    if (!buffers[f]) return fail(-EINVAL, "frame " + std::to_string(f) + ": null buffer");
+  if (int rc = check_no_null_buffer(n, buffers)) return rc;
   const grt_gbuffer_info& i0 = buffers[0]->info;
   for (uint32_t f = 0; f < n; ++f) {
     const std::string frame = "frame " + std::to_string(f) + ": ";
     const grt_gbuffer_info& i = buffers[f]->info;
     for (uint32_t g = 0; g < f; ++g)
       if (buffers[g] == buffers[f]) return fail(-EINVAL, frame + "the g-buffer is frame " + std::to_string(g) + "'s too");
-    if (i.device != i0.device)
-      return fail(-EINVAL, frame + "the g-buffer is on device " + std::to_string(i.device) + ", frame 0's on device " +
-                               std::to_string(i0.device));
-    if (i.rows != i0.rows || i.cols != i0.cols)
-      return fail(-EINVAL, frame + "the g-buffer has " + std::to_string(i.rows) + " x " + std::to_string(i.cols) +
-                               " pixels, frame 0's " + std::to_string(i0.rows) + " x " + std::to_string(i0.cols));
+    if (int rc = check_frame(buffers, f)) return rc;
     if (i.row0 != 0 || i.col0 != 0 || (int64_t)i.rows != i.camera.rows || (int64_t)i.cols != i.camera.cols)
       return fail(-EINVAL, frame + "the g-buffer holds the rectangle (" + std::to_string(i.row0) + ", " +
                                std::to_string(i.col0) + ", " + std::to_string(i.rows) + ", " + std::to_string(i.cols) +
@@ -735,14 +700,15 @@ static int check_sequence_buffers(uint32_t n, grt_gbuffer* const* buffers, bool 
 }
 
 // The pixels of `pixels` that buffer f does not hold yet, ascending and unique
-// (grt_gbuffer_supersample's rules).
-static int missing_of(uint32_t f, const grt_gbuffer* gb, uint64_t n, const uint32_t* pixels, std::vector<uint32_t>* px) {
+// (ascending pixel index: two runs append the same bytes).  prefix: "frame k: " of a stack.
+static int missing_of(const std::string& prefix, const grt_gbuffer* gb, uint64_t n, const uint32_t* pixels,
+                      std::vector<uint32_t>* px) {
   px->clear();
   px->reserve(n);
   for (uint64_t k = 0; k < n; ++k) {
     if (pixels[k] >= gb->info.n_pixels)
-      return fail(-EINVAL, "frame " + std::to_string(f) + ": g-buffer: pixel " + std::to_string(pixels[k]) +
-                               " is outside the " + std::to_string(gb->info.n_pixels) + " pixels of the buffer");
+      return fail(-EINVAL, prefix + "g-buffer: pixel " + std::to_string(pixels[k]) + " is outside the " +
+                               std::to_string(gb->info.n_pixels) + " pixels of the buffer");
     if (gb->sub.h_block.empty() || gb->sub.h_block[pixels[k]] == grt::GBUFFER_NIL) px->push_back(pixels[k]);
   }
   std::sort(px->begin(), px->end());
@@ -766,6 +732,8 @@ struct SubSeqTimes {
 // then the cut: per frame of the chunk, device-to-device copies of its slice of every array
 // to the end of its own set, and gbuffer_sub_append with the layer offsets rebased from the
 // chunk's to the set's.  The sets' counts move only after a chunk is complete.
+// Not sub_fill's body: that one runs the default / KerrBL unit straight into the set and
+// accepts rectangle buffers; this one the sequence unit over whole frames, into a stack.
 static int sub_fill_sequence(grt_scene* tracer, uint32_t K, grt_gbuffer* const* buffers, uint32_t spa,
                              const std::vector<std::vector<uint32_t>>& px, SubSeqTimes* T) {
   const grt_gbuffer_info& i0 = buffers[0]->info;
@@ -792,12 +760,11 @@ static int sub_fill_sequence(grt_scene* tracer, uint32_t K, grt_gbuffer* const* 
       h_local[start[k] + j] = px[k][j];
       h_stack[start[k] + j] = (uint32_t)(k * npix + px[k][j]);
     }
-  std::vector<grt::DevCamera> cams(K);
-  for (uint32_t k = 0; k < K; ++k) fill_dev_camera(buffers[k]->info.camera, cams[k]);
+  std::vector<grt_camera_desc> cams(K);  // the buffers' recorded cameras
+  for (uint32_t k = 0; k < K; ++k) cams[k] = buffers[k]->info.camera;
   DevBuf b_cams;
-  if ((rc = b_cams.alloc(K * sizeof(grt::DevCamera)))) return rc;
-  HIP_TRY(hipMemcpy(b_cams.p, cams.data(), K * sizeof(grt::DevCamera), hipMemcpyHostToDevice));
-  const grt::CamTable ct{(const grt::DevCamera*)b_cams.p, rows, K};
+  grt::CamTable ct;
+  if ((rc = upload_cam_table(cams.data(), K, rows, b_cams, &ct))) return rc;
   for (uint32_t k = 0; k < K; ++k) {
     if (px[k].empty()) continue;
     if ((rc = buffers[k]->sub.ensure_map(npix))) return rc;
@@ -806,18 +773,14 @@ static int sub_fill_sequence(grt_scene* tracer, uint32_t K, grt_gbuffer* const* 
   SuperBufs C;  // the chunking of enqueue_supersample, over the concatenation
   C.plan(m, spa);
   const uint64_t chunk_pix = C.chunk_pix, cap = C.cap;
-  DevBuf d_local, d_stack, pix, dx, dy, xyza, cls, hits, counts, local, temp;
-  DevBuf status, stop, steps, sky_u, sky_v, sky_z, object, u, v, z, radius;  // the transient stacked set
+  DevBuf d_local, d_stack, pix, dx, dy, xyza, cls, hits;
+  GBufferDev stack;  // the transient stacked set of one chunk; its layer_start is the chunk's own scan
+  LayerScan scan;
   if ((rc = d_local.alloc(4 * m)) || (rc = d_stack.alloc(4 * m)) || (rc = pix.alloc(4 * cap)) ||
       (rc = dx.alloc(8 * cap)) || (rc = dy.alloc(8 * cap)) || (rc = xyza.alloc(16 * cap)) || (rc = cls.alloc(cap)) ||
-      (rc = hits.alloc(4 * cap)) || (rc = counts.alloc(8 * (cap + 1))) || (rc = local.alloc(8 * (cap + 1))) ||
-      (rc = status.alloc(cap)) || (rc = stop.alloc(cap)) || (rc = steps.alloc(4 * cap)) || (rc = sky_u.alloc(8 * cap)) ||
-      (rc = sky_v.alloc(8 * cap)) || (rc = sky_z.alloc(8 * cap)))
+      (rc = hits.alloc(4 * cap)) || (rc = stack.alloc(false, cap)) || (rc = scan.alloc(cap)))
     return rc;
   uint64_t cap_layers = 0;
-  size_t temp_bytes = 0;
-  HIP_TRY(grt::gbuffer_layer_scan(nullptr, nullptr, cap, nullptr, nullptr, nullptr, &temp_bytes, nullptr));
-  if ((rc = temp.alloc(temp_bytes))) return rc;
   HIP_TRY(hipMemcpy(d_local.p, h_local.data(), 4 * m, hipMemcpyHostToDevice));
   HIP_TRY(hipMemcpy(d_stack.p, h_stack.data(), 4 * m, hipMemcpyHostToDevice));
   hipStream_t st = nullptr;
@@ -826,7 +789,8 @@ static int sub_fill_sequence(grt_scene* tracer, uint32_t K, grt_gbuffer* const* 
     uint64_t a, b;  // the frame's pixels of the chunk, [a, b) of its mc
   };
   std::vector<Seg> segs;
-  std::vector<uint64_t> lb;  // the chunk's layer offset at each segment's first ray, then the total
+  std::vector<uint64_t> at;  // each segment's first ray of the chunk, then the chunk's end
+  std::vector<uint64_t> lb;  // the chunk's layer offset there: each segment's first, then the total
   uint32_t k0 = 0;           // first frame that may have pixels in the chunk
   for (uint64_t base = 0; base < m; base += chunk_pix) {
     const uint64_t mc = std::min(chunk_pix, m - base), nr = mc * per;
@@ -838,81 +802,36 @@ static int sub_fill_sequence(grt_scene* tracer, uint32_t K, grt_gbuffer* const* 
     }
     HIP_TRY(grt::launch_make_offsets_stack((const uint32_t*)d_stack.p + base, mc, spa, rows, cols, (uint32_t*)pix.p,
                                            (double*)dx.p, (double*)dy.p, st));
-    grt::WorkList wo;
-    std::memset(&wo, 0, sizeof(wo));
-    wo.rows = K * rows;
-    wo.cols = cols;
-    wo.n_items = nr;
-    wo.pixel_index = (const uint32_t*)pix.p;
-    wo.dx = (const double*)dx.p;
-    wo.dy = (const double*)dy.p;
-    const grt::Outputs o{(float*)xyza.p,     (uint8_t*)cls.p,  (uint8_t*)status.p, nullptr,
-                         (uint32_t*)steps.p, (uint8_t*)stop.p, (uint32_t*)hits.p};
+    const grt::WorkList wo = offsets_worklist(0, 0, K * rows, cols, nr, (const uint32_t*)pix.p, (const double*)dx.p,
+                                              (const double*)dy.p);
+    const grt::Outputs o{(float*)xyza.p, (uint8_t*)cls.p, stack.status(), nullptr,
+                         stack.steps(),  stack.stop(),    (uint32_t*)hits.p};
     float t_ms = 0;
     ++T->chunks;
     if ((rc = trace_exact(tracer, *dc, wo, o, T->acc, &t_ms, &ct, &T->traces))) return rc;
     T->trace_ms += t_ms;
     if ((rc = stream_order(*dc, st))) return rc;
     HIP_TRY(hipEventRecord(dc->ev0, st));
-    HIP_TRY(grt::gbuffer_layer_scan((const uint8_t*)status.p, (const uint32_t*)hits.p, nr, (uint64_t*)counts.p,
-                                    (uint64_t*)local.p, temp.p, &temp_bytes, st));
-    lb.assign(segs.size() + 1, 0);
-    for (size_t q = 0; q <= segs.size(); ++q) {
-      const uint64_t at = (q < segs.size() ? segs[q].a : mc) * per;
-      HIP_TRY(hipMemcpy(&lb[q], (const uint64_t*)local.p + at, 8, hipMemcpyDeviceToHost));
-    }
+    at.clear();
+    for (const Seg& g : segs) at.push_back(g.a * per);
+    at.push_back(nr);
+    if ((rc = scan.run(stack.status(), (const uint32_t*)hits.p, nr, stack.layer_start(), st, at, &lb))) return rc;
     const uint64_t total = lb.back();
-    if (total > cap_layers || !object.p) {
+    if (total > cap_layers || !stack.a[GB_object].p) {  // nothing of the last chunk is kept
       const uint64_t want = std::max<uint64_t>({total, 2 * cap_layers, 4096});
-      for (DevBuf* b : {&object, &u, &v, &z, &radius}) {
-        if (b->p) (void)hipFree(b->p);
-        b->p = nullptr;
-      }
-      if ((rc = object.alloc(want)) || (rc = u.alloc(8 * want)) || (rc = v.alloc(8 * want)) ||
-          (rc = z.alloc(8 * want)) || (rc = radius.alloc(8 * want)))
-        return rc;
+      if ((rc = stack.alloc(true, want))) return rc;
       cap_layers = want;
     }
-    grt::Workspace ws;
-    if ((rc = ensure_workspace(*dc, nr, &ws))) return rc;  // the carving of the trace above
-    ws.pool = dc->d_pool;
-    const grt::GBufferArrays stack{nr,
-                                   (const uint8_t*)status.p,
-                                   (const uint8_t*)stop.p,
-                                   (const uint64_t*)local.p,
-                                   (double*)sky_u.p,
-                                   (double*)sky_v.p,
-                                   (double*)sky_z.p,
-                                   (uint8_t*)object.p,
-                                   (double*)u.p,
-                                   (double*)v.p,
-                                   (double*)z.p,
-                                   (double*)radius.p};
-    HIP_TRY(grt::seq::launch_gbuffer_fill(tracer->desc.geometry, dc->d_scene, wo, ws, stack, st, ct));
+    if ((rc = enqueue_fill(tracer, *dc, wo, nr, stack.view(0, nr), st, &ct))) return rc;
     for (size_t q = 0; q < segs.size(); ++q) {
       GBufferSub& S = buffers[segs[q].frame]->sub;
       const uint64_t mk = segs[q].b - segs[q].a, nk = mk * per, r0 = segs[q].a * per;
       const uint64_t l0 = lb[q], nl = lb[q + 1] - lb[q];
       if ((rc = S.reserve_pixels(S.n_pix + mk)) || (rc = S.reserve_layers(S.n_layers + nl))) return rc;
       const uint64_t off = S.n_rays(), loff = S.n_layers;
-      auto cut = [&](DevBuf& dst, uint64_t to, const DevBuf& src, uint64_t from, uint64_t count, uint64_t size) {
-        return count ? hipMemcpyAsync((char*)dst.p + to * size, (const char*)src.p + from * size, count * size,
-                                      hipMemcpyDeviceToDevice, st)
-                     : hipSuccess;
-      };
-      HIP_TRY(cut(S.status, off, status, r0, nk, 1));
-      HIP_TRY(cut(S.stop, off, stop, r0, nk, 1));
-      HIP_TRY(cut(S.steps, off, steps, r0, nk, 4));
-      HIP_TRY(cut(S.sky_u, off, sky_u, r0, nk, 8));
-      HIP_TRY(cut(S.sky_v, off, sky_v, r0, nk, 8));
-      HIP_TRY(cut(S.sky_z, off, sky_z, r0, nk, 8));
-      HIP_TRY(cut(S.object, loff, object, l0, nl, 1));
-      HIP_TRY(cut(S.u, loff, u, l0, nl, 8));
-      HIP_TRY(cut(S.v, loff, v, l0, nl, 8));
-      HIP_TRY(cut(S.z, loff, z, l0, nl, 8));
-      HIP_TRY(cut(S.radius, loff, radius, l0, nl, 8));
-      // layer_start[off + i] = local[r0 + i] - l0 + loff: the rebase, in wrapping u64 arithmetic
-      HIP_TRY(grt::gbuffer_sub_append((const uint64_t*)local.p + r0, nk, loff - l0, (uint64_t*)S.layer_start.p + off,
+      if ((rc = stack.copy_slice(S.arr, off, loff, r0, l0, nk, nl, st))) return rc;
+      // layer_start[off + i] = the chunk's [r0 + i] - l0 + loff: the rebase, in wrapping u64 arithmetic
+      HIP_TRY(grt::gbuffer_sub_append(stack.layer_start() + r0, nk, loff - l0, S.arr.layer_start() + off,
                                       (const uint32_t*)d_local.p + base + segs[q].a, mk, (uint32_t)S.n_pix,
                                       (uint32_t*)S.sub_block.p, (uint32_t*)S.sub_pixel.p, st));
     }
@@ -942,16 +861,7 @@ int grt_gbuffer_supersample(grt_scene* tracer, grt_gbuffer* gb, uint32_t spa, ui
   if ((rc = check_spa(gb, spa)) || (rc = check_tracer(gb, tracer))) return rc;
   if (stats) std::memset(stats, 0, sizeof(*stats));
   std::vector<uint32_t> px;
-  px.reserve(n);
-  for (uint64_t k = 0; k < n; ++k) {
-    if (pixels[k] >= gb->info.n_pixels)
-      return fail(-EINVAL, "g-buffer: pixel " + std::to_string(pixels[k]) + " is outside the " +
-                               std::to_string(gb->info.n_pixels) + " pixels of the buffer");
-    if (gb->sub.h_block.empty() || gb->sub.h_block[pixels[k]] == grt::GBUFFER_NIL) px.push_back(pixels[k]);
-  }
-  // ascending pixel index: two runs append the same bytes
-  std::sort(px.begin(), px.end());
-  px.erase(std::unique(px.begin(), px.end()), px.end());
+  if ((rc = missing_of("", gb, n, pixels, &px))) return rc;
   unsigned long long acc[8] = {0, 0, 0, 0, 0, 0, 0, 0};
   double ms[2] = {0.0, 0.0};
   if ((rc = sub_fill(tracer, gb, spa, px, acc, ms))) return rc;
@@ -1014,10 +924,10 @@ int grt_gbuffer_shade_section(grt_scene* s, grt_gbuffer* gb, const grt_adaptive_
     fails.ray_stop = B.stop;
     fails.ray_steps = B.steps;
     const grt::Outputs so{B.xyza, B.cls, B.status, B.x64, B.steps, B.stop, nullptr};
-    const grt::GBufferArrays sv = S.view(0, S.n_rays());
+    const grt::GBufferArrays sv = S.view();
     for (uint32_t c = 0; c < B.n_chunks; ++c) {
       const uint64_t base = (uint64_t)c * B.chunk_pix;
-      HIP_TRY(grt::launch_gbuffer_shade_sub(dc->d_scene, sv, (const uint32_t*)S.steps.p, (const uint32_t*)S.sub_block.p,
+      HIP_TRY(grt::launch_gbuffer_shade_sub(dc->d_scene, sv, S.arr.steps(), (const uint32_t*)S.sub_block.p,
                                             P.held_px + base, B.chunk_pix, d_cnt + 2, base, spa, so, st));
       HIP_TRY(grt::launch_average(P.held_px + base, P.held_px + base, B.chunk_pix, d_cnt + 2, base, spa, B.x64, B.status,
                                   b.x64, fails, st));
@@ -1099,7 +1009,7 @@ int grt_gbuffer_supersample_sequence(grt_scene* tracer, uint32_t n, grt_gbuffer*
   std::vector<std::vector<uint32_t>> px(n);
   for (uint32_t f = 0; f < n; ++f) {
     if (n_pixels[f] && !pixels[f]) return fail(-EINVAL, "frame " + std::to_string(f) + ": null pixel list");
-    if ((rc = missing_of(f, buffers[f], n_pixels[f], pixels[f], &px[f]))) return rc;
+    if ((rc = missing_of("frame " + std::to_string(f) + ": ", buffers[f], n_pixels[f], pixels[f], &px[f]))) return rc;
   }
   SubSeqTimes T;
   rc = sub_fill_sequence(tracer, n, buffers, spa, px, &T);
@@ -1145,9 +1055,7 @@ int grt_gbuffer_shade_section_sequence(grt_scene* s, uint32_t n, grt_gbuffer* co
   if (per > (uint64_t)INT_MAX) return fail(-EOVERFLOW, "frame larger than INT_MAX pixels");
   // frames per launch group: whole buffers within the group's rays, at least one; the
   // split compacts the group's slots with 32-bit counts
-  uint64_t g = std::max<uint64_t>(1, g_seq_group.load(std::memory_order_relaxed) / per);
-  g = std::min<uint64_t>(g, n);
-  g = std::min<uint64_t>(g, std::max<uint64_t>(1, (uint64_t)INT_MAX / per));
+  const uint64_t g = frames_per_group(per, n, INT_MAX);
   const uint32_t n_groups = (uint32_t)((n + g - 1) / g);
   DeviceCopy* dc;
   if ((rc = ensure_device(s, device, &dc))) return rc;
@@ -1186,8 +1094,8 @@ int grt_gbuffer_shade_section_sequence(grt_scene* s, uint32_t n, grt_gbuffer* co
     for (uint32_t f = 0; f < kg; ++f) {
       const grt_gbuffer* gb = buffers[f0 + f];
       const GBufferSub& S = gb->sub;
-      frames[f] = grt::GBufferFrame{gb->view(), (const uint32_t*)gb->steps.p};
-      subs[f] = grt::GBufferSubFrame{S.view(0, S.n_rays()), (const uint32_t*)S.steps.p, (const uint32_t*)S.sub_block.p};
+      frames[f] = grt::GBufferFrame{gb->view(), gb->arr.steps()};
+      subs[f] = grt::GBufferSubFrame{S.view(), S.arr.steps(), (const uint32_t*)S.sub_block.p};
       if (!supersampled) continue;
       lists[f] = P.fails[f].f;
       lists[f].count = P.d_cnt + 4 * f + 1;
@@ -1359,27 +1267,11 @@ int grt_gbuffer_sub_download(const grt_gbuffer* gb, uint32_t* sub_pixel, const g
   const GBufferSub& S = gb->sub;
   const uint64_t m = S.n_pix, n = S.n_rays(), l = S.n_layers;
   if (S.spa == 0 || m == 0) return 0;  // nothing to copy
-  if (!sub_pixel || !h || !h->status || !h->stop || !h->steps || !h->sky_u || !h->sky_v || !h->sky_redshift ||
-      !h->layer_start)
-    return fail(-EINVAL, "null argument");
-  if (l && (!h->object || !h->u || !h->v || !h->redshift || !h->radius)) return fail(-EINVAL, "null layer array");
+  if (!sub_pixel || !h || GBufferPtrs(*h).missing(false)) return fail(-EINVAL, "null argument");
+  if (l && GBufferPtrs(*h).missing(true)) return fail(-EINVAL, "null layer array");
   HIP_TRY(hipSetDevice(gb->info.device));
   HIP_TRY(hipMemcpy(sub_pixel, S.sub_pixel.p, 4 * m, hipMemcpyDeviceToHost));
-  HIP_TRY(hipMemcpy(h->status, S.status.p, n, hipMemcpyDeviceToHost));
-  HIP_TRY(hipMemcpy(h->stop, S.stop.p, n, hipMemcpyDeviceToHost));
-  HIP_TRY(hipMemcpy(h->steps, S.steps.p, 4 * n, hipMemcpyDeviceToHost));
-  HIP_TRY(hipMemcpy(h->sky_u, S.sky_u.p, 8 * n, hipMemcpyDeviceToHost));
-  HIP_TRY(hipMemcpy(h->sky_v, S.sky_v.p, 8 * n, hipMemcpyDeviceToHost));
-  HIP_TRY(hipMemcpy(h->sky_redshift, S.sky_z.p, 8 * n, hipMemcpyDeviceToHost));
-  HIP_TRY(hipMemcpy(h->layer_start, S.layer_start.p, 8 * (n + 1), hipMemcpyDeviceToHost));
-  if (l) {
-    HIP_TRY(hipMemcpy(h->object, S.object.p, l, hipMemcpyDeviceToHost));
-    HIP_TRY(hipMemcpy(h->u, S.u.p, 8 * l, hipMemcpyDeviceToHost));
-    HIP_TRY(hipMemcpy(h->v, S.v.p, 8 * l, hipMemcpyDeviceToHost));
-    HIP_TRY(hipMemcpy(h->redshift, S.z.p, 8 * l, hipMemcpyDeviceToHost));
-    HIP_TRY(hipMemcpy(h->radius, S.radius.p, 8 * l, hipMemcpyDeviceToHost));
-  }
-  return 0;
+  return S.arr.copy(*h, n, l, hipMemcpyDeviceToHost);
 }
 
 int grt_gbuffer_sub_upload(grt_gbuffer* gb, const grt_gbuffer_sub_info* sub, const uint32_t* sub_pixel,
@@ -1398,20 +1290,7 @@ int grt_gbuffer_sub_upload(grt_gbuffer* gb, const grt_gbuffer_sub_info* sub, con
   if (N->spa && m) {
     if ((rc = N->reserve_pixels(m)) || (rc = N->reserve_layers(l))) return rc;
     HIP_TRY(hipMemcpy(N->sub_pixel.p, sub_pixel, 4 * m, hipMemcpyHostToDevice));
-    HIP_TRY(hipMemcpy(N->status.p, h->status, n, hipMemcpyHostToDevice));
-    HIP_TRY(hipMemcpy(N->stop.p, h->stop, n, hipMemcpyHostToDevice));
-    HIP_TRY(hipMemcpy(N->steps.p, h->steps, 4 * n, hipMemcpyHostToDevice));
-    HIP_TRY(hipMemcpy(N->sky_u.p, h->sky_u, 8 * n, hipMemcpyHostToDevice));
-    HIP_TRY(hipMemcpy(N->sky_v.p, h->sky_v, 8 * n, hipMemcpyHostToDevice));
-    HIP_TRY(hipMemcpy(N->sky_z.p, h->sky_redshift, 8 * n, hipMemcpyHostToDevice));
-    HIP_TRY(hipMemcpy(N->layer_start.p, h->layer_start, 8 * (n + 1), hipMemcpyHostToDevice));
-    if (l) {
-      HIP_TRY(hipMemcpy(N->object.p, h->object, l, hipMemcpyHostToDevice));
-      HIP_TRY(hipMemcpy(N->u.p, h->u, 8 * l, hipMemcpyHostToDevice));
-      HIP_TRY(hipMemcpy(N->v.p, h->v, 8 * l, hipMemcpyHostToDevice));
-      HIP_TRY(hipMemcpy(N->z.p, h->redshift, 8 * l, hipMemcpyHostToDevice));
-      HIP_TRY(hipMemcpy(N->radius.p, h->radius, 8 * l, hipMemcpyHostToDevice));
-    }
+    if ((rc = N->arr.copy(*h, n, l, hipMemcpyHostToDevice))) return rc;
     N->n_pix = m;
     N->n_layers = l;
     HIP_TRY(grt::gbuffer_sub_index((const uint32_t*)N->sub_pixel.p, m, gb->info.n_pixels, (uint32_t*)N->sub_block.p,
@@ -1419,18 +1298,7 @@ int grt_gbuffer_sub_upload(grt_gbuffer* gb, const grt_gbuffer_sub_info* sub, con
     HIP_TRY(hipDeviceSynchronize());
     for (uint64_t j = 0; j < m; ++j) N->h_block[sub_pixel[j]] = (uint32_t)j;
   }
-  // the old set's arrays are freed with N
-  std::swap(gb->sub.spa, N->spa);
-  std::swap(gb->sub.n_pix, N->n_pix);
-  std::swap(gb->sub.cap_pix, N->cap_pix);
-  std::swap(gb->sub.n_layers, N->n_layers);
-  std::swap(gb->sub.cap_layers, N->cap_layers);
-  std::swap(gb->sub.h_block, N->h_block);
-  for (DevBuf GBufferSub::*f : {&GBufferSub::sub_pixel, &GBufferSub::sub_block, &GBufferSub::status, &GBufferSub::stop,
-                                &GBufferSub::steps, &GBufferSub::sky_u, &GBufferSub::sky_v, &GBufferSub::sky_z,
-                                &GBufferSub::layer_start, &GBufferSub::object, &GBufferSub::u, &GBufferSub::v,
-                                &GBufferSub::z, &GBufferSub::radius})
-    std::swap((gb->sub.*f).p, ((*N).*f).p);
+  std::swap(gb->sub, *N);  // the old set's arrays are freed with N
   return 0;
 }
 

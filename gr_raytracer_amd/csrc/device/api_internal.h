@@ -109,6 +109,9 @@ int stream_order(DeviceCopy& dc, hipStream_t st);
 int stream_done(DeviceCopy& dc, hipStream_t st);
 void fill_dev_camera(const grt_camera_desc& c, grt::DevCamera& cam);
 grt::WorkList rect_worklist(uint32_t row0, uint32_t col0, uint32_t rows, uint32_t cols);
+// the offsets-mode list of n_items (pixel, dx, dy) items of the rectangle, all device arrays
+grt::WorkList offsets_worklist(uint32_t row0, uint32_t col0, uint32_t rows, uint32_t cols, uint64_t n_items,
+                               const uint32_t* pix, const double* dx, const double* dy);
 int check_rect(const grt_scene* s, uint64_t row0, uint64_t col0, uint64_t rows, uint64_t cols);
 int check_shard(const grt_row_shard* sh);
 int enqueue_trace(grt_scene* s, DeviceCopy& dc, const grt::WorkList& wl_in, const grt::Outputs& o,
@@ -125,10 +128,21 @@ int trace_to_host(grt_scene* s, DeviceCopy& dc, const grt::WorkList& wl, uint64_
                   float* xyza_out, uint8_t* class_out, uint8_t* status_out, const grt_aux_out* aux,
                   unsigned long long acc[8], float* ms_out, const grt::CamTable* ct = nullptr);
 
+// A device allocation and its owner: moved, never copied (a copy would free it twice).
 struct DevBuf {
   void* p = nullptr;
-  ~DevBuf() {
+  DevBuf() = default;
+  DevBuf(const DevBuf&) = delete;
+  DevBuf& operator=(const DevBuf&) = delete;
+  DevBuf(DevBuf&& o) noexcept : p(o.p) { o.p = nullptr; }
+  DevBuf& operator=(DevBuf&& o) noexcept {
+    std::swap(p, o.p);  // o frees what this held
+    return *this;
+  }
+  ~DevBuf() { reset(); }
+  void reset() {
     if (p) (void)hipFree(p);
+    p = nullptr;
   }
   int alloc(size_t n) {
     if (n == 0) n = 16;
@@ -136,6 +150,9 @@ struct DevBuf {
     return 0;
   }
 };
+
+// the cameras in device form, uploaded to `buf` (api.hip); *ct: the table over all of them
+int upload_cam_table(const grt_camera_desc* cameras, uint32_t n, uint32_t rows, DevBuf& buf, grt::CamTable* ct);
 
 // ---- api_adaptive.hip ----
 // Bump allocator over the device's grow-only adaptive arena.  Plan the whole call's
@@ -155,6 +172,10 @@ int ad_reserve(DeviceCopy& dc, uint64_t bytes);
 constexpr uint64_t SUB_CHUNK = 1ull << 21;  // sub-rays per supersample trace launch
 extern std::atomic<uint64_t> g_sub_chunk;    // grt_set_sub_chunk (tests force several chunks)
 extern std::atomic<uint64_t> g_seq_group;    // grt_set_sequence_group: rays per launch group
+// Frames per launch group of a stack of n frames of `per` rays: whole frames within the
+// group's rays, at least one; at most max_slots rays (0: no cap) and, where the stack's rows
+// are 32-bit indices, 2^32 - 1 stacked rows of `rows` a frame (0: no cap).
+uint64_t frames_per_group(uint64_t per, uint64_t n, uint64_t max_slots = 0, uint64_t rows = 0);
 
 // Buffers of the supersample pass over at most n_max selected pixels.
 struct SuperBufs {

@@ -27,7 +27,11 @@ constexpr uint64_t MAX_LAYERS = 1ull << 40;
 bool same(double a, double b) { return std::memcmp(&a, &b, sizeof(double)) == 0; }
 
 // bytes of the arrays after the header
-uint64_t payload_bytes(uint64_t n, uint64_t l) { return 8 * (n + 1) + 24 * n + 32 * l + 4 * n + 2 * n + l; }
+uint64_t payload_bytes(uint64_t n, uint64_t l) {
+  uint64_t bytes = 0;
+  for (const grt_host::GBufferField& f : grt_host::GBUFFER_FIELDS) bytes += f.bytes(n, l);
+  return bytes;
+}
 
 struct File {
   FILE* f = nullptr;
@@ -53,10 +57,8 @@ int gbuffer_check_info(const grt_gbuffer_info* info) {
 
 int gbuffer_check_arrays(const grt_gbuffer_info* info, const grt_gbuffer_arrays* a) {
   if (int rc = gbuffer_check_info(info)) return rc;
-  if (!a || !a->status || !a->stop || !a->steps || !a->sky_u || !a->sky_v || !a->sky_redshift || !a->layer_start)
-    return fail(-EINVAL, "g-buffer: null array");
-  if (info->n_layers && (!a->object || !a->u || !a->v || !a->redshift || !a->radius))
-    return fail(-EINVAL, "g-buffer: null layer array");
+  if (!a || GBufferPtrs(*a).missing(false)) return fail(-EINVAL, "g-buffer: null array");
+  if (info->n_layers && GBufferPtrs(*a).missing(true)) return fail(-EINVAL, "g-buffer: null layer array");
   const uint64_t n = info->n_pixels;
   if (a->layer_start[0] != 0) return fail(-EINVAL, "g-buffer: layer_start does not begin at 0");
   for (uint64_t i = 0; i < n; ++i)
@@ -90,10 +92,8 @@ int gbuffer_sub_check(const grt_gbuffer_info* info, const grt_gbuffer_sub_info* 
   if (!a) return 0;
   const uint64_t m = sub->n_sub_pixels, n = sub->n_sub_rays, l = sub->n_sub_layers;
   if (m && !sub_pixel) return fail(-EINVAL, "g-buffer: null sub_pixel");
-  if (!a->status || !a->stop || !a->steps || !a->sky_u || !a->sky_v || !a->sky_redshift || !a->layer_start)
-    return fail(-EINVAL, "g-buffer: null sub-ray array");
-  if (l && (!a->object || !a->u || !a->v || !a->redshift || !a->radius))
-    return fail(-EINVAL, "g-buffer: null sub-ray layer array");
+  if (GBufferPtrs(*a).missing(false)) return fail(-EINVAL, "g-buffer: null sub-ray array");
+  if (l && GBufferPtrs(*a).missing(true)) return fail(-EINVAL, "g-buffer: null sub-ray layer array");
   {
     std::vector<bool> seen(info->n_pixels, false);
     for (uint64_t j = 0; j < m; ++j) {
@@ -194,18 +194,8 @@ int grt_gbuffer_write_file(const char* path, const grt_gbuffer_info* info, const
   put(MAGIC, 8);
   put(head, 8);
   put(info, sizeof(*info));
-  put(a->layer_start, 8 * (n + 1));
-  put(a->sky_u, 8 * n);
-  put(a->sky_v, 8 * n);
-  put(a->sky_redshift, 8 * n);
-  put(a->u, 8 * l);
-  put(a->v, 8 * l);
-  put(a->redshift, 8 * l);
-  put(a->radius, 8 * l);
-  put(a->steps, 4 * n);
-  put(a->status, n);
-  put(a->stop, n);
-  put(a->object, l);
+  const grt_host::GBufferPtrs P(*a);
+  for (int k = 0; k < grt_host::GB_N_FIELDS; ++k) put(P.p[k], grt_host::GBUFFER_FIELDS[k].bytes(n, l));
   FILE* f = file.f;
   file.f = nullptr;
   if (std::fclose(f) != 0) ok = false;
@@ -244,25 +234,13 @@ int grt_gbuffer_read_file(const char* path, grt_gbuffer_info* info, const grt_gb
     *info = in;
     return 0;
   }
-  if (!a->status || !a->stop || !a->steps || !a->sky_u || !a->sky_v || !a->sky_redshift || !a->layer_start ||
-      (l && (!a->object || !a->u || !a->v || !a->redshift || !a->radius)))
-    return fail(-EINVAL, "g-buffer: null array");
+  const grt_host::GBufferPtrs P(*a);
+  if (P.missing(false) || (l && P.missing(true))) return fail(-EINVAL, "g-buffer: null array");
   bool ok = true;
   auto get = [&](void* p, uint64_t bytes) {
     if (ok && bytes) ok = std::fread(p, 1, bytes, file.f) == bytes;
   };
-  get(a->layer_start, 8 * (n + 1));
-  get(a->sky_u, 8 * n);
-  get(a->sky_v, 8 * n);
-  get(a->sky_redshift, 8 * n);
-  get(a->u, 8 * l);
-  get(a->v, 8 * l);
-  get(a->redshift, 8 * l);
-  get(a->radius, 8 * l);
-  get(a->steps, 4 * n);
-  get(a->status, n);
-  get(a->stop, n);
-  get(a->object, l);
+  for (int k = 0; k < grt_host::GB_N_FIELDS; ++k) get(P.p[k], grt_host::GBUFFER_FIELDS[k].bytes(n, l));
   if (!ok) return fail(-EIO, name + "cannot read the arrays");
   if (int rc = grt_host::gbuffer_check_arrays(&in, a)) return rc;
   *info = in;
@@ -301,18 +279,8 @@ int grt_gbuffer_sub_write_file(const char* path, const grt_gbuffer_info* info, c
   put(&si, sizeof(si));
   put(sub_pixel, 4 * m);
   if (si.samples_per_axis) {
-    put(a->layer_start, 8 * (n + 1));
-    put(a->sky_u, 8 * n);
-    put(a->sky_v, 8 * n);
-    put(a->sky_redshift, 8 * n);
-    put(a->u, 8 * l);
-    put(a->v, 8 * l);
-    put(a->redshift, 8 * l);
-    put(a->radius, 8 * l);
-    put(a->steps, 4 * n);
-    put(a->status, n);
-    put(a->stop, n);
-    put(a->object, l);
+    const grt_host::GBufferPtrs P(*a);
+    for (int k = 0; k < grt_host::GB_N_FIELDS; ++k) put(P.p[k], grt_host::GBUFFER_FIELDS[k].bytes(n, l));
   }
   FILE* f = file.f;
   file.f = nullptr;
@@ -363,26 +331,15 @@ int grt_gbuffer_sub_read_file(const char* path, const grt_gbuffer_info* info, gr
     *sub = si;
     return 0;
   }
-  if ((m && !sub_pixel) || !a->status || !a->stop || !a->steps || !a->sky_u || !a->sky_v || !a->sky_redshift ||
-      !a->layer_start || (l && (!a->object || !a->u || !a->v || !a->redshift || !a->radius)))
+  const grt_host::GBufferPtrs P(*a);
+  if ((m && !sub_pixel) || P.missing(false) || (l && P.missing(true)))
     return fail(-EINVAL, "g-buffer: null sub-ray array");
   bool ok = true;
   auto get = [&](void* p, uint64_t bytes) {
     if (ok && bytes) ok = std::fread(p, 1, bytes, file.f) == bytes;
   };
   get(sub_pixel, 4 * m);
-  get(a->layer_start, 8 * (n + 1));
-  get(a->sky_u, 8 * n);
-  get(a->sky_v, 8 * n);
-  get(a->sky_redshift, 8 * n);
-  get(a->u, 8 * l);
-  get(a->v, 8 * l);
-  get(a->redshift, 8 * l);
-  get(a->radius, 8 * l);
-  get(a->steps, 4 * n);
-  get(a->status, n);
-  get(a->stop, n);
-  get(a->object, l);
+  for (int k = 0; k < grt_host::GB_N_FIELDS; ++k) get(P.p[k], grt_host::GBUFFER_FIELDS[k].bytes(n, l));
   if (!ok) return fail(-EIO, name + "cannot read the arrays");
   if (int rc = grt_host::gbuffer_sub_check(info, &si, sub_pixel, a)) return rc;
   *sub = si;

@@ -40,6 +40,48 @@ int supersample_shard(grt_scene* s, int device, void* stream, const grt_row_shar
                       double min_lum, const double* d_min_lum, const double* d_frame_ya, const uint8_t* d_frame_class,
                       const double* sampling_mask_xyza, double* d_xyza64, const uint32_t* d_local_steps,
                       uint64_t* d_n_supersampled, uint64_t* d_stats, grt_subsample_failures* failures);
+// The twelve arrays of a g-buffer or of a sub-sample set, once, for the file (gbuffer.cpp) and
+// the device (api_gbuffer.hip): X(member of grt_gbuffer_arrays, bytes per element, one
+// element per layer (else per ray), elements beyond the count).  The order is the file's.
+#define GRT_GBUFFER_FIELDS(X)                                                                          \
+  X(layer_start, 8, false, 1) X(sky_u, 8, false, 0) X(sky_v, 8, false, 0) X(sky_redshift, 8, false, 0) \
+  X(u, 8, true, 0) X(v, 8, true, 0) X(redshift, 8, true, 0) X(radius, 8, true, 0)                      \
+  X(steps, 4, false, 0) X(status, 1, false, 0) X(stop, 1, false, 0) X(object, 1, true, 0)
+enum GBufferFieldId {
+#define X(name, size, layer, extra) GB_##name,
+  GRT_GBUFFER_FIELDS(X)
+#undef X
+  GB_N_FIELDS
+};
+struct GBufferField {
+  uint32_t size;
+  bool layer;
+  uint32_t extra;
+  uint64_t bytes(uint64_t rays, uint64_t layers) const { return size * ((layer ? layers : rays) + extra); }
+};
+constexpr GBufferField GBUFFER_FIELDS[GB_N_FIELDS] = {
+#define X(name, size, layer, extra) {size, layer, extra},
+    GRT_GBUFFER_FIELDS(X)
+#undef X
+};
+#define X(name, size, layer, extra) static_assert(sizeof(*grt_gbuffer_arrays{}.name) == size, #name);
+GRT_GBUFFER_FIELDS(X)
+#undef X
+// the arrays of `a` as untyped pointers, in the table's order (hidden: the library exports none of it)
+struct __attribute__((visibility("hidden"))) GBufferPtrs {
+  void* p[GB_N_FIELDS];
+  explicit GBufferPtrs(const grt_gbuffer_arrays& a) {
+#define X(name, size, layer, extra) p[GB_##name] = a.name;
+    GRT_GBUFFER_FIELDS(X)
+#undef X
+  }
+  // a per-ray (`layer`: per-layer) array is null
+  bool missing(bool layer) const {
+    for (int k = 0; k < GB_N_FIELDS; ++k)
+      if (GBUFFER_FIELDS[k].layer == layer && !p[k]) return true;
+    return false;
+  }
+};
 // Consistency of a g-buffer's sizes, and of its arrays with them (gbuffer.cpp): what a file
 // reader or an upload must hold before a kernel indexes by them.  -EINVAL with a message.
 int gbuffer_check_info(const grt_gbuffer_info* info);

@@ -190,6 +190,24 @@ def _sections(grt, info):
     return list(np.cumsum(sizes))
 
 
+FILE_ORDER = ("layer_start", "sky_u", "sky_v", "sky_redshift", "u", "v", "redshift", "radius", "steps", "status", "stop",
+              "object")
+
+
+def test_file_layout_is_pinned(grt, tmp_path):
+    """Every array at its own place of the file: a round trip cannot see two arrays of equal
+    size swapped in the writer and the reader alike."""
+    info, arrays = _synthetic(grt, COUNTS_MIXED)
+    assert (int(info.n_pixels), int(info.n_layers)) == (12, 66)
+    path = tmp_path / "a.grtg"
+    grt.GBuffer.write_file(path, info, arrays)
+    data = path.read_bytes()
+    bounds = _sections(grt, info)
+    assert bounds[-1] == len(data) and len(bounds) == 4 + len(FILE_ORDER)
+    for k, name in enumerate(FILE_ORDER):
+        assert data[bounds[3 + k]:bounds[4 + k]] == arrays[name].tobytes(), name
+
+
 def test_file_rejections(grt, tmp_path):
     L = grt._lib
     info, arrays = _synthetic(grt, COUNTS_MIXED)

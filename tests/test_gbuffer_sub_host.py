@@ -11,7 +11,7 @@ import numpy as np
 import pytest
 
 from conftest import ROOT, SCENES
-from test_gbuffer_host import COUNTS_MIXED, _synthetic
+from test_gbuffer_host import COUNTS_MIXED, FILE_ORDER, _sections, _synthetic
 
 GRT = ROOT / "gr_raytracer_amd" / "lib" / "grt"
 SPA = 2
@@ -112,6 +112,27 @@ def test_sidecar_round_trip(grt, tmp_path, empty):
     grt.GBuffer.write_sub_file(tmp_path / "c.sub", on1, sub, arrays)
     assert (tmp_path / "c.sub").read_bytes() == data
     assert bytes(grt.GBuffer.read_sub_file(path, on1)[0]) == bytes(sub)
+
+
+def test_sidecar_layout_is_pinned(grt, tmp_path):
+    """Every array at its own place of the sidecar, sub_pixel before the twelve: a round trip
+    cannot see two arrays of equal size swapped in the writer and the reader alike."""
+    L = grt._lib
+    info, _ = _synthetic(grt, COUNTS_MIXED)
+    assert (int(info.n_pixels), int(info.n_layers)) == (12, 66)
+    sub, arrays = _sub(grt, info, PIXELS, COUNTS)
+    path = tmp_path / "a.grtg.sub"
+    grt.GBuffer.write_sub_file(path, info, sub, arrays)
+    data = path.read_bytes()
+    # the .grtg file's sections for the set's sizes, moved behind the sub info and sub_pixel
+    sized = L.GBufferInfo.from_buffer_copy(bytes(info))
+    sized.n_pixels, sized.n_layers = len(COUNTS), sum(COUNTS)
+    sub_pixel = _sections(grt, sized)[3] + C.sizeof(L.GBufferSubInfo)
+    bounds = [b + C.sizeof(L.GBufferSubInfo) + 4 * len(PIXELS) for b in _sections(grt, sized)[3:]]
+    assert bounds[-1] == len(data) and len(bounds) == 1 + len(FILE_ORDER)
+    assert data[sub_pixel:bounds[0]] == arrays["sub_pixel"].tobytes()
+    for k, name in enumerate(FILE_ORDER):
+        assert data[bounds[k]:bounds[k + 1]] == arrays[name].tobytes(), name
 
 
 def _read_rc(grt, path, info):
