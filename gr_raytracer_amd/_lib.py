@@ -190,6 +190,14 @@ class GBufferSequenceReport(C.Structure):
                 ("n_traces", C.c_uint32), ("wall_ms", _d), ("trace_ms", _d), ("fill_ms", _d)]
 
 
+class GBufferMultiReport(C.Structure):
+    """grt_gbuffer_multi_report: per rank, what it traced, filled and sent; devices[0]'s gather."""
+    _fields_ = [("n_devices", C.c_uint32), ("transport", C.c_uint32), ("n_traces", C.c_uint32 * GRT_MULTI_MAX_DEVICES),
+                ("rows", C.c_uint64 * GRT_MULTI_MAX_DEVICES), ("layers", C.c_uint64 * GRT_MULTI_MAX_DEVICES),
+                ("block_bytes", C.c_uint64 * GRT_MULTI_MAX_DEVICES), ("trace_ms", _d * GRT_MULTI_MAX_DEVICES),
+                ("fill_ms", _d * GRT_MULTI_MAX_DEVICES), ("gather_ms", _d), ("wall_ms", _d)]
+
+
 class GBufferSectionSequenceReport(C.Structure):
     """grt_gbuffer_section_sequence_report: launch groups, totals and times of the stacked adaptive re-shade."""
     _fields_ = [("n_frames", C.c_uint32), ("n_launches", C.c_uint32), ("n_selected", C.c_uint64),
@@ -336,6 +344,8 @@ def lib() -> C.CDLL:
         "grt_gbuffer_destroy": (C.c_int, [vp]),
         "grt_gbuffer_trace_sequence": (C.c_int, [vp, C.c_int, u32, C.POINTER(CameraDesc), C.POINTER(vp),
                                                  C.POINTER(Stats), C.POINTER(GBufferSequenceReport)]),
+        "grt_gbuffer_trace_multi": (C.c_int, [vp, C.c_int, C.POINTER(C.c_int), u32, C.POINTER(vp), C.POINTER(Stats),
+                                              C.POINTER(GBufferMultiReport)]),
         "grt_gbuffer_shade_sequence": (C.c_int, [vp, u32, C.POINTER(vp), C.POINTER(FrameOut), C.POINTER(C.c_float)]),
         "grt_gbuffer_supersample_sequence": (C.c_int, [vp, u32, C.POINTER(vp), u32, C.POINTER(u64),
                                                        C.POINTER(C.POINTER(C.c_uint32)), C.POINTER(Stats),
@@ -416,7 +426,7 @@ EXPORTED_SYMBOLS = [
     "grt_gbuffer_supersample", "grt_gbuffer_shade_section", "grt_gbuffer_sub_info_get", "grt_gbuffer_sub_download",
     "grt_gbuffer_sub_upload", "grt_gbuffer_sub_write_file", "grt_gbuffer_sub_read_file",
     "grt_gbuffer_trace_sequence", "grt_gbuffer_shade_sequence", "grt_gbuffer_supersample_sequence",
-    "grt_gbuffer_shade_section_sequence",
+    "grt_gbuffer_shade_section_sequence", "grt_gbuffer_trace_multi",
 ]
 
 

@@ -10,7 +10,7 @@
 //     | render-sequence --camera-path P [--filename-pattern frame-%04d.png] [--first-index 0]
 //     | render-ray -r ROW -c COL [--filename rendered-ray.csv]
 //     | render-ray-at -p x,y,z -d x,y,z [--filename rendered-ray-at.csv]
-//     | gbuffer --filename a.grtg [--adaptive]
+//     | gbuffer --filename a.grtg [--adaptive | --gpus N | --devices A,B,...]
 //     | reshade --gbuffer a.grtg [--filename out.png|out.hdr] [--adaptive]
 //     | gbuffer-sequence --camera-path P --filename-pattern a-%04d.grtg [--first-index 0]
 //                        [--adaptive-stacked]
@@ -48,6 +48,10 @@
 // the sidecar if there is one, traces the sub-rays of the pixels its appearance selects
 // and the set does not hold (with the file's camera and integration parameters), writes
 // what `render` of its config writes, and rewrites the sidecar when the set grew.
+// `gbuffer` with --gpus / --devices (and --transport, --band-rows) traces the 1-spp frame
+// over several GPUs (grt_gbuffer_trace_multi) and writes the same bytes; --adaptive with a
+// device list, and a device list on `reshade` or the sequence subcommands, are usage errors:
+// the sub-rays of a multi-traced buffer are `reshade --adaptive`'s top-up on one GPU.
 // gbuffer-sequence / reshade-sequence (not in the reference): the two above for a camera
 // path.  `gbuffer-sequence` traces the path's frames stacked over one load of the scene
 // (grt_gbuffer_trace_sequence) and writes frame k to --filename-pattern at index
@@ -96,6 +100,7 @@ static int usage(const char* msg) {
                "       grt [global options] --config-file FILE render-ray -r ROW -c COL [--filename F]\n"
                "       grt [global options] --config-file FILE render-ray-at -p X,Y,Z -d X,Y,Z [--filename F]\n"
                "       grt [global options] --config-file FILE gbuffer --filename F.grtg [--adaptive]\n"
+               "           (--gpus N / --devices A,B,...: the 1-spp trace over several GPUs, the same file)\n"
                "       grt [global options] --config-file FILE reshade --gbuffer F.grtg [--filename F] [--adaptive]\n"
                "           (--adaptive: the config's [adaptive_sampling]; the sub-rays live in F.grtg.sub)\n"
                "           (reshade: --width/--height must be the buffer's frame; camera flags are ignored)\n"
@@ -677,12 +682,18 @@ int main(int argc, char** argv) {
     return usage("render-ray-at needs --position and --direction");
   if (action == "gbuffer" && filename.empty()) return usage("gbuffer needs --filename");
   if (action == "reshade" && gbuffer_file.empty()) return usage("reshade needs --gbuffer");
-  if ((action == "gbuffer" || action == "reshade") && !multi_devices.empty())
-    return usage("gbuffer and reshade run on one GPU (--device); --gpus / --devices do not apply");
+  // the multi-GPU g-buffer is the 1-spp trace (grt_gbuffer_trace_multi): the sub-rays are a top-up on the buffer's GPU
+  if (action == "gbuffer" && gbuffer_adaptive && !multi_devices.empty())
+    return usage("gbuffer --adaptive runs on one GPU (--device); --gpus / --devices do not apply: trace with "
+                 "`gbuffer --gpus N`, then `reshade --adaptive` tops up the sub-rays on the buffer's GPU");
+  if (action == "reshade" && !multi_devices.empty())
+    return usage("reshade runs on one GPU (--device); --gpus / --devices do not apply: trace with `gbuffer --gpus N`, "
+                 "then `reshade [--adaptive]` shades (and tops up) on the buffer's GPU");
   if (action == "gbuffer-sequence" || action == "reshade-sequence") {  // every usage error before the GPU is touched
     std::string probe;
     if (!multi_devices.empty())
-      return usage((action + " runs on one GPU (--device); --gpus / --devices do not apply").c_str());
+      return usage((action + " runs on one GPU (--device); --gpus / --devices do not apply: a single frame traces with "
+                    "`gbuffer --gpus N`, then `reshade --adaptive` tops up on the buffer's GPU").c_str());
     if (action == "gbuffer-sequence" && camera_path.empty()) return usage("gbuffer-sequence needs --camera-path");
     if (action == "gbuffer-sequence" && !have_pattern)
       return usage("gbuffer-sequence needs --filename-pattern (a-%04d.grtg)");
@@ -824,10 +835,21 @@ int main(int argc, char** argv) {
     grt_gbuffer* gb = nullptr;
     grt_stats st;
     t_phase = clk::now();
-    if (grt_gbuffer_trace(scene, device, 0, 0, (uint32_t)opts.height, (uint32_t)opts.width, &gb, &st) ||
+    grt_gbuffer_multi_report grep;
+    const bool multi = !multi_devices.empty();
+    if ((multi ? grt_gbuffer_trace_multi(scene, (int)multi_devices.size(), multi_devices.data(), band_rows, &gb, &st, &grep)
+               : grt_gbuffer_trace(scene, device, 0, 0, (uint32_t)opts.height, (uint32_t)opts.width, &gb, &st)) ||
         grt_gbuffer_info_get(gb, &gb_info)) {
       std::fprintf(stderr, "Error: %s\n", grt_last_error());
       return 1;
+    }
+    if (multi) {
+      for (uint32_t k = 0; k < grep.n_devices; ++k)
+        std::fprintf(stderr, "[grt] rank %u (GPU %d): %llu rows, %llu layers, %u trace(s), trace %.1f ms, scan + fill %.2f ms\n",
+                     k, multi_devices[k], (unsigned long long)grep.rows[k], (unsigned long long)grep.layers[k],
+                     grep.n_traces[k], grep.trace_ms[k], grep.fill_ms[k]);
+      std::fprintf(stderr, "[grt] %u GPU(s); transport %s, gather %.2f ms\n", grep.n_devices,
+                   transport_name(grep.transport), grep.gather_ms);
     }
     grt_gbuffer_section_report srep;
     if (gbuffer_adaptive) {  // this scene's own adaptive frame: the buffer then holds its selection's sub-rays

@@ -1557,6 +1557,14 @@ int check_shard(const grt_row_shard* sh) {
   if (sh->band_rows == 0) return fail(-EINVAL, "band_rows must be >= 1");
   return 0;
 }
+grt::WorkList shard_worklist(const grt_scene* s, const grt_row_shard* sh) {
+  uint32_t rows = grt_shard_row_count((uint32_t)s->desc.camera.rows, sh);
+  grt::WorkList wl = rect_worklist(0, 0, rows, (uint32_t)s->desc.camera.cols);
+  wl.band_rows = sh->band_rows;
+  wl.shard = sh->shard;
+  wl.n_shards = sh->n_shards;
+  return wl;
+}
 }  // namespace grt_api
 
 extern "C" {
@@ -1575,15 +1583,6 @@ uint32_t grt_shard_row_count(uint32_t frame_rows, const grt_row_shard* sh) {
 uint32_t grt_shard_frame_row(uint32_t local_row, const grt_row_shard* sh) {
   if (!sh) return local_row;
   return grt::shard_frame_row(sh->band_rows, sh->shard, sh->n_shards, local_row);
-}
-
-static grt::WorkList shard_worklist(const grt_scene* s, const grt_row_shard* sh) {
-  uint32_t rows = grt_shard_row_count((uint32_t)s->desc.camera.rows, sh);
-  grt::WorkList wl = rect_worklist(0, 0, rows, (uint32_t)s->desc.camera.cols);
-  wl.band_rows = sh->band_rows;
-  wl.shard = sh->shard;
-  wl.n_shards = sh->n_shards;
-  return wl;
 }
 
 int grt_render_shard(grt_scene* s, int device, const grt_row_shard* sh, float* xyza_out, uint8_t* class_out,

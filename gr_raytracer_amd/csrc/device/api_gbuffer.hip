@@ -223,6 +223,7 @@ struct LayerScan {
           const std::vector<uint64_t>& at, std::vector<uint64_t>* starts) {
     HIP_TRY(grt::gbuffer_layer_scan(status, hits, n, (uint64_t*)counts.p, layer_start, temp.p, &temp_bytes, st));
     starts->assign(at.size(), 0);
+    if (st) HIP_TRY(hipStreamSynchronize(st));  // a stream of its own: the copies below do not wait for it
     for (size_t q = 0; q < at.size(); ++q)
       HIP_TRY(hipMemcpy(&(*starts)[q], layer_start + at[q], 8, hipMemcpyDeviceToHost));
     return 0;
@@ -243,6 +244,87 @@ static int enqueue_fill(const grt_scene* s, DeviceCopy& dc, const grt::WorkList&
   else HIP_TRY(grt::launch_gbuffer_fill(geom, dc.d_scene, wl, ws, gb, st));
   return 0;
 }
+
+// ---- a row-band shard's buffer as one block, and the frame's buffer it goes into (api_internal.h) ----
+static grt::GBufferArrays block_view(const GBufferBlock& B, uint8_t* b) {
+  auto f64 = [&](int k) { return (double*)(b + B.off[k]); };
+  return grt::GBufferArrays{B.n, b + B.off[GB_status], b + B.off[GB_stop], (const uint64_t*)(b + B.off[GB_layer_start]),
+                            f64(GB_sky_u), f64(GB_sky_v), f64(GB_sky_redshift), b + B.off[GB_object], f64(GB_u),
+                            f64(GB_v), f64(GB_redshift), f64(GB_radius)};
+}
+
+GRT_API_NAMESPACE {
+
+// grt_gbuffer_trace's steps over the shard's work list, into the block instead of a buffer's
+// own arrays, the scan and the fill on the caller's stream.
+int gbuffer_trace_shard(grt_scene* s, int device, hipStream_t st, const grt_row_shard& sh,
+                        const GBufferReserve& reserve, GBufferShard* R) {
+  const grt::WorkList wl = shard_worklist(s, &sh);
+  const uint64_t n = (uint64_t)wl.rows * wl.cols;
+  DeviceCopy* dc;
+  int rc;
+  if ((rc = ensure_device(s, device, &dc))) return rc;
+  std::lock_guard<std::mutex> lk(dc->mu);
+  HIP_TRY(hipSetDevice(device));
+  GBufferBlock B(n, 0);
+  uint8_t* base = nullptr;
+  if ((rc = reserve(B.bytes, 0, &base))) return rc;
+  if (n == 0) {  // layer_start's one entry
+    HIP_TRY(hipMemsetAsync(base + B.off[GB_layer_start], 0, 8, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    R->block = B;
+    R->base = base;
+    return 0;
+  }
+  DevBuf xyza, cls, hits;
+  LayerScan scan;
+  if ((rc = xyza.alloc(16 * n)) || (rc = cls.alloc(n)) || (rc = hits.alloc(4 * n)) || (rc = scan.alloc(n))) return rc;
+  uint8_t* status = base + B.off[GB_status];
+  uint64_t* layer_start = (uint64_t*)(base + B.off[GB_layer_start]);
+  const grt::Outputs o{(float*)xyza.p, (uint8_t*)cls.p, status, nullptr, (uint32_t*)(base + B.off[GB_steps]),
+                       base + B.off[GB_stop], (uint32_t*)hits.p};
+  if ((rc = trace_exact(s, *dc, wl, o, R->acc, &R->trace_ms, nullptr, &R->n_traces))) return rc;
+  if ((rc = stream_order(*dc, st))) return rc;
+  HIP_TRY(hipEventRecord(dc->ev0, st));
+  std::vector<uint64_t> total;  // the layers of the shard
+  if ((rc = scan.run(status, (const uint32_t*)hits.p, n, layer_start, st, {n}, &total))) return rc;
+  B = GBufferBlock(n, total[0]);
+  if ((rc = reserve(B.bytes, B.ray_bytes, &base)) || (rc = enqueue_fill(s, *dc, wl, n, block_view(B, base), st)))
+    return rc;
+  HIP_TRY(hipEventRecord(dc->ev1, st));
+  HIP_TRY(hipEventSynchronize(dc->ev1));
+  HIP_TRY(hipEventElapsedTime(&R->fill_ms, dc->ev0, dc->ev1));
+  if ((rc = stream_done(*dc, st))) return rc;
+  HIP_TRY(hipStreamSynchronize(st));
+  R->block = B;
+  R->base = base;
+  return 0;
+}
+
+int gbuffer_frame_alloc(const grt_scene* s, int device, uint64_t n_layers, grt_gbuffer** out, void* p[GB_N_FIELDS]) {
+  *out = nullptr;
+  HIP_TRY(hipSetDevice(device));
+  std::unique_ptr<grt_gbuffer> gb(new grt_gbuffer());
+  grt_gbuffer_info& info = gb->info;
+  info.rows = (uint32_t)s->desc.camera.rows;
+  info.cols = (uint32_t)s->desc.camera.cols;
+  info.n_pixels = (uint64_t)info.rows * info.cols;
+  info.n_layers = n_layers;
+  info.device = device;
+  info_from_scene(s->desc, s->desc.camera, &info);
+  int rc;
+  if ((rc = gb->arr.alloc(false, info.n_pixels)) || (rc = gb->arr.alloc(true, n_layers))) return rc;
+  for (int k = 0; k < GB_N_FIELDS; ++k) p[k] = gb->arr.a[k].p;
+  *out = gb.release();
+  return 0;
+}
+
+void gbuffer_set_times(grt_gbuffer* gb, double trace_ms, double fill_ms) {
+  gb->times[0] = trace_ms;
+  gb->times[1] = fill_ms;
+}
+
+}  // namespace grt_api
 
 extern "C" {
 

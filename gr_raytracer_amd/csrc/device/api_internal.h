@@ -8,11 +8,13 @@
 #include <atomic>
 #include <cerrno>
 #include <cstdint>
+#include <functional>
 #include <mutex>
 #include <string>
 #include <vector>
 
 #include "grt_api.h"
+#include "../host/host_internal.h"
 #include "dev_scene.h"
 #include "kernels.h"
 
@@ -114,6 +116,8 @@ grt::WorkList offsets_worklist(uint32_t row0, uint32_t col0, uint32_t rows, uint
                                const uint32_t* pix, const double* dx, const double* dy);
 int check_rect(const grt_scene* s, uint64_t row0, uint64_t col0, uint64_t rows, uint64_t cols);
 int check_shard(const grt_row_shard* sh);
+// the rectangle work list of the shard's local rows, full width
+grt::WorkList shard_worklist(const grt_scene* s, const grt_row_shard* sh);
 int enqueue_trace(grt_scene* s, DeviceCopy& dc, const grt::WorkList& wl_in, const grt::Outputs& o,
                   unsigned long long* d_stats, hipStream_t stream, const grt::CamTable* ct = nullptr,
                   bool exact = false);
@@ -428,5 +432,50 @@ struct AdaptivePlan {
     return 0;
   }
 };
+
+// ---- api_gbuffer.hip: a row-band shard's buffer as one block (grt_gbuffer_trace_multi, multi.hip) ----
+// The layout of the block: the twelve arrays of GRT_GBUFFER_FIELDS over n rays and `layers`
+// layers, each 256-B aligned, the per-ray ones first, so that their places do not move when
+// the layer total becomes known.
+struct GBufferBlock {
+  uint64_t n = 0, layers = 0;
+  uint64_t off[grt_host::GB_N_FIELDS] = {};
+  uint64_t ray_bytes = 0, bytes = 0;  // the per-ray arrays; the whole block
+  GBufferBlock() = default;
+  GBufferBlock(uint64_t n_, uint64_t layers_) : n(n_), layers(layers_) {
+    for (int pass = 0; pass < 2; ++pass) {
+      for (int k = 0; k < grt_host::GB_N_FIELDS; ++k) {
+        const grt_host::GBufferField& f = grt_host::GBUFFER_FIELDS[k];
+        if (f.layer != (pass == 1)) continue;
+        off[k] = bytes;
+        bytes += (f.bytes(n, layers) + 255) & ~255ull;
+      }
+      if (pass == 0) ray_bytes = bytes;
+    }
+  }
+};
+// What one rank made of its shard.
+struct GBufferShard {
+  GBufferBlock block;
+  uint8_t* base = nullptr;
+  uint32_t n_traces = 0;
+  float trace_ms = 0, fill_ms = 0;
+  unsigned long long acc[8] = {0, 0, 0, 0, 0, 0, 0, 0};  // as trace_sync's
+};
+// The block's memory, the caller's: at least `bytes` at *base, the first `keep` bytes of what
+// the last call returned kept; nothing is in flight on the block when it is called.
+using GBufferReserve = std::function<int(uint64_t bytes, uint64_t keep, uint8_t** base)>;
+// Trace and fill the shard `sh` of the scene's frame on `device` into one block: the exact
+// trace (again with a larger pool while it loses candidates, 3 traces at most), the layer
+// scan and the fill on `st`, under the device copy's mutex from the trace to the end of the
+// fill.  `reserve` is called once before the trace (the per-ray arrays) and once when the
+// layer total is known.  `st` is idle on return.  A shard without rows gives an empty block.
+int gbuffer_trace_shard(grt_scene* s, int device, hipStream_t st, const grt_row_shard& sh,
+                        const GBufferReserve& reserve, GBufferShard* out);
+// An ordinary buffer of the scene's whole frame on `device` with n_layers layers, its arrays
+// allocated and unwritten: p[k] is array k of GRT_GBUFFER_FIELDS.  Freed by grt_gbuffer_destroy.
+int gbuffer_frame_alloc(const grt_scene* s, int device, uint64_t n_layers, grt_gbuffer** out,
+                        void* p[grt_host::GB_N_FIELDS]);
+void gbuffer_set_times(grt_gbuffer* gb, double trace_ms, double fill_ms);
 
 }  // namespace grt_api

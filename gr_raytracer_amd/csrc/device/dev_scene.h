@@ -211,6 +211,21 @@ inline uint32_t shard_frame_row(uint32_t band_rows, uint32_t shard, uint32_t n_s
   return ((local / band_rows) * n_shards + shard) * band_rows + local % band_rows;
 }
 
+// Frame row -> (shard, local row): the inverse of shard_frame_row.
+#if defined(__HIPCC__)
+__host__ __device__
+#endif
+inline void frame_row_source(uint32_t band_rows, uint32_t n_shards, uint32_t row, uint32_t* shard, uint32_t* local) {
+  if (n_shards <= 1) {
+    *shard = 0;
+    *local = row;
+    return;
+  }
+  const uint32_t band = row / band_rows;
+  *shard = band % n_shards;
+  *local = (band / n_shards) * band_rows + row % band_rows;
+}
+
 #ifndef GRT_INTEGRATE_WAVES
 #define GRT_INTEGRATE_WAVES 2  // waves per SIMD of the Kerr-Schild and volumetric integrate kernels
 #endif

@@ -2,7 +2,8 @@
 // of its sub-sample set (grt_gbuffer_supersample, grt_gbuffer_shade_section): the split of
 // a selection into held and missing pixels (of one buffer, or of a stack of buffers at once:
 // grt_gbuffer_shade_section_sequence), the append of a traced chunk, the pixel -> block map
-// of an uploaded set.
+// of an uploaded set; and the assembly of a frame's buffer from the buffers of its row-band
+// shards (grt_gbuffer_trace_multi).
 //
 // A pixel's layers are the window-nearest hits that enter its blend: the trace's own
 // `hits` output, and none for a pixel the trace aborted (status != 0).  The offsets are
@@ -14,6 +15,7 @@
 #include <climits>
 
 #include "kernels.h"
+#include "gbuffer_gather.h"
 
 namespace grt {
 
@@ -167,6 +169,84 @@ hipError_t gbuffer_sub_index(const uint32_t* d_sub_pixel, uint64_t n_sub_pixels,
   if (e != hipSuccess || n_sub_pixels == 0) return e;
   hipLaunchKernelGGL(gbuffer_sub_index_kernel, dim3((unsigned)((n_sub_pixels + 255) / 256)), dim3(256), 0, stream,
                      d_sub_pixel, n_sub_pixels, d_sub_block);
+  return hipGetLastError();
+}
+
+// ---- a frame's buffer from its row-band shards (grt_gbuffer_trace_multi, gbuffer_gather.h) ----
+// Frame order from local order, a grid-stride loop over the frame's pixels: consecutive
+// pixels of a band row are consecutive in their shard, so a wave reads contiguous runs of a
+// row of each array (another GPU's, over xGMI, under the peer transport) and writes
+// contiguous ones.  The pixel's layer count is the difference of its owner's offsets; entry
+// n_pixels of the counts is the scan's extra 0.
+using grt_host::GB_layer_start;
+using grt_host::GB_object;
+using grt_host::GB_sky_redshift;
+using grt_host::GB_sky_u;
+using grt_host::GB_sky_v;
+using grt_host::GB_status;
+using grt_host::GB_steps;
+using grt_host::GB_stop;
+
+__global__ void __launch_bounds__(256) gbuffer_gather_pixels_kernel(GBufferGatherShape G, GBufferGatherSrc S,
+                                                                    GBufferGatherDst D,
+                                                                    uint64_t* __restrict__ counts) {
+  for (uint64_t p = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; p <= G.n_pixels;
+       p += (uint64_t)gridDim.x * blockDim.x) {
+    if (p == G.n_pixels) {
+      counts[p] = 0;
+      continue;
+    }
+    uint32_t s;
+    const uint64_t lp = gbuffer_gather_pixel(G, p, &s);
+    D.p[GB_status][p] = S.p[GB_status][s][lp];
+    D.p[GB_stop][p] = S.p[GB_stop][s][lp];
+    ((uint32_t*)D.p[GB_steps])[p] = ((const uint32_t*)S.p[GB_steps][s])[lp];
+    ((uint64_t*)D.p[GB_sky_u])[p] = ((const uint64_t*)S.p[GB_sky_u][s])[lp];
+    ((uint64_t*)D.p[GB_sky_v])[p] = ((const uint64_t*)S.p[GB_sky_v][s])[lp];
+    ((uint64_t*)D.p[GB_sky_redshift])[p] = ((const uint64_t*)S.p[GB_sky_redshift][s])[lp];
+    const uint64_t* ls = (const uint64_t*)S.p[GB_layer_start][s];
+    counts[p] = ls[lp + 1] - ls[lp];
+  }
+}
+
+hipError_t launch_gbuffer_gather_pixels(const GBufferGatherShape& G, const GBufferGatherSrc& S,
+                                        const GBufferGatherDst& D, uint64_t* d_counts, hipStream_t stream) {
+  const unsigned gx = (unsigned)((G.n_pixels + 1 + 255) / 256 < 8192 ? (G.n_pixels + 1 + 255) / 256 : 8192);
+  hipLaunchKernelGGL(gbuffer_gather_pixels_kernel, dim3(gx), dim3(256), 0, stream, G, S, D, d_counts);
+  return hipGetLastError();
+}
+
+hipError_t gbuffer_gather_scan(const uint64_t* d_counts, uint64_t n_pixels, uint64_t* d_layer_start, void* d_temp,
+                               size_t* temp_bytes, hipStream_t stream) {
+  if (n_pixels + 1 > (uint64_t)INT_MAX) return hipErrorInvalidValue;
+  return hipcub::DeviceScan::ExclusiveSum(d_temp, *temp_bytes, d_counts, d_layer_start, (int)(n_pixels + 1), stream);
+}
+
+// One lane per frame layer and array (blockIdx.y: u, v, redshift, radius, then object), a
+// grid-stride loop.  The lanes of a wave lie in one band or in a few consecutive ones, so
+// they read and write consecutive elements (8 B each, 1 B for `object`); the bisection's
+// probes are the same for most of a wave (at most log2 of the band count, 12 at 4096 bands).
+__global__ void __launch_bounds__(256) gbuffer_gather_layers_kernel(GBufferGatherShape G, GBufferGatherSrc S,
+                                                                    GBufferGatherDst D) {
+  const int k = gbuffer_gather_layer_field((int)blockIdx.y);
+  const uint64_t* __restrict__ frame_start = (const uint64_t*)D.p[GB_layer_start];
+  uint8_t* __restrict__ out = D.p[k];
+  for (uint64_t q = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; q < G.n_layers;
+       q += (uint64_t)gridDim.x * blockDim.x) {
+    uint32_t s;
+    const uint64_t j = gbuffer_gather_layer(G, frame_start, S, q, &s);
+    const uint8_t* __restrict__ src = S.p[k][s];
+    if (k == GB_object) out[q] = src[j];
+    else ((uint64_t*)out)[q] = ((const uint64_t*)src)[j];
+  }
+}
+
+hipError_t launch_gbuffer_gather_layers(const GBufferGatherShape& G, const GBufferGatherSrc& S,
+                                        const GBufferGatherDst& D, hipStream_t stream) {
+  if (G.n_layers == 0) return hipSuccess;
+  const uint64_t want = (G.n_layers + 255) / 256;
+  const unsigned gx = (unsigned)(want < 8192 ? want : 8192);
+  hipLaunchKernelGGL(gbuffer_gather_layers_kernel, dim3(gx, GB_GATHER_LAYER_FIELDS), dim3(256), 0, stream, G, S, D);
   return hipGetLastError();
 }
 

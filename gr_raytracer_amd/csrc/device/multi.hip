@@ -22,6 +22,11 @@
 // RCCL path does.  Neither loads RCCL, and under both a device list may name one GPU
 // several times: each entry is a rank with its own stream, events and arena, which runs
 // the whole N > 1 host path on one GPU (tests/test_multi_peer.py).
+//
+// grt_gbuffer_trace_multi runs the same ranks, context, barrier and transports for the
+// frame's geometry buffer: each rank traces and fills its shard into one block
+// (gbuffer_trace_shard, api_gbuffer.hip), and devices[0] assembles the blocks into an
+// ordinary grt_gbuffer with the two kernels of gbuffer.hip (gbuffer_gather.h).
 #include <dlfcn.h>
 #include <hip/hip_runtime.h>
 #include <rccl/rccl.h>
@@ -43,6 +48,8 @@
 #include "grt_api.h"
 #include "../host/host_internal.h"
 #include "dev_scene.h"
+#include "api_internal.h"
+#include "gbuffer_gather.h"
 
 namespace grt {
 
@@ -66,19 +73,6 @@ struct GatherLayout {
 struct GatherDst {
   uint8_t* p[RF_N];  // frame-order output of gathered field k
 };
-
-// Frame row -> (shard, local row): the inverse of shard_frame_row (dev_scene.h).
-__host__ __device__ inline void frame_row_source(uint32_t band_rows, uint32_t n_shards, uint32_t row,
-                                                 uint32_t* shard, uint32_t* local) {
-  if (n_shards <= 1) {
-    *shard = 0;
-    *local = row;
-    return;
-  }
-  const uint32_t band = row / band_rows;
-  *shard = band % n_shards;
-  *local = (band / n_shards) * band_rows + row % band_rows;
-}
 
 // Frame pixel p's field k: the shard that holds it, and its byte offset from the start of
 // what L.src is relative to (the gathered buffer, or the shard's own block).
@@ -175,10 +169,7 @@ __global__ void __launch_bounds__(256) pack_ya_kernel(const double* __restrict__
 
 namespace {
 
-int fail(int code, const std::string& msg) {
-  grt_host::set_error(msg);
-  return code;
-}
+using grt_api::fail;  // and HIP_TRY (api_internal.h)
 
 // RCCL is bound at the first multi-GPU frame (dlopen of librccl.so.1), not linked: a
 // process that never renders over several GPUs (the single-GPU CLI, the Python host) does
@@ -220,14 +211,6 @@ const Rccl& rccl() {
   }();
   return r;
 }
-#define HIP_TRY(expr)                                                                    \
-  do {                                                                                   \
-    hipError_t _e = (expr);                                                              \
-    if (_e != hipSuccess) {                                                              \
-      (void)hipGetLastError();                                                           \
-      return fail(-EIO, std::string(#expr) + ": " + hipGetErrorString(_e));             \
-    }                                                                                    \
-  } while (0)
 #define NCCL_TRY(expr)                                                                   \
   do {                                                                                   \
     ncclResult_t _r = (expr);                                                            \
@@ -353,8 +336,9 @@ int get_ctx(const std::vector<int>& devs, int transport, MultiCtx** out) {
 }
 
 // A device list: 1..GRT_MULTI_MAX_DEVICES valid ordinals, distinct unless `repeats` (the
-// peer transports: each entry is a rank of its own).
-int check_devices(int n_devices, const int* devices, bool repeats, std::vector<int>* out) {
+// peer transports: each entry is a rank of its own).  bad_ordinal: the code for an ordinal
+// the machine does not have.
+int check_devices(int n_devices, const int* devices, bool repeats, std::vector<int>* out, int bad_ordinal = -ENODEV) {
   if (!devices) return fail(-EINVAL, "null argument");
   if (n_devices < 1 || n_devices > grt::MULTI_MAX) return fail(-EINVAL, "n_devices must be in 1..GRT_MULTI_MAX_DEVICES");
   std::vector<int> devs(devices, devices + n_devices);
@@ -364,7 +348,7 @@ int check_devices(int n_devices, const int* devices, bool repeats, std::vector<i
   int ndev = 0;
   HIP_TRY(hipGetDeviceCount(&ndev));
   for (int d : devs)
-    if (d < 0 || d >= ndev) return fail(-ENODEV, "invalid device ordinal");
+    if (d < 0 || d >= ndev) return fail(bad_ordinal, "invalid device ordinal");
   *out = std::move(devs);
   return 0;
 }
@@ -772,6 +756,191 @@ void device_part(grt_scene* scene, MultiCtx& C, const Plan& P, int i, const grt_
   }
 }
 
+// No communicator is still being created when a call returns (a frame that failed before its
+// collectives has not waited for them).
+void settle_comms(MultiCtx& C) {
+  std::shared_future<std::string> f;
+  {
+    std::lock_guard<std::mutex> lk(C.cm);
+    if (C.started) f = C.comm_ready;
+  }
+  if (f.valid()) (void)f.get();
+}
+
+// ---- grt_gbuffer_trace_multi: the frame's geometry buffer over the ranks ----
+struct GbPlan {
+  uint32_t rows = 0, cols = 0, band = 0, n_dev = 0;
+  int transport = GRT_TRANSPORT_RCCL;  // the transport this call runs
+};
+// The frame's table: each rank's block where its owner left it, and its sizes.  A rank
+// writes its own entries before it arrives at the first barrier with ok = true; the others
+// read them after that barrier, and only when it let them pass.
+struct GbTable {
+  const uint8_t* base[grt::MULTI_MAX] = {};
+  uint64_t n_local[grt::MULTI_MAX] = {}, layers[grt::MULTI_MAX] = {}, bytes[grt::MULTI_MAX] = {};
+};
+struct GbResult {
+  int rc = 0;
+  std::string err;
+  grt_api::GBufferShard sh;
+  float gather_ms = 0;
+};
+
+// A rank's arena grown to `bytes`, its first `keep` bytes kept (copied on the rank's stream
+// and waited for).  Grow-only, as device_part's.
+int arena_reserve(MultiDev& M, uint64_t bytes, uint64_t keep) {
+  if (bytes <= M.bytes) return 0;
+  HIP_TRY(hipStreamSynchronize(M.st));
+  void* p = nullptr;
+  HIP_TRY(hipMalloc(&p, bytes));
+  if (keep && M.mem) {
+    hipError_t e = hipMemcpyAsync(p, M.mem, keep, hipMemcpyDeviceToDevice, M.st);
+    if (e == hipSuccess) e = hipStreamSynchronize(M.st);
+    if (e != hipSuccess) {
+      (void)hipGetLastError();
+      (void)hipFree(p);
+      return fail(-EIO, std::string("cannot move a g-buffer block: ") + hipGetErrorString(e));
+    }
+  }
+  if (M.mem) (void)hipFree(M.mem);
+  M.mem = p;
+  M.bytes = bytes;
+  return 0;
+}
+
+// One rank's part of one buffer: its shard traced and filled into one block of its arena
+// (gbuffer_trace_shard, api_gbuffer.hip), the block published, the first barrier, on
+// devices[0] every allocation of the assembly (the sizes come from the table), the second
+// barrier, then the transport, and on devices[0] the assembly (gbuffer.hip).  device_part's
+// invariants hold: the transport, a collective under RCCL, is entered only after a barrier
+// that all threads pass with no error so far, so a devices[0] that cannot allocate ends the
+// call on every rank instead of leaving the others sending to it; a stream is idle before
+// its rank reaches a barrier or returns; a failed rank arrives at every barrier it has not
+// reached with ok = false; and devices[0]'s stream, the last reader of every block, is
+// synchronised before its part returns.  The context enabled peer access when it was
+// created, so every block is allocated after that.
+void gbuffer_part(grt_scene* scene, MultiCtx& C, const GbPlan& P, int i, Barrier& bar, GbTable& T, GbResult& R,
+                  grt_gbuffer** frame) {
+  MultiDev& M = C.d[i];
+  const int dev = M.device;
+  const bool rccl_path = P.transport == GRT_TRANSPORT_RCCL;
+  const bool direct = P.transport == GRT_TRANSPORT_PEER;
+  const int n_barriers = 2;
+  int passed = 0;
+  bool noted = false;
+  auto barrier = [&]() -> bool {
+    ++passed;
+    return bar.arrive(true);
+  };
+  // devices[0]'s staging (every block back to back) and scan scratch, and the buffer until
+  // it is complete: freed after the stream is idle, on failure too
+  grt_api::DevBuf staging, counts, temp;
+  std::unique_ptr<grt_gbuffer, int (*)(grt_gbuffer*)> made(nullptr, grt_gbuffer_destroy);
+  auto run = [&]() -> int {
+    HIP_TRY(hipSetDevice(dev));
+    if (!rccl_path && injected_failure(i, 1)) return fail(-EIO, "injected failure before the trace");
+    const hipStream_t st = M.st;
+    const grt_row_shard sh{P.band, (uint32_t)i, P.n_dev};
+    int rc = grt_api::gbuffer_trace_shard(
+        scene, dev, st, sh,
+        [&](uint64_t bytes, uint64_t keep, uint8_t** base) -> int {
+          if (int rc2 = arena_reserve(M, bytes, keep)) return rc2;
+          *base = (uint8_t*)M.mem;
+          return 0;
+        },
+        &R.sh);
+    noted = true;
+    if (rccl_path) C.note_launched();
+    if (rc) return rc;
+    HIP_TRY(hipSetDevice(dev));
+    HIP_TRY(hipStreamSynchronize(st));
+    T.base[i] = R.sh.base;
+    T.n_local[i] = R.sh.block.n;
+    T.layers[i] = R.sh.block.layers;
+    T.bytes[i] = R.sh.block.bytes;
+    if (rccl_path)
+      if (int rc2 = comms_ready(C)) return rc2;
+    if (!barrier()) return fail(-ECANCELED, "another device failed");
+    if (!rccl_path && injected_failure(i, 3)) return fail(-EIO, "injected failure before the gather");
+    // devices[0]: every allocation of the assembly, before the barrier that lets the ranks
+    // into the transport.  The layer total is the sum of the ranks' totals, so the frame's
+    // arrays need no read-back.
+    const uint64_t F = (uint64_t)P.rows * P.cols;
+    uint64_t off[grt::MULTI_MAX + 1] = {}, total = 0;
+    size_t temp_bytes = 0;
+    grt::GBufferGatherDst D{};
+    if (i == 0) {
+      for (uint32_t s = 0; s < P.n_dev; ++s) {
+        off[s + 1] = off[s] + T.bytes[s];
+        total += T.layers[s];
+      }
+      if (!direct)
+        if (int rc2 = staging.alloc(off[P.n_dev])) return rc2;
+      grt_gbuffer* gb = nullptr;
+      void* fp[grt::GB_FIELDS];
+      if (int rc2 = grt_api::gbuffer_frame_alloc(scene, dev, total, &gb, fp)) return rc2;
+      made.reset(gb);
+      for (int k = 0; k < grt::GB_FIELDS; ++k) D.p[k] = (uint8_t*)fp[k];
+      HIP_TRY(grt::gbuffer_gather_scan(nullptr, F, nullptr, nullptr, &temp_bytes, st));
+      int rc2;
+      if ((rc2 = counts.alloc(8 * (F + 1))) || (rc2 = temp.alloc(temp_bytes))) return rc2;
+    }
+    if (!barrier()) return fail(-ECANCELED, "another device failed");
+    HIP_TRY(hipEventRecord(M.ev[4], st));
+    // ONE thing per rank moves: its block
+    if (rccl_path) {
+      NCCL_TRY(rccl().GroupStart());
+      NCCL_TRY(rccl().Send(R.sh.base, T.bytes[i], ncclUint8, 0, C.comms[i], st));
+      if (i == 0)
+        for (uint32_t s = 0; s < P.n_dev; ++s)
+          NCCL_TRY(rccl().Recv((uint8_t*)staging.p + off[s], T.bytes[s], ncclUint8, (int)s, C.comms[i], st));
+      NCCL_TRY(rccl().GroupEnd());
+    } else if (i == 0 && !direct) {
+      for (uint32_t s = 0; s < P.n_dev; ++s)
+        if (int rc2 = copy_block((uint8_t*)staging.p + off[s], dev, T.base[s], C.d[s].device, T.bytes[s], st))
+          return rc2;
+    }
+    if (i == 0) {
+      // the same two kernels under every transport: only the base pointers differ
+      const grt::GBufferGatherShape G{P.rows, P.cols, P.band, P.n_dev, F, total};
+      grt::GBufferGatherSrc S{};
+      for (uint32_t s = 0; s < P.n_dev; ++s) {
+        const grt_api::GBufferBlock B(T.n_local[s], T.layers[s]);
+        const uint8_t* b = direct ? T.base[s] : (const uint8_t*)staging.p + off[s];
+        for (int k = 0; k < grt::GB_FIELDS; ++k) S.p[k][s] = b + B.off[k];
+      }
+      HIP_TRY(grt::launch_gbuffer_gather_pixels(G, S, D, (uint64_t*)counts.p, st));
+      uint64_t* frame_start = (uint64_t*)D.p[grt_host::GB_layer_start];
+      HIP_TRY(grt::gbuffer_gather_scan((const uint64_t*)counts.p, F, frame_start, temp.p, &temp_bytes, st));
+      // the offsets are the single-device ones only if they end at the ranks' total; the
+      // layer kernel indexes by them, so it runs after the check
+      uint64_t end = 0;
+      HIP_TRY(hipMemcpyAsync(&end, frame_start + F, 8, hipMemcpyDeviceToHost, st));
+      HIP_TRY(hipStreamSynchronize(st));
+      if (end != total)
+        return fail(-EIO, "the frame's layer offsets end at " + std::to_string(end) + ", the ranks filled " +
+                              std::to_string(total) + " layers");
+      HIP_TRY(grt::launch_gbuffer_gather_layers(G, S, D, st));
+    }
+    HIP_TRY(hipEventRecord(M.ev[5], st));
+    HIP_TRY(hipStreamSynchronize(st));
+    HIP_TRY(hipEventElapsedTime(&R.gather_ms, M.ev[4], M.ev[5]));
+    if (i == 0) *frame = made.release();
+    return 0;
+  };
+  R.rc = run();
+  if (!noted && rccl_path) C.note_launched();  // failed before its trace: the others must not wait
+  if (R.rc) {
+    R.err = grt_last_error();
+    // peer transports: what this rank enqueued may read other ranks' blocks, and its own is
+    // read by devices[0] once it passes the second barrier; the stream is idle before this
+    // thread arrives anywhere or returns (under RCCL a collective that failed part-way
+    // would never let it become so)
+    if (!rccl_path && hipSetDevice(dev) == hipSuccess) (void)hipStreamSynchronize(M.st);
+    for (; passed < n_barriers; ++passed) bar.arrive(false);
+  }
+}
+
 }  // namespace
 
 extern "C" {
@@ -845,15 +1014,7 @@ int grt_render_frame_multi(grt_scene* scene, int n_devices, const int* devices, 
                       std::ref(bar), std::ref(T), std::ref(R[i]));
     device_part(scene, *C, P, 0, cfg, sampling_mask_xyza, out, failures, bar, T, R[0]);
     for (auto& t : th) t.join();
-    {  // no communicator is still being created when this call returns (a frame that
-       // failed before its collectives has not waited for them)
-      std::shared_future<std::string> f;
-      {
-        std::lock_guard<std::mutex> l2(C->cm);
-        if (C->started) f = C->comm_ready;
-      }
-      if (f.valid()) (void)f.get();
-    }
+    settle_comms(*C);
     for (uint32_t i = 0; i < P.n_dev; ++i)
       if (R[i].rc && R[i].rc != -ECANCELED)
         return fail(R[i].rc, (ranks ? "rank " + std::to_string(i) + " (device " + std::to_string(devs[i]) + ")"
@@ -927,6 +1088,92 @@ int grt_render_frame_multi(grt_scene* scene, int n_devices, const int* devices, 
   return 0;
 }
 
+int grt_gbuffer_trace_multi(grt_scene* scene, int n_devices, const int* devices, uint32_t band_rows,
+                            grt_gbuffer** out, grt_stats* stats, grt_gbuffer_multi_report* report) {
+  const auto t0 = std::chrono::steady_clock::now();
+  if (out) *out = nullptr;
+  if (stats) std::memset(stats, 0, sizeof(*stats));
+  if (report) std::memset(report, 0, sizeof(*report));
+  if (!scene || !devices || !out) return fail(-EINVAL, "null argument");
+  if (band_rows == 0) return fail(-EINVAL, "band_rows must be >= 1");
+  const int transport = g_transport.load();
+  std::vector<int> devs;
+  if (int rc = check_devices(n_devices, devices, transport != GRT_TRANSPORT_RCCL, &devs, -EINVAL)) return rc;
+  for (uint32_t k = 0; k < scene->desc.n_objects; ++k)
+    if (scene->desc.objects[k].kind == GRT_OBJ_VOLUMETRIC_DISC)
+      return fail(-ENOTSUP, "a VolumetricDisc's colour is raymarched: the scene has no geometry buffer");
+  GbPlan P;
+  P.n_dev = (uint32_t)n_devices;
+  P.band = band_rows;
+  {
+    const int64_t r = scene->desc.camera.rows, c = scene->desc.camera.cols;
+    if (r <= 0 || c <= 0 || r > (int64_t)UINT32_MAX || c > (int64_t)UINT32_MAX)
+      return fail(-EINVAL, "camera frame size out of range");
+    P.rows = (uint32_t)r;
+    P.cols = (uint32_t)c;
+  }
+  if ((uint64_t)P.rows * P.cols + 1 > (uint64_t)INT32_MAX) return fail(-EOVERFLOW, "more than INT_MAX - 1 pixels");
+  MultiCtx* C;
+  if (int rc = get_ctx(devs, transport, &C)) return rc;
+  std::lock_guard<std::mutex> lk(C->mu);
+  // a device pair that cannot be mapped: the blocks move by copies
+  P.transport = (transport == GRT_TRANSPORT_PEER && !C->peer_mapped) ? GRT_TRANSPORT_PEER_STAGED : transport;
+  std::vector<GbResult> R(P.n_dev);
+  grt_gbuffer* frame = nullptr;
+  {
+    Barrier bar(n_devices);
+    GbTable T;
+    std::vector<std::thread> th;
+    for (int i = 1; i < n_devices; ++i)
+      th.emplace_back(gbuffer_part, scene, std::ref(*C), std::cref(P), i, std::ref(bar), std::ref(T), std::ref(R[i]),
+                      &frame);
+    gbuffer_part(scene, *C, P, 0, bar, T, R[0], &frame);
+    for (auto& t : th) t.join();
+    settle_comms(*C);
+  }
+  int failed = -1;  // the first rank with an error of its own, else the first that was cancelled
+  for (uint32_t i = 0; i < P.n_dev && failed < 0; ++i)
+    if (R[i].rc && R[i].rc != -ECANCELED) failed = (int)i;
+  for (uint32_t i = 0; i < P.n_dev && failed < 0; ++i)
+    if (R[i].rc) failed = (int)i;
+  if (failed >= 0) {
+    if (frame) (void)grt_gbuffer_destroy(frame);
+    return fail(R[failed].rc,
+                "rank " + std::to_string(failed) + " (device " + std::to_string(devs[failed]) + "): " + R[failed].err);
+  }
+  double trace_ms = 0, fill_ms = 0;
+  for (uint32_t i = 0; i < P.n_dev; ++i) {
+    trace_ms = std::max(trace_ms, (double)R[i].sh.trace_ms);
+    fill_ms = std::max(fill_ms, (double)R[i].sh.fill_ms);
+  }
+  grt_api::gbuffer_set_times(frame, trace_ms, fill_ms + R[0].gather_ms);
+  if (stats) {
+    for (uint32_t i = 0; i < P.n_dev; ++i) {
+      stats->accepted_steps += R[i].sh.acc[0];
+      stats->attempts += R[i].sh.acc[1];
+      stats->rays += R[i].sh.acc[2];
+      stats->hit_overflows += R[i].sh.acc[3];
+    }
+    stats->kernel_ms = trace_ms;
+  }
+  if (report) {
+    report->n_devices = P.n_dev;
+    report->transport = (uint32_t)P.transport;
+    report->gather_ms = R[0].gather_ms;
+    for (uint32_t i = 0; i < P.n_dev; ++i) {
+      report->n_traces[i] = R[i].sh.n_traces;
+      report->rows[i] = R[i].sh.block.n / P.cols;
+      report->layers[i] = R[i].sh.block.layers;
+      report->block_bytes[i] = R[i].sh.block.bytes;
+      report->trace_ms[i] = R[i].sh.trace_ms;
+      report->fill_ms[i] = R[i].sh.fill_ms;
+    }
+    report->wall_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+  }
+  *out = frame;
+  return 0;
+}
+
 void grt_multi_release(void) {
   std::lock_guard<std::mutex> lk(g_ctx_mu);
   for (auto& c : g_ctx) {
@@ -958,6 +1205,8 @@ int grt_get_multi_transport(void) { return g_transport.load(); }
 // Test hook (not in grt_api.h): the next frame of a peer transport fails on `rank` with
 // -EIO from host code, before it enqueues anything of `stage` (1: its trace, 2: the
 // supersample pass after the allgather, 3: devices[0]'s gather after the last barrier).
+// grt_gbuffer_trace_multi honours stages 1 (before the rank's trace) and 3 (after its first
+// barrier, before devices[0]'s allocations, the second barrier, the transport and the assembly).
 // One-shot: it clears itself when it fires; rank < 0 disarms it.  No GPU state is touched.
 int grt_debug_multi_fail(int rank, int stage) {
   if (rank < 0) {
@@ -1034,6 +1283,58 @@ int grt_debug_gather_peer_host(uint32_t rows, uint32_t cols, uint32_t band_rows,
         std::memcpy(dst[f] + p * e, blocks[s] + off, e);
       }
     ++k;
+  }
+  return 0;
+}
+
+// Test hook (not in grt_api.h): the assembly of grt_gbuffer_trace_multi run on the host with
+// the two kernels' index functions (gbuffer_gather_pixel, gbuffer_gather_layer) in plain
+// loops, the counterpart of grt_debug_gather_peer_host.  shards[s]: shard s's twelve arrays
+// as its rank holds them, local order, n_local[s] pixels (unused for a shard without rows);
+// frame: the frame's arrays, rows * cols pixels and as many layers as the shards hold.
+int grt_debug_gbuffer_gather_host(uint32_t rows, uint32_t cols, uint32_t band_rows, uint32_t n_shards,
+                                  const grt_gbuffer_arrays* shards, const uint64_t* n_local,
+                                  const grt_gbuffer_arrays* frame) {
+  if (!shards || !n_local || !frame || n_shards == 0 || n_shards > (uint32_t)grt::MULTI_MAX || band_rows == 0)
+    return fail(-EINVAL, "gbuffer_gather: bad argument");
+  const grt_host::GBufferPtrs F(*frame);
+  grt::GBufferGatherShape G{rows, cols, band_rows, n_shards, (uint64_t)rows * cols, 0};
+  grt::GBufferGatherSrc S{};
+  for (uint32_t s = 0; s < n_shards; ++s) {
+    grt_row_shard sh{band_rows, s, n_shards};
+    if (n_local[s] != (uint64_t)grt_shard_row_count(rows, &sh) * cols)
+      return fail(-EINVAL, "gbuffer_gather: n_local is not the shard's pixel count");
+    if (n_local[s] == 0) continue;
+    const grt_host::GBufferPtrs P(shards[s]);
+    if (P.missing(false)) return fail(-EINVAL, "gbuffer_gather: a shard with rows has a null array");
+    for (int k = 0; k < grt::GB_FIELDS; ++k) S.p[k][s] = (const uint8_t*)P.p[k];
+    G.n_layers += shards[s].layer_start[n_local[s]];
+  }
+  if (F.missing(false) || (G.n_layers && F.missing(true))) return fail(-EINVAL, "gbuffer_gather: null frame array");
+  uint64_t* start = frame->layer_start;
+  uint64_t sum = 0;
+  for (uint64_t p = 0; p < G.n_pixels; ++p) {  // gbuffer_gather_pixels_kernel, then the scan
+    uint32_t s;
+    const uint64_t lp = grt::gbuffer_gather_pixel(G, p, &s);
+    for (int k = 0; k < grt::GB_FIELDS; ++k) {
+      const grt_host::GBufferField& f = grt_host::GBUFFER_FIELDS[k];
+      if (f.layer || k == grt_host::GB_layer_start) continue;
+      std::memcpy((uint8_t*)F.p[k] + p * f.size, S.p[k][s] + lp * f.size, f.size);
+    }
+    const uint64_t* ls = (const uint64_t*)S.p[grt_host::GB_layer_start][s];
+    start[p] = sum;
+    sum += ls[lp + 1] - ls[lp];
+  }
+  start[G.n_pixels] = sum;
+  if (sum != G.n_layers) return fail(-EIO, "gbuffer_gather: the frame's layer offsets do not end at the shards' total");
+  for (int y = 0; y < grt::GB_GATHER_LAYER_FIELDS; ++y) {  // gbuffer_gather_layers_kernel
+    const int k = grt::gbuffer_gather_layer_field(y);
+    const uint32_t e = grt_host::GBUFFER_FIELDS[k].size;
+    for (uint64_t q = 0; q < G.n_layers; ++q) {
+      uint32_t s;
+      const uint64_t j = grt::gbuffer_gather_layer(G, start, S, q, &s);
+      std::memcpy((uint8_t*)F.p[k] + q * e, S.p[k][s] + j * e, e);
+    }
   }
   return 0;
 }

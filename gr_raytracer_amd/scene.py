@@ -241,6 +241,35 @@ class Scene:
             gb.shade_section(self, adaptive=adaptive, tracer=self)
         return gb
 
+    def trace_gbuffer_multi(self, devices=(0,), band_rows: int = 16, transport=None) -> "GBuffer":
+        """The whole frame's geometry buffer traced over `devices` (grt_gbuffer_trace_multi: the
+        cyclic row bands of `render_frame_multi`, one host thread per rank, every rank's part
+        gathered and assembled on devices[0]).  The result is the ordinary GBuffer of
+        `trace_gbuffer(device=devices[0])`, byte for byte, with the summed `stats` and the
+        call's `report` (GBufferMultiReport) as attributes.  transport: as
+        `render_frame_multi`'s, set for this call and restored afterwards; under the peer
+        transports `devices` may repeat an ordinal (one rank per entry)."""
+        devs = (C.c_int * max(len(devices), 1))(*devices)
+        h = C.c_void_p()
+        st = L.Stats()
+        rep = L.GBufferMultiReport()
+        lib = L.lib()
+        before = None
+        if transport is not None:
+            mode = L.MULTI_TRANSPORTS[transport] if isinstance(transport, str) else int(transport)
+            before = lib.grt_get_multi_transport()
+            L.check(lib.grt_set_multi_transport(mode), "grt_set_multi_transport")
+        try:
+            rc = lib.grt_gbuffer_trace_multi(self._s, len(devices), devs, band_rows, C.byref(h), C.byref(st),
+                                             C.byref(rep))
+        finally:
+            if before is not None:
+                lib.grt_set_multi_transport(before)
+        L.check(rc, "grt_gbuffer_trace_multi")
+        gb = GBuffer(h, _stats_dict(st))
+        gb.report = rep
+        return gb
+
     def trace_gbuffer_sequence(self, cameras, device: int = 0,
                                adaptive: Optional[L.AdaptiveConfig] = None) -> "GBufferSequence":
         """K cameras (CameraDesc, each with the scene's rows and cols) over this scene, traced

@@ -613,8 +613,9 @@ int grt_set_sequence_group(uint64_t rays);
  * with a GRT_OBJ_VOLUMETRIC_DISC are refused (-ENOTSUP): its colour is raymarched, not a
  * function of (u, v, redshift, temperature).  One rectangle on one device, at 1 spp or with
  * the adaptive pass's sub-rays (the sub-sample set below), or the whole frames of a camera
- * sequence, one buffer each (grt_gbuffer_trace_sequence below): no offset lists, row shards
- * or multi-GPU frames.
+ * sequence, one buffer each (grt_gbuffer_trace_sequence below), or the whole frame at 1 spp
+ * over several GPUs, assembled into one buffer on the first (grt_gbuffer_trace_multi below):
+ * no offset lists, and no row shards as buffers of their own.
  * A grt_gbuffer is not synchronised: one host thread at a time per buffer. */
 typedef struct grt_gbuffer grt_gbuffer; /* device-resident, owns its arrays */
 
@@ -689,6 +690,44 @@ int grt_gbuffer_upload(const grt_gbuffer_info* info, const grt_gbuffer_arrays* h
 int grt_gbuffer_shade(grt_scene* appearance, const grt_gbuffer* gb, float* xyza_out, uint8_t* class_out,
                       uint8_t* status_out, double* xyza64_out, float* kernel_ms);
 int grt_gbuffer_destroy(grt_gbuffer* gb);
+
+/* ---- The g-buffer of the whole frame, traced over several GPUs ----
+ * grt_render_frame_multi's row bands (band b -> devices[b % n_devices]), one host thread per
+ * rank with the streams, scratch and barrier of the same cached context: each rank traces
+ * its own shard with the exact kernels and fills its part as grt_gbuffer_trace does (a rank
+ * that loses hit candidates grows its own pool and traces its own shard again, at most 3
+ * traces, else -ENOMEM), laid out as ONE block.  After a barrier, devices[0]'s allocations and a
+ * second barrier (so that no rank enters the transport when any has failed) the blocks reach
+ * devices[0] by the transport of grt_set_multi_transport (read once per call; a peer list
+ * with a pair that cannot be mapped runs staged), where two kernels put the per-pixel arrays
+ * into frame order, an exclusive sum of the layer counts gives the frame's layer_start, and
+ * every layer moves to its place by its band.  The result is an ordinary grt_gbuffer of the
+ * whole camera frame on devices[0]: its grt_gbuffer_info and all twelve arrays are byte for
+ * byte those of grt_gbuffer_trace(scene, devices[0], 0, 0, rows, cols, ...), so every call
+ * above and below works on it unchanged.  grt_gbuffer_trace_times: [0] the slowest rank's
+ * trace, [1] the slowest rank's scan + fill plus gather_ms.  stats (nullable): summed as
+ * grt_render_frame_multi sums them.
+ * Device lists as grt_render_frame_multi's: 1..16 entries, an ordinal may repeat under the
+ * peer transports (one rank per entry), a repeat under GRT_TRANSPORT_RCCL is -EINVAL, and so
+ * is an ordinal the machine does not have.  -ENOTSUP for a scene with a VolumetricDisc,
+ * -EINVAL for band_rows = 0 or a null scene, devices or out, -EOVERFLOW for a frame of more
+ * than INT_MAX - 1 pixels: all before any launch.  On any failure *out is NULL and nothing
+ * stays allocated outside the cached context; a failure on one rank ends the call on all
+ * ("rank k (device d): ...").  No N > 1 frame over distinct GPUs has run on hardware under
+ * any transport. */
+typedef struct grt_gbuffer_multi_report {
+  uint32_t n_devices, transport;                 /* the grt_multi_transport that ran */
+  uint32_t n_traces[GRT_MULTI_MAX_DEVICES];      /* per rank; > 1 when its hit pool had to grow */
+  uint64_t rows[GRT_MULTI_MAX_DEVICES];
+  uint64_t layers[GRT_MULTI_MAX_DEVICES];        /* layers each rank filled */
+  uint64_t block_bytes[GRT_MULTI_MAX_DEVICES];   /* what the gather moved from each rank */
+  double trace_ms[GRT_MULTI_MAX_DEVICES], fill_ms[GRT_MULTI_MAX_DEVICES];
+  double gather_ms;                              /* devices[0]: transport + assembly, events */
+  double wall_ms;
+} grt_gbuffer_multi_report;
+
+int grt_gbuffer_trace_multi(grt_scene* scene, int n_devices, const int* devices, uint32_t band_rows,
+                            grt_gbuffer** out, grt_stats* stats, grt_gbuffer_multi_report* report);
 
 /* Host only.  The shape key of a scene descriptor. */
 void grt_gbuffer_shape_of(const grt_scene_desc* desc, grt_gbuffer_shape* out);
