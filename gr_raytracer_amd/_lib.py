@@ -363,6 +363,13 @@ def lib() -> C.CDLL:
         "grt_gbuffer_shade_section": (C.c_int, [vp, vp, C.POINTER(AdaptiveConfig), _pd, vp, _pd, C.POINTER(C.c_uint8),
                                                 C.POINTER(C.c_uint8), C.POINTER(C.c_uint64),
                                                 C.POINTER(SubsampleFailures), C.POINTER(GBufferSectionReport)]),
+        "grt_orbit_rate": (C.c_int, [C.c_int32, _d, _d, _d, _pd]),
+        "grt_gbuffer_orbit_uv": (C.c_int, [C.POINTER(GBufferShape), u64, C.POINTER(C.c_uint8), _pd, _pd, _pd, _d, _pd,
+                                           _pd]),
+        "grt_gbuffer_shade_times": (C.c_int, [vp, vp, u32, _pd, C.POINTER(FrameOut), C.POINTER(C.c_float)]),
+        "grt_gbuffer_shade_section_at": (C.c_int, [vp, vp, C.POINTER(AdaptiveConfig), _pd, vp, _pd,
+                                                   C.POINTER(C.c_uint8), C.POINTER(C.c_uint8), C.POINTER(C.c_uint64),
+                                                   C.POINTER(SubsampleFailures), C.POINTER(GBufferSectionReport), _d]),
         "grt_gbuffer_sub_info_get": (C.c_int, [vp, C.POINTER(GBufferSubInfo)]),
         "grt_gbuffer_sub_download": (C.c_int, [vp, C.POINTER(C.c_uint32), C.POINTER(GBufferArrays)]),
         "grt_gbuffer_sub_upload": (C.c_int, [vp, C.POINTER(GBufferSubInfo), C.POINTER(C.c_uint32),
@@ -427,6 +434,7 @@ EXPORTED_SYMBOLS = [
     "grt_gbuffer_sub_upload", "grt_gbuffer_sub_write_file", "grt_gbuffer_sub_read_file",
     "grt_gbuffer_trace_sequence", "grt_gbuffer_shade_sequence", "grt_gbuffer_supersample_sequence",
     "grt_gbuffer_shade_section_sequence", "grt_gbuffer_trace_multi",
+    "grt_orbit_rate", "grt_gbuffer_orbit_uv", "grt_gbuffer_shade_times", "grt_gbuffer_shade_section_at",
 ]
 
 

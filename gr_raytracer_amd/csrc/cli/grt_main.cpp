@@ -16,6 +16,8 @@
 //                        [--adaptive-stacked]
 //     | reshade-sequence --gbuffer-pattern a-%04d.grtg --frames K [--first-index 0]
 //                        [--filename-pattern frame-%04d.png] [--adaptive-stacked]
+//     | reshade-orbit --gbuffer a.grtg --times T0,DT,K --filename-pattern f-%04d.png
+//                     [--raw-out-pattern f-%04d.raw] [--first-index 0] [--adaptive]
 //     | blackbody -t T [-r Z]
 //     | blackbody-spectrum [--min-temperature T] [--max-temperature T] [--min-redshift Z]
 //                          [--max-redshift Z] [--width N] [--height N] [-f FILE]
@@ -69,6 +71,13 @@
 // appearance and tracer, loads the sidecars that exist, tops the sets up in one stacked call,
 // writes each frame as `render` of its config writes it (--show-sampling-mask included) and
 // rewrites the sidecars that grew.
+// reshade-orbit (not in the reference): the frames of one geometry buffer with the disc's
+// texture orbiting at the shade pass's own emitter rate (grt_api.h, "the disc's orbital
+// motion"): frame k at coordinate time T0 + k DT, K frames from one trace in stacked launches
+// (grt_gbuffer_shade_times), each written as `reshade` writes its frame to --filename-pattern
+// (and --raw-out-pattern) at index --first-index + k.  With --adaptive the frames are
+// `reshade --adaptive`'s at those times, one after the other (grt_gbuffer_shade_section_at);
+// the sidecar is loaded once and rewritten once at the end when the set grew.
 #include <algorithm>
 #include <charconv>
 #include <chrono>
@@ -109,6 +118,9 @@ static int usage(const char* msg) {
                "       grt [global options] --config-file FILE reshade-sequence --gbuffer-pattern F-%%04d.grtg\n"
                "           --frames K [--first-index N] [--filename-pattern frame-%%04d.png] [--adaptive-stacked]\n"
                "           (--adaptive-stacked: the adaptive frames of the sequence, the sub-rays in F-%%04d.grtg.sub)\n"
+               "       grt [global options] --config-file FILE reshade-orbit --gbuffer F.grtg --times T0,DT,K\n"
+               "           --filename-pattern F-%%04d.png [--raw-out-pattern F-%%04d.raw] [--first-index N] [--adaptive]\n"
+               "           (frame k: the disc's texture after orbiting for T0 + k DT; one trace, K frames)\n"
                "       grt [global options] blackbody -t T [-r Z]\n"
                "       grt [global options] blackbody-spectrum [--min-temperature T] [--max-temperature T]\n"
                "           [--min-redshift Z] [--max-redshift Z] [--width N] [--height N] [-f FILE]\n",
@@ -479,6 +491,8 @@ int main(int argc, char** argv) {
   bool have_pattern = false;    // --filename-pattern given (gbuffer-sequence has no default)
   bool gbuffer_adaptive = false;  // gbuffer / reshade --adaptive: the config's [adaptive_sampling]
   bool seq_adaptive = false;      // gbuffer-sequence / reshade-sequence --adaptive-stacked: the same, stacked
+  std::string orbit_times, raw_out_pattern;  // reshade-orbit --times T0,DT,K, --raw-out-pattern
+  double orbit_t0 = 0.0, orbit_dt = 0.0;
   long long first_index = 0;
   std::vector<std::string> args(argv + 1, argv + argc);
   for (size_t i = 0; i < args.size(); ++i) {
@@ -502,12 +516,15 @@ int main(int argc, char** argv) {
     std::string v;
     if (action.empty() && (a == "render" || a == "render-sequence" || a == "render-ray" || a == "render-ray-at" ||
                            a == "blackbody" || a == "blackbody-spectrum" || a == "gbuffer" || a == "reshade" ||
-                           a == "gbuffer-sequence" || a == "reshade-sequence")) {
+                           a == "gbuffer-sequence" || a == "reshade-sequence" || a == "reshade-orbit")) {
       action = a;
       continue;
     }
     if (action.empty() && a == "--show-sampling-mask") { opts.show_sampling_mask = 1; continue; }
-    if ((action == "gbuffer" || action == "reshade") && a == "--adaptive") { gbuffer_adaptive = true; continue; }
+    if ((action == "gbuffer" || action == "reshade" || action == "reshade-orbit") && a == "--adaptive") {
+      gbuffer_adaptive = true;
+      continue;
+    }
     if ((action == "gbuffer-sequence" || action == "reshade-sequence") && a == "--adaptive-stacked") {
       seq_adaptive = true;
       continue;
@@ -560,9 +577,12 @@ int main(int argc, char** argv) {
     if (a == "--resource-root") { resource_root = v; continue; }
     if (a == "--raw-out") { raw_out = v; continue; }
     if (!action.empty()) {  // subcommand options
-      const bool seq_action = action == "render-sequence" || action == "gbuffer-sequence" || action == "reshade-sequence";
+      const bool seq_action = action == "render-sequence" || action == "gbuffer-sequence" ||
+                              action == "reshade-sequence" || action == "reshade-orbit";
       if (a == "--filename" && !seq_action) filename = v;
-      else if (action == "reshade" && a == "--gbuffer") gbuffer_file = v;
+      else if ((action == "reshade" || action == "reshade-orbit") && a == "--gbuffer") gbuffer_file = v;
+      else if (action == "reshade-orbit" && a == "--times") orbit_times = v;
+      else if (action == "reshade-orbit" && a == "--raw-out-pattern") raw_out_pattern = v;
       else if ((action == "render-sequence" || action == "gbuffer-sequence") && a == "--camera-path") camera_path = v;
       else if (seq_action && a == "--filename-pattern") {
         filename_pattern = v;
@@ -647,7 +667,7 @@ int main(int argc, char** argv) {
   }
   if (action.empty())
     return usage("missing subcommand (render, render-sequence, render-ray, render-ray-at, gbuffer, reshade, "
-                 "gbuffer-sequence, reshade-sequence, blackbody, blackbody-spectrum)");
+                 "gbuffer-sequence, reshade-sequence, reshade-orbit, blackbody, blackbody-spectrum)");
   if (action == "blackbody") {  // run_blackbody (cli/blackbody.rs:7-25): no scene needed
     if (!have_temperature) return usage("blackbody needs --temperature");
     double xyz[3];
@@ -707,6 +727,27 @@ int main(int argc, char** argv) {
     if (action == "reshade-sequence" && !raw_out.empty() && !expand_pattern(raw_out, first_index, &probe))
       return usage("--raw-out of reshade-sequence is a pattern: it needs one %d or %0Nd conversion");
   }
+  if (action == "reshade-orbit") {  // every usage error before the GPU is touched
+    std::string probe;
+    std::vector<double> t;
+    if (gbuffer_file.empty()) return usage("reshade-orbit needs --gbuffer");
+    if (!multi_devices.empty()) return usage("reshade-orbit runs on one GPU (--device); --gpus / --devices do not apply");
+    if (orbit_times.empty()) return usage("reshade-orbit needs --times T0,DT,K");
+    if (!split_csv(orbit_times, t) || t.size() != 3 || !std::isfinite(t[0]) || !std::isfinite(t[1]) ||
+        !(t[2] >= 0.0 && t[2] <= 4294967295.0) || t[2] != std::floor(t[2]))
+      return usage("--times must be T0,DT,K: two finite numbers and a frame count");
+    if (t[2] == 0.0) return usage("--times: K must be at least 1");
+    if (!std::isfinite(t[0] + (t[2] - 1.0) * t[1])) return usage("--times: the last frame's time is not finite");
+    orbit_t0 = t[0];
+    orbit_dt = t[1];
+    n_frames = (long long)t[2];
+    if (!have_pattern) return usage("reshade-orbit needs --filename-pattern (f-%04d.png)");
+    if (!expand_pattern(filename_pattern, first_index, &probe))
+      return usage("--filename-pattern needs one %d or %0Nd conversion for the frame index");
+    if (!raw_out_pattern.empty() && !expand_pattern(raw_out_pattern, first_index, &probe))
+      return usage("--raw-out-pattern needs one %d or %0Nd conversion for the frame index");
+    if (!raw_out.empty()) return usage("reshade-orbit writes many frames: give --raw-out-pattern, not --raw-out");
+  }
   if (filename.empty())
     filename = (action == "render" || action == "reshade") ? "render.png" : (action == "render-ray" ? "rendered-ray.csv" : "rendered-ray-at.csv");
   if (config_file.empty()) return usage("Config file is required for this action");
@@ -754,7 +795,7 @@ int main(int argc, char** argv) {
 #undef GRT_SAME
     }
   }
-  if (action == "reshade") {  // the file's header and length, before the GPU is touched
+  if (action == "reshade" || action == "reshade-orbit") {  // the file's header and length, before the GPU is touched
     if (config_file.empty()) return usage("Config file is required for this action");
     if (grt_gbuffer_read_file(gbuffer_file.c_str(), &gb_info, nullptr)) {
       std::fprintf(stderr, "Error: %s\n", grt_last_error());
@@ -987,6 +1028,132 @@ int main(int argc, char** argv) {
                               &ph_write))
       return wrc;
     std::fprintf(stderr, "[grt] INFO saved image to %s\n", filename.c_str());
+    std::fprintf(stderr, "[grt] phases (ms): load %.1f, create %.1f, hip init %.1f, render %.1f, output %.1f, "
+                 "write %.1f, since start %.1f\n", ph_load, ph_create, ph_init, ph_render, ph_output, ph_write,
+                 ms_since(t_start));
+    elapsed();
+    grt_gbuffer_destroy(gb);
+    if (tracer) grt_scene_destroy(tracer);
+    grt_scene_destroy(scene);
+    grt_host_scene_destroy(hs);
+    return 0;
+  }
+  if (action == "reshade-orbit") {  // one traced frame at K times under this config's appearance
+    const uint32_t K = (uint32_t)n_frames;
+    const size_t n = gb_info.n_pixels, nl = gb_info.n_layers;
+    GBufferHost host(n, nl);
+    const grt_gbuffer_arrays arr = host.arrays();
+    grt_gbuffer* gb = nullptr;
+    t_phase = clk::now();
+    if (grt_gbuffer_read_file(gbuffer_file.c_str(), &gb_info, &arr) || grt_gbuffer_upload(&gb_info, &arr, device, &gb)) {
+      std::fprintf(stderr, "Error: %s\n", grt_last_error());
+      return 1;
+    }
+    std::vector<double> times(K);
+    for (uint32_t k = 0; k < K; ++k) times[k] = orbit_t0 + (double)k * orbit_dt;
+    std::vector<double> xyza(n * 4 * K);
+    float shade_ms = 0;
+    grt_scene* tracer = nullptr;
+    std::vector<uint8_t> status(gbuffer_adaptive ? n * K : 0);
+    std::vector<uint64_t> nsel(K, 0);
+    const uint64_t fail_cap = gbuffer_adaptive ? 1u << 16 : 0;  // failed sub-rays logged per frame
+    std::vector<uint32_t> fail_pix(fail_cap * K), fail_sample(fail_cap * K), fail_steps(fail_cap * K);
+    std::vector<uint8_t> fail_status(fail_cap * K), fail_stop(fail_cap * K);
+    std::vector<grt_subsample_failures> fails(K);
+    double mask[4];
+    const double* maskp = nullptr;
+    if (gbuffer_adaptive) {
+      // as `reshade --adaptive`: this config's scene with the file's recorded camera and
+      // integration parameters is the appearance and the tracer of the missing sub-rays
+      grt_scene_desc td = *d;
+      td.camera = gb_info.camera;
+      td.max_steps = gb_info.max_steps;
+      td.max_radius = gb_info.max_radius;
+      td.step_size = gb_info.step_size;
+      td.epsilon = gb_info.epsilon;
+      td.horizon_epsilon = gb_info.horizon_epsilon;
+      if (grt_scene_create(&td, &tracer)) {
+        std::fprintf(stderr, "Error: %s\n", grt_last_error());
+        return 1;
+      }
+      const std::string sidecar = gbuffer_file + ".sub";
+      grt_gbuffer_sub_info before;
+      std::memset(&before, 0, sizeof(before));
+      if (FILE* f = std::fopen(sidecar.c_str(), "rb")) {  // the sidecar, if present
+        std::fclose(f);
+        if (grt_gbuffer_sub_read_file(sidecar.c_str(), &gb_info, &before, nullptr, nullptr)) {
+          std::fprintf(stderr, "Error: %s\n", grt_last_error());
+          return 1;
+        }
+        GBufferSubHost h(before);
+        const grt_gbuffer_arrays sarr = h.rays.arrays();
+        if (grt_gbuffer_sub_read_file(sidecar.c_str(), &gb_info, &before, h.sub_pixel.data(), &sarr) ||
+            grt_gbuffer_sub_upload(gb, &before, h.sub_pixel.data(), &sarr)) {
+          std::fprintf(stderr, "Error: %s\n", grt_last_error());
+          return 1;
+        }
+      }
+      if (opts.show_sampling_mask) {
+        grt_srgb_to_xyza(opts.sampling_mask_color[0], opts.sampling_mask_color[1], opts.sampling_mask_color[2], 255, mask);
+        maskp = mask;
+      }
+      for (uint32_t k = 0; k < K; ++k) {  // the frames one after the other: each may top the set up
+        fails[k] = grt_subsample_failures{fail_cap, fail_pix.data() + fail_cap * k, fail_sample.data() + fail_cap * k,
+                                          fail_status.data() + fail_cap * k, 0, fail_stop.data() + fail_cap * k,
+                                          fail_steps.data() + fail_cap * k};
+        grt_gbuffer_section_report srep;
+        if (grt_gbuffer_shade_section_at(tracer, gb, &ac, maskp, tracer, xyza.data() + n * 4 * k, nullptr,
+                                         status.data() + n * k, &nsel[k], &fails[k], &srep, times[k])) {
+          std::fprintf(stderr, "Error: %s\n", grt_last_error());
+          return 1;
+        }
+        shade_ms += (float)srep.shade_ms;
+        std::fprintf(stderr, "[grt] adaptive re-shade, frame %u (t = %s): %llu selected pixels, %llu held, %llu traced "
+                     "(%llu sub-rays, %.1f ms)\n", k, grt_host::rust_display_f64(times[k]).c_str(),
+                     (unsigned long long)srep.n_selected, (unsigned long long)srep.n_held,
+                     (unsigned long long)srep.n_traced, (unsigned long long)srep.top_up.rays, srep.trace_ms);
+      }
+      grt_gbuffer_sub_info after;
+      if (grt_gbuffer_sub_info_get(gb, &after)) return 1;
+      if (after.n_sub_pixels > before.n_sub_pixels) {  // the set grew: the next re-shade finds it
+        if (save_sub_sidecar(gb, gb_info, sidecar)) {
+          std::fprintf(stderr, "Error: %s\n", grt_last_error());
+          return 1;
+        }
+        std::fprintf(stderr, "[grt] INFO saved sub-sample set to %s\n", sidecar.c_str());
+      }
+    } else {
+      grt_frame_out fo{nullptr, xyza.data(), nullptr, nullptr, nullptr, nullptr};
+      if (grt_gbuffer_shade_times(scene, gb, K, times.data(), &fo, &shade_ms)) {
+        std::fprintf(stderr, "Error: %s\n", grt_last_error());
+        return 1;
+      }
+    }
+    ph_render = ms_since(t_phase);
+    std::fprintf(stderr, "[grt] re-shaded %llu pixels, %llu layers from %s at %u times, kernel %.2f ms\n",
+                 (unsigned long long)n, (unsigned long long)nl, gbuffer_file.c_str(), K, shade_ms);
+    for (uint32_t k = 0; k < K; ++k) {  // each frame tone-mapped on its own, as `reshade` does
+      std::string name, raw;
+      (void)expand_pattern(filename_pattern, first_index + k, &name);
+      if (!raw_out_pattern.empty()) (void)expand_pattern(raw_out_pattern, first_index + k, &raw);
+      const bool hdr = name.size() >= 4 && name.compare(name.size() - 4, 4, ".hdr") == 0;
+      if (hdr) {
+        std::fprintf(stderr, "[grt] INFO Creating HDR image\n");
+      } else {
+        std::fprintf(stderr, "[grt] INFO Creating non-HDR image\n");
+        std::fprintf(stderr, "[grt] INFO Tone mapping method: %s\n",
+                     opts.tone_mapping == GRT_TONE_GLOBAL_LINEAR ? "GlobalLinear" : "Reinhard");
+      }
+      if (gbuffer_adaptive) {  // the frame's ray log, as `reshade --adaptive` writes it
+        const std::vector<uint8_t> f_status(status.begin() + n * k, status.begin() + n * (k + 1));
+        log_frame_rays(0, 0, gb_info.cols, f_status, host.stop, host.steps, ac.enabled && !maskp, nsel[k], fails[k]);
+      }
+      const std::vector<double> f_xyza(xyza.begin() + n * 4 * k, xyza.begin() + n * 4 * (k + 1));
+      if (int wrc = write_frame(name, raw, f_xyza, gb_info.cols, gb_info.rows, opts.tone_mapping, device, &ph_output,
+                                &ph_write))
+        return wrc;
+      std::fprintf(stderr, "[grt] INFO saved image to %s\n", name.c_str());
+    }
     std::fprintf(stderr, "[grt] phases (ms): load %.1f, create %.1f, hip init %.1f, render %.1f, output %.1f, "
                  "write %.1f, since start %.1f\n", ph_load, ph_create, ph_init, ph_render, ph_output, ph_write,
                  ms_since(t_start));

@@ -9,6 +9,7 @@
 #include <chrono>
 #include <cerrno>
 #include <climits>
+#include <cmath>
 #include <cstring>
 #include <memory>
 #include <mutex>
@@ -154,6 +155,9 @@ struct grt_gbuffer {
   double times[2] = {0.0, 0.0};  // trace, scan + fill (ms)
   GBufferDev arr;
   GBufferSub sub;
+  // scratch of grt_gbuffer_shade_times: the layers' orbit rates, written once per call;
+  // allocated by the first such call and kept (the buffer's layers never change)
+  mutable DevBuf omega;
   grt_gbuffer() { std::memset(&info, 0, sizeof(info)); }
   grt::GBufferArrays view() const { return arr.view(0, info.n_pixels); }
 };
@@ -951,11 +955,17 @@ int grt_gbuffer_supersample(grt_scene* tracer, grt_gbuffer* gb, uint32_t spa, ui
   return 0;
 }
 
-int grt_gbuffer_shade_section(grt_scene* s, grt_gbuffer* gb, const grt_adaptive_config* cfg, const double* mask_xyza,
+}  // extern "C"
+
+// grt_gbuffer_shade_section (time == nullptr: the static kernels, exactly its launches) and
+// grt_gbuffer_shade_section_at (the kernels at *time): one pipeline.  The set is geometry:
+// a top-up appends what grt_gbuffer_supersample leaves, whatever the time.
+static int shade_section_impl(grt_scene* s, grt_gbuffer* gb, const grt_adaptive_config* cfg, const double* mask_xyza,
                               grt_scene* tracer, double* xyza_out, uint8_t* class_out, uint8_t* status_out,
                               uint64_t* n_supersampled, grt_subsample_failures* failures,
-                              grt_gbuffer_section_report* report) {
+                              grt_gbuffer_section_report* report, const double* time) {
   if (!s || !gb || !cfg || !xyza_out) return fail(-EINVAL, "null argument");
+  if (time && !std::isfinite(*time)) return fail(-EINVAL, "g-buffer: the time is not finite");
   if (cfg->samples_per_axis == 0) return fail(-EINVAL, "adaptive_sampling.samples_per_axis must be greater than zero");
   int rc = grt_gbuffer_shape_compatible(&gb->info.shape, &s->desc);
   if (rc) return rc;
@@ -1009,8 +1019,12 @@ int grt_gbuffer_shade_section(grt_scene* s, grt_gbuffer* gb, const grt_adaptive_
     const grt::GBufferArrays sv = S.view();
     for (uint32_t c = 0; c < B.n_chunks; ++c) {
       const uint64_t base = (uint64_t)c * B.chunk_pix;
-      HIP_TRY(grt::launch_gbuffer_shade_sub(dc->d_scene, sv, S.arr.steps(), (const uint32_t*)S.sub_block.p,
-                                            P.held_px + base, B.chunk_pix, d_cnt + 2, base, spa, so, st));
+      if (time)
+        HIP_TRY(grt::launch_gbuffer_shade_sub_at(dc->d_scene, sv, S.arr.steps(), (const uint32_t*)S.sub_block.p,
+                                                 P.held_px + base, B.chunk_pix, d_cnt + 2, base, spa, *time, so, st));
+      else
+        HIP_TRY(grt::launch_gbuffer_shade_sub(dc->d_scene, sv, S.arr.steps(), (const uint32_t*)S.sub_block.p,
+                                              P.held_px + base, B.chunk_pix, d_cnt + 2, base, spa, so, st));
       HIP_TRY(grt::launch_average(P.held_px + base, P.held_px + base, B.chunk_pix, d_cnt + 2, base, spa, B.x64, B.status,
                                   b.x64, fails, st));
     }
@@ -1028,7 +1042,8 @@ int grt_gbuffer_shade_section(grt_scene* s, grt_gbuffer* gb, const grt_adaptive_
   if ((rc = stream_order(*dc, st))) return rc;
   if (supersampled) HIP_TRY(hipMemsetAsync(d_cnt, 0, 32, st));
   HIP_TRY(hipEventRecord(dc->ev0, st));
-  HIP_TRY(grt::launch_gbuffer_shade(dc->d_scene, gb->view(), b.outputs(), st));
+  if (time) HIP_TRY(grt::launch_gbuffer_shade_at(dc->d_scene, gb->view(), *time, b.outputs(), st));
+  else HIP_TRY(grt::launch_gbuffer_shade(dc->d_scene, gb->view(), b.outputs(), st));
   if (supersampled) {
     if ((rc = P.enqueue_select(st, b.x64, b.cls, adaptive_params(cfg, w, h, cfg->minimum_luminance), d_cnt))) return rc;
     if (mask_xyza) HIP_TRY(grt::launch_paint(P.sel, n, d_cnt, mask_xyza, b.x64, st));
@@ -1076,6 +1091,78 @@ int grt_gbuffer_shade_section(grt_scene* s, grt_gbuffer* gb, const grt_adaptive_
     if (n_supersampled) *n_supersampled = cnt[0];
     if ((rc = P.fails[0].read(cnt[1], spa, sub_pass ? failures : nullptr))) return rc;
   }
+  return 0;
+}
+
+extern "C" {
+
+int grt_gbuffer_shade_section(grt_scene* s, grt_gbuffer* gb, const grt_adaptive_config* cfg, const double* mask_xyza,
+                              grt_scene* tracer, double* xyza_out, uint8_t* class_out, uint8_t* status_out,
+                              uint64_t* n_supersampled, grt_subsample_failures* failures,
+                              grt_gbuffer_section_report* report) {
+  return shade_section_impl(s, gb, cfg, mask_xyza, tracer, xyza_out, class_out, status_out, n_supersampled, failures,
+                            report, nullptr);
+}
+
+int grt_gbuffer_shade_section_at(grt_scene* s, grt_gbuffer* gb, const grt_adaptive_config* cfg, const double* mask_xyza,
+                                 grt_scene* tracer, double* xyza_out, uint8_t* class_out, uint8_t* status_out,
+                                 uint64_t* n_supersampled, grt_subsample_failures* failures,
+                                 grt_gbuffer_section_report* report, double time) {
+  return shade_section_impl(s, gb, cfg, mask_xyza, tracer, xyza_out, class_out, status_out, n_supersampled, failures,
+                            report, &time);
+}
+
+int grt_gbuffer_shade_times(grt_scene* s, const grt_gbuffer* gb, uint32_t n_times, const double* times,
+                            const grt_frame_out* out, float* kernel_ms) {
+  if (!s || !gb || !times || !out) return fail(-EINVAL, "null argument");
+  if (n_times == 0) return fail(-EINVAL, "grt_gbuffer_shade_times needs at least one time");
+  for (uint32_t k = 0; k < n_times; ++k)
+    if (!std::isfinite(times[k])) return fail(-EINVAL, "times[" + std::to_string(k) + "] is not finite");
+  if (!out->xyza && !out->xyza64) return fail(-EINVAL, "grt_frame_out needs xyza or xyza64");
+  int rc = grt_gbuffer_shape_compatible(&gb->info.shape, &s->desc);
+  if (rc) return rc;
+  const int device = gb->info.device;
+  const uint64_t per = gb->info.n_pixels;
+  if (per == 0 || per > (uint64_t)INT_MAX) return fail(-EINVAL, "frames of 0 or more than INT_MAX pixels");
+  const uint64_t g = frames_per_group(per, n_times);  // whole frames, at least one (grt_set_sequence_group)
+  DeviceCopy* dc;
+  if ((rc = ensure_device(s, device, &dc))) return rc;
+  std::lock_guard<std::mutex> lk(dc->mu);
+  HIP_TRY(hipSetDevice(device));
+  const uint64_t ng = per * g;  // slots of a full group
+  DevBuf xyza, cls, status, x64, stop, steps, d_times;
+  if ((rc = xyza.alloc(16 * ng)) || (rc = cls.alloc(ng)) || (rc = status.alloc(ng))) return rc;
+  if (out->xyza64 && (rc = x64.alloc(32 * ng))) return rc;
+  if (out->stop && (rc = stop.alloc(ng))) return rc;
+  if (out->steps && (rc = steps.alloc(4 * ng))) return rc;
+  if ((rc = d_times.alloc(8 * (uint64_t)n_times))) return rc;
+  HIP_TRY(hipMemcpy(d_times.p, times, 8 * (uint64_t)n_times, hipMemcpyHostToDevice));
+  if (!gb->omega.p && (rc = gb->omega.alloc(8 * gb->info.n_layers))) return rc;  // a buffer's layers never change
+  const grt::Outputs o{(float*)xyza.p,     (uint8_t*)cls.p,  (uint8_t*)status.p, (double*)x64.p,
+                       (uint32_t*)steps.p, (uint8_t*)stop.p, nullptr};
+  hipStream_t st = nullptr;
+  float total_ms = 0;
+  for (uint32_t f0 = 0; f0 < n_times; f0 += (uint32_t)g) {
+    const uint32_t kg = (uint32_t)std::min<uint64_t>(g, n_times - f0);
+    const uint64_t n = per * kg, at = per * f0;
+    HIP_TRY(hipEventRecord(dc->ev0, st));
+    if (f0 == 0)  // the layers' rates, once per call, in the first group's event time
+      HIP_TRY(grt::launch_gbuffer_orbit_rate(dc->d_scene, gb->view(), gb->info.n_layers, (double*)gb->omega.p, st));
+    HIP_TRY(grt::launch_gbuffer_shade_times(dc->d_scene, gb->view(), gb->arr.steps(), (const double*)d_times.p + f0, kg,
+                                            (const double*)gb->omega.p, o, st));
+    HIP_TRY(hipEventRecord(dc->ev1, st));
+    HIP_TRY(hipEventSynchronize(dc->ev1));
+    float t = 0;
+    HIP_TRY(hipEventElapsedTime(&t, dc->ev0, dc->ev1));
+    total_ms += t;
+    if (out->xyza) HIP_TRY(hipMemcpy(out->xyza + 4 * at, xyza.p, 16 * n, hipMemcpyDeviceToHost));
+    if (out->xyza64) HIP_TRY(hipMemcpy(out->xyza64 + 4 * at, x64.p, 32 * n, hipMemcpyDeviceToHost));
+    if (out->ray_class) HIP_TRY(hipMemcpy(out->ray_class + at, cls.p, n, hipMemcpyDeviceToHost));
+    if (out->status) HIP_TRY(hipMemcpy(out->status + at, status.p, n, hipMemcpyDeviceToHost));
+    if (out->stop) HIP_TRY(hipMemcpy(out->stop + at, stop.p, n, hipMemcpyDeviceToHost));
+    if (out->steps) HIP_TRY(hipMemcpy(out->steps + at, steps.p, 4 * n, hipMemcpyDeviceToHost));
+  }
+  if (kernel_ms) *kernel_ms = total_ms;
   return 0;
 }
 

@@ -201,6 +201,23 @@ hipError_t launch_gbuffer_shade_sub_stack(const DevScene* d_scene, const GBuffer
                                           uint64_t npix, const uint32_t* d_sel, uint64_t n_sel,
                                           const unsigned long long* d_count, uint64_t base, uint32_t spa,
                                           const Outputs& out, hipStream_t stream);
+// The disc's orbital motion (geodesic.hip): `gb` shaded at d_times[0..n_times) in one launch
+// (gbuffer_shade_times_kernel), frame k into slots [k * gb.n, (k + 1) * gb.n) of out, d_steps
+// the buffer's recorded step counts; and launch_gbuffer_shade / launch_gbuffer_shade_sub at one
+// time t (gbuffer_shade_at_kernel, gbuffer_shade_sub_at_kernel).  The K-times kernel reads each
+// layer's rate from d_omega (n_layers doubles), which launch_gbuffer_orbit_rate writes once per
+// call; the single-time kernels compute it where a layer is coloured.
+hipError_t launch_gbuffer_orbit_rate(const DevScene* d_scene, const GBufferArrays& gb, uint64_t n_layers,
+                                     double* d_omega, hipStream_t stream);
+hipError_t launch_gbuffer_shade_times(const DevScene* d_scene, const GBufferArrays& gb, const uint32_t* d_steps,
+                                      const double* d_times, uint32_t n_times, const double* d_omega, const Outputs& out,
+                                      hipStream_t stream);
+hipError_t launch_gbuffer_shade_at(const DevScene* d_scene, const GBufferArrays& gb, double t, const Outputs& out,
+                                   hipStream_t stream);
+hipError_t launch_gbuffer_shade_sub_at(const DevScene* d_scene, const GBufferArrays& sub, const uint32_t* d_sub_steps,
+                                       const uint32_t* d_sub_block, const uint32_t* d_sel, uint64_t n_sel,
+                                       const unsigned long long* d_count, uint64_t base, uint32_t spa, double t,
+                                       const Outputs& out, hipStream_t stream);
 // The selected pixels d_sel (*d_count of them, ascending) split by sub_block into the ones
 // the set holds and the ones it misses, each in ascending order, with their counts
 // (gbuffer.hip; n_max <= INT_MAX entries of room).  d_flags: 2 * n_max bytes of scratch.

@@ -613,6 +613,24 @@ def _gbuffer_sub_host_arrays(sub: L.GBufferSubInfo, arrays: Optional[dict] = Non
     return out, c, L.ptr(out["sub_pixel"], C.c_uint32)
 
 
+def _frame_out_arrays(k: int, n: int, fields):
+    """(dict of zeroed [k, n(, 4)] arrays for `fields`, the grt_frame_out over them)."""
+    want = set(fields)
+    arrays = {}
+    for name, shape, dt in (("xyza", (k, n, 4), np.float32), ("xyza64", (k, n, 4), np.float64),
+                            ("class", (k, n), np.uint8), ("status", (k, n), np.uint8), ("stop", (k, n), np.uint8),
+                            ("steps", (k, n), np.uint32)):
+        if name in want:
+            arrays[name] = np.zeros(shape, dt)
+    out = L.FrameOut(L.ptr(arrays["xyza"], C.c_float) if "xyza" in arrays else None,
+                     L.dptr(arrays["xyza64"]) if "xyza64" in arrays else None,
+                     L.ptr(arrays["class"], C.c_uint8) if "class" in arrays else None,
+                     L.ptr(arrays["status"], C.c_uint8) if "status" in arrays else None,
+                     L.ptr(arrays["stop"], C.c_uint8) if "stop" in arrays else None,
+                     L.ptr(arrays["steps"], C.c_uint32) if "steps" in arrays else None)
+    return arrays, out
+
+
 class GBufferMissing(L.GrtError):
     """shade_section without a tracer met selected pixels the sub-sample set does not hold
     (-ENODATA); `report` is the call's report (n_missing)."""
@@ -668,6 +686,25 @@ class GBuffer:
         res.stats = {"kernel_ms": float(ms.value)}
         return res
 
+    def shade_orbit(self, scene: "Scene", times, fields=("xyza", "xyza64", "class", "status", "stop", "steps"),
+                    device: Optional[int] = None) -> dict:
+        """The buffer under `scene`'s appearance at each of `times`, the disc's texture
+        orbiting at the emitter's own rate (grt_gbuffer_shade_times; "fast light": one
+        coordinate time per frame, no light-travel delay).  Frame k is `shade` of the buffer
+        whose (u, v) went through gbuffer_orbit_uv at times[k], bit for bit.  Returns what
+        shade_sequence returns: the `fields` with a leading frame axis, plus "stats"."""
+        info = self.info
+        if device is not None and device != info.device:
+            raise L.GrtError(f"grt_gbuffer_shade_times failed (-22): the g-buffer is on device {info.device}, "
+                             f"not {device}")
+        t = np.ascontiguousarray(times, np.float64).reshape(-1)
+        arrays, out = _frame_out_arrays(len(t), int(info.n_pixels), fields)
+        ms = C.c_float()
+        L.check(L.lib().grt_gbuffer_shade_times(scene._s, self._h, len(t), L.dptr(t), C.byref(out), C.byref(ms)),
+                "grt_gbuffer_shade_times")
+        arrays["stats"] = {"kernel_ms": float(ms.value)}
+        return arrays
+
     @property
     def sub_info(self) -> L.GBufferSubInfo:
         """Sizes of the sub-sample set (samples_per_axis 0: the buffer holds none)."""
@@ -698,13 +735,15 @@ class GBuffer:
 
     def shade_section(self, scene: "Scene", adaptive: Optional[L.AdaptiveConfig] = None,
                       tracer: Optional["Scene"] = None, sampling_mask_xyza=None, failure_capacity: int = 0,
-                      log_events: bool = False):
+                      log_events: bool = False, time: Optional[float] = None):
         """The adaptive frame of the buffer under `scene`'s appearance
         (grt_gbuffer_shade_section): bit-identical to `render_section_ex` of a scene with
         this appearance and the traced geometry, camera and integration parameters.
         Selected pixels whose sub-rays the buffer does not hold are traced under `tracer`
-        and appended; without a tracer they raise GBufferMissing.  Returns (SectionResult,
-        report dict); the result's stats are the top-up's."""
+        and appended; without a tracer they raise GBufferMissing.  With `time` the disc's
+        texture has orbited for that coordinate time (grt_gbuffer_shade_section_at; the set
+        keeps unrotated numbers).  Returns (SectionResult, report dict); the result's stats
+        are the top-up's."""
         n = int(self.info.n_pixels)
         out = np.zeros((n, 4), np.float64)
         cls = np.zeros(n, np.uint8)
@@ -720,18 +759,21 @@ class GBuffer:
                                     L.ptr(fst, C.c_uint8), 0, L.ptr(fsp, C.c_uint8) if log_events else None,
                                     L.ptr(fn, C.c_uint32) if log_events else None)
         rep = L.GBufferSectionReport()
-        rc = L.lib().grt_gbuffer_shade_section(scene._s, self._h, C.byref(adaptive or scene.adaptive),
-                                               L.dptr(mask) if mask is not None else None,
-                                               tracer._s if tracer is not None else None, L.dptr(out),
-                                               L.ptr(cls, C.c_uint8), L.ptr(status, C.c_uint8), C.byref(nsel),
-                                               C.byref(fails), C.byref(rep))
+        what = "grt_gbuffer_shade_section" if time is None else "grt_gbuffer_shade_section_at"
+        args = (scene._s, self._h, C.byref(adaptive or scene.adaptive), L.dptr(mask) if mask is not None else None,
+                tracer._s if tracer is not None else None, L.dptr(out), L.ptr(cls, C.c_uint8),
+                L.ptr(status, C.c_uint8), C.byref(nsel), C.byref(fails), C.byref(rep))
+        if time is None:
+            rc = L.lib().grt_gbuffer_shade_section(*args)
+        else:
+            rc = L.lib().grt_gbuffer_shade_section_at(*args, float(time))
         report = {"n_selected": int(rep.n_selected), "n_held": int(rep.n_held), "n_traced": int(rep.n_traced),
                   "n_missing": int(rep.n_missing), "shade_ms": float(rep.shade_ms), "trace_ms": float(rep.trace_ms),
                   "top_up": _stats_dict(rep.top_up)}
         if rc == -errno.ENODATA:
             msg = L.lib().grt_last_error().decode(errors="replace")
-            raise GBufferMissing(f"grt_gbuffer_shade_section failed ({rc}): {msg}", report)
-        L.check(rc, "grt_gbuffer_shade_section")
+            raise GBufferMissing(f"{what} failed ({rc}): {msg}", report)
+        L.check(rc, what)
         m = min(int(fails.count), failure_capacity)
         rows = np.stack([fp[:m], fs[:m], fst[:m].astype(np.uint32)], axis=1)
         if not log_events:
@@ -833,19 +875,7 @@ def shade_sequence(buffers, scene: "Scene", fields=("xyza", "xyza64", "class", "
     bufs = list(buffers)
     k = len(bufs)
     n = int(bufs[0].info.n_pixels) if k else 0
-    want = set(fields)
-    arrays = {}
-    for name, shape, dt in (("xyza", (k, n, 4), np.float32), ("xyza64", (k, n, 4), np.float64),
-                            ("class", (k, n), np.uint8), ("status", (k, n), np.uint8), ("stop", (k, n), np.uint8),
-                            ("steps", (k, n), np.uint32)):
-        if name in want:
-            arrays[name] = np.zeros(shape, dt)
-    out = L.FrameOut(L.ptr(arrays["xyza"], C.c_float) if "xyza" in arrays else None,
-                     L.dptr(arrays["xyza64"]) if "xyza64" in arrays else None,
-                     L.ptr(arrays["class"], C.c_uint8) if "class" in arrays else None,
-                     L.ptr(arrays["status"], C.c_uint8) if "status" in arrays else None,
-                     L.ptr(arrays["stop"], C.c_uint8) if "stop" in arrays else None,
-                     L.ptr(arrays["steps"], C.c_uint32) if "steps" in arrays else None)
+    arrays, out = _frame_out_arrays(k, n, fields)
     handles = (C.c_void_p * max(k, 1))(*[b._h for b in bufs])
     ms = C.c_float()
     L.check(L.lib().grt_gbuffer_shade_sequence(scene._s, k, handles, C.byref(out), C.byref(ms)),
@@ -943,6 +973,30 @@ def shade_section_sequence(buffers, scene: "Scene", adaptive: Optional[L.Adaptiv
         arrays["n_failed_subsamples"].append(int(fails[f].count) - len(events))
         arrays["subsample_events"].append(events)
     return arrays, report
+
+
+def orbit_rate(geometry: int, radius: float, a: float, r: float) -> float:
+    """d(phi)/dt of the shade pass's disc emitter at radius r (grt_orbit_rate): sqrt(M) /
+    (r^1.5 + a sqrt(M)) with M = radius / 2; +0.0 for the flat charts."""
+    out = C.c_double()
+    L.check(L.lib().grt_orbit_rate(int(geometry), float(radius), float(a), float(r), C.byref(out)), "grt_orbit_rate")
+    return float(out.value)
+
+
+def gbuffer_orbit_uv(shape: L.GBufferShape, object, u, v, radius, time: float):
+    """(u', v') of layer arrays (a buffer's or a sub-sample set's) at coordinate time `time`:
+    the host restatement of the rule GBuffer.shade_orbit applies on the device
+    (grt_gbuffer_orbit_uv).  Disc layers turn about (0.5, 0.5) by -Omega(radius) * time; every
+    other layer is returned unchanged."""
+    obj = np.ascontiguousarray(object, np.uint8).reshape(-1)
+    n = len(obj)
+    arr = [np.ascontiguousarray(x, np.float64).reshape(-1) for x in (u, v, radius)]
+    if any(len(x) != n for x in arr):
+        raise L.GrtError("grt_gbuffer_orbit_uv failed (-22): object, u, v and radius differ in length")
+    uo, vo = np.zeros(n, np.float64), np.zeros(n, np.float64)
+    L.check(L.lib().grt_gbuffer_orbit_uv(C.byref(shape), n, L.ptr(obj, C.c_uint8), L.dptr(arr[0]), L.dptr(arr[1]),
+                                         L.dptr(arr[2]), float(time), L.dptr(uo), L.dptr(vo)), "grt_gbuffer_orbit_uv")
+    return uo, vo
 
 
 def gbuffer_compatible(traced: L.SceneDesc, appearance: L.SceneDesc) -> None:

@@ -940,6 +940,63 @@ int grt_gbuffer_shade_section_sequence(grt_scene* appearance, uint32_t n, grt_gb
                                        uint64_t* n_supersampled /* [n] */, grt_subsample_failures* failures /* [n] */,
                                        uint64_t* per_frame /* [n][4] */, grt_gbuffer_section_sequence_report* report);
 
+/* ---- the disc's orbital motion from one geometry buffer ----
+ * The shade pass takes a disc emitter's four-velocity from a circular orbit with
+ *   Omega(r) = sqrt(M) / (r^1.5 + a sqrt(M)),  M = radius / 2
+ * (the Doppler shift and the beaming come from it), so a disc whose texture orbits at that
+ * rate is the animation of the very scene being rendered.  It needs no geodesic: a buffer
+ * keeps, per layer, the disc's texture coordinates and its radius.  The rule:
+ *   orbit_rate(geometry, r_s, a, r): +0.0 for GRT_GEOM_EUCLIDEAN and
+ *     GRT_GEOM_EUCLIDEAN_SPHERICAL (the emitter is at rest there); else m = 0.5 r_s,
+ *     sm = sqrt(m), sm / (pow(r, 1.5) + a sm);
+ *   orbit_uv(omega, t, u, v): th = omega t; (u, v) unchanged bit for bit when th == 0 or th is
+ *     not finite; else (s, c) = sincos(th), du = u - 0.5, dv = v - 0.5,
+ *     u' = 0.5 + (du c + dv s), v' = 0.5 + (dv c - du s)
+ * -- matter seen at in-plane angle phi at time t sat at phi - Omega t at time 0, and a disc's
+ * uv is 0.5 + 0.5 rho (cos phi, sin phi), so the lookup point turns about (0.5, 0.5).  It
+ * applies to the layers of GRT_OBJ_DISC objects with r = the layer's recorded radius; sphere
+ * layers and the celestial sphere are static.  r_s and a are the appearance scene's (the
+ * shape key makes them the traced ones).
+ * "Fast light": all layers of a frame are shaded at the same coordinate time t.  The buffer
+ * does not record t along the ray, and light-travel delay is ignored.
+ * Host and device state the rule with the same operations in the same order, without
+ * contraction, over the same glibc-exact pow and sincos: they agree bit for bit for
+ * |Omega t| < 105414350 (the range of the exact sincos); beyond it the device uses the
+ * fallback the render uses, within 1 ulp.
+ * Not covered: light-travel delay, VolumetricDisc scenes (refused as everywhere), the fused
+ * arithmetic, stacked adaptive frames over many times (loop grt_gbuffer_shade_section_at),
+ * times combined with camera sequences, the multi-GPU frame, user-given rotation laws. */
+/* d(phi)/dt of the shade pass's disc emitter at radius r; +0.0 for the flat charts.
+ * -EINVAL: unknown geometry, null out. */
+int grt_orbit_rate(int32_t geometry, double radius, double a, double r, double* omega);
+/* Host restatement of the rule over layer arrays (a buffer's or a sub-sample set's): the
+ * reference the device is tested against, and a tool for users who post-process downloaded
+ * arrays.  -EINVAL: null pointer, non-finite time, unknown geometry, an object index >=
+ * shape->n_objects (nothing is written then).  u_out / v_out may alias u / v. */
+int grt_gbuffer_orbit_uv(const grt_gbuffer_shape* shape, uint64_t n_layers, const uint8_t* object,
+                         const double* u, const double* v, const double* radius, double time,
+                         double* u_out, double* v_out);
+/* n_times frames of one buffer under `appearance`, frame k at times[k], frame-major in `out`
+ * (fields as grt_gbuffer_shade_sequence; stop and steps are copies of the recorded ones per
+ * frame): one kernel launch and one set of device-to-host copies per group of
+ * grt_set_sequence_group rays (whole frames, at least one).  Frame k equals grt_gbuffer_shade
+ * of the buffer whose disc layers' (u, v) went through grt_gbuffer_orbit_uv at times[k], bit
+ * for bit; a time of 0 gives grt_gbuffer_shade's frame.  -EINVAL for n_times = 0, a
+ * non-finite time, a shape key that differs (grt_last_error names the field), or neither
+ * xyza nor xyza64 given.  kernel_ms (nullable): summed event time of the launches. */
+int grt_gbuffer_shade_times(grt_scene* appearance, const grt_gbuffer* gb, uint32_t n_times,
+                            const double* times, const grt_frame_out* out, float* kernel_ms);
+/* grt_gbuffer_shade_section at one time: the same pipeline with the 1-spp pass and the
+ * sub-ray pass shaded at `time`.  The sub-sample set stays pure geometry: a top-up appends
+ * the unrotated numbers grt_gbuffer_supersample leaves, and the time enters only at the
+ * texture lookup.  The selection at `time` may need pixels the set lacks: the tracer /
+ * -ENODATA rules are grt_gbuffer_shade_section's.  -EINVAL for a non-finite time. */
+int grt_gbuffer_shade_section_at(grt_scene* appearance, grt_gbuffer* gb, const grt_adaptive_config* cfg,
+                                 const double* sampling_mask_xyza, grt_scene* tracer, double* xyza_out,
+                                 uint8_t* class_out, uint8_t* status_out, uint64_t* n_supersampled,
+                                 grt_subsample_failures* failures, grt_gbuffer_section_report* report,
+                                 double time);
+
 /* The device hit pool that keeps the window candidates past a ray's GRT_MAX_HITS slots
  * (no reference counterpart: the reference's per-ray Vec grows, scene.rs:139-152).
  * A trace starts with the pool at its minimum (grt_set_hit_pool_min, 2^20 records) or
