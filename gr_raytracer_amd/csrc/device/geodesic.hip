@@ -136,59 +136,7 @@ namespace seq {
 #define GRT_RAY_TIMES 0  // diagnostic builds only: per-ray schedule record (tools/c4_ray_times.py)
 #endif
 
-// The OCML fallbacks below run outside glibc's fast paths only (never for the angles and
-// controller ratios of a render): out of line, so their code stays out of the hot loops.
-#ifndef GRT_SLOW_NOINLINE
-#define GRT_SLOW_NOINLINE 1
-#endif
-#if GRT_SLOW_NOINLINE
-#define GRT_SLOW __device__ __attribute__((noinline, cold))
-#else
-#define GRT_SLOW GDEV
-#endif
-GRT_SLOW double ocml_pow(double x, double y) { return pow(x, y); }
-// returned by value: a pointer into the caller's frame passed to an out-of-line call would
-// keep the caller's (sin, cos) in scratch memory at every rsincos site, fast path included
-struct SinCos {
-  double s, c;
-};
-GRT_SLOW SinCos ocml_sincos(double x) {
-  SinCos r;
-  sincos(x, &r.s, &r.c);
-  return r;
-}
-GRT_SLOW double ocml_sin(double x) { return sin(x); }
-GRT_SLOW double ocml_cos(double x) { return cos(x); }
-
-// f64::powf == glibc pow: bit-exact on glibc's fast path, OCML outside it.
-GDEV double rpow(double x, double y) {
-  double r;
-  if (glibc::pow_fast(x, y, &r)) return r;
-  return ocml_pow(x, y);
-}
-// f64::sin / f64::cos of one operand in one reference function: the compiler fuses
-// them into glibc's sincos (glibc_math.h); a lone sin() stays glibc's sin.  Both are
-// bit-exact for |x| < 105414350; OCML beyond (never reached by angles here).
-GDEV void rsincos(double x, double* s, double* c) {
-  double ss, cc;
-  if (!glibc::sincos_fast(x, &ss, &cc)) {
-    const SinCos r = ocml_sincos(x);
-    ss = r.s;
-    cc = r.c;
-  }
-  *s = ss;
-  *c = cc;
-}
-GDEV double rsin(double x) {
-  double r;
-  if (glibc::sin_fast(x, &r)) return r;
-  return ocml_sin(x);
-}
-GDEV double rcos(double x) {
-  double r;
-  if (glibc::cos_fast(x, &r)) return r;
-  return ocml_cos(x);
-}
+#include "appearance.h"
 
 // x1 / y and x2 / y with one reciprocal refinement.  This is the compiler's own IEEE f64
 // division expansion (div_scale, rcp, 2 Newton steps, div_fmas, div_fixup -- identical
@@ -396,42 +344,9 @@ constexpr int MAX_RETRY = 100;
 constexpr double H_MAX = 1.0, H_MIN = 1e-12, H_GROWTH = 4.0;
 constexpr double POW_SATURATED = 1800.0;  // (H_GROWTH / BETA)^5 = 1734.1, plus margin
 
-GDEV double rclamp(double v, double lo, double hi) {  // f64::clamp
-  if (v < lo) v = lo;
-  if (v > hi) v = hi;
-  return v;
-}
 GDEV double rem_euclid(double x, double m) {
   double r = fmod(x, m);
   return r < 0.0 ? r + fabs(m) : r;
-}
-GDEV uint32_t sat_u32(double v) {
-  if (!(v > 0.0)) return 0u;
-  if (v >= 4294967296.0) return 0xffffffffu;
-  return (uint32_t)v;
-}
-GDEV uint64_t sat_u64(double v) {
-  if (!(v > 0.0)) return 0ull;
-  if (v >= 18446744073709551616.0) return ~0ull;
-  return (uint64_t)v;
-}
-
-struct XYZA {
-  double x, y, z, a;
-};
-
-// color.rs:49-69  ("other over self")
-GDEV XYZA blend(const XYZA& self, const XYZA& other) {
-  double ab = rclamp(self.a, 0.0, 1.0);
-  double af = rclamp(other.a, 0.0, 1.0);
-  double ao = af + ab * (1.0 - af);
-  if (ao <= 0.0) return XYZA{0.0, 0.0, 0.0, 0.0};
-  XYZA r;
-  r.x = (other.x * af + self.x * ab * (1.0 - af)) / ao;
-  r.y = (other.y * af + self.y * ab * (1.0 - af)) / ao;
-  r.z = (other.z * af + self.z * ab * (1.0 - af)) / ao;
-  r.a = ao;
-  return r;
 }
 
 // Per-ray constants: observer energy (redshift.rs:40-60) and, for KerrBL, the
@@ -1491,124 +1406,6 @@ GDEV bool killing_coefficients(const DevScene& S, double r, double* u_t, double*
   *u_t = ut;
   *u_phi = omega * ut;
   return true;
-}
-
-// ============================================================== shading =========
-GDEV XYZA texel(const DevScene& S, const DevTexture& t, uint32_t x, uint32_t y) {
-  uint32_t px = t.rgba[(uint64_t)y * t.width + x];
-  double r = S.srgb_lin[px & 0xffu];
-  double g = S.srgb_lin[(px >> 8) & 0xffu];
-  double b = S.srgb_lin[(px >> 16) & 0xffu];
-  XYZA c;  // srgb_to_xyz (color.rs:310-332), nalgebra gemv order
-  c.x = 0.4124564 * r;
-  c.x = 0.3575761 * g + c.x;
-  c.x = 0.1804375 * b + c.x;
-  c.y = 0.2126729 * r;
-  c.y = 0.7151522 * g + c.y;
-  c.y = 0.0721750 * b + c.y;
-  c.z = 0.0193339 * r;
-  c.z = 0.1191920 * g + c.z;
-  c.z = 0.9503041 * b + c.z;
-  c.a = (double)(px >> 24) / 255.0;
-  return c;
-}
-
-// The reference's table searches (binary search, then idx = partition point - 1) over a
-// sorted table a[0..n) with a[0] < x < a[n - 1]: the last idx with a[idx] <= x.  Both
-// tables are evenly spaced grids (host/setup.cpp: x0 + i * step), so the index is guessed
-// from the spacing and corrected by comparisons against the table itself: the same idx
-// for any sorted table (a poor guess only costs more steps), with two dependent loads
-// instead of the ~10 of the bisection.
-GDEV uint32_t lut_index(const double* a, uint32_t n, double a0, double a_last, double x) {
-  const double g = (x - a0) * ((double)(n - 1) / (a_last - a0));
-  uint32_t idx = g >= (double)(n - 2) ? n - 2 : (g > 0.0 ? (uint32_t)g : 0u);
-  while (idx < n - 2 && a[idx + 1] <= x) ++idx;
-  while (idx > 0 && a[idx] > x) --idx;
-  return idx;
-}
-
-// texture.rs:149-195 over a (log10 T, XYZ) table in global memory or LDS
-GDEV XYZA sample_blackbody_lut(const double* lt, const double* c, uint32_t n, double temperature) {
-  double log_t = log10(fmax(temperature, 10.0));
-  const double lt_first = lt[0], lt_last = lt[n - 1];
-  if (!isfinite(log_t) || log_t <= lt_first) return XYZA{c[0], c[1], c[2], 1.0};
-  if (log_t >= lt_last) return XYZA{c[3 * (n - 1)], c[3 * (n - 1) + 1], c[3 * (n - 1) + 2], 1.0};
-  const uint32_t idx = lut_index(lt, n, lt_first, lt_last, log_t);
-  double lt0 = lt[idx], lt1 = lt[idx + 1];
-  const double* c0 = c + 3 * idx;
-  const double* c1 = c + 3 * (idx + 1);
-  double t = (log_t - lt0) / (lt1 - lt0);
-  return XYZA{c0[0] + t * (c1[0] - c0[0]), c0[1] + t * (c1[1] - c0[1]), c0[2] + t * (c1[2] - c0[2]), 1.0};
-}
-GDEV XYZA sample_blackbody(const DevScene& S, double temperature) {
-  return sample_blackbody_lut(S.bb_log_t, S.bb_xyz, S.bb_n, temperature);
-}
-
-// TextureMap::color_at_uv (texture.rs:93-257); bb_lt / bb_xyz: the blackbody table
-// (S.bb_log_t / S.bb_xyz, or an LDS copy of it)
-GDEV XYZA texture_color_lut(const DevScene& S, const DevTexture& t, double u, double v, double redshift,
-                            double temperature, const double* bb_lt, const double* bb_xyz) {
-  XYZA c;
-  if (t.kind == GRT_TEX_BITMAP) {
-    uint32_t width = t.width, height = t.height;
-    double p_x = (double)width * u;
-    double p_y = (double)height * v;
-    uint32_t xf = min(sat_u32(floor(p_x)), width - 1);
-    uint32_t yf = min(sat_u32(floor(p_y)), height - 1);
-    uint32_t xc = min(sat_u32(ceil(p_x)), width - 1);
-    uint32_t yc = min(sat_u32(ceil(p_y)), height - 1);
-    XYZA c00 = texel(S, t, xf, yf), c01 = texel(S, t, xf, yc);
-    XYZA c11 = texel(S, t, xc, yc), c10 = texel(S, t, xc, yf);
-    double dx = p_x - (double)xf;
-    double dy = p_y - (double)yf;
-    double w00 = (1.0 - dx) * (1.0 - dy);
-    double w01 = (1.0 - dx) * dy;
-    double w10 = dx * (1.0 - dy);
-    double w11 = dx * dy;
-    c.x = w00 * c00.x + w10 * c10.x + w01 * c01.x + w11 * c11.x;
-    c.y = w00 * c00.y + w10 * c10.y + w01 * c01.y + w11 * c11.y;
-    c.z = w00 * c00.z + w10 * c10.z + w01 * c01.z + w11 * c11.z;
-    c.a = w00 * c00.a + w10 * c10.a + w01 * c01.a + w11 * c11.a;
-  } else if (t.kind == GRT_TEX_CHECKER) {
-    uint64_t ut = sat_u64(floor(u * t.cw));
-    uint64_t vt = sat_u64(floor(v * t.ch));
-    const double* cc = ((ut + vt) % 2 == 0) ? t.c1 : t.c2;
-    c = XYZA{cc[0], cc[1], cc[2], cc[3]};
-  } else {
-    c = sample_blackbody_lut(bb_lt, bb_xyz, S.bb_n, temperature * redshift);
-  }
-  // apply_beaming (color.rs:72-80): powf(redshift, e); pow(x, +-0) is 1 for every x (C99
-  // F.9.4.4, glibc), so the stock scenes' exponent 0 skips the call
-  double f = t.beaming == 0.0 ? 1.0 : rpow(redshift, t.beaming);
-  return XYZA{c.x * f, c.y * f, c.z * f, c.a};
-}
-GDEV XYZA texture_color(const DevScene& S, const DevTexture& t, double u, double v, double redshift,
-                        double temperature) {
-  return texture_color_lut(S, t, u, v, redshift, temperature, S.bb_log_t, S.bb_xyz);
-}
-
-// KerrTemperatureComputer::compute_temperature (temperature.rs:198-253); lut_r / lut_t:
-// the object's (r, T) table in global memory or an LDS copy
-GDEV int compute_temperature_lut(const DevObject& o, const double* lut_r, const double* lut_t, double radius,
-                                 double* out) {
-  if (o.temp_kind == GRT_TEMP_CONSTANT) {
-    *out = o.temp_constant;
-    return GRT_OK;
-  }
-  if (!isfinite(radius)) return GRT_ERR_NON_FINITE_RADIUS;
-  if (radius < o.r_isco) return GRT_ERR_BELOW_RISCO;
-  uint32_t n = o.lut_n;
-  const double r_first = lut_r[0], r_last = lut_r[n - 1];
-  if (radius <= r_first) { *out = lut_t[0]; return GRT_OK; }
-  if (radius >= r_last) { *out = lut_t[n - 1]; return GRT_OK; }
-  const uint32_t idx = lut_index(lut_r, n, r_first, r_last, radius);
-  double r0 = lut_r[idx], t0 = lut_t[idx], r1 = lut_r[idx + 1], t1 = lut_t[idx + 1];
-  double t = (radius - r0) / (r1 - r0);
-  *out = t0 + t * (t1 - t0);
-  return GRT_OK;
-}
-GDEV int compute_temperature(const DevObject& o, double radius, double* out) {
-  return compute_temperature_lut(o, o.lut_r, o.lut_t, radius, out);
 }
 
 #include "volumetric.h"
@@ -3601,22 +3398,6 @@ GDEV int shade_record(const DevScene& S, const RayConst& rc, const DevObject& o,
   return GRT_OK;
 }
 
-// (the step count goes to out.steps from store_ray, KerrBL's from shade_kernel)
-GDEV void write_out(const Outputs& out, uint64_t idx, const XYZA& c, int cls, int status, int stop, uint32_t hits) {
-  if (out.hits) out.hits[idx] = hits;
-  reinterpret_cast<float4*>(out.xyza)[idx] = make_float4((float)c.x, (float)c.y, (float)c.z, (float)c.a);
-  out.cls[idx] = (uint8_t)cls;
-  out.status[idx] = (uint8_t)status;
-  if (out.xyza64) {
-    double* d = out.xyza64 + 4 * idx;
-    d[0] = c.x;
-    d[1] = c.y;
-    d[2] = c.z;
-    d[3] = c.a;
-  }
-  if (out.stop) out.stop[idx] = (uint8_t)stop;
-}
-
 // ---- a ray's candidates in window order: workspace slots 0..GRT_WS_SLOTS-1, then the
 // hit pool's list (HitPool).
 struct RecRef {
@@ -3936,414 +3717,6 @@ hipError_t launch_gbuffer_fill(int geometry, const DevScene* d_scene, const Work
   }
 }
 #endif  // GRT_MAIN_TU || GRT_KERR_BL_TU || GRT_SEQ
-
-#if GRT_MAIN_TU
-// Deferred shade: shade_kernel's window colours, terminal colour and composite from a
-// geometry buffer and the appearance scene S (textures, LUTs, temperatures, the celestial
-// sphere, the hit threshold) -- no geometry, one lane per pixel.  The operations and their
-// order are shade_kernel's, so the pixel has its bits.  Two passes over a pixel's layers:
-// front to back for the opacity, back to front for the blend (each layer's colour is
-// evaluated in both; a pixel may have any number of layers).
-GDEV int gbuffer_layer_color(const DevScene& S, const GBufferArrays& gb, uint64_t k, XYZA* col) {
-  const DevObject& o = S.obj[gb.object[k]];
-  double temperature;
-  if (o.kind != GRT_OBJ_SPHERE) {
-    int e = compute_temperature(o, gb.radius[k], &temperature);
-    if (e != GRT_OK) return e;
-  } else {
-    temperature = o.temperature;
-  }
-  *col = texture_color(S, o.tex, gb.u[k], gb.v[k], gb.redshift[k], temperature);
-  return GRT_OK;
-}
-
-// One ray of a buffer (`src` in gb's arrays) shaded into output slot `dst`: the body of
-// gbuffer_shade_kernel below, for gbuffer_shade_sub_kernel.  That kernel keeps its own copy
-// of these lines: calling this function from it compiles to other code than the one its
-// times were measured on (tools/kernel_hashes.py), and its code is to stay as it is.
-GDEV void gbuffer_shade_ray(const DevScene& S, const GBufferArrays& gb, uint64_t src, const Outputs& out,
-                            uint64_t dst) {
-  const int status = gb.status[src];
-  const int stop = gb.stop[src];
-  const XYZA fail{0.0, 0.0, 0.0, 1.0};
-  if (status != GRT_OK) {
-    write_out(out, dst, fail, GRT_CLASS_ESCAPED, status, stop, 0u);
-    return;
-  }
-  const uint64_t l0 = gb.layer_start[src], l1 = gb.layer_start[src + 1];
-  double opacity = 0.0;
-  for (uint64_t k = l0; k < l1; ++k) {
-    XYZA col;
-    int e = gbuffer_layer_color(S, gb, k, &col);
-    if (e != GRT_OK) {  // a temperature error the traced scene did not have: the window error's pixel
-      write_out(out, dst, fail, GRT_CLASS_ESCAPED, e, stop, (uint32_t)(k - l0));
-      return;
-    }
-    double alpha = rclamp(col.a, 0.0, 1.0);
-    opacity = alpha + opacity * (1.0 - alpha);
-  }
-  XYZA result{0.0, 0.0, 0.0, 1.0};
-  int cls = GRT_CLASS_CAPTURED;
-  if (stop == GRT_STOP_HORIZON || stop == GRT_STOP_CLOSED_ORBIT) {
-    result = blend(result, XYZA{0.0, 0.0, 0.0, 1.0});
-  } else if (stop == GRT_STOP_CELESTIAL) {
-    result = blend(result, texture_color(S, S.celestial, gb.sky_u[src], gb.sky_v[src], gb.sky_redshift[src],
-                                         S.celestial_temperature));
-    cls = GRT_CLASS_ESCAPED;
-  }
-  for (uint64_t k = l1; k > l0; --k) {
-    XYZA col{0.0, 0.0, 0.0, 0.0};
-    (void)gbuffer_layer_color(S, gb, k - 1, &col);
-    result = blend(result, col);
-  }
-  if (opacity >= S.hit_threshold) cls = GRT_CLASS_HIT;
-  write_out(out, dst, result, cls, status, stop, (uint32_t)(l1 - l0));
-}
-
-__global__ void __launch_bounds__(256) gbuffer_shade_kernel(const DevScene* __restrict__ Sp, GBufferArrays gb,
-                                                            Outputs out) {
-  const DevScene& S = *Sp;
-  glibc::tables_to_lds();  // whole block, before the early return
-  const uint64_t idx = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (idx >= gb.n) return;
-  const int status = gb.status[idx];
-  const int stop = gb.stop[idx];
-  const XYZA fail{0.0, 0.0, 0.0, 1.0};
-  if (status != GRT_OK) {
-    write_out(out, idx, fail, GRT_CLASS_ESCAPED, status, stop, 0u);
-    return;
-  }
-  const uint64_t l0 = gb.layer_start[idx], l1 = gb.layer_start[idx + 1];
-  double opacity = 0.0;
-  for (uint64_t k = l0; k < l1; ++k) {
-    XYZA col;
-    int e = gbuffer_layer_color(S, gb, k, &col);
-    if (e != GRT_OK) {  // a temperature error the traced scene did not have: the window error's pixel
-      write_out(out, idx, fail, GRT_CLASS_ESCAPED, e, stop, (uint32_t)(k - l0));
-      return;
-    }
-    double alpha = rclamp(col.a, 0.0, 1.0);
-    opacity = alpha + opacity * (1.0 - alpha);
-  }
-  XYZA result{0.0, 0.0, 0.0, 1.0};
-  int cls = GRT_CLASS_CAPTURED;
-  if (stop == GRT_STOP_HORIZON || stop == GRT_STOP_CLOSED_ORBIT) {
-    result = blend(result, XYZA{0.0, 0.0, 0.0, 1.0});
-  } else if (stop == GRT_STOP_CELESTIAL) {
-    result = blend(result, texture_color(S, S.celestial, gb.sky_u[idx], gb.sky_v[idx], gb.sky_redshift[idx],
-                                         S.celestial_temperature));
-    cls = GRT_CLASS_ESCAPED;
-  }
-  for (uint64_t k = l1; k > l0; --k) {
-    XYZA col{0.0, 0.0, 0.0, 0.0};
-    (void)gbuffer_layer_color(S, gb, k - 1, &col);
-    result = blend(result, col);
-  }
-  if (opacity >= S.hit_threshold) cls = GRT_CLASS_HIT;
-  write_out(out, idx, result, cls, status, stop, (uint32_t)(l1 - l0));
-}
-
-// The supersample pass of an adaptive re-shade (grt_gbuffer_shade_section): one lane per
-// (held selected pixel j, stratum s) of a chunk of the list `sel` (entries base + j <
-// *d_count).  Sub-ray sub_block[sel[j]] * per + s of the buffer's sub-sample set `sub` is
-// shaded as gbuffer_shade_kernel shades a pixel, into slot j * per + s: the layout
-// average_kernel reads, with the sub-ray's step count beside it.
-__global__ void __launch_bounds__(256) gbuffer_shade_sub_kernel(const DevScene* __restrict__ Sp, GBufferArrays sub,
-                                                                const uint32_t* __restrict__ sub_steps,
-                                                                const uint32_t* __restrict__ sub_block,
-                                                                const uint32_t* __restrict__ sel, uint64_t n_sel,
-                                                                const unsigned long long* __restrict__ d_count,
-                                                                uint64_t base, uint32_t per, Outputs out) {
-  const DevScene& S = *Sp;
-  // a block past the held pixels (the empty chunks of a pass) has nothing to do
-  if (base + (uint64_t)blockIdx.x * blockDim.x / per >= *d_count) return;
-  glibc::tables_to_lds();  // whole block, before the per-lane early return
-  const uint64_t k = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  const uint64_t j = k / per;
-  if (j >= n_sel || base + j >= *d_count) return;
-  const uint64_t src = (uint64_t)sub_block[sel[j]] * per + k % per;
-  if (src >= sub.n) return;  // a pixel the set does not hold: the split never lists one
-  if (out.steps) out.steps[k] = sub_steps[src];
-  gbuffer_shade_ray(S, sub, src, out, k);
-}
-
-// The supersample pass of an adaptive re-shade of a stack of buffers
-// (grt_gbuffer_shade_section_sequence): gbuffer_shade_sub_kernel with the set found per lane.
-// `sel` holds stacked indices P = frame * npix + pixel of held selected pixels (entries
-// base + j < *d_count); the frame's entry of the device table gives its set, the set's step
-// counts and its sub_block.  Sub-ray sub_block[pixel] * per + s of that set is shaded by
-// gbuffer_shade_ray into the chunk's slot j * per + s, the layout average_kernel reads.
-__global__ void __launch_bounds__(256) gbuffer_shade_sub_stack_kernel(const DevScene* __restrict__ Sp,
-                                                                      const GBufferSubFrame* __restrict__ frames,
-                                                                      uint32_t n_frames, uint64_t npix,
-                                                                      const uint32_t* __restrict__ sel, uint64_t n_sel,
-                                                                      const unsigned long long* __restrict__ d_count,
-                                                                      uint64_t base, uint32_t per, Outputs out) {
-  const DevScene& S = *Sp;
-  // a block past the held pixels (the empty chunks of a pass) has nothing to do
-  if (base + (uint64_t)blockIdx.x * blockDim.x / per >= *d_count) return;
-  glibc::tables_to_lds();  // whole block, before the per-lane early return
-  const uint64_t k = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  const uint64_t j = k / per;
-  if (j >= n_sel || base + j >= *d_count) return;
-  const uint64_t p = sel[j], f = p / npix;
-  if (f >= n_frames) return;  // an index past the stack: the split never lists one
-  const GBufferSubFrame fr = frames[f];
-  const uint64_t src = (uint64_t)fr.sub_block[p - f * npix] * per + k % per;
-  if (src >= fr.sub.n) return;  // a pixel the set does not hold: the split never lists one
-  if (out.steps) out.steps[k] = fr.steps[src];
-  gbuffer_shade_ray(S, fr.sub, src, out, k);
-}
-
-// The deferred shade of a stack of equally sized buffers (grt_gbuffer_shade_sequence): one
-// lane per (frame, pixel) of a launch group, the frame's arrays from a device table, the
-// pixel shaded as gbuffer_shade_kernel shades it into slot frame * per + pixel of the
-// stacked outputs, with the recorded step count beside it when asked for.
-__global__ void __launch_bounds__(256) gbuffer_shade_stack_kernel(const DevScene* __restrict__ Sp,
-                                                                  const GBufferFrame* __restrict__ frames,
-                                                                  uint32_t n_frames, uint64_t per, Outputs out) {
-  const DevScene& S = *Sp;
-  glibc::tables_to_lds();  // whole block, before the early return
-  const uint64_t idx = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (idx >= (uint64_t)n_frames * per) return;
-  const uint64_t f = idx / per, src = idx - f * per;
-  const GBufferFrame fr = frames[f];
-  if (src >= fr.gb.n) return;  // a frame of another size: the host refuses such a stack
-  if (out.steps) out.steps[idx] = fr.steps[src];
-  gbuffer_shade_ray(S, fr.gb, src, out, idx);
-}
-
-// ---- the disc's orbital motion (grt_gbuffer_shade_times, grt_gbuffer_shade_section_at) ----
-// shade_record's disc emitter moves on a circular orbit with killing_coefficients' omega, so
-// a disc texture that orbits at that rate is the animation of the scene being shaded: at
-// coordinate time t the matter seen at in-plane angle phi sat at phi - omega t at time 0, and
-// disc uv is 0.5 + 0.5 rho (cos phi, sin phi), so the lookup point turns about (0.5, 0.5) by
-// -omega t.  "Fast light": every layer of a frame is shaded at the same t; the buffer does not
-// record the coordinate time along the ray, and light-travel delay is ignored.
-// The rule is restated on the host with the same operations in the same order
-// (host/orbit.cpp: grt_orbit_rate, grt_gbuffer_orbit_uv).
-//
-// d(phi)/dt of the emitter at radius r: killing_coefficients' omega (a new function: that one
-// is the trace kernels' and stays as it is); the flat charts' emitter is at rest.
-GDEV double orbit_rate(const DevScene& S, double r) {
-  if (S.geometry == GRT_GEOM_EUCLIDEAN || S.geometry == GRT_GEOM_EUCLIDEAN_SPHERICAL) return 0.0;
-  const double m = 0.5 * S.radius;
-  const double sqrt_m = sqrt(m);
-  return sqrt_m / (rpow(r, 1.5) + S.a * sqrt_m);
-}
-
-GDEV void orbit_uv(double omega, double t, double* u, double* v) {
-  const double th = omega * t;
-  if (th == 0.0 || !isfinite(th)) return;  // (u, v) unchanged, bit for bit
-  double s, c;
-  rsincos(th, &s, &c);
-  const double du = *u - 0.5, dv = *v - 0.5;
-  *u = 0.5 + (du * c + dv * s);
-  *v = 0.5 + (dv * c - du * s);
-}
-
-// gbuffer_layer_color at time t: a disc layer's (u, v) goes through orbit_uv first.  CACHED:
-// the layer's rate is read from omega[k] (gbuffer_orbit_rate_kernel wrote it); else it is
-// computed here.  The same expression either way, so the same bits.
-template <bool CACHED>
-GDEV int gbuffer_layer_color_at(const DevScene& S, const GBufferArrays& gb, uint64_t k, double t,
-                                const double* __restrict__ omega, XYZA* col) {
-  const DevObject& o = S.obj[gb.object[k]];
-  double temperature;
-  if (o.kind != GRT_OBJ_SPHERE) {
-    int e = compute_temperature(o, gb.radius[k], &temperature);
-    if (e != GRT_OK) return e;
-  } else {
-    temperature = o.temperature;
-  }
-  double u = gb.u[k], v = gb.v[k];
-  if (o.kind == GRT_OBJ_DISC) orbit_uv(CACHED ? omega[k] : orbit_rate(S, gb.radius[k]), t, &u, &v);
-  *col = texture_color(S, o.tex, u, v, gb.redshift[k], temperature);
-  return GRT_OK;
-}
-
-// gbuffer_shade_ray at time t: its operations in its order, the layers' colours from
-// gbuffer_layer_color_at in both passes.
-template <bool CACHED = false>
-GDEV void gbuffer_shade_ray_at(const DevScene& S, const GBufferArrays& gb, uint64_t src, double t, const Outputs& out,
-                               uint64_t dst, const double* __restrict__ omega = nullptr) {
-  const int status = gb.status[src];
-  const int stop = gb.stop[src];
-  const XYZA fail{0.0, 0.0, 0.0, 1.0};
-  if (status != GRT_OK) {
-    write_out(out, dst, fail, GRT_CLASS_ESCAPED, status, stop, 0u);
-    return;
-  }
-  const uint64_t l0 = gb.layer_start[src], l1 = gb.layer_start[src + 1];
-  double opacity = 0.0;
-  for (uint64_t k = l0; k < l1; ++k) {
-    XYZA col;
-    int e = gbuffer_layer_color_at<CACHED>(S, gb, k, t, omega, &col);
-    if (e != GRT_OK) {
-      write_out(out, dst, fail, GRT_CLASS_ESCAPED, e, stop, (uint32_t)(k - l0));
-      return;
-    }
-    double alpha = rclamp(col.a, 0.0, 1.0);
-    opacity = alpha + opacity * (1.0 - alpha);
-  }
-  XYZA result{0.0, 0.0, 0.0, 1.0};
-  int cls = GRT_CLASS_CAPTURED;
-  if (stop == GRT_STOP_HORIZON || stop == GRT_STOP_CLOSED_ORBIT) {
-    result = blend(result, XYZA{0.0, 0.0, 0.0, 1.0});
-  } else if (stop == GRT_STOP_CELESTIAL) {
-    result = blend(result, texture_color(S, S.celestial, gb.sky_u[src], gb.sky_v[src], gb.sky_redshift[src],
-                                         S.celestial_temperature));
-    cls = GRT_CLASS_ESCAPED;
-  }
-  for (uint64_t k = l1; k > l0; --k) {
-    XYZA col{0.0, 0.0, 0.0, 0.0};
-    (void)gbuffer_layer_color_at<CACHED>(S, gb, k - 1, t, omega, &col);
-    result = blend(result, col);
-  }
-  if (opacity >= S.hit_threshold) cls = GRT_CLASS_HIT;
-  write_out(out, dst, result, cls, status, stop, (uint32_t)(l1 - l0));
-}
-
-// One buffer at n_times times in one launch (grt_gbuffer_shade_times): one lane per (frame,
-// pixel) of a launch group, frame k at times[k], into slot k * gb.n + pixel of the stacked
-// outputs (gbuffer_shade_stack_kernel's layout), the recorded step count beside it when asked.
-// The layers' rates come from omega[], written once per call by the pre-pass below: the
-// n_times * 2 colour evaluations of a layer read 8 bytes instead of redoing pow, sqrt and a
-// division (measured against the inline form: DESIGN.md section 15).
-__global__ void __launch_bounds__(256) gbuffer_shade_times_kernel(const DevScene* __restrict__ Sp, GBufferArrays gb,
-                                                                  const uint32_t* __restrict__ steps,
-                                                                  const double* __restrict__ times, uint32_t n_times,
-                                                                  const double* __restrict__ omega, Outputs out) {
-  const DevScene& S = *Sp;
-  glibc::tables_to_lds();  // whole block, before the early return
-  const uint64_t idx = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (idx >= (uint64_t)n_times * gb.n) return;
-  const uint64_t f = idx / gb.n, src = idx - f * gb.n;
-  if (out.steps) out.steps[idx] = steps[src];
-  gbuffer_shade_ray_at<true>(S, gb, src, times[f], out, idx, omega);
-}
-
-// The pre-pass of grt_gbuffer_shade_times: orbit_rate of every disc layer, once per call (the
-// entry of another layer is never read).
-__global__ void __launch_bounds__(256) gbuffer_orbit_rate_kernel(const DevScene* __restrict__ Sp, GBufferArrays gb,
-                                                                 uint64_t n_layers, double* __restrict__ omega) {
-  const DevScene& S = *Sp;
-  glibc::tables_to_lds();  // whole block, before the early return
-  const uint64_t k = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (k >= n_layers) return;
-  omega[k] = S.obj[gb.object[k]].kind == GRT_OBJ_DISC ? orbit_rate(S, gb.radius[k]) : 0.0;
-}
-
-// gbuffer_shade_kernel at one time (the 1-spp pass of grt_gbuffer_shade_section_at).
-__global__ void __launch_bounds__(256) gbuffer_shade_at_kernel(const DevScene* __restrict__ Sp, GBufferArrays gb,
-                                                               double t, Outputs out) {
-  const DevScene& S = *Sp;
-  glibc::tables_to_lds();  // whole block, before the early return
-  const uint64_t idx = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (idx >= gb.n) return;
-  gbuffer_shade_ray_at(S, gb, idx, t, out, idx);
-}
-
-// gbuffer_shade_sub_kernel at one time (the supersample pass of grt_gbuffer_shade_section_at):
-// the set's numbers are the unrotated ones; the time enters at the texture lookup only.
-__global__ void __launch_bounds__(256) gbuffer_shade_sub_at_kernel(const DevScene* __restrict__ Sp, GBufferArrays sub,
-                                                                   const uint32_t* __restrict__ sub_steps,
-                                                                   const uint32_t* __restrict__ sub_block,
-                                                                   const uint32_t* __restrict__ sel, uint64_t n_sel,
-                                                                   const unsigned long long* __restrict__ d_count,
-                                                                   uint64_t base, uint32_t per, double t, Outputs out) {
-  const DevScene& S = *Sp;
-  // a block past the held pixels (the empty chunks of a pass) has nothing to do
-  if (base + (uint64_t)blockIdx.x * blockDim.x / per >= *d_count) return;
-  glibc::tables_to_lds();  // whole block, before the per-lane early return
-  const uint64_t k = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  const uint64_t j = k / per;
-  if (j >= n_sel || base + j >= *d_count) return;
-  const uint64_t src = (uint64_t)sub_block[sel[j]] * per + k % per;
-  if (src >= sub.n) return;  // a pixel the set does not hold: the split never lists one
-  if (out.steps) out.steps[k] = sub_steps[src];
-  gbuffer_shade_ray_at(S, sub, src, t, out, k);
-}
-
-hipError_t launch_gbuffer_orbit_rate(const DevScene* d_scene, const GBufferArrays& gb, uint64_t n_layers,
-                                     double* d_omega, hipStream_t stream) {
-  if (n_layers == 0) return hipSuccess;
-  hipLaunchKernelGGL(gbuffer_orbit_rate_kernel, dim3((unsigned)((n_layers + 255) / 256)), dim3(256), 0, stream, d_scene,
-                     gb, n_layers, d_omega);
-  return hipGetLastError();
-}
-
-hipError_t launch_gbuffer_shade_times(const DevScene* d_scene, const GBufferArrays& gb, const uint32_t* d_steps,
-                                      const double* d_times, uint32_t n_times, const double* d_omega, const Outputs& out,
-                                      hipStream_t stream) {
-  const uint64_t n = (uint64_t)n_times * gb.n;
-  if (n == 0) return hipSuccess;
-  if (n > 0xffffffffull * 256) return hipErrorInvalidValue;
-  if (!d_omega) return hipErrorInvalidValue;
-  hipLaunchKernelGGL(gbuffer_shade_times_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, stream, d_scene, gb,
-                     d_steps, d_times, n_times, d_omega, out);
-  return hipGetLastError();
-}
-
-hipError_t launch_gbuffer_shade_at(const DevScene* d_scene, const GBufferArrays& gb, double t, const Outputs& out,
-                                   hipStream_t stream) {
-  if (gb.n == 0) return hipSuccess;
-  hipLaunchKernelGGL(gbuffer_shade_at_kernel, dim3((unsigned)((gb.n + 255) / 256)), dim3(256), 0, stream, d_scene, gb, t,
-                     out);
-  return hipGetLastError();
-}
-
-hipError_t launch_gbuffer_shade_sub_at(const DevScene* d_scene, const GBufferArrays& sub, const uint32_t* d_sub_steps,
-                                       const uint32_t* d_sub_block, const uint32_t* d_sel, uint64_t n_sel,
-                                       const unsigned long long* d_count, uint64_t base, uint32_t spa, double t,
-                                       const Outputs& out, hipStream_t stream) {
-  const uint64_t n = n_sel * spa * spa;
-  if (n == 0) return hipSuccess;
-  hipLaunchKernelGGL(gbuffer_shade_sub_at_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, stream, d_scene, sub,
-                     d_sub_steps, d_sub_block, d_sel, n_sel, d_count, base, spa * spa, t, out);
-  return hipGetLastError();
-}
-
-hipError_t launch_gbuffer_shade_stack(const DevScene* d_scene, const GBufferFrame* d_frames, uint32_t n_frames,
-                                      uint64_t per, const Outputs& out, hipStream_t stream) {
-  const uint64_t n = (uint64_t)n_frames * per;
-  if (n == 0) return hipSuccess;
-  if (n > 0xffffffffull * 256) return hipErrorInvalidValue;
-  hipLaunchKernelGGL(gbuffer_shade_stack_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, stream, d_scene,
-                     d_frames, n_frames, per, out);
-  return hipGetLastError();
-}
-
-hipError_t launch_gbuffer_shade(const DevScene* d_scene, const GBufferArrays& gb, const Outputs& out,
-                                hipStream_t stream) {
-  if (gb.n == 0) return hipSuccess;
-  hipLaunchKernelGGL(gbuffer_shade_kernel, dim3((unsigned)((gb.n + 255) / 256)), dim3(256), 0, stream, d_scene, gb, out);
-  return hipGetLastError();
-}
-
-hipError_t launch_gbuffer_shade_sub(const DevScene* d_scene, const GBufferArrays& sub, const uint32_t* d_sub_steps,
-                                    const uint32_t* d_sub_block, const uint32_t* d_sel, uint64_t n_sel,
-                                    const unsigned long long* d_count, uint64_t base, uint32_t spa, const Outputs& out,
-                                    hipStream_t stream) {
-  const uint64_t n = n_sel * spa * spa;
-  if (n == 0) return hipSuccess;
-  hipLaunchKernelGGL(gbuffer_shade_sub_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, stream, d_scene, sub,
-                     d_sub_steps, d_sub_block, d_sel, n_sel, d_count, base, spa * spa, out);
-  return hipGetLastError();
-}
-
-hipError_t launch_gbuffer_shade_sub_stack(const DevScene* d_scene, const GBufferSubFrame* d_frames, uint32_t n_frames,
-                                          uint64_t npix, const uint32_t* d_sel, uint64_t n_sel,
-                                          const unsigned long long* d_count, uint64_t base, uint32_t spa,
-                                          const Outputs& out, hipStream_t stream) {
-  const uint64_t n = n_sel * spa * spa;
-  if (n == 0) return hipSuccess;
-  if (npix == 0 || n_frames == 0 || n > 0xffffffffull * 256) return hipErrorInvalidValue;
-  hipLaunchKernelGGL(gbuffer_shade_sub_stack_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, stream, d_scene,
-                     d_frames, n_frames, npix, d_sel, n_sel, d_count, base, spa * spa, out);
-  return hipGetLastError();
-}
-#endif  // GRT_MAIN_TU
 
 // ------------------------------------------------------------------ launch -------
 // Plain scenes: integrate [-> tail] -> shade.  Volumetric scenes: integrate [-> tail] ->

@@ -1,4 +1,4 @@
-// kernels.h — launch entry points of the gfx950 kernels (geodesic.hip, adaptive.hip).
+// kernels.h — launch entry points of the gfx950 kernels (geodesic.hip, gbuffer_shade.hip, adaptive.hip).
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -166,11 +166,11 @@ hipError_t launch_gbuffer_fill(int geometry, const DevScene* d_scene, const Work
 // A stacked buffer cut into its frames (gbuffer.hip): frame_start[i] = stack_start[i] -
 // stack_start[0] for i <= n, where stack_start points at the frame's first pixel.
 hipError_t gbuffer_rebase(const uint64_t* d_stack_start, uint64_t n, uint64_t* d_frame_start, hipStream_t stream);
-// Deferred shade of `gb` under the appearance scene (gbuffer_shade_kernel, geodesic.hip).
+// Deferred shade of `gb` under the appearance scene (gbuffer_shade_kernel, gbuffer_shade.hip).
 hipError_t launch_gbuffer_shade(const DevScene* d_scene, const GBufferArrays& gb, const Outputs& out,
                                 hipStream_t stream);
 // Deferred shade of n_frames buffers of `per` pixels each in one launch
-// (gbuffer_shade_stack_kernel, geodesic.hip): d_frames is a device table of the buffers'
+// (gbuffer_shade_stack_kernel, gbuffer_shade.hip): d_frames is a device table of the buffers'
 // views and recorded step counts; out spans n_frames * per slots, frame-major.
 struct GBufferFrame {
   GBufferArrays gb;
@@ -182,14 +182,14 @@ hipError_t launch_gbuffer_shade_stack(const DevScene* d_scene, const GBufferFram
 // jittered sub-rays, each reduced as a 1-spp ray is; sub-ray b * spa^2 + s is stratum s of
 // block b, and sub_block[pixel] is the pixel's block or GBUFFER_NIL.
 constexpr uint32_t GBUFFER_NIL = 0xffffffffu;
-// Supersample pass of the adaptive re-shade (gbuffer_shade_sub_kernel, geodesic.hip): a
+// Supersample pass of the adaptive re-shade (gbuffer_shade_sub_kernel, gbuffer_shade.hip): a
 // chunk of n_sel entries at position `base` of the held list d_sel (*d_count entries),
 // shaded into out at j * spa^2 + s (out.steps takes the sub-rays' step counts).
 hipError_t launch_gbuffer_shade_sub(const DevScene* d_scene, const GBufferArrays& sub, const uint32_t* d_sub_steps,
                                     const uint32_t* d_sub_block, const uint32_t* d_sel, uint64_t n_sel,
                                     const unsigned long long* d_count, uint64_t base, uint32_t spa, const Outputs& out,
                                     hipStream_t stream);
-// The same for the buffers of a stack (gbuffer_shade_sub_stack_kernel, geodesic.hip): d_sel
+// The same for the buffers of a stack (gbuffer_shade_sub_stack_kernel, gbuffer_shade.hip): d_sel
 // holds stacked indices P = frame * npix + pixel of held selected pixels, and entry P / npix
 // of the device table d_frames gives the frame's set, its step counts and its sub_block.
 struct GBufferSubFrame {
@@ -201,7 +201,7 @@ hipError_t launch_gbuffer_shade_sub_stack(const DevScene* d_scene, const GBuffer
                                           uint64_t npix, const uint32_t* d_sel, uint64_t n_sel,
                                           const unsigned long long* d_count, uint64_t base, uint32_t spa,
                                           const Outputs& out, hipStream_t stream);
-// The disc's orbital motion (geodesic.hip): `gb` shaded at d_times[0..n_times) in one launch
+// The disc's orbital motion (gbuffer_shade.hip): `gb` shaded at d_times[0..n_times) in one launch
 // (gbuffer_shade_times_kernel), frame k into slots [k * gb.n, (k + 1) * gb.n) of out, d_steps
 // the buffer's recorded step counts; and launch_gbuffer_shade / launch_gbuffer_shade_sub at one
 // time t (gbuffer_shade_at_kernel, gbuffer_shade_sub_at_kernel).  The K-times kernel reads each

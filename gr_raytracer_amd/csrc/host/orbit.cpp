@@ -1,5 +1,5 @@
 // orbit.cpp — host restatement of the disc's orbital motion (grt_api.h: grt_orbit_rate,
-// grt_gbuffer_orbit_uv).  The rule is the device's (device/geodesic.hip: orbit_rate, orbit_uv)
+// grt_gbuffer_orbit_uv).  The rule is the device's (device/gbuffer_shade.hip: orbit_rate, orbit_uv)
 // with the same operations in the same order, compiled without contraction, over the host
 // build of device/glibc_math.h: pow_fast / sincos_fast, and the host libm outside their fast
 // paths.  Device and host agree bit for bit for |omega t| < 105414350, the range of the exact
