@@ -957,7 +957,7 @@ int grt_debug_class_order(grt_scene* s, int device, const grt_row_shard* sh, uin
   return 0;
 }
 
-// Test hook (not in grt_api.h): the range-free divisions and square root (geodesic.hip
+// Test hook (not in grt_api.h): the range-free divisions and square root (geodesic_rhs.h
 // div_inrange, div2_inrange, div_fx, sqrt_fx) against the compiler's over the exponent
 // plane (arith_map_kernel): map[2047 * 2047], zmap[2047], smap[2047] flag bytes.
 int grt_debug_arith_map(int device, uint32_t samples, uint64_t seed, uint8_t* map, uint8_t* zmap, uint8_t* smap) {
@@ -1057,7 +1057,7 @@ int grt_debug_rhs_check(grt_scene* s, int device, uint64_t n, const double* stat
 
 #if GRT_PATH_COUNT
 // Diagnostic builds only (not in grt_api.h): the integrate kernels' path counters since the
-// last reset (geodesic.hip path_count): out[28], [k] wave-level, [14 + k] lane-level.
+// last reset (geodesic_rhs.h path_count): out[28], [k] wave-level, [14 + k] lane-level.
 int grt_debug_path_counts(uint64_t* out, int reset) {
   if (!out) return fail(-EINVAL, "null argument");
   HIP_TRY(grt::path_read((unsigned long long*)out, reset != 0));

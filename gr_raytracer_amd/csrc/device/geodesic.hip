@@ -22,6 +22,18 @@
 // libm (sin/cos of the camera position, tan(alpha/2), LUTs) are evaluated on the
 // host.  pow() is glibc's own algorithm restated bit-exactly (glibc_math.h); the
 // remaining per-step transcendentals (sin/cos/atan2/acos) use the device libm (OCML).
+//
+// Layers in their own files, each on the ones before it (the include sites below say
+// which unit builds which):
+//   geodesic_rhs.h    range-free division / sqrt, metrics, the sincos dispatch, the RHS   every unit
+//   geodesic_rkf.h    RKF45 attempts, LDS stage parking                                   every unit
+//   geodesic_probe.h  work-order kernels (probes, impact and class keys)                  exact build, sequence
+//   geodesic_fill.h   gbuffer_fill_kernel                                                 exact build, KerrBL, sequence
+// Still here, between them and in this order: chart helpers, chord tests and the camera
+// ray; the trace (integrate_kernel, tail_kernel); the exact build's trajectory kernel,
+// device checks and invariant monitors; shade_kernel.  The unit macros and every GRT_*
+// knob are in this file (tools/build_variant.sh edits them here), and so is every launch
+// function.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
@@ -135,1086 +147,52 @@ namespace seq {
 #ifndef GRT_RAY_TIMES
 #define GRT_RAY_TIMES 0  // diagnostic builds only: per-ray schedule record (tools/c4_ray_times.py)
 #endif
-
-#include "appearance.h"
-
-// x1 / y and x2 / y with one reciprocal refinement.  This is the compiler's own IEEE f64
-// division expansion (div_scale, rcp, 2 Newton steps, div_fmas, div_fixup -- identical
-// instructions), with the y-only part shared.  The shared part is v_div_scale(y, y, x),
-// whose result depends on x only when |x| is extreme (exponent gap >= 768, x/y
-// denormal, or exp(x) <= 53); the host enables this (DevScene::div_share) only when
-// both numerators are normal with |exponent| < 500, where it cannot.  Every quotient
-// is therefore bit-identical to x / y.
-GDEV void div2_same_den(double x1, double x2, double y, double* q1, double* q2) {
-  bool f0, f1, f2;
-  const double ds0 = __builtin_amdgcn_div_scale(x1, y, false, &f0);
-  const double rcp = __builtin_amdgcn_rcp(ds0);
-  const double fma0 = __builtin_fma(-ds0, rcp, 1.0);
-  const double fma1 = __builtin_fma(rcp, fma0, rcp);
-  const double fma2 = __builtin_fma(-ds0, fma1, 1.0);
-  const double fma3 = __builtin_fma(fma1, fma2, fma1);
-  const double n1 = __builtin_amdgcn_div_scale(x1, y, true, &f1);
-  const double m1 = n1 * fma3;
-  *q1 = __builtin_amdgcn_div_fixup(__builtin_amdgcn_div_fmas(__builtin_fma(-ds0, m1, n1), fma3, m1, f1), y, x1);
-  const double n2 = __builtin_amdgcn_div_scale(x2, y, true, &f2);
-  const double m2 = n2 * fma3;
-  *q2 = __builtin_amdgcn_div_fixup(__builtin_amdgcn_div_fmas(__builtin_fma(-ds0, m2, n2), fma3, m2, f2), y, x2);
-}
-
-// x / y as that same expansion without its range steps, for operands the caller has
-// shown to be normals with |x|, |y|, |x / y| all within 2^-600 .. 2^600: there
-// v_div_scale returns its operand unchanged and raises no flag (the exponent gap is
-// < 768, neither 1 / y nor x / y is denormal, exp(x) > 53), so v_div_fmas is a plain
-// fma, and v_div_fixup, which only rewrites NaN / infinity / zero / overflow / underflow
-// cases, passes the quotient through.
-// The same instructions on the same values, hence x / y's bits.  Measured over the whole
-// exponent plane, the exact region is larger (E: |y| normal below 2^1022, x of exponent
-// >= -969, gap -1021 .. 1022; the gap >= 768 scaling is an identity there too), and the
-// first failures are one exponent outside it (tests/test_gpu_arith.py
-// ::test_range_free_arithmetic_map, profiles/r05a/arith_map.json).
-// 8 VALU instead of 11; div2_inrange shares 1 / y: 11 instead of 16.
-GDEV double div_inrange(double x, double y) {
-  const double rcp = __builtin_amdgcn_rcp(y);
-  const double fma0 = __builtin_fma(-y, rcp, 1.0);
-  const double fma1 = __builtin_fma(rcp, fma0, rcp);
-  const double fma2 = __builtin_fma(-y, fma1, 1.0);
-  const double fma3 = __builtin_fma(fma1, fma2, fma1);
-  const double m = x * fma3;
-  return __builtin_fma(__builtin_fma(-y, m, x), fma3, m);
-}
-GDEV void div2_inrange(double x1, double x2, double y, double* q1, double* q2) {
-  const double rcp = __builtin_amdgcn_rcp(y);
-  const double fma0 = __builtin_fma(-y, rcp, 1.0);
-  const double fma1 = __builtin_fma(rcp, fma0, rcp);
-  const double fma2 = __builtin_fma(-y, fma1, 1.0);
-  const double fma3 = __builtin_fma(fma1, fma2, fma1);
-  const double m1 = x1 * fma3;
-  *q1 = __builtin_fma(__builtin_fma(-y, m1, x1), fma3, m1);
-  const double m2 = x2 * fma3;
-  *q2 = __builtin_fma(__builtin_fma(-y, m2, x2), fma3, m2);
-}
-// |x| in (2^-300, 2^300), NaN excluded: two compares with the abs modifier
-GDEV bool in_div_range(double x) { return fabs(x) > 0x1p-300 && fabs(x) < 0x1p300; }
-
-// x / y as the compiler's expansion without its two v_div_scale steps but with
-// v_div_fixup: exact (the same instructions on the same values) when y is a normal within
-// 2^+-600 and x is 0 or a normal with |x|, |x / y| within 2^+-600 -- v_div_scale would
-// return its operand unchanged with no flag (so v_div_fmas is a plain fma), and
-// v_div_fixup rewrites the zero-numerator case from the operands alone (a -0 / y chain
-// gives +0; the fixup returns the signed zero).  9 VALU instead of 11.
-GDEV double div_fx(double x, double y) {
-  const double rcp = __builtin_amdgcn_rcp(y);
-  const double fma0 = __builtin_fma(-y, rcp, 1.0);
-  const double fma1 = __builtin_fma(rcp, fma0, rcp);
-  const double fma2 = __builtin_fma(-y, fma1, 1.0);
-  const double fma3 = __builtin_fma(fma1, fma2, fma1);
-  const double m = x * fma3;
-  return __builtin_amdgcn_div_fixup(__builtin_fma(__builtin_fma(-y, m, x), fma3, m), y, x);
-}
-
-// Kerr-Schild metric quotients: the compiler's division, or div_fx (FD) where the caller
-// has established ks_fd_ok for the state
-template <bool FD>
-GDEV double kdiv(double x, double y) {
-  if constexpr (FD) return div_fx(x, y);
-  else return x / y;
-}
-// sqrt(x) as the compiler's f64 expansion for gfx950 without its range steps: for a
-// normal x >= 2^-767 the input scaling (ldexp by 0), the output rescaling and the
-// zero / infinity select are identities, leaving v_rsq_f64 and the Newton steps on the
-// same values, hence sqrt's bits (device check: tests/test_gpu_arith.py: exact for every
-// x >= 2^-969, the first failure at 2^-971).  10 VALU instead of 17.
-GDEV double sqrt_fx(double x) {
-  const double r = __builtin_amdgcn_rsq(x);
-  double g = x * r, h = r * 0.5;
-  const double e = __builtin_fma(-h, g, 0.5);
-  g = __builtin_fma(g, e, g);
-  h = __builtin_fma(h, e, h);
-  double d = __builtin_fma(-g, g, x);
-  g = __builtin_fma(d, h, g);
-  d = __builtin_fma(-g, g, x);
-  return __builtin_fma(d, h, g);
-}
-template <bool FD>
-GDEV double ksqrt(double x) {
-  if constexpr (FD && GRT_FAST_SQRT_KS) return sqrt_fx(x);
-  else return sqrt(x);
-}
-
-#if GRT_MAIN_TU
-// Device check of div_inrange / div2_inrange / div_fx / sqrt_fx against the compiler's
-// division and sqrt over the whole exponent plane (tests/test_gpu_parity.py
-// ::test_range_free_arithmetic_map): thread (ex, ey), ex, ey biased exponents 0 .. 2046
-// (0: subnormals), runs `samples` operand pairs x = +-m_x 2^(ex-1023), y = +-m_y 2^(ey-1023)
-// -- the first four with extreme mantissas (0 / all ones), the rest splitmix64-random, and
-// a second numerator x2 of the same exponent for div2_inrange -- and sets in map[ex][ey]:
-//   1 div_inrange(x, y) != x / y      2 div2_inrange(x, x2, y) != (x / y, x2 / y)
-//   4 div_fx(x, y) != x / y
-// Threads with ex == 0 also set zmap[ey] |= 8 when div_fx(+-0, y) != +-0 / y, and threads
-// with ey == 0 set smap[ex] |= 16 when sqrt_fx(x) != sqrt(x) for positive x of exponent ex.
-__global__ void arith_map_kernel(uint32_t samples, uint64_t seed, uint8_t* map, uint8_t* zmap, uint8_t* smap) {
-  const uint32_t cell = blockIdx.x * blockDim.x + threadIdx.x;
-  if (cell >= 2047u * 2047u) return;
-  const uint32_t ex = cell / 2047u, ey = cell % 2047u;
-  auto mix = [](uint64_t z) {
-    z += 0x9e3779b97f4a7c15ull;
-    z = (z ^ (z >> 30)) * 0xbf58476d1ce4e5b9ull;
-    z = (z ^ (z >> 27)) * 0x94d049bb133111ebull;
-    return z ^ (z >> 31);
-  };
-  constexpr uint64_t MANT = 0x000fffffffffffffull;
-  auto bits = [](double v) { return (uint64_t)__double_as_longlong(v); };
-  auto make = [](uint64_t sign, uint64_t e, uint64_t m) {
-    return __longlong_as_double((long long)((sign << 63) | (e << 52) | m));
-  };
-  uint32_t flags = 0, zflags = 0, sflags = 0;
-  for (uint32_t k = 0; k < samples; ++k) {
-    const uint64_t u = mix(seed ^ ((uint64_t)cell * 64 + 3 * k + 1)), v = mix(seed ^ ((uint64_t)cell * 64 + 3 * k + 2)),
-                   w = mix(seed ^ ((uint64_t)cell * 64 + 3 * k + 3));
-    const uint64_t mx = k < 4 ? ((k & 1) ? MANT : 0) : (u & MANT);
-    const uint64_t my = k < 4 ? ((k & 2) ? MANT : 0) : (v & MANT);
-    const double x = make(u >> 63, ex, mx), y = make(v >> 63, ey, my), x2 = make(w >> 63, ex, w & MANT);
-    volatile double vx = x, vy = y, vx2 = x2;  // keep the reference divisions as divisions
-    const double ref1 = vx / vy, ref2 = vx2 / vy;
-    double q1, q2;
-    div2_inrange(x, x2, y, &q1, &q2);
-    if (bits(div_inrange(x, y)) != bits(ref1)) flags |= 1u;
-    if (bits(q1) != bits(ref1) || bits(q2) != bits(ref2)) flags |= 2u;
-    if (bits(div_fx(x, y)) != bits(ref1)) flags |= 4u;
-    if (ex == 0) {
-      const double z0 = (u >> 62) & 1 ? -0.0 : 0.0;
-      volatile double vz = z0;
-      if (bits(div_fx(z0, y)) != bits(vz / vy)) zflags |= 8u;
-    }
-    if (ey == 0) {
-      const double sx = fabs(x);
-      volatile double vsx = sx;
-      if (bits(sqrt_fx(sx)) != bits(sqrt(vsx))) sflags |= 16u;
-    }
-  }
-  map[cell] = (uint8_t)flags;
-  if (ex == 0) zmap[ey] = (uint8_t)zflags;
-  if (ey == 0) smap[ex] = (uint8_t)sflags;
-}
-
-// Device check of the seeded reciprocals of the region-B Schwarzschild RHS (rcp_seed.h)
-// against the compiler's division (tests/test_gpu_rcp_seed.py): tuple i = (r, radius, a,
-// sin, cos) in t[5 i ..]; flags[i] gets bit
-//   1 radius / r   2 2 / r   4 radius / (r r)   8 (radius / (r r)) / a   16 (2 cos) / sin
-// for each quotient whose bits differ.  a comes from the tuple, not from r, so that the
-// test can put it on the predicate's edge.
-__global__ void rcp_seed_check_kernel(uint64_t n, const double* __restrict__ t, uint8_t* __restrict__ flags) {
-  const uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= n) return;
-  const double r = t[5 * i], radius = t[5 * i + 1], a = t[5 * i + 2], st = t[5 * i + 3], ct = t[5 * i + 4];
-  auto bits = [](double v) { return (uint64_t)__double_as_longlong(v); };
-  auto hw_rcp = [](double v) { return __builtin_amdgcn_rcp(v); };
-  const double rr = r * r, two_ct = 2.0 * ct;
-  double Yr, Yrr, Ya, Yst;
-  rcpseed::rcp_r_rr(r, rr, hw_rcp, &Yr, &Yrr);
-  rcpseed::rcp_pair(a, st, hw_rcp, &Ya, &Yst);
-  const double a_prime = rcpseed::div_by_rcp(radius, rr, Yrr);
-  volatile double v_r = r, v_radius = radius, v_a = a, v_st = st, v_rr = rr, v_two = 2.0, v_two_ct = two_ct,
-                  v_a_prime = a_prime;  // keep the reference divisions as divisions
-  uint32_t f = 0;
-  if (bits(rcpseed::div_by_rcp(radius, r, Yr)) != bits(v_radius / v_r)) f |= 1u;
-  if (bits(rcpseed::div_by_rcp(2.0, r, Yr)) != bits(v_two / v_r)) f |= 2u;
-  if (bits(a_prime) != bits(v_radius / v_rr)) f |= 4u;
-  if (bits(rcpseed::div_by_rcp(a_prime, a, Ya)) != bits(v_a_prime / v_a)) f |= 8u;
-  if (bits(rcpseed::div_by_rcp(two_ct, st, Yst)) != bits(v_two_ct / v_st)) f |= 16u;
-  flags[i] = (uint8_t)f;
-}
-#endif  // GRT_MAIN_TU
-
-constexpr double PI = 3.14159265358979323846;
-constexpr double TWO_PI = 2.0 * 3.14159265358979323846;
-
-// runge_kutta.rs:16-84
-constexpr double B21 = 2.0 / 9.0;
-constexpr double B31 = 1.0 / 12.0, B32 = 1.0 / 4.0;
-constexpr double B41 = 69.0 / 128.0, B42 = -243.0 / 128.0, B43 = 135.0 / 64.0;
-constexpr double B51 = -17.0 / 12.0, B52 = 27.0 / 4.0, B53 = -27.0 / 5.0, B54 = 16.0 / 15.0;
-constexpr double B61 = 65.0 / 432.0, B62 = -5.0 / 16.0, B63 = 13.0 / 16.0, B64 = 4.0 / 27.0,
-                 B65 = 5.0 / 144.0;
-// CH1..CH6, CT1..CT6 (CH2 = CT2 = 0.0): rkf_weights.h, shared with the host check
-constexpr double BETA = 0.9;
-constexpr double INV_ORDER = 1.0 / 5.0;
-constexpr double SMALL_ERR = 1e-5;
-constexpr int MAX_RETRY = 100;
-constexpr double H_MAX = 1.0, H_MIN = 1e-12, H_GROWTH = 4.0;
-constexpr double POW_SATURATED = 1800.0;  // (H_GROWTH / BETA)^5 = 1734.1, plus margin
-
-GDEV double rem_euclid(double x, double m) {
-  double r = fmod(x, m);
-  return r < 0.0 ? r + fabs(m) : r;
-}
-
-// Per-ray constants: observer energy (redshift.rs:40-60) and, for KerrBL, the
-// conserved E, L_z, Carter Q (kerr_bl.rs:505-577).
-struct RayConst {
-  double obs;
-  double e, lz, q;
-  double pt, pphi;  // RayFrequencyData p_t, p_phi (redshift.rs:45-60), volumetric scenes only
-};
-
-// =========================================================== geometry kernels ======
-// ---- Kerr-Schild helpers (kerr.rs:31-110) ----
-template <bool FD = false>
-GDEV double ks_r_sqr(double a, double x, double y, double z) {
-  double rho_sqr = x * x + y * y + z * z;
-  return 0.5 * (rho_sqr - a * a + ksqrt<FD>((rho_sqr - a * a) * (rho_sqr - a * a) + 4.0 * a * a * z * z));
-}
-// metric(): symmetric by construction; returns the 10 distinct entries in g.
-template <bool FD = false>
-GDEV void ks_metric(double radius, double a, double x, double y, double z, double g[4][4]) {
-  double r_sqr = ks_r_sqr<FD>(a, x, y, z);
-  double r = ksqrt<FD>(r_sqr);
-  double f = kdiv<FD>(r * r * r * radius, r * r * r * r + a * a * z * z);
-  double k_0 = 1.0;
-  double k_x = kdiv<FD>(r * x + a * y, r_sqr + a * a);
-  double k_y = kdiv<FD>(r * y - a * x, r_sqr + a * a);
-  double k_z = kdiv<FD>(z, r);
-  g[0][0] = k_0 * k_0 * f - 1.0;
-  g[0][1] = k_0 * k_x * f;
-  g[0][2] = k_0 * k_y * f;
-  g[0][3] = k_0 * k_z * f;
-  g[1][1] = k_x * k_x * f + 1.0;
-  g[1][2] = k_x * k_y * f;
-  g[1][3] = k_x * k_z * f;
-  g[2][2] = k_y * k_y * f + 1.0;
-  g[2][3] = k_y * k_z * f;
-  g[3][3] = k_z * k_z * f + 1.0;
-  g[1][0] = g[0][1];
-  g[2][0] = g[0][2];
-  g[2][1] = g[1][2];
-  g[3][0] = g[0][3];
-  g[3][1] = g[1][3];
-  g[3][2] = g[2][3];
-}
-template <bool FD = false>
-GDEV void ks_metric_contra(double radius, double a, double x, double y, double z, double g[4][4]) {
-  double r_sqr = ks_r_sqr<FD>(a, x, y, z);
-  double r = ksqrt<FD>(r_sqr);
-  double f = kdiv<FD>(r * r * r * radius, r * r * r * r + a * a * z * z);
-  double kc[4];
-  kc[0] = -1.0;
-  kc[1] = kdiv<FD>(r * x + a * y, r_sqr + a * a);
-  kc[2] = kdiv<FD>(r * y - a * x, r_sqr + a * a);
-  kc[3] = kdiv<FD>(z, r);
-#pragma unroll
-  for (int i = 0; i < 4; ++i)
-#pragma unroll
-    for (int j = 0; j < 4; ++j) {
-      double eta = (i == j) ? (i == 0 ? -1.0 : 1.0) : 0.0;
-      g[i][j] = eta - f * kc[i] * kc[j];
-    }
-}
-// nalgebra gemv order: y_i = A_i0 x_0; y_i = A_ik x_k + y_i
-GDEV void mat_vec(const double A[4][4], const double* x, double* y) {
-#pragma unroll
-  for (int i = 0; i < 4; ++i) {
-    double s = A[i][0] * x[0];
-#pragma unroll
-    for (int k = 1; k < 4; ++k) s = A[i][k] * x[k] + s;
-    y[i] = s;
-  }
-}
-GDEV double quad_form(const double* v, const double M[4][4], const double* w) {
-  double s = 0.0;
-#pragma unroll
-  for (int j = 0; j < 4; ++j) {
-    double r = v[0] * M[0][j];
-#pragma unroll
-    for (int k = 1; k < 4; ++k) r = v[k] * M[k][j] + r;
-    s = (j == 0) ? r * w[0] : r * w[j] + s;
-  }
-  return s;
-}
-
-// kerr.rs:149-186 + :228-235: returns 0.5 * p^T (G dG_i G) p, which equals
-// -0.5 * p^T d_matrix_contravariant(i) p exactly (negation commutes with rounding).
-template <bool FD = false>
-GDEV double ks_accel(double radius, double a, int index, double x, double y, double z,
-                     const double G[4][4], const double* p) {
-  double c = index == 1 ? x : (index == 2 ? y : z);
-  double h = 1e-10 * fmax(fabs(c), 1.0);
-  double dx = index == 1 ? h : 0.0, dy = index == 2 ? h : 0.0, dz = index == 3 ? h : 0.0;
-  double mp[4][4], mm[4][4];
-  ks_metric<FD>(radius, a, x + dx, y + dy, z + dz, mp);
-  ks_metric<FD>(radius, a, x - dx, y - dy, z - dz, mm);
-  double two_h = 2.0 * h;
-  double D[4][4];
-#pragma unroll
-  for (int i = 0; i < 4; ++i)
-#pragma unroll
-    for (int j = 0; j < 4; ++j) D[i][j] = kdiv<FD>(mp[i][j] - mm[i][j], two_h);
-  double GD[4][4];
-#pragma unroll
-  for (int j = 0; j < 4; ++j)
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-      double s = G[i][0] * D[0][j];
-#pragma unroll
-      for (int k = 1; k < 4; ++k) s = G[i][k] * D[k][j] + s;
-      GD[i][j] = s;
-    }
-  // stream the columns of (GD)G straight into the quadratic form
-  double q = 0.0;
-#pragma unroll
-  for (int j = 0; j < 4; ++j) {
-    double col[4];
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-      double s = GD[i][0] * G[0][j];
-#pragma unroll
-      for (int k = 1; k < 4; ++k) s = GD[i][k] * G[k][j] + s;
-      col[i] = s;
-    }
-    double r = p[0] * col[0];
-#pragma unroll
-    for (int k = 1; k < 4; ++k) r = p[k] * col[k] + r;
-    q = (j == 0) ? r * p[0] : r * p[j] + q;
-  }
-  return 0.5 * q;
-}
-
-// ---- KerrBL helpers (kerr_bl.rs:62-118, :253-272) ----
-GDEV double bl_delta(double r, double r_s, double a) { return r * r - r_s * r + a * a; }
-GDEV void metric_bl(double r_s, double a, double r, double sin_t, double cos_t, double g[4][4]) {
-  double sig = r * r + a * a * (cos_t * cos_t);
-  double sin2 = sin_t * sin_t;
-#pragma unroll
-  for (int i = 0; i < 4; ++i)
-#pragma unroll
-    for (int j = 0; j < 4; ++j) g[i][j] = 0.0;
-  g[0][0] = -(1.0 - r_s * r / sig);
-  g[1][1] = sig / bl_delta(r, r_s, a);
-  g[2][2] = sig;
-  g[3][3] = (r * r + a * a + a * a * r_s * r * sin2 / sig) * sin2;
-  double g_tph = -a * r_s * r * sin2 / sig;
-  g[0][3] = g_tph;
-  g[3][0] = g_tph;
-}
-
 #ifndef GRT_PATH_COUNT
 #define GRT_PATH_COUNT 0  // diagnostic builds only: count code paths per wave and per lane
 #endif
-#if GRT_PATH_COUNT
-// Diagnostic counters of integrate_kernel, [k] wave-level executions (one lane counts each),
-// [8 + k] the same in lanes.  Kerr-Schild RHS: 0 range-free form, 1 IEEE form.  Light
-// charts' RHS: 0 region-B table with range-free divisions, 1 region-B Taylor with them,
-// 2 region-B with the IEEE divisions, 3 general (branchy) sincos.  All: 4 near-field window
-// pass, 5 accepted step, 6 attempt, 7 attempt taken again in the full form (rkf_short_ok
-// missed).  What the waves of path 3 hold: 8 every lane in glibc's region A
-// (2^-27 <= |x| < 0.855469) on do_sin's table path, 9 every lane in region A otherwise,
-// 10 every lane in region C (|x| >= 2.426265) with quadrant n = 2, 11 mixed.  Counted besides
-// those four: 12 every lane in region B (its table and Taylor cases mixed) with div_ok, 13 every
-// lane in region B with div_ok missed on some lane.
-constexpr int NPATH = 14;
-__shared__ unsigned long long path_lds[2 * NPATH];
-__device__ unsigned long long g_path[2 * NPATH];
-GDEV void path_count(int k) {
-  const uint64_t m = __ballot(1);  // the lanes executing this path together
-  if ((int)(threadIdx.x & 63) == __ffsll((long long)m) - 1) {
-    atomicAdd(&path_lds[k], 1ull);
-    atomicAdd(&path_lds[NPATH + k], (unsigned long long)__popcll(m));
-  }
-}
-#define PATH_COUNT(k) path_count(k)
-#else
-#define PATH_COUNT(k) ((void)0)
-#endif
-
-// sincos(theta), then body(sin, cos, fast).  When every lane of the wave is in one of
-// sincos's region-B cases (x near pi/2; glibc_math.h sincos_b_*), the sincos is the
-// straight-line form of that case and body runs in the same basic block, so its own
-// dependency chains (the divisions) interleave with the sincos polynomial; fast = true
-// there (the caller passes fast_ok = whether body may then take its fast form).  The same
-// bits as rsincos in every case (tests/test_glibc_math.py).
-// div_ok (per lane): the body's divisions may drop their range steps (div_inrange) in the
-// region-B cases; body's fourth argument says so at compile time (std::true_type), so
-// each form is one basic block from the sincos through the body.
-// UNIT (Schwarzschild only): with `unit` set (DevScene::unit_radius, a scene constant in a
-// scalar register) the range-free cases hand body its unit-radius form, div_form<2>.  The
-// scalar branch is taken before the sincos, so that form too is one basic block from the
-// sincos through the body (a ballot between the two cost 1 %: DESIGN.md 3).
-template <int K>
-using div_form = std::integral_constant<int, K>;  // 0 IEEE, 1 range-free, 2 range-free with radius == 1.0
-template <bool FDIV = false, bool UNIT = false, class F>
-GDEV void with_sincos(double theta, bool fast_ok, F&& body, bool div_ok = false, bool unit = false) {
-#if GRT_SINCOS_B
-  if (fast_ok) {
-    double st, ct;
-    const bool tab = glibc::sincos_b_table_ok(theta), tay = glibc::sincos_b_taylor_ok(theta);
-    if constexpr (FDIV) {
-      if (__ballot(!(tab & div_ok)) == 0) {
-        PATH_COUNT(0);
-        if constexpr (UNIT) {
-          if (unit) {
-            glibc::sincos_b_table(theta, &st, &ct);
-            body(st, ct, true, div_form<2>{});
-            return;
-          }
-        }
-        glibc::sincos_b_table(theta, &st, &ct);
-        body(st, ct, true, std::true_type{});
-        return;
-      }
-      if (__ballot(!(tay & div_ok)) == 0) {
-        PATH_COUNT(1);
-        if constexpr (UNIT) {
-          if (unit) {
-            glibc::sincos_b_taylor(theta, &st, &ct);
-            body(st, ct, true, div_form<2>{});
-            return;
-          }
-        }
-        glibc::sincos_b_taylor(theta, &st, &ct);
-        body(st, ct, true, std::true_type{});
-        return;
-      }
-    }
-    if (__ballot(!tab) == 0) {
-      PATH_COUNT(2);
-      glibc::sincos_b_table(theta, &st, &ct);
-      body(st, ct, true, std::false_type{});
-      return;
-    }
-    if (__ballot(!tay) == 0) {
-      PATH_COUNT(2);
-      glibc::sincos_b_taylor(theta, &st, &ct);
-      body(st, ct, true, std::false_type{});
-      return;
-    }
-  }
-#endif
-  PATH_COUNT(3);
-#if GRT_PATH_COUNT
-  {
-    const uint32_t k = (uint32_t)(glibc::as_u64(theta) >> 32) & 0x7fffffffu;
-    const bool ra = k >= 0x3e400000u && k < 0x3feb6000u, ra_tab = ra && !(fabs(theta) < glibc::TAYLOR_MAX);
-    double ca, cda;
-    const bool rc2 = k >= 0x400368fdu && k < 0x419921fbu && glibc::reduce_sincos_nf(theta, &ca, &cda) == 2;
-    const bool rb = k >= 0x3feb6000u && k < 0x400368fdu;
-    if (fast_ok && __ballot(!(rb & div_ok)) == 0) PATH_COUNT(12);
-    else if (fast_ok && __ballot(!rb) == 0) PATH_COUNT(13);
-    if (__ballot(!ra_tab) == 0) PATH_COUNT(8);
-    else if (__ballot(!ra) == 0) PATH_COUNT(9);
-    else if (__ballot(!rc2) == 0) PATH_COUNT(10);
-    else PATH_COUNT(11);
-  }
-#endif
-  double st, ct;
-  rsincos(theta, &st, &ct);
-  body(st, ct, false, std::false_type{});
-}
-
-// Whether every quotient and square root of rhs<KERR> at state (x, y, z) is in the exact
-// region of div_fx / sqrt_fx.  That region (measured over the whole exponent plane,
-// tests/test_gpu_arith.py::test_range_free_arithmetic_map) is E: y normal with
-// |y| < 2^1022, x = 0 or of exponent >= -969, exponent gap within -1021 .. 1022; sqrt_fx:
-// x >= 2^-969.  Bound chain, with cap = S.ks_cap <= 2^32 (host: 2^ceil(log2(2 max_radius)),
-// within 2^10 .. 2^32) and S.div_fast (radius within 2^+-20, a = 0 or within 2^+-20):
-//  * the state: each coordinate 0 or 2^-100 <= |c| < cap; D = rho^2 - a^2 >= 2^-10 + 2^-31 rho^2.
-//  * the finite-difference points of ks_accel move one coordinate by h = 1e-10 max(|c|, 1):
-//    it stays 0 / >= 2^-86 / +-1e-10 and <= 2^32, and rho^2 moves by < 2^-32 (rho^2 + 1), so
-//    D >= 2^-11 and rho^2 < 2^66 at every point the metric is evaluated.
-//  * sqrt_fx arguments: D^2 + 4 a^2 z^2 in 2^-22 .. 2^133; r^2 = (D + sqrt(..)) / 2 in
-//    2^-11 .. 2^66 (r^2 <= rho^2), so r in 2^-5.5 .. 2^33.
-//  * f = r^3 radius / (r^4 + a^2 z^2): numerator 2^-36.5 .. 2^119, denominator 2^-22 .. 2^133.
-//  * k_x, k_y: numerator r x + a y is 0, or a nonzero sum of terms >= 2^-120 (>= 2^-172, a
-//    multiple of the smaller term's ulp), <= 2^66; denominator r^2 + a^2 in 2^-11 .. 2^67.
-//    k_z = z / r: numerator 0 or >= 2^-100, denominator 2^-5.5 .. 2^33.  So every k is 0 or
-//    within 2^-239 .. 2^76, f within 2^-170 .. 2^15, metric entries 0 or within 2^-648 .. 2^168.
-//  * D_ij = (mp - mm) / 2h: numerator 0 or >= an ulp of the smaller entry (>= 2^-700), <= 2^169;
-//    2h = 2e-10 max(|c|, 1) within 2^-33 .. 2^0.
-// Every numerator is 0 or of exponent -700 .. 169, every denominator of exponent -33 .. 133:
-// inside E, with the box |x|, |y|, |x / y| <= 2^+-600 of the earlier argument to spare.  The
-// device check of the whole RHS against its IEEE form on states at these edges, cap 2^15 and
-// 2^32: tests/test_gpu_arith.py::test_rhs_kerr_schild_fast_form_matches_ieee.
-GDEV bool ks_fd_ok(double a, double x, double y, double z, double cap) {
-  auto c_ok = [cap](double c) { return (c == 0.0) | ((fabs(c) >= 0x1p-100) & (fabs(c) < cap)); };
-  const double rho2 = x * x + y * y + z * z;
-  return c_ok(x) & c_ok(y) & c_ok(z) & (rho2 - a * a >= 0x1p-10 + 0x1p-31 * rho2);
-}
-// Region-B division predicates of the Schwarzschild and KerrBL RHS (see there)
-GDEV bool schw_div_ok(const DevScene& S, double r) {
-  return S.div_fast && (fabs(r) > 0x1p-100) & (fabs(r) < 0x1p100) & (fabs(r - S.radius) > S.radius * 0x1p-40);
-}
-// What the render asks at each RHS: r > S.div_r_lo and r < 2^100, where the host (api.hip)
-// sets div_r_lo to radius (1 + 2^-40), moved up until schw_div_ok's third test holds at
-// div_r_lo itself.  With S.div_fast (0 < radius within 2^+-50) this implies schw_div_ok:
-// r > div_r_lo > radius > 2^-50 gives |r| > 2^-100, and the rounded r - radius is monotone
-// in r, so it is >= div_r_lo - radius > 2^-40 radius.  So the proofs at rhs<SCHWARZSCHILD>
-// hold unchanged on this subset, in two compares instead of a subtraction and three.  A ray
-// inside the horizon or at a negative r takes the IEEE divisions, as every r may.
-GDEV bool schw_div_ok_render(const DevScene& S, double r) {
-#if GRT_DIV_OK_CHEAP
-  return S.div_fast && (r > S.div_r_lo) & (r < 0x1p100);
-#else
-  return schw_div_ok(S, r);
-#endif
-}
-GDEV bool bl_div_ok(const DevScene& S, double r, double del, double l_z) {
-  return S.div_fast && (fabs(r) < 0x1p100) & in_div_range(del) & (fabs(l_z) > 0x1p-200) & (fabs(l_z) < 0x1p100);
-}
-
-
-// ---- the ODE right-hand sides ----
-// MODE 0: the render's RHS.  MODE 1 / 2 (rhs_check_kernel only): region-B sincos (or no
-// sincos: Kerr-Schild), then the range-free (1) or the IEEE (2) form of the body, whatever
-// the predicates say -- the check compares the two where the predicate holds.
-template <int G, int MODE = 0>
-GDEV void rhs(const DevScene& S, const RayConst& rc, const double* y, double* o) {
-  if constexpr (G == GRT_GEOM_SCHWARZSCHILD) {  // schwarzschild.rs:54-80
-    double radius = S.radius;
-    double r = y[1], theta = y[2];
-    double v_t = y[4], v_r = y[5], v_theta = y[6], v_phi = y[7];
-    auto body = [&](double st, double ct, bool fast, auto fdiv) {
-      if constexpr (decltype(fdiv)::value != 0) {
-        // rcp_seed.h: 1 / (r r) seeded from the refined 1 / r
-        auto hw_rcp = [](double v) { return __builtin_amdgcn_rcp(v); };
-        const double rr = r * r;
-        double Yr, Yrr, Ya, Yst;
-        rcpseed::rcp_r_rr(r, rr, hw_rcp, &Yr, &Yrr);
-        double radius_over_r, two_over_r, a, a_prime;
-        if constexpr (decltype(fdiv)::value == 2) {
-          // radius == 1.0 (S.unit_radius): the same bits from 6 fewer instructions (rcp_seed.h)
-          rcpseed::unit_radius_quotients(r, rr, Yr, Yrr, &radius_over_r, &two_over_r, &a, &a_prime);
-          rcpseed::rcp_pair(a, st, hw_rcp, &Ya, &Yst);
-        } else {
-          radius_over_r = rcpseed::div_by_rcp(radius, r, Yr);
-          two_over_r = rcpseed::div_by_rcp(2.0, r, Yr);
-          a = 1.0 - radius_over_r;
-          rcpseed::rcp_pair(a, st, hw_rcp, &Ya, &Yst);
-          a_prime = rcpseed::div_by_rcp(radius, rr, Yrr);
-        }
-        double aprime_over_a = rcpseed::div_by_rcp(a_prime, a, Ya);
-        o[0] = v_t;
-        o[1] = v_r;
-        o[2] = v_theta;
-        o[3] = v_phi;
-        o[4] = -(aprime_over_a)*v_t * v_r;
-        o[5] = -0.5 * a * a_prime * v_t * v_t + 0.5 * (aprime_over_a)*v_r * v_r +
-               a * r * (v_theta * v_theta + v_phi * v_phi * st * st);
-        o[6] = -(two_over_r)*v_r * v_theta + st * ct * v_phi * v_phi;
-        o[7] = -(two_over_r)*v_phi * v_r - rcpseed::div_by_rcp(2.0 * ct, st, Yst) * v_theta * v_phi;
-        return;
-      }
-      double radius_over_r, two_over_r;
-#if GRT_SHARED_DIV
-      if (fast || S.div_share) {
-        div2_same_den(radius, 2.0, r, &radius_over_r, &two_over_r);
-      } else
-#endif
-      {
-        radius_over_r = radius / r;
-        two_over_r = 2.0 / r;
-      }
-      double a = 1.0 - radius_over_r;
-      double a_prime = radius / (r * r);
-      double aprime_over_a = a_prime / a;
-      o[0] = v_t;
-      o[1] = v_r;
-      o[2] = v_theta;
-      o[3] = v_phi;
-      o[4] = -(aprime_over_a)*v_t * v_r;
-      o[5] = -0.5 * a * a_prime * v_t * v_t + 0.5 * (aprime_over_a)*v_r * v_r +
-             a * r * (v_theta * v_theta + v_phi * v_phi * st * st);
-      o[6] = -(two_over_r)*v_r * v_theta + st * ct * v_phi * v_phi;
-      o[7] = -(two_over_r)*v_phi * v_r - 2.0 * ct / st * v_theta * v_phi;
-    };
-    // fast form: the shared reciprocal, decided with the wave-uniform case (S.div_share).
-    // Divisions without range steps (div_inrange) in region B: there sin theta >= 0.75 and
-    // 2^-55 < |cos theta| < 0.66, and with S.div_fast (0 < radius within 2^+-50),
-    // 2^-100 < |r| < 2^100 and |r - radius| > 2^-40 radius (so |a| > 2^-42), every operand
-    // and quotient of the five divisions is within 2^+-600 (schw_div_ok; device check of the
-    // two forms at the predicate's edges: tests/test_gpu_arith.py
-    // ::test_rhs_schwarzschild_fast_form_matches_ieee).  1 / (r r) takes its seed from the
-    // refined 1 / r instead of a v_rcp_f64 of its own (rcp_seed.h: 16 cycles of the SIMD
-    // against a multiply's 4, tools/valu_issue_cost.hip); the new intermediates are the seed
-    // Y_r Y_r within 2^+-200 and its Newton residual 1 - (r r) Y_r Y_r within 2^-50 of 0,
-    // both inside E with the box to spare (tests/test_gpu_rcp_seed.py).  S.unit_radius
-    // (radius == 1.0 and S.div_fast, every black-hole scene of the reference): the third
-    // form, value-identical there, so it needs no predicate of its own.
-    if constexpr (MODE != 0) {
-      double st, ct;
-      if (glibc::sincos_b_table_ok(theta)) glibc::sincos_b_table(theta, &st, &ct);
-      else glibc::sincos_b_taylor(theta, &st, &ct);
-      if constexpr (MODE == 1) {  // the form the render takes for this scene
-        if (S.unit_radius) body(st, ct, true, div_form<2>{});
-        else body(st, ct, true, std::true_type{});
-      } else body(st, ct, true, std::false_type{});
-      return;
-    }
-    with_sincos<GRT_FAST_DIV, GRT_UNIT_RADIUS>(theta, S.div_share, body, schw_div_ok_render(S, r),
-                                               S.unit_radius != 0);
-  } else if constexpr (G == GRT_GEOM_EUCLIDEAN_SPHERICAL) {  // euclidean_spherical.rs:48-70
-    double r = y[1], theta = y[2];
-    double v_t = y[4], v_r = y[5], v_theta = y[6], v_phi = y[7];
-    double st, ct;
-    rsincos(theta, &st, &ct);
-    o[0] = v_t;
-    o[1] = v_r;
-    o[2] = v_theta;
-    o[3] = v_phi;
-    o[4] = 0.0;
-    o[5] = r * (v_theta * v_theta + v_phi * v_phi * st * st);
-    o[6] = -(2.0 / r) * v_r * v_theta + st * ct * v_phi * v_phi;
-    o[7] = -(2.0 / r) * v_phi * v_r - 2.0 * ct / st * v_theta * v_phi;
-  } else if constexpr (G == GRT_GEOM_KERR_BL) {  // kerr_bl.rs:141-174
-    double radius = S.radius, a = S.a, e = rc.e, l_z = rc.lz, q = rc.q;
-    double r = y[1], theta = y[2];
-    const double del = bl_delta(r, radius, a);
-    auto body = [&](double st, double ct, bool, auto fdiv) {
-      double r2a2 = r * r + a * a;
-      double p_r = r2a2 * e - a * l_z;
-      double sin2 = st * st;
-      if constexpr (decltype(fdiv)::value) {
-        double r2a2_del, a_del;
-        div2_inrange(r2a2, a, del, &r2a2_del, &a_del);
-        o[0] = r2a2_del * p_r + a * (l_z - a * e * sin2);
-        o[1] = y[4];
-        o[2] = y[5];
-        o[3] = a_del * p_r + div_inrange(l_z, sin2) - a * e;
-        double le = l_z - a * e;
-        double carter = le * le + q;
-        o[4] = (4.0 * r * e * p_r - (2.0 * r - radius) * carter) / 2.0;
-        o[5] = (-2.0 * a * a * e * e * ct * st + div_inrange(2.0 * l_z * l_z * ct, st * (st * st))) / 2.0;
-        o[6] = 0.0;
-        o[7] = 0.0;
-        return;
-      }
-      o[0] = r2a2 / del * p_r + a * (l_z - a * e * sin2);
-      o[1] = y[4];
-      o[2] = y[5];
-      o[3] = a / del * p_r + l_z / sin2 - a * e;
-      double le = l_z - a * e;
-      double carter = le * le + q;
-      o[4] = (4.0 * r * e * p_r - (2.0 * r - radius) * carter) / 2.0;
-      o[5] = (-2.0 * a * a * e * e * ct * st + 2.0 * l_z * l_z * ct / (st * (st * st))) / 2.0;
-      o[6] = 0.0;
-      o[7] = 0.0;
-    };
-    // Divisions without range steps (div_inrange) in region B: there sin theta >= 0.75 and
-    // 2^-55 < |cos theta| < 0.66, and with S.div_fast (radius, |a| within 2^+-50),
-    // 2^-200 < |l_z| < 2^100, |r| < 2^100 and del within 2^+-300, every operand and
-    // quotient of the four divisions is within 2^+-600 (bl_div_ok; device check:
-    // tests/test_gpu_arith.py::test_rhs_kerr_bl_fast_form_matches_ieee).
-    if constexpr (MODE != 0) {
-      double st, ct;
-      if (glibc::sincos_b_table_ok(theta)) glibc::sincos_b_table(theta, &st, &ct);
-      else glibc::sincos_b_taylor(theta, &st, &ct);
-      if constexpr (MODE == 1) body(st, ct, true, std::true_type{});
-      else body(st, ct, true, std::false_type{});
-      return;
-    }
-    with_sincos<GRT_FAST_DIV_BL>(theta, true, body, bl_div_ok(S, r, del, l_z));
-  } else if constexpr (G == GRT_GEOM_KERR) {  // kerr.rs:200-241
-    double radius = S.radius, a = S.a;
-    double x = y[1], yy = y[2], z = y[3];
-    double p[4] = {y[4], y[5], y[6], y[7]};
-    auto body = [&](auto fd) {
-      constexpr bool FD = decltype(fd)::value;
-      double Gc[4][4];
-      ks_metric_contra<FD>(radius, a, x, yy, z, Gc);
-      double xdot[4];
-      mat_vec(Gc, p, xdot);
-      o[0] = xdot[0];
-      o[1] = xdot[1];
-      o[2] = xdot[2];
-      o[3] = xdot[3];
-      o[4] = 0.0;
-      o[5] = ks_accel<FD>(radius, a, 1, x, yy, z, Gc, p);
-      o[6] = ks_accel<FD>(radius, a, 2, x, yy, z, Gc, p);
-      o[7] = ks_accel<FD>(radius, a, 3, x, yy, z, Gc, p);
-    };
-    if constexpr (MODE != 0) {
-      if constexpr (MODE == 1) body(std::true_type{});
-      else body(std::false_type{});
-      return;
-    }
-#if GRT_FAST_DIV_KS
-    // The metric quotients without v_div_scale (div_fx) when every lane's state passes
-    // ks_fd_ok (wave-uniform, like the region-B forms above)
-    if (S.div_fast && __ballot(!ks_fd_ok(a, x, yy, z, S.ks_cap)) == 0) {
-      PATH_COUNT(0);
-      body(std::true_type{});
-      return;
-    }
-#endif
-    PATH_COUNT(1);
-    body(std::false_type{});
-  } else {  // Euclidean, euclidean.rs:47-53
-    o[0] = y[4];
-    o[1] = y[5];
-    o[2] = y[6];
-    o[3] = y[7];
-    o[4] = 0.0;
-    o[5] = 0.0;
-    o[6] = 0.0;
-    o[7] = 0.0;
-  }
-}
-
-// Lane K's value of v in every lane of its quad (DPP quad_perm [K,K,K,K], no LDS).
-template <int K>
-GDEV double quad_bcast(double v) {
-  constexpr int ctrl = K | (K << 2) | (K << 4) | (K << 6);
-  const int lo = __builtin_amdgcn_mov_dpp(__double2loint(v), ctrl, 0xf, 0xf, false);
-  const int hi = __builtin_amdgcn_mov_dpp(__double2hiint(v), ctrl, 0xf, 0xf, false);
-  return __hiloint2double(hi, lo);
-}
-
-// rhs<KERR> on the 4 lanes of a quad (tail_kernel): every lane forms the contravariant
-// metric and xdot as rhs<KERR> does; lane `sub` < 3 evaluates acceleration component
-// sub + 1 (lane 3 repeats component 3), and the three components are broadcast across
-// the quad.  Every value comes out of the same operations as in rhs<KERR>, so o is
-// bit-identical in all four lanes; the quad's lanes must be active together.
-template <bool FD>
-GDEV void rhs_ks_quad_form(const DevScene& S, const double* y, double* o, int sub) {
-  const double radius = S.radius, a = S.a;
-  const double x = y[1], yy = y[2], z = y[3];
-  const double p[4] = {y[4], y[5], y[6], y[7]};
-  double Gc[4][4];
-  ks_metric_contra<FD>(radius, a, x, yy, z, Gc);
-  double xdot[4];
-  mat_vec(Gc, p, xdot);
-  const double acc = ks_accel<FD>(radius, a, sub < 3 ? sub + 1 : 3, x, yy, z, Gc, p);
-  o[0] = xdot[0];
-  o[1] = xdot[1];
-  o[2] = xdot[2];
-  o[3] = xdot[3];
-  o[4] = 0.0;
-  o[5] = quad_bcast<0>(acc);
-  o[6] = quad_bcast<1>(acc);
-  o[7] = quad_bcast<2>(acc);
-}
-// with rhs<KERR>'s range-free metric quotients and square roots when every lane's state
-// passes ks_fd_ok (the quad's four lanes hold the same state)
-GDEV void rhs_ks_quad(const DevScene& S, const double* y, double* o, int sub) {
-#if GRT_FAST_DIV_KS
-  if (S.div_fast && __ballot(!ks_fd_ok(S.a, y[1], y[2], y[3], S.ks_cap)) == 0) {
-    rhs_ks_quad_form<true>(S, y, o, sub);
-    return;
-  }
-#endif
-  rhs_ks_quad_form<false>(S, y, o, sub);
-}
-
-template <int G, bool QUAD>
-GDEV void rhs_sel(const DevScene& S, const RayConst& rc, const double* y, double* o, int sub) {
-  if constexpr (QUAD) {
-    static_assert(G == GRT_GEOM_KERR, "the quad-split RHS is the Kerr-Schild one");
-    rhs_ks_quad(S, y, o, sub);
-  } else {
-    rhs<G>(S, rc, y, o);
-  }
-}
-
-// Number of state components that can be non-zero: KerrBL's y[6], y[7] are
-// identically 0 (its RHS returns literal zeros), so every RKF term on them is an
-// exact +-0 and the norm term a2 + a6 == a2; skipping them is bit-exact.
-template <int G>
-struct Dim {
-  static constexpr int D = (G == GRT_GEOM_KERR_BL) ? 6 : 8;
-};
-
-// One rkf45_step (runge_kutta.rs:86-125).  Returns the SQUARED truncation error norm:
-// the controller takes the (correctly rounded) sqrt only when the decision needs it.
-// UNIT_H: every lane of the wave has h == 1.0 (H_MAX, the far field), where h * o is o
-// itself (x * 1.0 == x for every finite and infinite x and keeps the sign of zero; a NaN
-// stays a NaN, which stops the ray either way), so the eight products per stage go.
-// Stage values k1..k4 parked in LDS (KLDS): slot j of component i of thread t at
-// kl_buf[(j * 8 + i) * KL_STRIDE + t].  The Kerr-Schild attempt keeps 6 x 8 stage doubles
-// live across RHS evaluations that need ~100 registers of their own; at 2 waves per SIMD
-// (256 registers) the compiler spilled ~90 registers to scratch.  The reads take their
-// offset through an empty asm that depends on the stage just computed, so the compiler
-// neither forwards the stored registers (keeping them live) nor hoists the reads above
-// that RHS evaluation.  Values are stored and re-read unchanged: the arithmetic is the same.
-constexpr int KL_STRIDE = 256;
-__shared__ double kl_buf[GRT_KL_STAGES * 8 * KL_STRIDE];  // 16 KB per stage, only in kernels that use it
-GDEV void kl_put(int j, const double* k, int D, int skip = -1) {
-#pragma unroll
-  for (int i = 0; i < 8; ++i)
-    if (i < D && i != skip) kl_buf[(j * 8 + i) * KL_STRIDE + (int)threadIdx.x] = k[i];
-}
-// threadIdx.x, opaque to the compiler and ordered after `dep`
-GDEV int kl_slot_after(double dep) {
-  int t = (int)threadIdx.x;
-  __asm__ volatile("" : "+v"(t) : "v"(dep));
-  return t;
-}
-GDEV double kl_get(int t, int j, int i) { return kl_buf[(j * 8 + i) * KL_STRIDE + t]; }
-
-// State components the RHS reads (the others -- t, and phi where the metric does not
-// depend on it -- only receive stage values, so their stage inputs are never formed).
-template <int G>
-GDEV constexpr bool rhs_reads(int i) {
-  if (G == GRT_GEOM_EUCLIDEAN) return i >= 4;
-  if (G == GRT_GEOM_KERR) return i >= 1;
-  return i == 1 || i == 2 || i >= 4;  // Schwarzschild, EuclideanSpherical, KerrBL: r, theta, velocities
-}
-
-// The state component whose derivative the RHS sets to the constant 0.0, or -1: p_t in
-// Kerr-Schild (kerr.rs:233-241, the metric does not depend on t).  Its stage values are
-// k_j = h * 0.0 = kz for every stage j of an attempt (kz = +0 for h > 0), so each of
-// rkf45_step's left-to-right sums for it, y + c_1 kz + ... + c_m kz, is a sum of signed
-// zeros (or NaNs) onto y, and IEEE addition gives it in one step: y + kz when every
-// coefficient is >= 0 (each term carries kz's sign), y + kz * kz when the signs are mixed
-// (some term is +0, which makes any later zero sum +0; kz * kz is +0, or NaN for a NaN
-// kz).  Its error term (a mixed sum, no y) squares to +0: kz * kz as well.  Same bits as
-// the full sums for every y, signed zeros and NaN included.
-template <int G>
-GDEV constexpr int zero_k() {
-  return G == GRT_GEOM_KERR ? 4 : -1;
-}
-
-// nalgebra norm(): 8-accumulator unrolled dot, ((a0+a4) + (a1+a5)) + (a2+a6) + (a3+a7)
-// z >= 0: e[z] * e[z] is given as zz (zero_k)
-template <int D>
-GDEV double err_norm_sq(const double* e, int z = -1, double zz = 0.0) {
-  double res;
-  if constexpr (D == 8) {
-    double sq[8];
-#pragma unroll
-    for (int i = 0; i < 8; ++i) sq[i] = (i == z) ? zz : e[i] * e[i];
-    res = sq[0] + sq[4];
-    res += sq[1] + sq[5];
-    res += sq[2] + sq[6];
-    res += sq[3] + sq[7];
-  } else {
-    res = e[0] * e[0] + e[4] * e[4];
-    res += e[1] * e[1] + e[5] * e[5];
-    res += e[2] * e[2];
-    res += e[3] * e[3];
-  }
-  return res;
-}
-
 #ifndef GRT_RK_FOLD
 #define GRT_RK_FOLD 1  // running RKF sums (rkf_attempt_fold) for every chart but Kerr-Schild
 #endif
+#ifndef GRT_PROBE_ESCAPE
+#define GRT_PROBE_ESCAPE 1  // end an outward-bound Kerr-Schild probe far from the hole at once
+#endif
 
-// rkf45_step with every left-to-right sum of runge_kutta.rs:94-124 evaluated as a running
-// sum as soon as its terms exist.  The sums are the reference's, term by term in the same
-// order ((y + B61*k1) + B62*k2) + ..., so every value is bit-identical to rkf_attempt_full;
-// what changes is how many stage values are live across an RHS evaluation:
-//   - a component the RHS does not read (rhs_reads) folds k_j into y_new and the error
-//     right away: 2 live values instead of up to 6;
-//   - the others keep k1..k3 until k4 exists, then fold k1..k4 into the stage-5 input, the
-//     stage-6 partial, y_new and the error: 3 live values across RHS 5 and 2 across RHS 6,
-//     instead of 4 and 5.
-//
-// SHORT: the sums without their k2 terms.  The Fehlberg weights CH2 and CT2 are 0.0, but
-// without fast-math `X + 0.0 * k2` stays a multiply and an add (0 * k2 is -0, or NaN for a
-// non-finite k2, and X + (+-0) can turn a -0 into +0): 24 instructions per attempt that
-// change a result bit only in the cases of this lemma.
-//   Lemma (Schwarzschild chart; 0 < h <= 1, which rclamp to [H_MIN, H_MAX] gives).
-//   If every yn'[i] of the short attempt is finite and not -0 and its err_sq' is finite,
-//   then yn and err_sq of the full attempt have the same bits.  (rkf_short_ok)
-// Proof.  Both forms compute the same k1..k6 (the stage inputs never hold a CH / CT term).
-//  * Zeros, a2 = k2[i] finite: t = 0.0 * a2 is +-0, and X + t differs from X only for
-//    X = -0 with t = +0 (a2 sign-positive), giving +0.  The running sums then add the same
-//    later terms to -0 (short) and +0 (full): the first non-zero term makes them equal for
-//    good, and while every later term is a zero the short sum is -0 (all of them -0) or
-//    both are +0.  So a difference that survives to yn shows as yn'[i] = -0 against
-//    yn[i] = +0, which the premise excludes.  The same holds for e[i], where it is a
-//    difference in the sign of a zero only, and e[i] enters err_sq as e[i] * e[i] alone:
-//    err_sq needs no premise beyond the one on a2.
-//  * a2 not finite: then 0.0 * a2 is NaN and yn[i], e[i] of the full form are NaN.  In this
-//    chart o[0..3] are the stage input's velocities (rhs: o[i] = y[4 + i]), so the short
-//    outputs are non-finite as well, against the premise:
-//      i >= 4: tmp3[i] = y[i] + B31 k1[i] + B32 k2[i] is non-finite (B32 != 0, and no sum
-//        of non-finite terms is finite), hence k3[i - 4] = h tmp3[i], hence yn'[i - 4]
-//        through CH3 k3[i - 4] (CH3 != 0).
-//      i < 4: k2[i] = h v with v = y[4 + i] + B21 k1[4 + i], stage 2's input velocity, and
-//        h <= 1, so v is non-finite.  Either y[4 + i] or k1[4 + i] is non-finite, hence
-//        yn'[4 + i] = y[4 + i] + CH1 k1[4 + i] + ... (CH1 != 0); or both are finite and the
-//        sum overflowed (two values near 1e308), which can leave yn'[4 + i] finite: but then
-//        stage 2's o[5] holds a term (coefficient) v v, non-finite whatever the coefficient
-//        (inf times 0 is NaN), so k2[5] is non-finite and the case i >= 4 gives yn'[1].
-// The identities hold under FMA contraction too: fma(0.0, a2, X) follows the same zero and
-// NaN rules (geodesic_fused.hip).  Host check over every combination of the special values:
-// tests/test_rkf_zero_terms.py; device check of both forms: tests/test_gpu_rkf_short.py.
-// KerrBL is out of scope: its k2[0] and k2[3] come from formulas (l_z / sin^2 ...) and reach
-// nothing but the dropped terms (o[6] = o[7] = 0 and the RHS reads neither t nor phi), so a
-// non-finite k2[0] or k2[3] can leave the short outputs finite where the full sum is NaN.
-template <int G, bool UNIT_H, bool QUAD, int NKL, bool SHORT = false>
-GDEV double rkf_attempt_fold(const DevScene& S, const RayConst& rc, const double* y, double h, double* yn,
-                             int sub) {
-  static_assert(!SHORT || G == GRT_GEOM_SCHWARZSCHILD, "short RKF sums: the lemma is the Schwarzschild chart's");
-  constexpr int D = Dim<G>::D;
-  double k1[8], k2[8], k3[8], k4[8], k5[8], k6[8], tmp[8], o[8], p6[8], e[8];
-  int t = 0;  // LDS slot, re-derived after each stage (kl_slot_after)
-#define KV(j, i) (((j) <= NKL) ? kl_get(t, (j) - 1, (i)) : k##j[i])
-#define STAGE(kj)                                                   \
-  _Pragma("unroll") for (int i = 0; i < D; ++i) kj[i] = UNIT_H ? o[i] : h * o[i];
-  rhs_sel<G, QUAD>(S, rc, y, o, sub);
-  STAGE(k1)
-#pragma unroll
-  for (int i = 0; i < D; ++i)
-    if (!rhs_reads<G>(i)) {
-      yn[i] = y[i] + CH1 * k1[i];
-      e[i] = CT1 * k1[i];
+#include "appearance.h"
+
+// The charts this unit builds kernels for, one bit per GRT_GEOM_*: the trace
+// (launch_trace), the exact-only kernels (geometry buffer fill, work-order probes) and
+// the exact build's diagnostics.
+constexpr unsigned ALL_CHARTS = 0x1f, KERR_CHART = 1u << GRT_GEOM_KERR, KERR_BL_CHART = 1u << GRT_GEOM_KERR_BL;
+#if GRT_MAIN_TU
+constexpr unsigned TRACE_CHARTS = ALL_CHARTS & ~KERR_BL_CHART;  // the exact KerrBL trace is grt::kerr_bl's
+constexpr unsigned FILL_CHARTS = TRACE_CHARTS;                  // and so is its geometry buffer fill
+constexpr unsigned PROBE_CHARTS = ALL_CHARTS;
+constexpr unsigned DIAG_CHARTS = ALL_CHARTS;  // trajectories, invariant monitors
+constexpr unsigned RHS_CHECK_CHARTS = 1u << GRT_GEOM_SCHWARZSCHILD | KERR_CHART | KERR_BL_CHART;  // the range-free forms
+#elif GRT_FUSED
+constexpr unsigned TRACE_CHARTS = ALL_CHARTS & ~KERR_CHART;  // Kerr-Schild always runs exact (grt_set_arithmetic)
+#elif GRT_KERR_BL_TU
+constexpr unsigned TRACE_CHARTS = KERR_BL_CHART, FILL_CHARTS = KERR_BL_CHART;
+#else  // GRT_SEQ
+constexpr unsigned TRACE_CHARTS = ALL_CHARTS, FILL_CHARTS = ALL_CHARTS, PROBE_CHARTS = ALL_CHARTS;
+#endif
+
+// f(std::integral_constant<int, G>()) for G = geometry when CHARTS has that chart;
+// hipErrorInvalidValue otherwise.  f is instantiated for the charts of CHARTS only.
+template <unsigned CHARTS, int G = 0, class F>
+static hipError_t with_chart(int geometry, const F& f) {
+  if constexpr ((CHARTS >> G) == 0) {
+    return hipErrorInvalidValue;
+  } else {
+    if constexpr ((CHARTS >> G) & 1u) {
+      if (geometry == G) return f(std::integral_constant<int, G>());
     }
-  if (NKL >= 1) kl_put(0, k1, D);
-#pragma unroll
-  for (int i = 0; i < D; ++i) tmp[i] = y[i] + B21 * k1[i];
-  if (D < 8) { tmp[6] = 0.0; tmp[7] = 0.0; }
-  rhs_sel<G, QUAD>(S, rc, tmp, o, sub);
-  STAGE(k2)
-#pragma unroll
-  for (int i = 0; i < D; ++i)
-    if (!rhs_reads<G>(i) && !SHORT) {
-      yn[i] = yn[i] + CH2 * k2[i];
-      e[i] = e[i] + CT2 * k2[i];
-    }
-  if (NKL >= 2) kl_put(1, k2, D);
-  if (NKL >= 1) t = kl_slot_after(k2[D - 1]);
-#pragma unroll
-  for (int i = 0; i < D; ++i) tmp[i] = y[i] + B31 * KV(1, i) + B32 * k2[i];
-  rhs_sel<G, QUAD>(S, rc, tmp, o, sub);
-  STAGE(k3)
-#pragma unroll
-  for (int i = 0; i < D; ++i)
-    if (!rhs_reads<G>(i)) {
-      yn[i] = yn[i] + CH3 * k3[i];
-      e[i] = e[i] + CT3 * k3[i];
-    }
-  if (NKL >= 3) kl_put(2, k3, D);
-  if (NKL >= 1) t = kl_slot_after(k3[D - 1]);
-#pragma unroll
-  for (int i = 0; i < D; ++i) tmp[i] = y[i] + B41 * KV(1, i) + B42 * KV(2, i) + B43 * k3[i];
-  rhs_sel<G, QUAD>(S, rc, tmp, o, sub);
-  STAGE(k4)
-  if (NKL >= 1) t = kl_slot_after(k4[D - 1]);
-#pragma unroll
-  for (int i = 0; i < D; ++i) {
-    if (!rhs_reads<G>(i)) {
-      yn[i] = yn[i] + CH4 * k4[i];
-      e[i] = e[i] + CT4 * k4[i];
-    } else {
-      const double a1 = KV(1, i), a2 = KV(2, i), a3 = KV(3, i), a4 = k4[i];
-      tmp[i] = y[i] + B51 * a1 + B52 * a2 + B53 * a3 + B54 * a4;
-      p6[i] = y[i] + B61 * a1 + B62 * a2 + B63 * a3 + B64 * a4;
-      if constexpr (SHORT) {
-        yn[i] = y[i] + CH1 * a1 + CH3 * a3 + CH4 * a4;
-        e[i] = CT1 * a1 + CT3 * a3 + CT4 * a4;
-      } else {
-        yn[i] = y[i] + CH1 * a1 + CH2 * a2 + CH3 * a3 + CH4 * a4;
-        e[i] = CT1 * a1 + CT2 * a2 + CT3 * a3 + CT4 * a4;
-      }
-    }
+    return with_chart<CHARTS, G + 1>(geometry, f);
   }
-  if (D < 8) { tmp[6] = 0.0; tmp[7] = 0.0; }
-  rhs_sel<G, QUAD>(S, rc, tmp, o, sub);
-  STAGE(k5)
-#pragma unroll
-  for (int i = 0; i < D; ++i) {
-    if (rhs_reads<G>(i)) tmp[i] = p6[i] + B65 * k5[i];
-    yn[i] = yn[i] + CH5 * k5[i];
-    e[i] = e[i] + CT5 * k5[i];
-  }
-  rhs_sel<G, QUAD>(S, rc, tmp, o, sub);
-  STAGE(k6)
-#pragma unroll
-  for (int i = 0; i < D; ++i) {
-    yn[i] = yn[i] + CH6 * k6[i];
-    e[i] = e[i] + CT6 * k6[i];
-  }
-#undef STAGE
-#undef KV
-  if (D < 8) {
-    yn[6] = 0.0;
-    yn[7] = 0.0;
-  }
-  return err_norm_sq<D>(e);
 }
 
-// QUAD: the Kerr-Schild RHS split over a quad (rhs_ks_quad), `sub` = lane & 3.
-// NKL: stages k1..k_NKL kept in LDS (see kl_put), 0 = none.
-// SHORT: without the zero-weight k2 terms (rkf_attempt_fold's lemma; the caller checks
-// rkf_short_ok and takes the attempt again in the full form where it fails).
-template <int G, bool UNIT_H = false, bool QUAD = false, int NKL = 0, bool SHORT = false>
-GDEV double rkf_attempt(const DevScene& S, const RayConst& rc, const double* y, double h,
-                        double* yn, int sub = 0) {
-  static_assert(!SHORT || (GRT_RK_FOLD && G == GRT_GEOM_SCHWARZSCHILD), "short RKF sums: rkf_attempt_fold only");
-  // Kerr-Schild keeps the plain form: its stages k1..k4 sit in LDS (NKL), which frees
-  // more registers than the running sums (measured: 17 -> 122 spilled VGPRs with them)
-  if constexpr (GRT_RK_FOLD && G != GRT_GEOM_KERR) {
-    return rkf_attempt_fold<G, UNIT_H, QUAD, NKL, SHORT>(S, rc, y, h, yn, sub);
-  }
-  constexpr int D = Dim<G>::D;
-  constexpr int Z = zero_k<G>();  // component with k_j = kz in every stage (zero_k)
-  double k1[8], k2[8], k3[8], k4[8], k5[8], k6[8], tmp[8], o[8];
-  int t = 0;  // LDS slot, re-derived after each stage (kl_slot_after)
-  // stage j's value k_j[i] (from LDS when parked there)
-#define KV(j, i) (((j) <= NKL) ? kl_get(t, (j) - 1, (i)) : k##j[i])
-  rhs_sel<G, QUAD>(S, rc, y, o, sub);
-  // signs: B21 > 0; B31, B32 > 0; B4x, B5x, B6x mixed; CH1..CH6 >= 0; CT mixed
-  const double kz = Z < 0 ? 0.0 : (UNIT_H ? o[Z < 0 ? 0 : Z] : h * o[Z < 0 ? 0 : Z]);
-  const double kzz = kz * kz;
-#pragma unroll
-  for (int i = 0; i < D; ++i) k1[i] = UNIT_H ? o[i] : h * o[i];
-  if (NKL >= 1) kl_put(0, k1, D, Z);
-#pragma unroll
-  for (int i = 0; i < D; ++i) tmp[i] = (i == Z) ? y[i] + kz : y[i] + B21 * k1[i];
-  if (D < 8) { tmp[6] = 0.0; tmp[7] = 0.0; }
-  rhs_sel<G, QUAD>(S, rc, tmp, o, sub);
-#pragma unroll
-  for (int i = 0; i < D; ++i) k2[i] = UNIT_H ? o[i] : h * o[i];
-  if (NKL >= 2) kl_put(1, k2, D, Z);
-  if (NKL >= 1) t = kl_slot_after(k2[D - 1]);
-#pragma unroll
-  for (int i = 0; i < D; ++i) tmp[i] = (i == Z) ? y[i] + kz : y[i] + B31 * KV(1, i) + B32 * k2[i];
-  rhs_sel<G, QUAD>(S, rc, tmp, o, sub);
-#pragma unroll
-  for (int i = 0; i < D; ++i) k3[i] = UNIT_H ? o[i] : h * o[i];
-  if (NKL >= 3) kl_put(2, k3, D, Z);
-  if (NKL >= 1) t = kl_slot_after(k3[D - 1]);
-#pragma unroll
-  for (int i = 0; i < D; ++i)
-    tmp[i] = (i == Z) ? y[i] + kzz : y[i] + B41 * KV(1, i) + B42 * KV(2, i) + B43 * k3[i];
-  rhs_sel<G, QUAD>(S, rc, tmp, o, sub);
-#pragma unroll
-  for (int i = 0; i < D; ++i) k4[i] = UNIT_H ? o[i] : h * o[i];
-  if (NKL >= 4) kl_put(3, k4, D, Z);
-  if (NKL >= 1) t = kl_slot_after(k4[D - 1]);
-#pragma unroll
-  for (int i = 0; i < D; ++i)
-    tmp[i] = (i == Z) ? y[i] + kzz : y[i] + B51 * KV(1, i) + B52 * KV(2, i) + B53 * KV(3, i) + B54 * k4[i];
-  rhs_sel<G, QUAD>(S, rc, tmp, o, sub);
-#pragma unroll
-  for (int i = 0; i < D; ++i) k5[i] = UNIT_H ? o[i] : h * o[i];
-  if (NKL >= 1) t = kl_slot_after(k5[D - 1]);
-#pragma unroll
-  for (int i = 0; i < D; ++i)
-    tmp[i] = (i == Z) ? y[i] + kzz
-                      : y[i] + B61 * KV(1, i) + B62 * KV(2, i) + B63 * KV(3, i) + B64 * KV(4, i) + B65 * k5[i];
-  rhs_sel<G, QUAD>(S, rc, tmp, o, sub);
-#pragma unroll
-  for (int i = 0; i < D; ++i) k6[i] = UNIT_H ? o[i] : h * o[i];
-  if (NKL >= 1) t = kl_slot_after(k6[D - 1]);
-  double e[8];
-#pragma unroll
-  for (int i = 0; i < D; ++i) {
-    if (i == Z) {  // e[Z] only enters the norm as e[Z]^2 = kz * kz
-      yn[i] = y[i] + kz;
-      e[i] = 0.0;
-      continue;
-    }
-    const double a1 = KV(1, i), a2 = KV(2, i), a3 = KV(3, i), a4 = KV(4, i);
-    yn[i] = y[i] + CH1 * a1 + CH2 * a2 + CH3 * a3 + CH4 * a4 + CH5 * k5[i] + CH6 * k6[i];
-    e[i] = CT1 * a1 + CT2 * a2 + CT3 * a3 + CT4 * a4 + CT5 * k5[i] + CT6 * k6[i];
-  }
-#undef KV
-  if (D < 8) {
-    yn[6] = 0.0;
-    yn[7] = 0.0;
-  }
-  return err_norm_sq<D>(e, Z, kzz);
-}
+#include "geodesic_rhs.h"
+#include "geodesic_rkf.h"
 
 // ---- chart helpers ----
 // Cartesian spatial position of a state (scene.rs:48-69 get_position / point.rs:125-154).
@@ -1410,7 +388,6 @@ GDEV bool killing_coefficients(const DevScene& S, double r, double* u_t, double*
 
 #include "volumetric.h"
 
-
 // ====================================================== window (chord) tests ======
 // Geometry only: the integrate kernel decides hit / no hit, the chord parameter t and
 // the hit point; everything that needs the emitter (energy, temperature, colour) is
@@ -1540,52 +517,46 @@ GDEV void init_state(const DevScene& S, const double* pos, double st, double ct,
   }
 }
 
-// The image coordinates of the ray in output slot idx of a work list: an offset list's
-// jittered pixel (get_ray_for_offset, camera.rs:247-254), or the pixel of a rectangle /
-// row-band shard (local row idx / cols, mapped to its frame row).
-#if GRT_SEQ
-// Stacked frames: integer row R of the stack is row R % cam_rows of frame R / cam_rows.
-// Returns that frame's camera and turns *R into the frame row: always from the integer
+// The camera of integer row *R of a work list, and *R as a row of that camera's frame.
+// The scene's camera, and *R as it is; in the sequence unit, over stacked frames: integer
+// row R of the stack is row R % cam_rows of frame R / cam_rows.  Always from the integer
 // row, before any sub-pixel jitter (a jittered row may leave its frame by half a pixel).
 // A row past the table (the host never makes one) takes the last camera, so that no load
 // leaves the table.
-GDEV const DevCamera& stacked_camera(const CamTable& ct, uint32_t* R) {
+GDEV const DevCamera& frame_camera(const DevScene& S, uint32_t* R CAMS_PARAM) {
+#if GRT_SEQ
   const uint32_t f = min(*R / ct.cam_rows, ct.n_cams - 1u);
   *R -= f * ct.cam_rows;
   return ct.cams[f];
+#else
+  return S.cam;
+#endif
 }
-// ray_pixel over the stack: the image coordinates within the ray's frame, and its camera.
-GDEV const DevCamera& ray_pixel(const WorkList& wl, const CamTable& ct, uint64_t idx, double* row, double* col) {
+// The pixel (r, c) of a work list's rectangle / row-band shard (local row r mapped to its
+// frame row): its image coordinates within its frame, and its camera.
+GDEV const DevCamera& rect_pixel(const DevScene& S, const WorkList& wl, uint32_t r, uint32_t c, double* row,
+                                 double* col CAMS_PARAM) {
+  uint32_t ri = wl.row0 + shard_frame_row(wl.band_rows, wl.shard, wl.n_shards, r);
+  const DevCamera& cam = frame_camera(S, &ri CAMS_ARG);
+  *row = (double)ri;
+  *col = (double)(wl.col0 + c);
+  return cam;
+}
+// The same of the ray in output slot idx of a work list: an offset list's jittered pixel
+// (get_ray_for_offset, camera.rs:247-254), or rectangle pixel (idx / cols, idx % cols).
+GDEV const DevCamera& ray_pixel(const DevScene& S, const WorkList& wl, uint64_t idx, double* row,
+                                double* col CAMS_PARAM) {
   if (wl.pixel_index) {
     const uint32_t pix = wl.pixel_index[idx];
     uint32_t ri = wl.row0 + pix / wl.cols;
-    const DevCamera& cam = stacked_camera(ct, &ri);
+    const DevCamera& cam = frame_camera(S, &ri CAMS_ARG);
     const double r = (double)ri, cc = (double)(wl.col0 + pix % wl.cols);
     *row = r + (wl.dy[idx] - 0.5);
     *col = cc + (wl.dx[idx] - 0.5);
     return cam;
   }
-  const uint32_t r = (uint32_t)(idx / wl.cols), cc = (uint32_t)(idx % wl.cols);
-  uint32_t ri = wl.row0 + shard_frame_row(wl.band_rows, wl.shard, wl.n_shards, r);
-  const DevCamera& cam = stacked_camera(ct, &ri);
-  *row = (double)ri;
-  *col = (double)(wl.col0 + cc);
-  return cam;
+  return rect_pixel(S, wl, (uint32_t)(idx / wl.cols), (uint32_t)(idx % wl.cols), row, col CAMS_ARG);
 }
-#else
-GDEV void ray_pixel(const WorkList& wl, uint64_t idx, double* row, double* col) {
-  if (wl.pixel_index) {
-    const uint32_t pix = wl.pixel_index[idx];
-    const double r = (double)(wl.row0 + pix / wl.cols), cc = (double)(wl.col0 + pix % wl.cols);
-    *row = r + (wl.dy[idx] - 0.5);
-    *col = cc + (wl.dx[idx] - 0.5);
-  } else {
-    const uint32_t r = (uint32_t)(idx / wl.cols), cc = (uint32_t)(idx % wl.cols);
-    *row = (double)(wl.row0 + shard_frame_row(wl.band_rows, wl.shard, wl.n_shards, r));
-    *col = (double)(wl.col0 + cc);
-  }
-}
-#endif
 
 // Create a camera ray's state (camera.rs:234-254 + init_state); also the observer
 // energy the redshift needs (redshift.rs:40-43).
@@ -1609,6 +580,14 @@ GDEV void init_ray(const DevScene& S, double row, double col, double* y, RayCons
     rc.pt = inner<G>(S, cam.pos, cam.sin_theta, cam.cos_theta, et, p);
     rc.pphi = inner<G>(S, cam.pos, cam.sin_theta, cam.cos_theta, ax, p);
   }
+}
+// The camera ray of rectangle pixel (r, c) of a work list.
+template <int G>
+GDEV void init_rect_ray(const DevScene& S, const WorkList& wl, uint32_t r, uint32_t c, double* y,
+                        RayConst& rc CAMS_PARAM) {
+  double row, col;
+  [[maybe_unused]] const DevCamera& cam = rect_pixel(S, wl, r, c, &row, &col CAMS_ARG);
+  init_ray<G>(S, row, col, y, rc CAM_ARG(cam));
 }
 
 // integrator.rs:203-268
@@ -1855,12 +834,7 @@ hipError_t path_read(unsigned long long* out, bool reset) {
 template <int G>
 GDEV double observer_energy(const DevScene& S, const WorkList& wl, uint64_t idx CAMS_PARAM) {
   double row, col, p[4];
-#if GRT_SEQ
-  const DevCamera& cam = ray_pixel(wl, ct, idx, &row, &col);
-#else
-  ray_pixel(wl, idx, &row, &col);
-  const DevCamera& cam = S.cam;
-#endif
+  const DevCamera& cam = ray_pixel(S, wl, idx, &row, &col CAMS_ARG);
   camera_momentum(cam, row, col, p);
   return inner<G>(S, cam.pos, cam.sin_theta, cam.cos_theta, cam.vel, p);
 }
@@ -2188,16 +1162,10 @@ __global__ void __launch_bounds__(256, integrate_waves(G, VOL)) integrate_kernel
         } else {
           double row, col;
           bool valid = true;
-#if GRT_SEQ
-          const DevCamera* cam = ct.cams;  // this lane's camera: the frame of its ray (a per-lane load)
-#endif
+          [[maybe_unused]] const DevCamera* cam;  // this lane's camera: in the sequence unit the frame of its ray (a per-lane load)
           if (wl.pixel_index) {  // offset list (get_ray_for_offset, camera.rs:247-254)
             idx = item;
-#if GRT_SEQ
-            cam = &ray_pixel(wl, ct, idx, &row, &col);
-#else
-            ray_pixel(wl, idx, &row, &col);
-#endif
+            cam = &ray_pixel(S, wl, idx, &row, &col CAMS_ARG);
           } else {  // 8x8 pixel tiles, row-major tiles: a wave starts on a compact patch
             uint64_t tile = item >> 6;
             if (wl.tile_order) tile = wl.tile_order[tile];  // longest-predicted tiles first
@@ -2205,10 +1173,11 @@ __global__ void __launch_bounds__(256, integrate_waves(G, VOL)) integrate_kernel
             uint32_t tr = (uint32_t)(tile / wl.tiles_x), tc = (uint32_t)(tile % wl.tiles_x);
             uint32_t r = tr * 8 + (w >> 3), cc = tc * 8 + (w & 7);
             valid = (r < wl.rows) && (cc < wl.cols);
-            // ray_pixel's rectangle / shard case, from (r, cc) directly
+            // rect_pixel(r, cc), written out: through the call, KerrBL's volumetric kernel changes its
+            // code in one unit or another
 #if GRT_SEQ
             uint32_t ri = wl.row0 + shard_frame_row(wl.band_rows, wl.shard, wl.n_shards, r);
-            cam = &stacked_camera(ct, &ri);
+            cam = &frame_camera(S, &ri CAMS_ARG);
             row = (double)ri;
 #else
             row = (double)(wl.row0 + shard_frame_row(wl.band_rows, wl.shard, wl.n_shards, r));
@@ -2551,7 +1520,90 @@ __global__ void __launch_bounds__(256, GRT_TAIL_WAVES) tail_kernel(const DevScen
   }
 }
 
-#if GRT_MAIN_TU  // trajectories, monitors, probes and test hooks: exact build only
+#if GRT_MAIN_TU  // trajectories, monitors and test hooks: exact build only
+// Device check of div_inrange / div2_inrange / div_fx / sqrt_fx against the compiler's
+// division and sqrt over the whole exponent plane (tests/test_gpu_parity.py
+// ::test_range_free_arithmetic_map): thread (ex, ey), ex, ey biased exponents 0 .. 2046
+// (0: subnormals), runs `samples` operand pairs x = +-m_x 2^(ex-1023), y = +-m_y 2^(ey-1023)
+// -- the first four with extreme mantissas (0 / all ones), the rest splitmix64-random, and
+// a second numerator x2 of the same exponent for div2_inrange -- and sets in map[ex][ey]:
+//   1 div_inrange(x, y) != x / y      2 div2_inrange(x, x2, y) != (x / y, x2 / y)
+//   4 div_fx(x, y) != x / y
+// Threads with ex == 0 also set zmap[ey] |= 8 when div_fx(+-0, y) != +-0 / y, and threads
+// with ey == 0 set smap[ex] |= 16 when sqrt_fx(x) != sqrt(x) for positive x of exponent ex.
+__global__ void arith_map_kernel(uint32_t samples, uint64_t seed, uint8_t* map, uint8_t* zmap, uint8_t* smap) {
+  const uint32_t cell = blockIdx.x * blockDim.x + threadIdx.x;
+  if (cell >= 2047u * 2047u) return;
+  const uint32_t ex = cell / 2047u, ey = cell % 2047u;
+  auto mix = [](uint64_t z) {
+    z += 0x9e3779b97f4a7c15ull;
+    z = (z ^ (z >> 30)) * 0xbf58476d1ce4e5b9ull;
+    z = (z ^ (z >> 27)) * 0x94d049bb133111ebull;
+    return z ^ (z >> 31);
+  };
+  constexpr uint64_t MANT = 0x000fffffffffffffull;
+  auto bits = [](double v) { return (uint64_t)__double_as_longlong(v); };
+  auto make = [](uint64_t sign, uint64_t e, uint64_t m) {
+    return __longlong_as_double((long long)((sign << 63) | (e << 52) | m));
+  };
+  uint32_t flags = 0, zflags = 0, sflags = 0;
+  for (uint32_t k = 0; k < samples; ++k) {
+    const uint64_t u = mix(seed ^ ((uint64_t)cell * 64 + 3 * k + 1)), v = mix(seed ^ ((uint64_t)cell * 64 + 3 * k + 2)),
+                   w = mix(seed ^ ((uint64_t)cell * 64 + 3 * k + 3));
+    const uint64_t mx = k < 4 ? ((k & 1) ? MANT : 0) : (u & MANT);
+    const uint64_t my = k < 4 ? ((k & 2) ? MANT : 0) : (v & MANT);
+    const double x = make(u >> 63, ex, mx), y = make(v >> 63, ey, my), x2 = make(w >> 63, ex, w & MANT);
+    volatile double vx = x, vy = y, vx2 = x2;  // keep the reference divisions as divisions
+    const double ref1 = vx / vy, ref2 = vx2 / vy;
+    double q1, q2;
+    div2_inrange(x, x2, y, &q1, &q2);
+    if (bits(div_inrange(x, y)) != bits(ref1)) flags |= 1u;
+    if (bits(q1) != bits(ref1) || bits(q2) != bits(ref2)) flags |= 2u;
+    if (bits(div_fx(x, y)) != bits(ref1)) flags |= 4u;
+    if (ex == 0) {
+      const double z0 = (u >> 62) & 1 ? -0.0 : 0.0;
+      volatile double vz = z0;
+      if (bits(div_fx(z0, y)) != bits(vz / vy)) zflags |= 8u;
+    }
+    if (ey == 0) {
+      const double sx = fabs(x);
+      volatile double vsx = sx;
+      if (bits(sqrt_fx(sx)) != bits(sqrt(vsx))) sflags |= 16u;
+    }
+  }
+  map[cell] = (uint8_t)flags;
+  if (ex == 0) zmap[ey] = (uint8_t)zflags;
+  if (ey == 0) smap[ex] = (uint8_t)sflags;
+}
+
+// Device check of the seeded reciprocals of the region-B Schwarzschild RHS (rcp_seed.h)
+// against the compiler's division (tests/test_gpu_rcp_seed.py): tuple i = (r, radius, a,
+// sin, cos) in t[5 i ..]; flags[i] gets bit
+//   1 radius / r   2 2 / r   4 radius / (r r)   8 (radius / (r r)) / a   16 (2 cos) / sin
+// for each quotient whose bits differ.  a comes from the tuple, not from r, so that the
+// test can put it on the predicate's edge.
+__global__ void rcp_seed_check_kernel(uint64_t n, const double* __restrict__ t, uint8_t* __restrict__ flags) {
+  const uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  const double r = t[5 * i], radius = t[5 * i + 1], a = t[5 * i + 2], st = t[5 * i + 3], ct = t[5 * i + 4];
+  auto bits = [](double v) { return (uint64_t)__double_as_longlong(v); };
+  auto hw_rcp = [](double v) { return __builtin_amdgcn_rcp(v); };
+  const double rr = r * r, two_ct = 2.0 * ct;
+  double Yr, Yrr, Ya, Yst;
+  rcpseed::rcp_r_rr(r, rr, hw_rcp, &Yr, &Yrr);
+  rcpseed::rcp_pair(a, st, hw_rcp, &Ya, &Yst);
+  const double a_prime = rcpseed::div_by_rcp(radius, rr, Yrr);
+  volatile double v_r = r, v_radius = radius, v_a = a, v_st = st, v_rr = rr, v_two = 2.0, v_two_ct = two_ct,
+                  v_a_prime = a_prime;  // keep the reference divisions as divisions
+  uint32_t f = 0;
+  if (bits(rcpseed::div_by_rcp(radius, r, Yr)) != bits(v_radius / v_r)) f |= 1u;
+  if (bits(rcpseed::div_by_rcp(2.0, r, Yr)) != bits(v_two / v_r)) f |= 2u;
+  if (bits(a_prime) != bits(v_radius / v_rr)) f |= 4u;
+  if (bits(rcpseed::div_by_rcp(a_prime, a, Ya)) != bits(v_a_prime / v_a)) f |= 8u;
+  if (bits(rcpseed::div_by_rcp(two_ct, st, Yst)) != bits(v_two_ct / v_st)) f |= 16u;
+  flags[i] = (uint8_t)f;
+}
+
 // ======================================================= trajectory kernel =======
 // Integrator::integrate with the whole Vec<Step> kept (integrator.rs:78-174), the path
 // of `render-ray` / `render-ray-at` (main.rs:117-171, ray.rs:35-54).  One lane per ray;
@@ -2728,23 +1780,11 @@ __global__ void __launch_bounds__(64) rhs_check_kernel(const DevScene* __restric
 hipError_t launch_rhs_check(int geometry, const DevScene* d_scene, const double* d_states, const double* d_consts,
                             uint64_t n, double* d_out, uint8_t* d_pred, hipStream_t stream) {
   const unsigned blocks = (unsigned)((n + 63) / 64);
-  switch (geometry) {
-    case GRT_GEOM_SCHWARZSCHILD:
-      hipLaunchKernelGGL(rhs_check_kernel<GRT_GEOM_SCHWARZSCHILD>, dim3(blocks), dim3(64), 0, stream, d_scene, d_states,
-                         d_consts, n, d_out, d_pred);
-      break;
-    case GRT_GEOM_KERR:
-      hipLaunchKernelGGL(rhs_check_kernel<GRT_GEOM_KERR>, dim3(blocks), dim3(64), 0, stream, d_scene, d_states, d_consts,
-                         n, d_out, d_pred);
-      break;
-    case GRT_GEOM_KERR_BL:
-      hipLaunchKernelGGL(rhs_check_kernel<GRT_GEOM_KERR_BL>, dim3(blocks), dim3(64), 0, stream, d_scene, d_states,
-                         d_consts, n, d_out, d_pred);
-      break;
-    default:
-      return hipErrorInvalidValue;
-  }
-  return hipGetLastError();
+  return with_chart<RHS_CHECK_CHARTS>(geometry, [&](auto g) {
+    hipLaunchKernelGGL(rhs_check_kernel<decltype(g)::value>, dim3(blocks), dim3(64), 0, stream, d_scene, d_states,
+                       d_consts, n, d_out, d_pred);
+    return hipGetLastError();
+  });
 }
 
 // Device check of the short RKF sums (tests/test_gpu_rkf_short.py): one Schwarzschild attempt
@@ -2800,27 +1840,10 @@ hipError_t path_read(unsigned long long* out, bool reset) {
 hipError_t launch_trajectories(int geometry, const DevScene* d_scene, const TrajectoryList& tl, hipStream_t stream) {
   if (tl.n == 0) return hipSuccess;
   const unsigned blocks = (unsigned)((tl.n + 63) / 64);
-  switch (geometry) {
-    case GRT_GEOM_EUCLIDEAN:
-      hipLaunchKernelGGL(trajectory_kernel<GRT_GEOM_EUCLIDEAN>, dim3(blocks), dim3(64), 0, stream, d_scene, tl);
-      break;
-    case GRT_GEOM_SCHWARZSCHILD:
-      hipLaunchKernelGGL(trajectory_kernel<GRT_GEOM_SCHWARZSCHILD>, dim3(blocks), dim3(64), 0, stream, d_scene, tl);
-      break;
-    case GRT_GEOM_KERR:
-      hipLaunchKernelGGL(trajectory_kernel<GRT_GEOM_KERR>, dim3(blocks), dim3(64), 0, stream, d_scene, tl);
-      break;
-    case GRT_GEOM_KERR_BL:
-      hipLaunchKernelGGL(trajectory_kernel<GRT_GEOM_KERR_BL>, dim3(blocks), dim3(64), 0, stream, d_scene, tl);
-      break;
-    case GRT_GEOM_EUCLIDEAN_SPHERICAL:
-      hipLaunchKernelGGL(trajectory_kernel<GRT_GEOM_EUCLIDEAN_SPHERICAL>, dim3(blocks), dim3(64), 0, stream, d_scene,
-                         tl);
-      break;
-    default:
-      return hipErrorInvalidValue;
-  }
-  return hipGetLastError();
+  return with_chart<DIAG_CHARTS>(geometry, [&](auto g) {
+    hipLaunchKernelGGL(trajectory_kernel<decltype(g)::value>, dim3(blocks), dim3(64), 0, stream, d_scene, tl);
+    return hipGetLastError();
+  });
 }
 
 // ====================================================== invariant monitors =======
@@ -2947,169 +1970,16 @@ hipError_t launch_health(int geometry, const DevScene* d_scene, const WorkList& 
                          uint8_t* d_status, hipStream_t stream) {
   if (n == 0) return hipSuccess;
   const unsigned blocks = (unsigned)((n + 63) / 64);
-  switch (geometry) {
-    case GRT_GEOM_EUCLIDEAN:
-      hipLaunchKernelGGL(health_kernel<GRT_GEOM_EUCLIDEAN>, dim3(blocks), dim3(64), 0, stream, d_scene, wl, n, d_out,
-                         d_status);
-      break;
-    case GRT_GEOM_SCHWARZSCHILD:
-      hipLaunchKernelGGL(health_kernel<GRT_GEOM_SCHWARZSCHILD>, dim3(blocks), dim3(64), 0, stream, d_scene, wl, n,
-                         d_out, d_status);
-      break;
-    case GRT_GEOM_KERR:
-      hipLaunchKernelGGL(health_kernel<GRT_GEOM_KERR>, dim3(blocks), dim3(64), 0, stream, d_scene, wl, n, d_out,
-                         d_status);
-      break;
-    case GRT_GEOM_KERR_BL:
-      hipLaunchKernelGGL(health_kernel<GRT_GEOM_KERR_BL>, dim3(blocks), dim3(64), 0, stream, d_scene, wl, n, d_out,
-                         d_status);
-      break;
-    case GRT_GEOM_EUCLIDEAN_SPHERICAL:
-      hipLaunchKernelGGL(health_kernel<GRT_GEOM_EUCLIDEAN_SPHERICAL>, dim3(blocks), dim3(64), 0, stream, d_scene, wl,
-                         n, d_out, d_status);
-      break;
-    default:
-      return hipErrorInvalidValue;
-  }
-  return hipGetLastError();
+  return with_chart<DIAG_CHARTS>(geometry, [&](auto g) {
+    hipLaunchKernelGGL(health_kernel<decltype(g)::value>, dim3(blocks), dim3(64), 0, stream, d_scene, wl, n, d_out,
+                       d_status);
+    return hipGetLastError();
+  });
 }
 
 #endif  // GRT_MAIN_TU
 #if GRT_MAIN_TU || GRT_SEQ  // the work-order probes: the exact builds of every chart
-// ============================================================ probe kernel =======
-// Work-order probe (scheduling only, never an output): one ray per 8x8 tile, the
-// tile's pixel (3, 3), integrated for at most `cap` accepted steps.  A frame's cost is
-// heavy-tailed where rays spiral into the horizon or orbit near the photon sphere
-// (C4: 6% of the rays carry 60% of the steps, up to max_steps each); with the counts
-// the host queues the long tiles first, so the frame does not end on a lone ray that
-// started late.  Writes the steps taken, or for a probe still going at the cap a key
-// above every finished count: cap + 2^30 (r - r_stop) / r_stop, r its radial coordinate
-// there and r_stop the horizon test's radius (cap alone without a horizon).  The capped
-// probes of a C4 shard all creep towards the horizon with steps of ~1e-8, and the
-// distance they have left predicts the ray's length (log-log correlation 0.98 with the
-// probe pixel's own count; the 300 tiles with a ray past 8e5 steps are among the 311
-// largest keys but 11; tools/c4_probe_features.py), so the longest tiles are queued first.
-#ifndef GRT_PROBE_ESCAPE
-#define GRT_PROBE_ESCAPE 1  // end an outward-bound Kerr-Schild probe far from the hole at once
-#endif
-// A Kerr-Schild probe moving outward beyond min(10 radius, max_radius / 2) escapes (no
-// turning point outside the photon orbits); its key becomes cap - 1: below every capped
-// probe's key (those rays are longer), above the rays that fell in early, and "finished"
-// for the edge-tile rule (schedule.hip).  So the cap (api.hip probe_cap) need not outlast
-// the escaping rays, and the pass ends sooner.  Scheduling only, never an output.
-template <int G>
-GDEV bool probe_escaped(const DevScene& S, const double* y, double& r_prev, uint32_t cap, uint32_t* key) {
-  if constexpr (G != GRT_GEOM_KERR || !GRT_PROBE_ESCAPE) {
-    return false;
-  } else {
-    const double r = sqrt(ks_r_sqr(S.a, y[1], y[2], y[3]));
-    const bool out = r > fmin(10.0 * S.radius, 0.5 * sqrt(S.max_radius_sq)) && r > r_prev;
-    r_prev = r;
-    if (out) *key = cap - 1;
-    return out;
-  }
-}
-
-// The probe's radial coordinate at its initial state, so that the first accepted step's
-// "moving outward" test compares against where the ray started (a camera far from the
-// hole, beyond the escape radius, must not end its inward probes at step 1).
-template <int G>
-GDEV double probe_r0(const DevScene& S, const double* y) {
-  if constexpr (G != GRT_GEOM_KERR || !GRT_PROBE_ESCAPE) {
-    return 0.0;
-  } else {
-    return sqrt(ks_r_sqr(S.a, y[1], y[2], y[3]));
-  }
-}
-
-template <int G>
-__global__ void __launch_bounds__(64) probe_kernel(const DevScene* __restrict__ Sp, WorkList wl, uint32_t n_tiles,
-                                                   uint32_t cap, uint32_t* __restrict__ steps_out CAMS_PARAM) {
-  const DevScene& S = *Sp;
-  glibc::tables_to_lds();
-  const uint32_t t = blockIdx.x * blockDim.x + threadIdx.x;
-  if (t >= n_tiles) return;
-  const uint32_t tr = t / wl.tiles_x, tc = t % wl.tiles_x;
-  const uint32_t r = min(tr * 8 + 3, wl.rows - 1), c = min(tc * 8 + 3, wl.cols - 1);
-  double y[8];
-  RayConst rc;
-#if GRT_SEQ
-  uint32_t ri = wl.row0 + shard_frame_row(wl.band_rows, wl.shard, wl.n_shards, r);
-  const DevCamera& cam = stacked_camera(ct, &ri);
-  init_ray<G>(S, (double)ri, (double)(wl.col0 + c), y, rc, cam);
-#else
-  init_ray<G>(S, (double)(wl.row0 + shard_frame_row(wl.band_rows, wl.shard, wl.n_shards, r)),
-              (double)(wl.col0 + c), y, rc);
-#endif
-  const uint64_t end = S.max_steps < (uint64_t)cap ? S.max_steps : (uint64_t)cap;
-  uint64_t i = 1;
-  double h = S.step_size;
-  double r_prev = probe_r0<G>(S, y);
-  uint32_t key = 0;
-  bool escaped = false;
-  for (; i < end; ++i) {
-    double h_cur = rclamp(h, H_MIN, H_MAX), h_next = 0.0, yn[8];
-    int retries = 0, ctl;
-    do {
-      const double err_sq = rkf_attempt<G>(S, rc, y, h_cur, yn);
-      ctl = step_control(S, err_sq, h_cur, retries, h_next);
-    } while (ctl == STEP_RETRY);
-    if (ctl == STEP_FAILED) break;
-    h = h_next;
-#pragma unroll
-    for (int k = 0; k < 8; ++k) y[k] = yn[k];
-    double cc[3];
-    bool c_valid = false;
-    if (should_stop<G>(S, y, cc, c_valid, i) != GRT_STOP_NONE) break;
-    if ((escaped = probe_escaped<G>(S, y, r_prev, cap, &key))) break;
-  }
-  if (!escaped) key = (uint32_t)i;
-  if (!escaped && i >= end) {
-    key = cap;
-    const bool horizon = G == GRT_GEOM_SCHWARZSCHILD || ((G == GRT_GEOM_KERR || G == GRT_GEOM_KERR_BL) && S.has_horizon);
-    if (horizon && S.horizon_r > 0.0) {
-      const double rad = (G == GRT_GEOM_KERR) ? sqrt(ks_r_sqr(S.a, y[1], y[2], y[3])) : y[1];
-      const double d = (rad - S.horizon_r) / S.horizon_r * 1073741824.0;
-      if (d > 0.0) key = cap + (uint32_t)fmin(d, (double)(0xffffffffu - cap));  // NaN: stays cap
-    }
-  }
-  steps_out[t] = key;
-}
-
-// Work-order key of a Schwarzschild tile without integrating: the predicted steps of its
-// probe pixel's ray from the impact parameter b = L / E of its initial momentum (E =
-// (1 - r_s / r) dt/dl, L = r^2 sqrt((dtheta/dl)^2 + sin^2 theta (dphi/dl)^2)).  A ray with
-// b above the photon orbit's b_c = (3 sqrt 3 / 2) r_s escapes to the celestial sphere
-// (~max_radius unit steps), one below it falls in (a few hundred steps), and near b_c
-// both wind round the photon sphere for ~ln(1 / |b / b_c - 1|) more turns.  Only the
-// queue order depends on it, never a result.
-__global__ void __launch_bounds__(64) impact_key_kernel(const DevScene* __restrict__ Sp, WorkList wl,
-                                                        uint32_t n_tiles, uint32_t* __restrict__ keys_out CAMS_PARAM) {
-  const DevScene& S = *Sp;
-  glibc::tables_to_lds();
-  const uint32_t t = blockIdx.x * blockDim.x + threadIdx.x;
-  if (t >= n_tiles) return;
-  const uint32_t tr = t / wl.tiles_x, tc = t % wl.tiles_x;
-  const uint32_t r = min(tr * 8 + 3, wl.rows - 1), c = min(tc * 8 + 3, wl.cols - 1);
-  double y[8];
-  RayConst rc;
-#if GRT_SEQ
-  uint32_t ri = wl.row0 + shard_frame_row(wl.band_rows, wl.shard, wl.n_shards, r);
-  const DevCamera& cam = stacked_camera(ct, &ri);
-  init_ray<GRT_GEOM_SCHWARZSCHILD>(S, (double)ri, (double)(wl.col0 + c), y, rc, cam);
-#else
-  init_ray<GRT_GEOM_SCHWARZSCHILD>(S, (double)(wl.row0 + shard_frame_row(wl.band_rows, wl.shard, wl.n_shards, r)),
-                                   (double)(wl.col0 + c), y, rc);
-#endif
-  const double rs = S.radius, rr = y[1], sn = sin(y[2]);
-  const double e = fabs((1.0 - rs / rr) * y[4]);
-  const double l = rr * rr * sqrt(y[6] * y[6] + sn * sn * y[7] * y[7]);
-  const double bc = 2.598076211353316 * rs;
-  const double b = l / e;
-  const double x = fmax(fabs(b - bc) / bc, 1e-12);
-  const double len = (b > bc ? sqrt(S.max_radius_sq) : 300.0) + 700.0 * fmax(0.0, -log(x));
-  keys_out[t] = (len > 0.0 && len < 4.0e9) ? (uint32_t)len : (len >= 4.0e9 ? 4000000000u : 0u);  // NaN: 0
-}
+#include "geodesic_probe.h"
 
 hipError_t launch_impact_keys(const DevScene* d_scene, const WorkList& wl, uint32_t n_tiles, uint32_t* d_keys,
                               hipStream_t stream CAMS_PARAM) {
@@ -3119,144 +1989,12 @@ hipError_t launch_impact_keys(const DevScene* d_scene, const WorkList& wl, uint3
   return hipGetLastError();
 }
 
-// Where a Schwarzschild camera ray ends up, without the chart integration: pi/2 - theta_f
-// of its asymptotic direction, for the corner pixels (8i, 8j) of the tile grid (clamped to
-// the frame).  In the far field a ray's theta is constant to O(b / r), so for nearly all
-// of its steps the RHS's sincos takes the case theta_f falls in (glibc_math.h: Taylor
-// within TAYLOR_MAX of pi/2, table elsewhere in region B), and a wave whose lanes agree
-// on the case runs one straight-line form (rhs path 12 / 13) instead of the general one.
-// schedule.hip groups the tiles by it.  The ray moves in the plane of its position and
-// its tangential momentum; with psi the angle swept in that plane, u = 1 / r obeys
-// u'' = -u + 1.5 r_s u^2 (fixed-step RK4 here), u(0) = 1 / r_0, u'(0) = -(dr/dl) / L with
-// L = r^2 dpsi/dl.  The direction after psi is cos(psi) n_0 + sin(psi) t_0 (n_0 the
-// camera's position direction, t_0 the tangential momentum's), hence theta_f.
-// Out: pi/2 - theta_f; CLASS_CAPTURED for a ray that reaches the horizon; NaN for one
-// still winding after CLASS_STEPS steps.  Only the queue order depends on it, never a result.
-constexpr float CLASS_CAPTURED = 1.0e30f;
-constexpr int CLASS_STEPS = 400;
-constexpr double CLASS_DPSI = 0.03125;  // 400 steps: 12.5 rad, two turns round the hole
-__global__ void __launch_bounds__(64) class_key_kernel(const DevScene* __restrict__ Sp, WorkList wl,
-                                                       uint32_t corners_x, uint32_t n_corners,
-                                                       float* __restrict__ a_out CAMS_PARAM) {
-  const DevScene& S = *Sp;
-  glibc::tables_to_lds();
-  const uint32_t t = blockIdx.x * blockDim.x + threadIdx.x;
-  if (t >= n_corners) return;
-  const uint32_t r = min((t / corners_x) * 8, wl.rows - 1), c = min((t % corners_x) * 8, wl.cols - 1);
-  double y[8];
-  RayConst rc;
-#if GRT_SEQ
-  uint32_t ri = wl.row0 + shard_frame_row(wl.band_rows, wl.shard, wl.n_shards, r);
-  const DevCamera& cam = stacked_camera(ct, &ri);
-  init_ray<GRT_GEOM_SCHWARZSCHILD>(S, (double)ri, (double)(wl.col0 + c), y, rc, cam);
-#else
-  init_ray<GRT_GEOM_SCHWARZSCHILD>(S, (double)(wl.row0 + shard_frame_row(wl.band_rows, wl.shard, wl.n_shards, r)),
-                                   (double)(wl.col0 + c), y, rc);
-#endif
-  const double rs = S.radius, st0 = sin(y[2]), ct0 = cos(y[2]);
-  const double tang = sqrt(y[6] * y[6] + st0 * st0 * y[7] * y[7]);  // dpsi/dl
-  const double l = y[1] * y[1] * tang;
-  const double u_hor = 1.0 / rs;
-  double u = 1.0 / y[1], v = -y[5] / l, psi = 0.0;
-  float a = __builtin_nanf("");
-  if (!(l > 0.0) || !isfinite(v)) {  // a radial ray keeps its direction, or falls in
-    a_out[t] = y[5] > 0.0 ? (float)(1.5707963267948966 - y[2]) : CLASS_CAPTURED;
-    return;
-  }
-  auto acc = [rs](double uu) { return -uu + 1.5 * rs * uu * uu; };
-  for (int k = 0; k < CLASS_STEPS; ++k) {
-    const double h = CLASS_DPSI;
-    const double k1u = v, k1v = acc(u);
-    const double k2u = v + 0.5 * h * k1v, k2v = acc(u + 0.5 * h * k1u);
-    const double k3u = v + 0.5 * h * k2v, k3v = acc(u + 0.5 * h * k2u);
-    const double k4u = v + h * k3v, k4v = acc(u + h * k3u);
-    const double un = u + h / 6.0 * (k1u + 2.0 * k2u + 2.0 * k3u + k4u);
-    const double vn = v + h / 6.0 * (k1v + 2.0 * k2v + 2.0 * k3v + k4v);
-    if (!(un > 0.0)) {  // escaped within this step: psi where u crosses 0
-      psi += h * u / (u - un);
-      // t_0's z component: the theta part of the tangential momentum, e_theta . z = -sin(theta)
-      const double tz = -st0 * (y[6] / tang);
-      const double nz = fmin(1.0, fmax(-1.0, cos(psi) * ct0 + sin(psi) * tz));
-      a = (float)(1.5707963267948966 - acos(nz));
-      break;
-    }
-    if (un >= u_hor) {
-      a = CLASS_CAPTURED;
-      break;
-    }
-    u = un;
-    v = vn;
-    psi += h;
-  }
-  a_out[t] = a;
-}
-
 hipError_t launch_class_keys(const DevScene* d_scene, const WorkList& wl, uint32_t corners_x, uint32_t n_corners,
                              float* d_a, hipStream_t stream CAMS_PARAM) {
   if (n_corners == 0) return hipSuccess;
   hipLaunchKernelGGL(class_key_kernel, dim3((n_corners + 63) / 64), dim3(64), 0, stream, d_scene, wl, corners_x,
                      n_corners, d_a CAMS_ARG);
   return hipGetLastError();
-}
-
-// probe_kernel<KERR> with each probe ray on the 4 lanes of a quad (rhs_ks_quad, as in
-// tail_kernel): the same operations on the same values, so the same keys (GPU test
-// tests/test_gpu_schedule.py).  For a pass of few probe rays (a 1/8 row-band shard of
-// C4: 32,768 tiles, 0.5 waves per SIMD as one lane each) the pass lasts as long as its
-// capped probes take to run `cap` steps at one wave's latency; splitting each RHS over a
-// quad cuts that latency, at 4x the lanes (2 waves per SIMD here).
-__global__ void __launch_bounds__(256, 2) probe_quad_kernel(const DevScene* __restrict__ Sp, WorkList wl,
-                                                            uint32_t n_tiles, uint32_t cap,
-                                                            uint32_t* __restrict__ steps_out CAMS_PARAM) {
-  constexpr int G = GRT_GEOM_KERR;
-  const DevScene& S = *Sp;
-  glibc::tables_to_lds();
-  const uint32_t t = (blockIdx.x * blockDim.x + threadIdx.x) >> 2;  // the quad's tile
-  const int sub = threadIdx.x & 3;
-  if (t >= n_tiles) return;  // the whole quad
-  const uint32_t tr = t / wl.tiles_x, tc = t % wl.tiles_x;
-  const uint32_t r = min(tr * 8 + 3, wl.rows - 1), c = min(tc * 8 + 3, wl.cols - 1);
-  double y[8];
-  RayConst rc;
-#if GRT_SEQ
-  uint32_t ri = wl.row0 + shard_frame_row(wl.band_rows, wl.shard, wl.n_shards, r);
-  const DevCamera& cam = stacked_camera(ct, &ri);
-  init_ray<G>(S, (double)ri, (double)(wl.col0 + c), y, rc, cam);
-#else
-  init_ray<G>(S, (double)(wl.row0 + shard_frame_row(wl.band_rows, wl.shard, wl.n_shards, r)),
-              (double)(wl.col0 + c), y, rc);
-#endif
-  const uint64_t end = S.max_steps < (uint64_t)cap ? S.max_steps : (uint64_t)cap;
-  uint64_t i = 1;
-  double h = S.step_size;
-  double r_prev = probe_r0<G>(S, y);
-  uint32_t key = 0;
-  bool escaped = false;
-  for (; i < end; ++i) {  // identical decisions in the quad's four lanes
-    double h_cur = rclamp(h, H_MIN, H_MAX), h_next = 0.0, yn[8];
-    int retries = 0, ctl;
-    do {
-      const double err_sq = rkf_attempt<G, false, true>(S, rc, y, h_cur, yn, sub);
-      ctl = step_control(S, err_sq, h_cur, retries, h_next);
-    } while (ctl == STEP_RETRY);
-    if (ctl == STEP_FAILED) break;
-    h = h_next;
-#pragma unroll
-    for (int k = 0; k < 8; ++k) y[k] = yn[k];
-    double cc[3];
-    bool c_valid = false;
-    if (should_stop<G>(S, y, cc, c_valid, i) != GRT_STOP_NONE) break;
-    if ((escaped = probe_escaped<G>(S, y, r_prev, cap, &key))) break;
-  }
-  if (!escaped) key = (uint32_t)i;
-  if (!escaped && i >= end) {
-    key = cap;
-    if (S.has_horizon && S.horizon_r > 0.0) {
-      const double d = (sqrt(ks_r_sqr(S.a, y[1], y[2], y[3])) - S.horizon_r) / S.horizon_r * 1073741824.0;
-      if (d > 0.0) key = cap + (uint32_t)fmin(d, (double)(0xffffffffu - cap));  // NaN: stays cap
-    }
-  }
-  if (sub == 0) steps_out[t] = key;
 }
 
 hipError_t launch_probe(int geometry, const DevScene* d_scene, const WorkList& wl, uint32_t n_tiles, uint32_t cap,
@@ -3268,34 +2006,12 @@ hipError_t launch_probe(int geometry, const DevScene* d_scene, const WorkList& w
     return hipGetLastError();
   }
   const unsigned blocks = (n_tiles + 63) / 64;
-  switch (geometry) {
-    case GRT_GEOM_EUCLIDEAN:
-      hipLaunchKernelGGL(probe_kernel<GRT_GEOM_EUCLIDEAN>, dim3(blocks), dim3(64), 0, stream, d_scene, wl, n_tiles,
-                         cap, d_steps CAMS_ARG);
-      break;
-    case GRT_GEOM_SCHWARZSCHILD:
-      hipLaunchKernelGGL(probe_kernel<GRT_GEOM_SCHWARZSCHILD>, dim3(blocks), dim3(64), 0, stream, d_scene, wl,
-                         n_tiles, cap, d_steps CAMS_ARG);
-      break;
-    case GRT_GEOM_KERR:
-      hipLaunchKernelGGL(probe_kernel<GRT_GEOM_KERR>, dim3(blocks), dim3(64), 0, stream, d_scene, wl, n_tiles, cap,
-                         d_steps CAMS_ARG);
-      break;
-    case GRT_GEOM_KERR_BL:
-      hipLaunchKernelGGL(probe_kernel<GRT_GEOM_KERR_BL>, dim3(blocks), dim3(64), 0, stream, d_scene, wl, n_tiles,
-                         cap, d_steps CAMS_ARG);
-      break;
-    case GRT_GEOM_EUCLIDEAN_SPHERICAL:
-      hipLaunchKernelGGL(probe_kernel<GRT_GEOM_EUCLIDEAN_SPHERICAL>, dim3(blocks), dim3(64), 0, stream, d_scene, wl,
-                         n_tiles, cap, d_steps CAMS_ARG);
-      break;
-    default:
-      return hipErrorInvalidValue;
-  }
-  return hipGetLastError();
+  return with_chart<PROBE_CHARTS>(geometry, [&](auto g) {
+    hipLaunchKernelGGL(probe_kernel<decltype(g)::value>, dim3(blocks), dim3(64), 0, stream, d_scene, wl, n_tiles, cap,
+                       d_steps CAMS_ARG);
+    return hipGetLastError();
+  });
 }
-
-
 #endif  // GRT_MAIN_TU || GRT_SEQ
 // ============================================================ shade kernel =======
 // Evaluate one recorded candidate: the emitter step at the intersection
@@ -3632,66 +2348,8 @@ __global__ void __launch_bounds__(256) shade_kernel(const DevScene* __restrict__
   write_out(out, idx, result, cls, status, stop, nh + n_pool_hits);
 }
 
-#if GRT_MAIN_TU || GRT_KERR_BL_TU || GRT_SEQ  // the geometry buffer: the exact units only
-// ============================================================ geometry buffer =====
-// After a 1-spp trace of a rectangle whose outputs (status, stop) are gb's: the numbers
-// shade_kernel<G, 0> reduces each ray to before any texture or temperature is applied --
-// per window-nearest hit (a "layer", front to back) its object and shade_record's (u, v,
-// redshift, radius), at layer_start[idx] + k; per ray that ended on the celestial sphere
-// celestial_args' (1 - u, v, redshift).  The same record walk as shade_kernel; one lane per
-// ray.  A ray whose status is not 0 has no layers (layer_start is the scan of the trace's
-// own hit counts, zeroed for those rays).  The sequence unit's (grt_gbuffer_trace_sequence)
-// fills the buffer of a whole stack: slot idx is a ray of frame idx / (rows * cols), and its
-// camera is that frame's (observer_energy).
-template <int G>
-__global__ void __launch_bounds__(256) gbuffer_fill_kernel(const DevScene* __restrict__ Sp, WorkList wl, Workspace ws,
-                                                           GBufferArrays gb CAMS_PARAM) {
-  const DevScene& S = *Sp;
-  glibc::tables_to_lds();  // whole block, before the early return
-  const uint64_t idx = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (idx >= gb.n) return;
-  double sky_u = 0.0, sky_v = 0.0, sky_z = 0.0;
-  if (gb.status[idx] == GRT_OK) {
-    RayConst rc;
-    double y[8];
-    const RayMeta mt = fin_get<G>(ws, idx, y, rc);
-    if constexpr (G != GRT_GEOM_KERR_BL) rc.obs = observer_energy<G>(S, wl, idx CAMS_ARG);
-    bool lost;
-    const uint32_t nr = rec_count(ws, idx, mt.nrec, &lost);
-    uint64_t at = gb.layer_start[idx];
-    const uint64_t end = gb.layer_start[idx + 1];
-    uint32_t pos = HIT_NIL;
-    for (uint32_t j = 0; j < nr; ++j) {
-      const RecRef r = rec_at(ws, idx, j, &pos);
-      const uint32_t win = rec_win(ws, r);
-      double p[4], pt[3], geo[4];
-      const uint32_t oi = rec_read(ws, r, p, pt);
-      XYZA col;
-      if (shade_record<G>(S, rc, S.obj[oi], p, pt, &col, false, geo) != GRT_OK) break;  // status would not be 0
-      const bool last_in_window = (j + 1 == nr) || (rec_next_win(ws, idx, j, r) != win);
-      if (last_in_window && at < end) {
-        gb.object[at] = (uint8_t)oi;
-        gb.u[at] = geo[0];
-        gb.v[at] = geo[1];
-        gb.redshift[at] = geo[2];
-        gb.radius[at] = geo[3];
-        ++at;
-      }
-    }
-    if (mt.stop == GRT_STOP_CELESTIAL) celestial_args<G>(S, rc, y, &sky_u, &sky_v, &sky_z);
-  }
-  gb.sky_u[idx] = sky_u;
-  gb.sky_v[idx] = sky_v;
-  gb.sky_redshift[idx] = sky_z;
-}
-
-template <int G>
-static hipError_t gbuffer_fill_g(const DevScene* d_scene, const WorkList& wl, const Workspace& ws,
-                                 const GBufferArrays& gb, hipStream_t stream CAMS_PARAM) {
-  hipLaunchKernelGGL((gbuffer_fill_kernel<G>), dim3((unsigned)((gb.n + 255) / 256)), dim3(256), 0, stream, d_scene, wl,
-                     ws, gb CAMS_ARG);
-  return hipGetLastError();
-}
+#if !GRT_FUSED  // the geometry buffer: the exact units only
+#include "geodesic_fill.h"
 
 hipError_t launch_gbuffer_fill(int geometry, const DevScene* d_scene, const WorkList& wl, const Workspace& ws,
                                const GBufferArrays& gb, hipStream_t stream CAMS_PARAM) {
@@ -3702,67 +2360,49 @@ hipError_t launch_gbuffer_fill(int geometry, const DevScene* d_scene, const Work
       gb.n != (wl.pixel_index ? wl.n_items : (uint64_t)wl.rows * wl.cols))
     return hipErrorInvalidValue;
 #endif
-  switch (geometry) {
-#if GRT_MAIN_TU || GRT_SEQ
-    case GRT_GEOM_EUCLIDEAN: return gbuffer_fill_g<GRT_GEOM_EUCLIDEAN>(d_scene, wl, ws, gb, stream CAMS_ARG);
-    case GRT_GEOM_SCHWARZSCHILD: return gbuffer_fill_g<GRT_GEOM_SCHWARZSCHILD>(d_scene, wl, ws, gb, stream CAMS_ARG);
-    case GRT_GEOM_KERR: return gbuffer_fill_g<GRT_GEOM_KERR>(d_scene, wl, ws, gb, stream CAMS_ARG);
-    case GRT_GEOM_EUCLIDEAN_SPHERICAL:
-      return gbuffer_fill_g<GRT_GEOM_EUCLIDEAN_SPHERICAL>(d_scene, wl, ws, gb, stream CAMS_ARG);
-#endif
-#if GRT_KERR_BL_TU || GRT_SEQ
-    case GRT_GEOM_KERR_BL: return gbuffer_fill_g<GRT_GEOM_KERR_BL>(d_scene, wl, ws, gb, stream CAMS_ARG);
-#endif
-    default: return hipErrorInvalidValue;
-  }
+  return with_chart<FILL_CHARTS>(geometry, [&](auto g) {
+    hipLaunchKernelGGL(gbuffer_fill_kernel<decltype(g)::value>, dim3((unsigned)((gb.n + 255) / 256)), dim3(256), 0,
+                       stream, d_scene, wl, ws, gb CAMS_ARG);
+    return hipGetLastError();
+  });
 }
-#endif  // GRT_MAIN_TU || GRT_KERR_BL_TU || GRT_SEQ
+#endif  // !GRT_FUSED
 
 // ------------------------------------------------------------------ launch -------
-// Plain scenes: integrate [-> tail] -> shade.  Volumetric scenes: integrate [-> tail] ->
+// Plain scenes: integrate [-> tail] -> shade.  Volumetric scenes (VOL): integrate [-> tail] ->
 // gather raymarch jobs -> march (persistent, lane refill) -> composite; ws.march must be
 // zeroed.  The tail (Kerr-Schild) continues the long rays the integrate kernel handed off.
-template <int G>
+template <int G, bool VOL>
 static hipError_t launch_g(const DevScene* d_scene, const WorkList& wl, const Workspace& ws_in, const Outputs& out,
                            unsigned long long* d_counter, unsigned long long* d_stats, int blocks, int threads,
-                           bool vol, const TailList& tl_in, int tail_blocks, hipStream_t stream CAMS_PARAM) {
+                           const TailList& tl_in, int tail_blocks, hipStream_t stream CAMS_PARAM) {
   const unsigned nb = (unsigned)((ws_in.n + 255) / 256);
   Workspace ws = ws_in;
   ws.steps = G == GRT_GEOM_KERR_BL ? nullptr : out.steps;  // store_ray writes the per-pixel step counts
   TailList tl = tl_in;
   if (G != GRT_GEOM_KERR || tail_blocks <= 0) tl.cap = 0;
-  if (!vol) {
-    hipLaunchKernelGGL((integrate_kernel<G, false>), dim3(blocks), dim3(threads), 0, stream, d_scene, wl, ws,
-                       d_counter, d_stats, tl CAMS_ARG);
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return e;
-    if constexpr (G == GRT_GEOM_KERR) {
-      if (tl.cap) {
-        hipLaunchKernelGGL((tail_kernel<G, false>), dim3(tail_blocks), dim3(256), 0, stream, d_scene, ws, tl,
-                           d_stats);
-        if ((e = hipGetLastError()) != hipSuccess) return e;
-      }
-    }
-    hipLaunchKernelGGL((shade_kernel<G, 0>), dim3(nb), dim3(256), 0, stream, d_scene, wl, ws, out, d_stats CAMS_ARG);
-    return hipGetLastError();
-  }
-  if (!ws.rec_dir || !ws.vcol || !ws.jobs || !ws.march) return hipErrorInvalidValue;
-  hipLaunchKernelGGL((integrate_kernel<G, true>), dim3(blocks), dim3(threads), 0, stream, d_scene, wl, ws,
-                     d_counter, d_stats, tl CAMS_ARG);
+  if (VOL && (!ws.rec_dir || !ws.vcol || !ws.jobs || !ws.march)) return hipErrorInvalidValue;
+  hipLaunchKernelGGL((integrate_kernel<G, VOL>), dim3(blocks), dim3(threads), 0, stream, d_scene, wl, ws, d_counter,
+                     d_stats, tl CAMS_ARG);
   hipError_t e = hipGetLastError();
   if (e != hipSuccess) return e;
   if constexpr (G == GRT_GEOM_KERR) {
     if (tl.cap) {
-      hipLaunchKernelGGL((tail_kernel<G, true>), dim3(tail_blocks), dim3(256), 0, stream, d_scene, ws, tl, d_stats);
+      hipLaunchKernelGGL((tail_kernel<G, VOL>), dim3(tail_blocks), dim3(256), 0, stream, d_scene, ws, tl, d_stats);
       if ((e = hipGetLastError()) != hipSuccess) return e;
     }
   }
-  hipLaunchKernelGGL((shade_kernel<G, 1>), dim3(nb), dim3(256), 0, stream, d_scene, wl, ws, out, d_stats CAMS_ARG);
-  if ((e = hipGetLastError()) != hipSuccess) return e;
-  hipLaunchKernelGGL((march_kernel<G>), dim3(blocks), dim3(256), 0, stream, d_scene, ws);
-  if ((e = hipGetLastError()) != hipSuccess) return e;
-  hipLaunchKernelGGL((shade_kernel<G, 2>), dim3(nb), dim3(256), 0, stream, d_scene, wl, ws, out, d_stats CAMS_ARG);
-  return hipGetLastError();
+  hipLaunchKernelGGL((shade_kernel<G, VOL ? 1 : 0>), dim3(nb), dim3(256), 0, stream, d_scene, wl, ws, out,
+                     d_stats CAMS_ARG);
+  e = hipGetLastError();
+  if constexpr (VOL) {
+    if (e != hipSuccess) return e;
+    hipLaunchKernelGGL((march_kernel<G>), dim3(blocks), dim3(256), 0, stream, d_scene, ws);
+    if ((e = hipGetLastError()) != hipSuccess) return e;
+    hipLaunchKernelGGL((shade_kernel<G, 2>), dim3(nb), dim3(256), 0, stream, d_scene, wl, ws, out, d_stats CAMS_ARG);
+    e = hipGetLastError();
+  }
+  return e;
 }
 
 hipError_t launch_trace(int geometry, const DevScene* d_scene, const WorkList& wl, const Workspace& ws,
@@ -3772,33 +2412,13 @@ hipError_t launch_trace(int geometry, const DevScene* d_scene, const WorkList& w
 #if GRT_SEQ
   if (!ct.cams || ct.cam_rows == 0 || ct.n_cams == 0) return hipErrorInvalidValue;
 #endif
-  switch (geometry) {
-#if !GRT_KERR_BL_TU
-    case GRT_GEOM_EUCLIDEAN:
-      return launch_g<GRT_GEOM_EUCLIDEAN>(d_scene, wl, ws, out, d_counter, d_stats, blocks, threads, vol, tl,
-                                          tail_blocks, stream CAMS_ARG);
-    case GRT_GEOM_SCHWARZSCHILD:
-      return launch_g<GRT_GEOM_SCHWARZSCHILD>(d_scene, wl, ws, out, d_counter, d_stats, blocks, threads, vol, tl,
-                                              tail_blocks, stream CAMS_ARG);
-#endif
-#if GRT_MAIN_TU || GRT_SEQ  // Kerr-Schild always runs exact (grt_set_arithmetic)
-    case GRT_GEOM_KERR:
-      return launch_g<GRT_GEOM_KERR>(d_scene, wl, ws, out, d_counter, d_stats, blocks, threads, vol, tl, tail_blocks,
-                                     stream CAMS_ARG);
-#endif
-#if !GRT_MAIN_TU  // the exact KerrBL trace is grt::kerr_bl's
-    case GRT_GEOM_KERR_BL:
-      return launch_g<GRT_GEOM_KERR_BL>(d_scene, wl, ws, out, d_counter, d_stats, blocks, threads, vol, tl,
-                                        tail_blocks, stream CAMS_ARG);
-#endif
-#if !GRT_KERR_BL_TU
-    case GRT_GEOM_EUCLIDEAN_SPHERICAL:
-      return launch_g<GRT_GEOM_EUCLIDEAN_SPHERICAL>(d_scene, wl, ws, out, d_counter, d_stats, blocks, threads, vol,
-                                                    tl, tail_blocks, stream CAMS_ARG);
-#endif
-    default:
-      return hipErrorInvalidValue;
-  }
+  return with_chart<TRACE_CHARTS>(geometry, [&](auto g) {
+    constexpr int G = decltype(g)::value;
+    return vol ? launch_g<G, true>(d_scene, wl, ws, out, d_counter, d_stats, blocks, threads, tl, tail_blocks,
+                                   stream CAMS_ARG)
+               : launch_g<G, false>(d_scene, wl, ws, out, d_counter, d_stats, blocks, threads, tl, tail_blocks,
+                                    stream CAMS_ARG);
+  });
 }
 
 #if GRT_FUSED || GRT_KERR_BL_TU || GRT_SEQ

@@ -1,4 +1,5 @@
-// kernels.h — launch entry points of the gfx950 kernels (geodesic.hip, gbuffer_shade.hip, adaptive.hip).
+// kernels.h — launch entry points of the gfx950 kernels (geodesic.hip and its geodesic_*.h layers,
+// gbuffer_shade.hip, adaptive.hip).
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -147,7 +148,7 @@ struct GBufferArrays {
 hipError_t gbuffer_layer_scan(const uint8_t* d_status, const uint32_t* d_hits, uint64_t n, uint64_t* d_counts,
                               uint64_t* d_layer_start, void* d_temp, size_t* temp_bytes, hipStream_t stream);
 // Fill `gb` from the workspace and hit pool a 1-spp rectangle trace of `wl` left behind
-// (gbuffer_fill_kernel: geodesic.hip for every chart but KerrBL, whose exact unit has its own).
+// (gbuffer_fill_kernel: geodesic_fill.h for every chart but KerrBL, whose exact unit has its own).
 hipError_t launch_gbuffer_fill(int geometry, const DevScene* d_scene, const WorkList& wl, const Workspace& ws,
                                const GBufferArrays& gb, hipStream_t stream);
 namespace kerr_bl {

@@ -1,4 +1,4 @@
-// rcp_seed.h — the range-free f64 division (geodesic.hip div_inrange) taken apart, so that
+// rcp_seed.h — the range-free f64 division (geodesic_rhs.h div_inrange) taken apart, so that
 // a reciprocal seed already in registers can stand in for v_rcp_f64.
 //
 // div_inrange(x, y) is  Y = refine2(y, rcp(y));  m = x Y;  q = fma(fma(-y, m, x), Y, m):
@@ -52,7 +52,7 @@ GRT_RCP_FN double div_by_rcp(double x, double y, double Y) {
 // The reciprocals of the region-B Schwarzschild RHS (schwarzschild.rs:54-80), whose five
 // quotients are radius / r, 2 / r, a' = radius / (r r), a' / a with a = 1 - radius / r, and
 // (2 cos) / sin.  RCP: the reciprocal estimate (v_rcp_f64 on the device).  Operand ranges:
-// schw_div_ok and region B (geodesic.hip).
+// schw_div_ok and region B (geodesic_rhs.h).
 // 1 / r and 1 / RN(r r) from one estimate
 template <class RCP>
 GRT_RCP_FN void rcp_r_rr(double r, double rr, RCP&& rcp, double* Yr, double* Yrr) {

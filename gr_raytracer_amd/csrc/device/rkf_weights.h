@@ -1,5 +1,5 @@
 // rkf_weights.h — the Fehlberg weights of rkf45_step's fifth-order result (CH) and of its
-// error estimate (CT), runge_kutta.rs:62-84.  Shared by the device (geodesic.hip) and the
+// error estimate (CT), runge_kutta.rs:62-84.  Shared by the device (geodesic_rkf.h) and the
 // host check of the sums without their zero-weight k2 terms
 // (tests/native/rkf_zero_terms_check.cpp).
 #pragma once

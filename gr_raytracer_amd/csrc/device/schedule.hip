@@ -4,7 +4,7 @@
 // horizon take ~5e5 accepted steps and the trapped ones the full max_steps (1e6),
 // while an escaping ray takes ~1.6e4.  The integrate kernel hands out 8x8 tiles from
 // one counter, so a long tile queued late ends the frame on a single busy lane.  The
-// probe kernel (geodesic.hip) traces one ray per tile for a capped number of steps (a
+// probe kernel (geodesic_probe.h) traces one ray per tile for a capped number of steps (a
 // probe still going at the cap gets a key above the cap from its state there); here each
 // tile's key is the largest probe key in its 3x3 tile neighbourhood (a shadow edge can
 // cut a tile whose probe pixel escapes; edge tiles get more, below), and the tiles are sorted by
@@ -48,7 +48,7 @@ __global__ void __launch_bounds__(256) dilate_kernel(const uint32_t* __restrict_
 }
 
 // Sincos class of a tile, from the predicted pi/2 - theta_f of its four corner pixels
-// (class_key_kernel, geodesic.hip): the case the RHS's sincos takes over the ~97% of an
+// (class_key_kernel, geodesic_probe.h): the case the RHS's sincos takes over the ~97% of an
 // escaping ray's steps that lie in the far field.
 //   0: every corner in the Taylor case (|pi/2 - theta_f| < TAYLOR_MAX);
 //   2: every corner in region B's table case, all on one side of the Taylor band;

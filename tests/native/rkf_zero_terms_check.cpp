@@ -1,4 +1,4 @@
-// Host check of the RKF45 sums without their zero-weight k2 terms (geodesic.hip
+// Host check of the RKF45 sums without their zero-weight k2 terms (geodesic_rkf.h
 // rkf_attempt_fold, SHORT) against the full sums, in the reference's left-to-right order
 // (runge_kutta.rs:94-124) with the device's weights (rkf_weights.h):
 //   yn = y + CH1 a1 + CH2 a2 + CH3 a3 + CH4 a4 + CH5 a5 + CH6 a6,   CH2 = 0.0

@@ -1,7 +1,7 @@
 """The range-free arithmetic of the render's RHS forms, on the GPU (marker `gpu`).
 
 The Schwarzschild / KerrBL region-B RHS divide with div_inrange / div2_inrange and the
-Kerr-Schild RHS with div_fx / sqrt_fx (geodesic.hip): the compiler's IEEE f64 division and
+Kerr-Schild RHS with div_fx / sqrt_fx (geodesic_rhs.h): the compiler's IEEE f64 division and
 sqrt expansions without their range steps.  Their exactness argument is a case analysis of
 v_div_scale / v_div_fixup over a claimed operand domain plus bound
 chains from each RHS's predicate (ks_fd_ok, schw_div_ok, bl_div_ok) into that domain.  Two

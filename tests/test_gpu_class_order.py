@@ -1,5 +1,5 @@
 """The Schwarzschild tile queue grouped by sincos case (grt_set_class_order, schedule.hip
-tile_class, geodesic.hip class_key_kernel; marker `gpu`).
+tile_class, geodesic_probe.h class_key_kernel; marker `gpu`).
 
 The order decides which lane traces which pixel and nothing else, so every comparison of
 rendered output is exact (array_equal).  Scene: schwarzschild.toml with C2's camera and

@@ -1,4 +1,4 @@
-"""The render's Schwarzschild division predicate (geodesic.hip schw_div_ok_render: r above
+"""The render's Schwarzschild division predicate (geodesic_rhs.h schw_div_ok_render: r above
 the host's edge radius (1 + 2^-40) and below 2^100), on the GPU (marker `gpu`).
 
 It admits a subset of schw_div_ok, whose range-free RHS tests/test_gpu_arith.py holds to

@@ -1,6 +1,6 @@
 """The Schwarzschild integrate kernel's two bit-neutral savings, on the GPU (marker `gpu`).
 
-* Short RKF sums (geodesic.hip rkf_attempt_fold, SHORT): the attempt without its zero-weight
+* Short RKF sums (geodesic_rkf.h rkf_attempt_fold, SHORT): the attempt without its zero-weight
   CH2 / CT2 terms, guarded by rkf_short_ok ("every yn finite and not -0, err_sq finite").
   test_short_attempt_equals_full_where_the_guard_admits runs single attempts in both forms
   (grt_debug_rkf_check) on ordinary states and on states planted with signed zeros,

@@ -1,7 +1,7 @@
 """Two instruction savings of the Schwarzschild integrate kernel that change no result bit,
 restated for the host and checked there (CPU only).
 
-* The RKF45 sums without their zero-weight k2 terms (geodesic.hip rkf_attempt_fold, SHORT;
+* The RKF45 sums without their zero-weight k2 terms (geodesic_rkf.h rkf_attempt_fold, SHORT;
   weights from gr_raytracer_amd/csrc/device/rkf_weights.h).  CH2 = CT2 = 0.0, so with k2
   finite the full sum differs from the short one only where a -0 partial sum meets the +0
   product, and the difference survives to the result only as short -0 against full +0; the

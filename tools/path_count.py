@@ -1,5 +1,5 @@
 """Code-path counts of the integrate kernel on one workload, from a diagnostic build
-(-DGRT_PATH_COUNT=1, loaded through GRT_LIB; geodesic.hip path_count): per path, how many
+(-DGRT_PATH_COUNT=1, loaded through GRT_LIB; geodesic_rhs.h path_count): per path, how many
 times a wave executed it (counted by its first active lane) and how many lanes did.
 Kerr-Schild RHS: 0 range-free, 1 IEEE.  Schwarzschild / KerrBL RHS: 0 region-B table
 with range-free divisions, 1 region-B Taylor with them, 2 region B with IEEE divisions,
