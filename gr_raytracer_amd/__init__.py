@@ -13,7 +13,7 @@ from .scene import (  # noqa: F401
     kerr_temperature_lut, load_scene, r_isco, srgb_to_xyza, stationary_velocity, xyz_to_srgb8, Trajectories, ray_at,
     write_trajectory_csv, format_f64, set_arithmetic, get_arithmetic, set_sequence_group, load_camera_path,
     GBuffer, GBufferMissing, gbuffer_compatible, GBufferSequence, shade_sequence,
-    supersample_sequence, shade_section_sequence, orbit_rate, gbuffer_orbit_uv,
+    supersample_sequence, shade_section_sequence, orbit_rate, gbuffer_orbit_uv, gbuffer_orbit_uv_retarded,
 )
 
 __all__ = [
@@ -23,5 +23,5 @@ __all__ = [
     "stationary_velocity", "xyz_to_srgb8", "Trajectories", "ray_at", "write_trajectory_csv", "format_f64",
     "set_arithmetic", "get_arithmetic", "set_sequence_group", "load_camera_path",
     "GBuffer", "GBufferMissing", "gbuffer_compatible", "GBufferSequence", "shade_sequence",
-    "supersample_sequence", "shade_section_sequence", "orbit_rate", "gbuffer_orbit_uv",
+    "supersample_sequence", "shade_section_sequence", "orbit_rate", "gbuffer_orbit_uv", "gbuffer_orbit_uv_retarded",
 ]

@@ -10,13 +10,13 @@
 //     | render-sequence --camera-path P [--filename-pattern frame-%04d.png] [--first-index 0]
 //     | render-ray -r ROW -c COL [--filename rendered-ray.csv]
 //     | render-ray-at -p x,y,z -d x,y,z [--filename rendered-ray-at.csv]
-//     | gbuffer --filename a.grtg [--adaptive | --gpus N | --devices A,B,...]
+//     | gbuffer --filename a.grtg [--adaptive | --gpus N | --devices A,B,...] [--lapse]
 //     | reshade --gbuffer a.grtg [--filename out.png|out.hdr] [--adaptive]
 //     | gbuffer-sequence --camera-path P --filename-pattern a-%04d.grtg [--first-index 0]
 //                        [--adaptive-stacked]
 //     | reshade-sequence --gbuffer-pattern a-%04d.grtg --frames K [--first-index 0]
 //                        [--filename-pattern frame-%04d.png] [--adaptive-stacked]
-//     | reshade-orbit --gbuffer a.grtg --times T0,DT,K --filename-pattern f-%04d.png
+//     | reshade-orbit --gbuffer a.grtg --times T0,DT,K --filename-pattern f-%04d.png [--retarded]
 //                     [--raw-out-pattern f-%04d.raw] [--first-index 0] [--adaptive]
 //     | blackbody -t T [-r Z]
 //     | blackbody-spectrum [--min-temperature T] [--max-temperature T] [--min-redshift Z]
@@ -78,6 +78,10 @@
 // (and --raw-out-pattern) at index --first-index + k.  With --adaptive the frames are
 // `reshade --adaptive`'s at those times, one after the other (grt_gbuffer_shade_section_at);
 // the sidecar is loaded once and rewritten once at the end when the set grew.
+// `gbuffer --lapse` also records each layer's light-travel time (grt_gbuffer_trace_lapse) and
+// writes it to F.grtg.lapse; F.grtg has the bytes it has without the flag.  `reshade-orbit
+// --retarded` reads that sidecar and shades every disc layer at its emission time
+// (grt_gbuffer_shade_times_retarded); a missing sidecar is a usage error.
 #include <algorithm>
 #include <charconv>
 #include <chrono>
@@ -108,7 +112,7 @@ static int usage(const char* msg) {
                "           [--filename-pattern frame-%%04d.png] [--first-index N]\n"
                "       grt [global options] --config-file FILE render-ray -r ROW -c COL [--filename F]\n"
                "       grt [global options] --config-file FILE render-ray-at -p X,Y,Z -d X,Y,Z [--filename F]\n"
-               "       grt [global options] --config-file FILE gbuffer --filename F.grtg [--adaptive]\n"
+               "       grt [global options] --config-file FILE gbuffer --filename F.grtg [--adaptive] [--lapse]\n"
                "           (--gpus N / --devices A,B,...: the 1-spp trace over several GPUs, the same file)\n"
                "       grt [global options] --config-file FILE reshade --gbuffer F.grtg [--filename F] [--adaptive]\n"
                "           (--adaptive: the config's [adaptive_sampling]; the sub-rays live in F.grtg.sub)\n"
@@ -119,7 +123,7 @@ static int usage(const char* msg) {
                "           --frames K [--first-index N] [--filename-pattern frame-%%04d.png] [--adaptive-stacked]\n"
                "           (--adaptive-stacked: the adaptive frames of the sequence, the sub-rays in F-%%04d.grtg.sub)\n"
                "       grt [global options] --config-file FILE reshade-orbit --gbuffer F.grtg --times T0,DT,K\n"
-               "           --filename-pattern F-%%04d.png [--raw-out-pattern F-%%04d.raw] [--first-index N] [--adaptive]\n"
+               "           --filename-pattern F-%%04d.png [--raw-out-pattern F-%%04d.raw] [--first-index N] [--adaptive | --retarded]\n"
                "           (frame k: the disc's texture after orbiting for T0 + k DT; one trace, K frames)\n"
                "       grt [global options] blackbody -t T [-r Z]\n"
                "       grt [global options] blackbody-spectrum [--min-temperature T] [--max-temperature T]\n"
@@ -492,6 +496,8 @@ int main(int argc, char** argv) {
   bool gbuffer_adaptive = false;  // gbuffer / reshade --adaptive: the config's [adaptive_sampling]
   bool seq_adaptive = false;      // gbuffer-sequence / reshade-sequence --adaptive-stacked: the same, stacked
   std::string orbit_times, raw_out_pattern;  // reshade-orbit --times T0,DT,K, --raw-out-pattern
+  bool gbuffer_lapse = false;   // gbuffer --lapse: record each layer's light-travel time (F.grtg.lapse)
+  bool orbit_retarded = false;  // reshade-orbit --retarded: every disc layer at its emission time
   double orbit_t0 = 0.0, orbit_dt = 0.0;
   long long first_index = 0;
   std::vector<std::string> args(argv + 1, argv + argc);
@@ -523,6 +529,14 @@ int main(int argc, char** argv) {
     if (action.empty() && a == "--show-sampling-mask") { opts.show_sampling_mask = 1; continue; }
     if ((action == "gbuffer" || action == "reshade" || action == "reshade-orbit") && a == "--adaptive") {
       gbuffer_adaptive = true;
+      continue;
+    }
+    if (action == "gbuffer" && a == "--lapse") {
+      gbuffer_lapse = true;
+      continue;
+    }
+    if (action == "reshade-orbit" && a == "--retarded") {
+      orbit_retarded = true;
       continue;
     }
     if ((action == "gbuffer-sequence" || action == "reshade-sequence") && a == "--adaptive-stacked") {
@@ -706,6 +720,9 @@ int main(int argc, char** argv) {
   if (action == "gbuffer" && gbuffer_adaptive && !multi_devices.empty())
     return usage("gbuffer --adaptive runs on one GPU (--device); --gpus / --devices do not apply: trace with "
                  "`gbuffer --gpus N`, then `reshade --adaptive` tops up the sub-rays on the buffer's GPU");
+  if (action == "gbuffer" && gbuffer_lapse && !multi_devices.empty())
+    return usage("gbuffer --lapse runs on one GPU (--device); --gpus / --devices do not apply: the multi-GPU buffer "
+                 "records no lapse");
   if (action == "reshade" && !multi_devices.empty())
     return usage("reshade runs on one GPU (--device); --gpus / --devices do not apply: trace with `gbuffer --gpus N`, "
                  "then `reshade [--adaptive]` shades (and tops up) on the buffer's GPU");
@@ -747,6 +764,16 @@ int main(int argc, char** argv) {
     if (!raw_out_pattern.empty() && !expand_pattern(raw_out_pattern, first_index, &probe))
       return usage("--raw-out-pattern needs one %d or %0Nd conversion for the frame index");
     if (!raw_out.empty()) return usage("reshade-orbit writes many frames: give --raw-out-pattern, not --raw-out");
+    if (orbit_retarded && gbuffer_adaptive)
+      return usage("reshade-orbit --retarded does not combine with --adaptive: the sub-sample set records no lapse, "
+                   "the adaptive frame stays fast-light");
+    if (orbit_retarded) {  // the lapse's sidecar must be there
+      FILE* f = std::fopen((gbuffer_file + ".lapse").c_str(), "rb");
+      if (!f)
+        return usage(("reshade-orbit --retarded needs the lapse sidecar " + gbuffer_file +
+                      ".lapse (trace with `gbuffer --lapse`)").c_str());
+      std::fclose(f);
+    }
   }
   if (filename.empty())
     filename = (action == "render" || action == "reshade") ? "render.png" : (action == "render-ray" ? "rendered-ray.csv" : "rendered-ray-at.csv");
@@ -809,6 +836,11 @@ int main(int argc, char** argv) {
     if ((int64_t)gb_info.cols != opts.width || (int64_t)gb_info.rows != opts.height)
       return usage(("--width / --height must be the g-buffer's frame, " + std::to_string(gb_info.cols) + " x " +
                     std::to_string(gb_info.rows)).c_str());
+    // the lapse's sidecar: its header, its binding to this buffer and its entries
+    if (orbit_retarded && grt_gbuffer_lapse_read_file((gbuffer_file + ".lapse").c_str(), &gb_info, nullptr)) {
+      std::fprintf(stderr, "Error: %s\n", grt_last_error());
+      return 1;
+    }
   }
 
   if (action == "render" && !multi_devices.empty() &&
@@ -879,7 +911,8 @@ int main(int argc, char** argv) {
     grt_gbuffer_multi_report grep;
     const bool multi = !multi_devices.empty();
     if ((multi ? grt_gbuffer_trace_multi(scene, (int)multi_devices.size(), multi_devices.data(), band_rows, &gb, &st, &grep)
-               : grt_gbuffer_trace(scene, device, 0, 0, (uint32_t)opts.height, (uint32_t)opts.width, &gb, &st)) ||
+               : (gbuffer_lapse ? grt_gbuffer_trace_lapse : grt_gbuffer_trace)(scene, device, 0, 0, (uint32_t)opts.height,
+                                                                               (uint32_t)opts.width, &gb, &st)) ||
         grt_gbuffer_info_get(gb, &gb_info)) {
       std::fprintf(stderr, "Error: %s\n", grt_last_error());
       return 1;
@@ -912,6 +945,15 @@ int main(int argc, char** argv) {
         (gbuffer_adaptive && save_sub_sidecar(gb, gb_info, filename + ".sub"))) {
       std::fprintf(stderr, "Error: %s\n", grt_last_error());
       return 1;
+    }
+    if (gbuffer_lapse) {  // the layers' light-travel times, beside the file
+      std::vector<double> lapse(nl);
+      if (grt_gbuffer_lapse_download(gb, lapse.data()) ||
+          grt_gbuffer_lapse_write_file((filename + ".lapse").c_str(), &gb_info, lapse.data(), nl)) {
+        std::fprintf(stderr, "Error: %s\n", grt_last_error());
+        return 1;
+      }
+      std::fprintf(stderr, "[grt] INFO saved lapse to %s.lapse\n", filename.c_str());
     }
     if (gbuffer_adaptive)
       std::fprintf(stderr, "[grt] sub-sample set: %llu selected pixels traced (%llu sub-rays, %.1f ms), saved to %s.sub\n",
@@ -1124,7 +1166,16 @@ int main(int argc, char** argv) {
       }
     } else {
       grt_frame_out fo{nullptr, xyza.data(), nullptr, nullptr, nullptr, nullptr};
-      if (grt_gbuffer_shade_times(scene, gb, K, times.data(), &fo, &shade_ms)) {
+      if (orbit_retarded) {  // the buffer's lapse from its sidecar (checked before the GPU was touched)
+        std::vector<double> lapse(nl);
+        if (grt_gbuffer_lapse_read_file((gbuffer_file + ".lapse").c_str(), &gb_info, lapse.data()) ||
+            grt_gbuffer_lapse_upload(gb, lapse.data(), nl)) {
+          std::fprintf(stderr, "Error: %s\n", grt_last_error());
+          return 1;
+        }
+      }
+      if ((orbit_retarded ? grt_gbuffer_shade_times_retarded : grt_gbuffer_shade_times)(scene, gb, K, times.data(), &fo,
+                                                                                        &shade_ms)) {
         std::fprintf(stderr, "Error: %s\n", grt_last_error());
         return 1;
       }

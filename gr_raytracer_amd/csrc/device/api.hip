@@ -108,11 +108,36 @@ int stream_done(DeviceCopy& dc, hipStream_t st) {
   return 0;
 }
 
+// The hit-time arrays of a lapse trace, as large as the workspace arena and the pool are now
+// (after ensure_workspace and ensure_pool): 8 B per slot per ray and 8 B per pool record.
+static int ensure_hit_times(DeviceCopy& dc) {
+  auto grow = [&](void** mem, uint64_t* cap, uint64_t want, uint64_t per) -> int {
+    if (*mem && *cap >= want) return 0;
+    if (*mem) {
+      (void)hipDeviceSynchronize();  // earlier async launches may still use the old array
+      (void)hipFree(*mem);
+    }
+    *mem = nullptr;
+    *cap = 0;
+    if (hipMalloc(mem, std::max<uint64_t>(want * per, 16)) != hipSuccess) {
+      (void)hipGetLastError();
+      *mem = nullptr;
+      return fail(-ENOMEM, "cannot allocate the hit times of a lapse trace");
+    }
+    *cap = want;
+    return 0;
+  };
+  if (int rc = grow(&dc.slot_time_mem, &dc.slot_time_cap, dc.ws_cap, 8ull * GRT_WS_SLOTS)) return rc;
+  return grow(&dc.pool_time_mem, &dc.pool_time_cap, dc.pool_cap, 8);
+}
+
 static grt::HitPool pool_view(const DeviceCopy& dc) {
   grt::HitPool hp;
   std::memset(&hp, 0, sizeof(hp));
   hp.head = dc.ws_head;
   hp.last = dc.ws_last;
+  hp.slot_time = (double*)dc.slot_time_mem;
+  hp.pool_time = (double*)dc.pool_time_mem;
   const uint64_t m = dc.pool_cap;
   char* p = (char*)dc.pool_mem;
   auto take = [&](uint64_t bytes) {
@@ -691,8 +716,9 @@ static int ray_times_reserve(uint64_t n, hipStream_t stream) {
 // frame from the table, and the sequence unit's exact kernels run (geodesic_seq.hip).
 // exact (the geometry buffer): the exact kernels whatever grt_set_arithmetic says.
 int enqueue_trace(grt_scene* s, DeviceCopy& dc, const grt::WorkList& wl_in, const grt::Outputs& o,
-                  unsigned long long* d_stats, hipStream_t stream, const grt::CamTable* ct, bool exact) {
+                  unsigned long long* d_stats, hipStream_t stream, const grt::CamTable* ct, bool exact, bool lapse) {
   grt::WorkList wl = wl_in;
+  if (lapse && (ct || !exact || dc.vol)) return fail(-EINVAL, "a lapse trace is exact, of one camera, without VolumetricDiscs");
   const Knobs k = Knobs::now();
   if (int rc0 = stream_order(dc, stream)) return rc0;
   if (schedule_wanted(s, wl, k)) {
@@ -724,6 +750,7 @@ int enqueue_trace(grt_scene* s, DeviceCopy& dc, const grt::WorkList& wl_in, cons
   rc = ensure_workspace(dc, n_out, &ws);
   if (rc) return rc;
   ws.n_live = wl.n_live;
+  if (lapse && (rc = ensure_hit_times(dc))) return rc;
   {  // the pool descriptor changes only when the pool or the workspace arena moved
     const grt::HitPool hp = pool_view(dc);
     if (std::memcmp(&hp, &dc.pool_desc, sizeof(hp)) != 0) {
@@ -748,7 +775,10 @@ int enqueue_trace(grt_scene* s, DeviceCopy& dc, const grt::WorkList& wl_in, cons
   const auto launch = fused ? grt::fused::launch_trace
                             : (s->desc.geometry == GRT_GEOM_KERR_BL ? grt::kerr_bl::launch_trace : grt::launch_trace);
   // the exact KerrBL kernels are a unit of their own (geodesic_kerr_bl.hip)
-  if (ct)  // a camera sequence: always the exact sequence unit
+  if (lapse)  // the buffer's trace that records hit times: the lapse unit and its KerrBL half
+    HIP_TRY((s->desc.geometry == GRT_GEOM_KERR_BL ? grt::lapse_kerr_bl::launch_trace : grt::lapse::launch_trace)(
+        s->desc.geometry, dc.d_scene, wl, ws, o, dc.d_counter, d_stats, blocks, threads, false, tl, tail_blocks, stream));
+  else if (ct)  // a camera sequence: always the exact sequence unit
     HIP_TRY(grt::seq::launch_trace(s->desc.geometry, dc.d_scene, wl, ws, o, dc.d_counter, d_stats, blocks, threads,
                                    dc.vol, tl, tail_blocks, stream, *ct));
   else
@@ -1185,6 +1215,8 @@ int grt_scene_destroy(grt_scene* s) {
     if (dc->ad_mem) (void)hipFree(dc->ad_mem);
     if (dc->tail_mem) (void)hipFree(dc->tail_mem);
     if (dc->pool_mem) (void)hipFree(dc->pool_mem);
+    if (dc->slot_time_mem) (void)hipFree(dc->slot_time_mem);
+    if (dc->pool_time_mem) (void)hipFree(dc->pool_time_mem);
     if (dc->ev0) (void)hipEventDestroy(dc->ev0);
     if (dc->ev1) (void)hipEventDestroy(dc->ev1);
     if (dc->ev_busy) (void)hipEventDestroy(dc->ev_busy);
@@ -1272,12 +1304,13 @@ void stats_from(const unsigned long long acc[8], double kernel_ms, grt_stats* st
 // One trace of `wl` on the null stream, waited for.  Adds its counters to acc and its
 // event time to *ms; *need = hit-pool records it asked for.
 int trace_sync(grt_scene* s, DeviceCopy& dc, const grt::WorkList& wl, const grt::Outputs& o,
-               unsigned long long acc[8], float* ms, unsigned long long* need, const grt::CamTable* ct, bool exact) {
+               unsigned long long acc[8], float* ms, unsigned long long* need, const grt::CamTable* ct, bool exact,
+               bool lapse) {
   hipStream_t st = nullptr;
   int rc;
   if ((rc = reset_counters(dc, st))) return rc;
   HIP_TRY(hipEventRecord(dc.ev0, st));
-  if ((rc = enqueue_trace(s, dc, wl, o, dc.d_stats, st, ct, exact))) return rc;
+  if ((rc = enqueue_trace(s, dc, wl, o, dc.d_stats, st, ct, exact, lapse))) return rc;
   HIP_TRY(hipEventRecord(dc.ev1, st));
   HIP_TRY(hipEventSynchronize(dc.ev1));
   if ((rc = read_counters(dc, acc))) return rc;

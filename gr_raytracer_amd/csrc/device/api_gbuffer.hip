@@ -158,6 +158,10 @@ struct grt_gbuffer {
   // scratch of grt_gbuffer_shade_times: the layers' orbit rates, written once per call;
   // allocated by the first such call and kept (the buffer's layers never change)
   mutable DevBuf omega;
+  // optional: each layer's light-travel time, n_layers doubles (grt_gbuffer_trace_lapse,
+  // grt_gbuffer_lapse_upload); not one of the twelve arrays
+  DevBuf lapse;
+  bool has_lapse = false;
   grt_gbuffer() { std::memset(&info, 0, sizeof(info)); }
   grt::GBufferArrays view() const { return arr.view(0, info.n_pixels); }
 };
@@ -199,12 +203,12 @@ static int check_tracer(const grt_gbuffer* gb, const grt_scene* t, bool camera =
 // one complete trace's.  acc[3] is 0 on success; *n_traces (nullable) counts the traces.
 static int trace_exact(grt_scene* s, DeviceCopy& dc, const grt::WorkList& wl, const grt::Outputs& o,
                        unsigned long long acc[8], float* ms, const grt::CamTable* ct = nullptr,
-                       uint32_t* n_traces = nullptr) {
+                       uint32_t* n_traces = nullptr, bool lapse = false) {
   for (int traces = 1;; ++traces) {
     unsigned long long need = 0;
     acc[3] = 0;
     if (n_traces) ++*n_traces;
-    if (int rc = trace_sync(s, dc, wl, o, acc, ms, &need, ct, true)) return rc;
+    if (int rc = trace_sync(s, dc, wl, o, acc, ms, &need, ct, true, lapse)) return rc;
     if (acc[3] == 0) return 0;
     if (traces == 3 || dc.pool_cap >= POOL_MAX)
       return fail(-ENOMEM, "the hit pool still overflows after " + std::to_string(traces) + " traces");
@@ -236,14 +240,19 @@ struct LayerScan {
 
 // The fill of `gb` on `st` after a complete trace of the n rays of `wl`: the workspace as
 // that trace carved it, its hit pool, and the fill kernel of the unit that traced -- the
-// sequence unit's with a camera table, else KerrBL's own or the default.
+// sequence unit's with a camera table, the lapse unit's with a lapse array (d_lapse, over the
+// buffer's layers), else KerrBL's own or the default.
 static int enqueue_fill(const grt_scene* s, DeviceCopy& dc, const grt::WorkList& wl, uint64_t n,
-                        const grt::GBufferArrays& gb, hipStream_t st, const grt::CamTable* ct = nullptr) {
+                        const grt::GBufferArrays& gb, hipStream_t st, const grt::CamTable* ct = nullptr,
+                        double* d_lapse = nullptr) {
   grt::Workspace ws;
   if (int rc = ensure_workspace(dc, n, &ws)) return rc;
   ws.pool = dc.d_pool;
   const int geom = s->desc.geometry;
-  if (ct) HIP_TRY(grt::seq::launch_gbuffer_fill(geom, dc.d_scene, wl, ws, gb, st, *ct));
+  if (d_lapse)
+    HIP_TRY((geom == GRT_GEOM_KERR_BL ? grt::lapse_kerr_bl::launch_gbuffer_fill : grt::lapse::launch_gbuffer_fill)(
+        geom, dc.d_scene, wl, ws, gb, st, d_lapse));
+  else if (ct) HIP_TRY(grt::seq::launch_gbuffer_fill(geom, dc.d_scene, wl, ws, gb, st, *ct));
   else if (geom == GRT_GEOM_KERR_BL) HIP_TRY(grt::kerr_bl::launch_gbuffer_fill(geom, dc.d_scene, wl, ws, gb, st));
   else HIP_TRY(grt::launch_gbuffer_fill(geom, dc.d_scene, wl, ws, gb, st));
   return 0;
@@ -330,10 +339,10 @@ void gbuffer_set_times(grt_gbuffer* gb, double trace_ms, double fill_ms) {
 
 }  // namespace grt_api
 
-extern "C" {
-
-int grt_gbuffer_trace(grt_scene* s, int device, uint32_t row0, uint32_t col0, uint32_t rows, uint32_t cols,
-                      grt_gbuffer** out, grt_stats* stats) {
+// grt_gbuffer_trace, and with `lapse` grt_gbuffer_trace_lapse: the same steps through the
+// lapse unit's trace and fill, the buffer's lapse array filled beside the twelve.
+static int gbuffer_trace_impl(grt_scene* s, int device, uint32_t row0, uint32_t col0, uint32_t rows, uint32_t cols,
+                              grt_gbuffer** out, grt_stats* stats, bool lapse) {
   if (!s || !out) return fail(-EINVAL, "null argument");
   *out = nullptr;
   if (rows == 0 || cols == 0) return fail(-EINVAL, "empty rectangle");
@@ -368,14 +377,19 @@ int grt_gbuffer_trace(grt_scene* s, int device, uint32_t row0, uint32_t col0, ui
   const grt::Outputs o{(float*)xyza.p, (uint8_t*)cls.p, A.status(), nullptr, A.steps(), A.stop(), (uint32_t*)hits.p};
   unsigned long long acc[8] = {0, 0, 0, 0, 0, 0, 0, 0};
   float ms = 0;
-  if ((rc = trace_exact(s, *dc, wl, o, acc, &ms))) return rc;
+  if ((rc = trace_exact(s, *dc, wl, o, acc, &ms, nullptr, nullptr, lapse))) return rc;
   hipStream_t st = nullptr;
   if ((rc = stream_order(*dc, st))) return rc;
   HIP_TRY(hipEventRecord(dc->ev0, st));
   std::vector<uint64_t> total;  // the layers of the rectangle
   if ((rc = scan.run(A.status(), (const uint32_t*)hits.p, n, A.layer_start(), st, {n}, &total))) return rc;
   info.n_layers = total[0];
-  if ((rc = A.alloc(true, info.n_layers)) || (rc = enqueue_fill(s, *dc, wl, n, gb->view(), st))) return rc;
+  if ((rc = A.alloc(true, info.n_layers))) return rc;
+  if (lapse) {
+    if ((rc = gb->lapse.alloc(8 * info.n_layers))) return rc;
+    gb->has_lapse = true;
+  }
+  if ((rc = enqueue_fill(s, *dc, wl, n, gb->view(), st, nullptr, (double*)gb->lapse.p))) return rc;
   HIP_TRY(hipEventRecord(dc->ev1, st));
   HIP_TRY(hipEventSynchronize(dc->ev1));
   float fill_ms = 0;
@@ -387,6 +401,42 @@ int grt_gbuffer_trace(grt_scene* s, int device, uint32_t row0, uint32_t col0, ui
   // (volumetric.h) adds to them, and scenes with a VolumetricDisc are refused above
   if (stats) stats_from(acc, ms, stats);
   *out = gb.release();
+  return 0;
+}
+
+extern "C" {
+
+int grt_gbuffer_trace(grt_scene* s, int device, uint32_t row0, uint32_t col0, uint32_t rows, uint32_t cols,
+                      grt_gbuffer** out, grt_stats* stats) {
+  return gbuffer_trace_impl(s, device, row0, col0, rows, cols, out, stats, false);
+}
+
+int grt_gbuffer_trace_lapse(grt_scene* s, int device, uint32_t row0, uint32_t col0, uint32_t rows, uint32_t cols,
+                            grt_gbuffer** out, grt_stats* stats) {
+  return gbuffer_trace_impl(s, device, row0, col0, rows, cols, out, stats, true);
+}
+
+int grt_gbuffer_lapse_download(const grt_gbuffer* gb, double* out) {
+  if (!gb || !out) return fail(-EINVAL, "null argument");
+  if (!gb->has_lapse) return fail(-ENODATA, "the g-buffer holds no lapse (grt_gbuffer_trace_lapse, grt_gbuffer_lapse_upload)");
+  HIP_TRY(hipSetDevice(gb->info.device));
+  if (gb->info.n_layers) HIP_TRY(hipMemcpy(out, gb->lapse.p, 8 * gb->info.n_layers, hipMemcpyDeviceToHost));
+  return 0;
+}
+
+int grt_gbuffer_lapse_upload(grt_gbuffer* gb, const double* lapse, uint64_t n_layers) {
+  if (!gb || (!lapse && n_layers)) return fail(-EINVAL, "null argument");
+  if (n_layers != gb->info.n_layers)
+    return fail(-EINVAL, "a lapse of " + std::to_string(n_layers) + " entries for a g-buffer of " +
+                             std::to_string(gb->info.n_layers) + " layers");
+  for (uint64_t k = 0; k < n_layers; ++k)
+    if (!std::isfinite(lapse[k])) return fail(-EINVAL, "lapse[" + std::to_string(k) + "] is not finite");
+  HIP_TRY(hipSetDevice(gb->info.device));
+  DevBuf fresh;
+  if (int rc = fresh.alloc(8 * n_layers)) return rc;
+  if (n_layers) HIP_TRY(hipMemcpy(fresh.p, lapse, 8 * n_layers, hipMemcpyHostToDevice));
+  gb->lapse = std::move(fresh);  // what the buffer held is freed
+  gb->has_lapse = true;
   return 0;
 }
 
@@ -1112,8 +1162,9 @@ int grt_gbuffer_shade_section_at(grt_scene* s, grt_gbuffer* gb, const grt_adapti
                             report, &time);
 }
 
-int grt_gbuffer_shade_times(grt_scene* s, const grt_gbuffer* gb, uint32_t n_times, const double* times,
-                            const grt_frame_out* out, float* kernel_ms) {
+// grt_gbuffer_shade_times, and with `retarded` grt_gbuffer_shade_times_retarded.
+static int shade_times_impl(grt_scene* s, const grt_gbuffer* gb, uint32_t n_times, const double* times,
+                            const grt_frame_out* out, float* kernel_ms, bool retarded) {
   if (!s || !gb || !times || !out) return fail(-EINVAL, "null argument");
   if (n_times == 0) return fail(-EINVAL, "grt_gbuffer_shade_times needs at least one time");
   for (uint32_t k = 0; k < n_times; ++k)
@@ -1121,6 +1172,8 @@ int grt_gbuffer_shade_times(grt_scene* s, const grt_gbuffer* gb, uint32_t n_time
   if (!out->xyza && !out->xyza64) return fail(-EINVAL, "grt_frame_out needs xyza or xyza64");
   int rc = grt_gbuffer_shape_compatible(&gb->info.shape, &s->desc);
   if (rc) return rc;
+  if (retarded && !gb->has_lapse)
+    return fail(-ENODATA, "the g-buffer holds no lapse (grt_gbuffer_trace_lapse, grt_gbuffer_lapse_upload)");
   const int device = gb->info.device;
   const uint64_t per = gb->info.n_pixels;
   if (per == 0 || per > (uint64_t)INT_MAX) return fail(-EINVAL, "frames of 0 or more than INT_MAX pixels");
@@ -1149,7 +1202,8 @@ int grt_gbuffer_shade_times(grt_scene* s, const grt_gbuffer* gb, uint32_t n_time
     if (f0 == 0)  // the layers' rates, once per call, in the first group's event time
       HIP_TRY(grt::launch_gbuffer_orbit_rate(dc->d_scene, gb->view(), gb->info.n_layers, (double*)gb->omega.p, st));
     HIP_TRY(grt::launch_gbuffer_shade_times(dc->d_scene, gb->view(), gb->arr.steps(), (const double*)d_times.p + f0, kg,
-                                            (const double*)gb->omega.p, o, st));
+                                            (const double*)gb->omega.p, retarded ? (const double*)gb->lapse.p : nullptr,
+                                            retarded, o, st));
     HIP_TRY(hipEventRecord(dc->ev1, st));
     HIP_TRY(hipEventSynchronize(dc->ev1));
     float t = 0;
@@ -1164,6 +1218,16 @@ int grt_gbuffer_shade_times(grt_scene* s, const grt_gbuffer* gb, uint32_t n_time
   }
   if (kernel_ms) *kernel_ms = total_ms;
   return 0;
+}
+
+int grt_gbuffer_shade_times(grt_scene* s, const grt_gbuffer* gb, uint32_t n_times, const double* times,
+                            const grt_frame_out* out, float* kernel_ms) {
+  return shade_times_impl(s, gb, n_times, times, out, kernel_ms, false);
+}
+
+int grt_gbuffer_shade_times_retarded(grt_scene* s, const grt_gbuffer* gb, uint32_t n_times, const double* times,
+                                     const grt_frame_out* out, float* kernel_ms) {
+  return shade_times_impl(s, gb, n_times, times, out, kernel_ms, true);
 }
 
 int grt_gbuffer_supersample_sequence(grt_scene* tracer, uint32_t n, grt_gbuffer* const* buffers, uint32_t spa,

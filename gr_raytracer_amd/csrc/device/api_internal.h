@@ -79,6 +79,12 @@ struct DeviceCopy {
   uint32_t *ws_head = nullptr, *ws_last = nullptr;  // per-ray list ends, carved from the workspace
   grt::HitPool* d_pool = nullptr;  // the descriptor the kernels read (device memory)
   grt::HitPool pool_desc{};        // what *d_pool holds
+  // lapse traces only (grt_gbuffer_trace_lapse; the first one allocates them, ensure_hit_times):
+  // the coordinate time of every candidate, beside the workspace slots and the pool records
+  void* slot_time_mem = nullptr;  // f64[GRT_WS_SLOTS][slot_time_cap], slot_time_cap >= ws_cap
+  uint64_t slot_time_cap = 0;
+  void* pool_time_mem = nullptr;  // f64[pool_time_cap], pool_time_cap >= pool_cap
+  uint64_t pool_time_cap = 0;
 };
 
 constexpr uint64_t POOL_MAX = (1ull << 31) - 1;      // job and list encodings hold 31 bits
@@ -118,16 +124,17 @@ int check_rect(const grt_scene* s, uint64_t row0, uint64_t col0, uint64_t rows, 
 int check_shard(const grt_row_shard* sh);
 // the rectangle work list of the shard's local rows, full width
 grt::WorkList shard_worklist(const grt_scene* s, const grt_row_shard* sh);
+// lapse (with exact, no ct, no VolumetricDisc): the lapse unit's kernels, which also record hit times
 int enqueue_trace(grt_scene* s, DeviceCopy& dc, const grt::WorkList& wl_in, const grt::Outputs& o,
                   unsigned long long* d_stats, hipStream_t stream, const grt::CamTable* ct = nullptr,
-                  bool exact = false);
+                  bool exact = false, bool lapse = false);
 int pool_check(DeviceCopy& dc, bool* again);
 int reset_counters(DeviceCopy& dc, hipStream_t st);
 int read_counters(DeviceCopy& dc, unsigned long long acc[8]);
 void stats_from(const unsigned long long acc[8], double kernel_ms, grt_stats* stats);
 int trace_sync(grt_scene* s, DeviceCopy& dc, const grt::WorkList& wl, const grt::Outputs& o,
                unsigned long long acc[8], float* ms, unsigned long long* need, const grt::CamTable* ct = nullptr,
-               bool exact = false);
+               bool exact = false, bool lapse = false);
 int trace_to_host(grt_scene* s, DeviceCopy& dc, const grt::WorkList& wl, uint64_t n, const grt_offsets* offs,
                   float* xyza_out, uint8_t* class_out, uint8_t* status_out, const grt_aux_out* aux,
                   unsigned long long acc[8], float* ms_out, const grt::CamTable* ct = nullptr);

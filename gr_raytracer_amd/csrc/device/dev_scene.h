@@ -159,6 +159,10 @@ struct HitPool {
   uint32_t* head;            // [n] per ray: pool record of candidate GRT_WS_SLOTS
   uint32_t* last;            // [n] per ray: pool record of the last candidate appended,
                              //     HIT_NIL once one was lost
+  // The lapse unit only (geodesic_lapse.hip; NULL until a lapse trace asks for them): the
+  // coordinate time y[0] of each candidate.  At the end, so that no other member moves.
+  double* slot_time;         // [GRT_WS_SLOTS][n] beside Workspace::rec, slot j of ray i at j * n + i
+  double* pool_time;         // [cap] beside the pool's records
 };
 
 // A window candidate in a workspace slot: 64 B, written whole (four 16-B stores) by the

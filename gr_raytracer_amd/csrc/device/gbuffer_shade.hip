@@ -33,10 +33,12 @@ namespace grt {
 // a disc texture that orbits at that rate is the animation of the scene being shaded: at
 // coordinate time t the matter seen at in-plane angle phi sat at phi - omega t at time 0, and
 // disc uv is 0.5 + 0.5 rho (cos phi, sin phi), so the lookup point turns about (0.5, 0.5) by
-// -omega t.  "Fast light": every layer of a frame is shaded at the same t; the buffer does not
-// record the coordinate time along the ray, and light-travel delay is ignored.
+// -omega t.  "Fast light": every layer of a frame is shaded at the same t, and light-travel delay
+// is ignored.  Retarded (grt_gbuffer_shade_times_retarded): a buffer traced with its lapse holds,
+// per layer, the coordinate time its light took to the camera, negated, and the layer is shaded
+// at its emission time t + lapse.
 // The rule is restated on the host with the same operations in the same order
-// (host/orbit.cpp: grt_orbit_rate, grt_gbuffer_orbit_uv).
+// (host/orbit.cpp: grt_orbit_rate, grt_gbuffer_orbit_uv, grt_gbuffer_orbit_uv_retarded).
 //
 // d(phi)/dt of the emitter at radius r: killing_coefficients' omega (geodesic.hip), as a
 // function of the appearance scene alone; the flat charts' emitter is at rest.
@@ -60,14 +62,16 @@ GDEV void orbit_uv(double omega, double t, double* u, double* v) {
 // How a shade treats time.  SHADE_STATIC: the buffer as traced (no orbit code at all).
 // SHADE_AT: at time t, a disc layer's rate computed where it is used.  SHADE_AT_CACHED: at
 // time t, the rate read from omega[k] (gbuffer_orbit_rate_kernel wrote it): the same
-// expression either way, so the same bits.
-enum ShadeMode { SHADE_STATIC, SHADE_AT, SHADE_AT_CACHED };
+// expression either way, so the same bits.  SHADE_RETARDED: SHADE_AT_CACHED with layer k at
+// its emission time t + lapse[k] (grt_gbuffer_shade_times_retarded): one add, then orbit_uv.
+enum ShadeMode { SHADE_STATIC, SHADE_AT, SHADE_AT_CACHED, SHADE_RETARDED };
 
 // The colour of layer k.  In the two time modes a disc layer's (u, v) goes through orbit_uv
-// before the texture lookup; t and omega are unused in SHADE_STATIC.
+// before the texture lookup; t and omega are unused in SHADE_STATIC, lapse in every mode but
+// SHADE_RETARDED.
 template <ShadeMode MODE>
 GDEV int gbuffer_layer_color(const DevScene& S, const GBufferArrays& gb, uint64_t k, double t,
-                             const double* __restrict__ omega, XYZA* col) {
+                             const double* __restrict__ omega, const double* __restrict__ lapse, XYZA* col) {
   const DevObject& o = S.obj[gb.object[k]];
   double temperature;
   if (o.kind != GRT_OBJ_SPHERE) {
@@ -77,7 +81,9 @@ GDEV int gbuffer_layer_color(const DevScene& S, const GBufferArrays& gb, uint64_
     temperature = o.temperature;
   }
   double u = gb.u[k], v = gb.v[k];
-  if constexpr (MODE != SHADE_STATIC) {
+  if constexpr (MODE == SHADE_RETARDED) {
+    if (o.kind == GRT_OBJ_DISC) orbit_uv(omega[k], t + lapse[k], &u, &v);
+  } else if constexpr (MODE != SHADE_STATIC) {
     if (o.kind == GRT_OBJ_DISC) orbit_uv(MODE == SHADE_AT_CACHED ? omega[k] : orbit_rate(S, gb.radius[k]), t, &u, &v);
   }
   *col = texture_color(S, o.tex, u, v, gb.redshift[k], temperature);
@@ -89,7 +95,8 @@ GDEV int gbuffer_layer_color(const DevScene& S, const GBufferArrays& gb, uint64_
 // colour is evaluated in both; a ray may have any number of layers).
 template <ShadeMode MODE>
 GDEV void gbuffer_shade_ray(const DevScene& S, const GBufferArrays& gb, uint64_t src, const Outputs& out, uint64_t dst,
-                            double t = 0.0, const double* __restrict__ omega = nullptr) {
+                            double t = 0.0, const double* __restrict__ omega = nullptr,
+                            const double* __restrict__ lapse = nullptr) {
   const int status = gb.status[src];
   const int stop = gb.stop[src];
   const XYZA fail{0.0, 0.0, 0.0, 1.0};
@@ -101,7 +108,7 @@ GDEV void gbuffer_shade_ray(const DevScene& S, const GBufferArrays& gb, uint64_t
   double opacity = 0.0;
   for (uint64_t k = l0; k < l1; ++k) {
     XYZA col;
-    int e = gbuffer_layer_color<MODE>(S, gb, k, t, omega, &col);
+    int e = gbuffer_layer_color<MODE>(S, gb, k, t, omega, lapse, &col);
     if (e != GRT_OK) {  // a temperature error the traced scene did not have: the window error's pixel
       write_out(out, dst, fail, GRT_CLASS_ESCAPED, e, stop, (uint32_t)(k - l0));
       return;
@@ -120,7 +127,7 @@ GDEV void gbuffer_shade_ray(const DevScene& S, const GBufferArrays& gb, uint64_t
   }
   for (uint64_t k = l1; k > l0; --k) {
     XYZA col{0.0, 0.0, 0.0, 0.0};
-    (void)gbuffer_layer_color<MODE>(S, gb, k - 1, t, omega, &col);
+    (void)gbuffer_layer_color<MODE>(S, gb, k - 1, t, omega, lapse, &col);
     result = blend(result, col);
   }
   if (opacity >= S.hit_threshold) cls = GRT_CLASS_HIT;
@@ -257,6 +264,21 @@ __global__ void __launch_bounds__(256) gbuffer_shade_times_kernel(const DevScene
   gbuffer_shade_ray<SHADE_AT_CACHED>(S, gb, src, out, idx, times[f], omega);
 }
 
+// gbuffer_shade_times_kernel under the retarded rule (grt_gbuffer_shade_times_retarded): the
+// same launch shape and output layout, each disc layer at times[f] + lapse[layer].
+__global__ void __launch_bounds__(256) gbuffer_shade_times_retarded_kernel(
+    const DevScene* __restrict__ Sp, GBufferArrays gb, const uint32_t* __restrict__ steps,
+    const double* __restrict__ times, uint32_t n_times, const double* __restrict__ omega,
+    const double* __restrict__ lapse, Outputs out) {
+  const DevScene& S = *Sp;
+  glibc::tables_to_lds();  // whole block, before the early return
+  const uint64_t idx = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (idx >= (uint64_t)n_times * gb.n) return;
+  const uint64_t f = idx / gb.n, src = idx - f * gb.n;
+  if (out.steps) out.steps[idx] = steps[src];
+  gbuffer_shade_ray<SHADE_RETARDED>(S, gb, src, out, idx, times[f], omega, lapse);
+}
+
 // The pre-pass of grt_gbuffer_shade_times: orbit_rate of every disc layer, once per call (the
 // entry of another layer is never read).
 __global__ void __launch_bounds__(256) gbuffer_orbit_rate_kernel(const DevScene* __restrict__ Sp, GBufferArrays gb,
@@ -277,12 +299,17 @@ hipError_t launch_gbuffer_orbit_rate(const DevScene* d_scene, const GBufferArray
 }
 
 hipError_t launch_gbuffer_shade_times(const DevScene* d_scene, const GBufferArrays& gb, const uint32_t* d_steps,
-                                      const double* d_times, uint32_t n_times, const double* d_omega, const Outputs& out,
-                                      hipStream_t stream) {
+                                      const double* d_times, uint32_t n_times, const double* d_omega,
+                                      const double* d_lapse, bool retarded, const Outputs& out, hipStream_t stream) {
   const uint64_t n = (uint64_t)n_times * gb.n;
   if (n == 0) return hipSuccess;
   if (n > 0xffffffffull * 256) return hipErrorInvalidValue;
-  if (!d_omega) return hipErrorInvalidValue;
+  if (!d_omega || (retarded && !d_lapse)) return hipErrorInvalidValue;
+  if (retarded) {
+    hipLaunchKernelGGL(gbuffer_shade_times_retarded_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, stream,
+                       d_scene, gb, d_steps, d_times, n_times, d_omega, d_lapse, out);
+    return hipGetLastError();
+  }
   hipLaunchKernelGGL(gbuffer_shade_times_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, stream, d_scene, gb,
                      d_steps, d_times, n_times, d_omega, out);
   return hipGetLastError();

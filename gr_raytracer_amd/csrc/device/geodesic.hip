@@ -28,7 +28,7 @@
 //   geodesic_rhs.h    range-free division / sqrt, metrics, the sincos dispatch, the RHS   every unit
 //   geodesic_rkf.h    RKF45 attempts, LDS stage parking                                   every unit
 //   geodesic_probe.h  work-order kernels (probes, impact and class keys)                  exact build, sequence
-//   geodesic_fill.h   gbuffer_fill_kernel                                                 exact build, KerrBL, sequence
+//   geodesic_fill.h   gbuffer_fill_kernel                                                 exact build, KerrBL, sequence, lapse
 // Still here, between them and in this order: chart helpers, chord tests and the camera
 // ray; the trace (integrate_kernel, tail_kernel); the exact build's trajectory kernel,
 // device checks and invariant monitors; shade_kernel.  The unit macros and every GRT_*
@@ -67,7 +67,20 @@
 #ifndef GRT_SEQ
 #define GRT_SEQ 0
 #endif
-#define GRT_MAIN_TU (!GRT_FUSED && !GRT_KERR_BL_TU && !GRT_SEQ)
+// GRT_LAPSE: this file compiled a fifth time, by geodesic_lapse.hip, into namespace
+// grt::lapse: the exact trace and geometry buffer fill of every chart but KerrBL, which also
+// keep the coordinate time y[0] of every recorded hit (grt_gbuffer_trace_lapse).  Everything
+// else is the code of the exact units; the time goes to two arrays named at the end of HitPool.
+// GRT_LAPSE_KERR_BL: and a sixth time, by geodesic_lapse_kerr_bl.hip, into namespace
+// grt::lapse_kerr_bl: the same for KerrBL, built as grt::kerr_bl is (without the machine-level
+// loop-invariant code motion; with it the integrate kernel spills 96 B per lane).
+#ifndef GRT_LAPSE
+#define GRT_LAPSE 0
+#endif
+#ifndef GRT_LAPSE_KERR_BL
+#define GRT_LAPSE_KERR_BL 0
+#endif
+#define GRT_MAIN_TU (!GRT_FUSED && !GRT_KERR_BL_TU && !GRT_SEQ && !GRT_LAPSE)
 
 namespace grt {
 #if GRT_FUSED
@@ -76,6 +89,10 @@ namespace fused {
 namespace kerr_bl {
 #elif GRT_SEQ
 namespace seq {
+#elif GRT_LAPSE && GRT_LAPSE_KERR_BL
+namespace lapse_kerr_bl {
+#elif GRT_LAPSE
+namespace lapse {
 #endif
 
 // The camera of a ray.  The other units read the scene's; the sequence unit hands its
@@ -93,6 +110,20 @@ namespace seq {
 #define CAM_PARAM
 #define CAM_ARG(c)
 #define CAM_OF(S) (S).cam
+#endif
+
+// The lapse unit: the coordinate time of a recorded hit, handed to hit_append (HIT_TIME_*),
+// and the buffer's lapse array, handed to gbuffer_fill_kernel (LAPSE_*).
+#if GRT_LAPSE
+#define HIT_TIME_PARAM , double th
+#define HIT_TIME_ARG , th
+#define LAPSE_PARAM , double* __restrict__ lapse
+#define LAPSE_ARG , lapse
+#else
+#define HIT_TIME_PARAM
+#define HIT_TIME_ARG
+#define LAPSE_PARAM
+#define LAPSE_ARG
 #endif
 
 #ifndef GDEV
@@ -173,8 +204,12 @@ constexpr unsigned RHS_CHECK_CHARTS = 1u << GRT_GEOM_SCHWARZSCHILD | KERR_CHART 
 constexpr unsigned TRACE_CHARTS = ALL_CHARTS & ~KERR_CHART;  // Kerr-Schild always runs exact (grt_set_arithmetic)
 #elif GRT_KERR_BL_TU
 constexpr unsigned TRACE_CHARTS = KERR_BL_CHART, FILL_CHARTS = KERR_BL_CHART;
-#else  // GRT_SEQ
+#elif GRT_SEQ
 constexpr unsigned TRACE_CHARTS = ALL_CHARTS, FILL_CHARTS = ALL_CHARTS, PROBE_CHARTS = ALL_CHARTS;
+#elif GRT_LAPSE_KERR_BL
+constexpr unsigned TRACE_CHARTS = KERR_BL_CHART, FILL_CHARTS = KERR_BL_CHART;
+#else  // GRT_LAPSE
+constexpr unsigned TRACE_CHARTS = ALL_CHARTS & ~KERR_BL_CHART, FILL_CHARTS = TRACE_CHARTS;
 #endif
 
 // f(std::integral_constant<int, G>()) for G = geometry when CHARTS has that chart;
@@ -930,7 +965,7 @@ GDEV void store_ray(const Workspace& ws, uint64_t idx, const double* y, const Ra
 // marked lost (ovf_last = HIT_NIL) and nothing more is linked; the count keeps growing so
 // that the host learns the size the trace needed.
 GDEV void hit_append(const Workspace& ws, uint64_t idx, uint32_t nrec, uint32_t win, uint32_t obj,
-                     const double* p, const double* pt, const double* dir) {
+                     const double* p, const double* pt, const double* dir HIT_TIME_PARAM) {
   const HitPool& hp = *ws.pool;
   const unsigned long long pos = atomicAdd(hp.count, 1ull);
   const bool first = nrec == GRT_WS_SLOTS;
@@ -951,6 +986,9 @@ GDEV void hit_append(const Workspace& ws, uint64_t idx, uint32_t nrec, uint32_t 
 #pragma unroll
     for (int q = 0; q < 3; ++q) hp.dir[q * m + pos] = dir[q];
   }
+#if GRT_LAPSE
+  hp.pool_time[pos] = th;
+#endif
   if (first) ws.pool->head[idx] = (uint32_t)pos;
   else hp.next[prev] = (uint32_t)pos;
   ws.pool->last[idx] = (uint32_t)pos;
@@ -990,8 +1028,16 @@ GDEV void window_pass(const DevScene& S, const Workspace& ws, const RayConst& rc
       shortest = distance;
       double ph[4];
       if (writer) lerp_momentum<G>(S, rc, y, yn, t, ph);
+#if GRT_LAPSE
+      // the hit's coordinate time, lerped over the window as the momentum is
+      [[maybe_unused]] double th = 0.0;
+      if (writer) th = y[0] + t * (yn[0] - y[0]);
+#endif
       if (writer && nrec < GRT_WS_SLOTS) {
         const uint64_t slot = (uint64_t)nrec * n + idx;
+#if GRT_LAPSE
+        ws.pool->slot_time[slot] = th;
+#endif
         double2* d = reinterpret_cast<double2*>(ws.rec + slot);
         d[0] = make_double2(ph[0], ph[1]);
         d[1] = make_double2(ph[2], ph[3]);
@@ -1004,7 +1050,7 @@ GDEV void window_pass(const DevScene& S, const Workspace& ws, const RayConst& rc
         }
       } else if (writer) {  // beyond the workspace slots: the hit pool
         double dir[3] = {cn[0] - c[0], cn[1] - c[1], cn[2] - c[2]};
-        hit_append(ws, idx, nrec, (uint32_t)i, k, ph, pt, VOL ? dir : nullptr);
+        hit_append(ws, idx, nrec, (uint32_t)i, k, ph, pt, VOL ? dir : nullptr HIT_TIME_ARG);
       }
       nrec++;
     }
@@ -2352,8 +2398,11 @@ __global__ void __launch_bounds__(256) shade_kernel(const DevScene* __restrict__
 #include "geodesic_fill.h"
 
 hipError_t launch_gbuffer_fill(int geometry, const DevScene* d_scene, const WorkList& wl, const Workspace& ws,
-                               const GBufferArrays& gb, hipStream_t stream CAMS_PARAM) {
+                               const GBufferArrays& gb, hipStream_t stream CAMS_PARAM LAPSE_PARAM) {
   if (gb.n == 0) return hipSuccess;
+#if GRT_LAPSE
+  if (!lapse) return hipErrorInvalidValue;
+#endif
 #if GRT_SEQ  // the stack from (0, 0): whole frames, one camera each, or an offset list over them (a slot per entry)
   if (!ct.cams || ct.cam_rows == 0 || ct.n_cams == 0 || wl.row0 != 0 || wl.col0 != 0 ||
       (uint64_t)wl.rows != (uint64_t)ct.cam_rows * ct.n_cams || (wl.pixel_index && (!wl.dx || !wl.dy)) ||
@@ -2362,7 +2411,7 @@ hipError_t launch_gbuffer_fill(int geometry, const DevScene* d_scene, const Work
 #endif
   return with_chart<FILL_CHARTS>(geometry, [&](auto g) {
     hipLaunchKernelGGL(gbuffer_fill_kernel<decltype(g)::value>, dim3((unsigned)((gb.n + 255) / 256)), dim3(256), 0,
-                       stream, d_scene, wl, ws, gb CAMS_ARG);
+                       stream, d_scene, wl, ws, gb CAMS_ARG LAPSE_ARG);
     return hipGetLastError();
   });
 }
@@ -2382,6 +2431,9 @@ static hipError_t launch_g(const DevScene* d_scene, const WorkList& wl, const Wo
   TailList tl = tl_in;
   if (G != GRT_GEOM_KERR || tail_blocks <= 0) tl.cap = 0;
   if (VOL && (!ws.rec_dir || !ws.vcol || !ws.jobs || !ws.march)) return hipErrorInvalidValue;
+#if GRT_LAPSE
+  if (VOL) return hipErrorInvalidValue;  // no raymarch kernels in this unit (VolumetricDisc scenes have no buffer)
+#endif
   hipLaunchKernelGGL((integrate_kernel<G, VOL>), dim3(blocks), dim3(threads), 0, stream, d_scene, wl, ws, d_counter,
                      d_stats, tl CAMS_ARG);
   hipError_t e = hipGetLastError();
@@ -2395,6 +2447,7 @@ static hipError_t launch_g(const DevScene* d_scene, const WorkList& wl, const Wo
   hipLaunchKernelGGL((shade_kernel<G, VOL ? 1 : 0>), dim3(nb), dim3(256), 0, stream, d_scene, wl, ws, out,
                      d_stats CAMS_ARG);
   e = hipGetLastError();
+#if !GRT_LAPSE
   if constexpr (VOL) {
     if (e != hipSuccess) return e;
     hipLaunchKernelGGL((march_kernel<G>), dim3(blocks), dim3(256), 0, stream, d_scene, ws);
@@ -2402,6 +2455,7 @@ static hipError_t launch_g(const DevScene* d_scene, const WorkList& wl, const Wo
     hipLaunchKernelGGL((shade_kernel<G, 2>), dim3(nb), dim3(256), 0, stream, d_scene, wl, ws, out, d_stats CAMS_ARG);
     e = hipGetLastError();
   }
+#endif
   return e;
 }
 
@@ -2412,6 +2466,13 @@ hipError_t launch_trace(int geometry, const DevScene* d_scene, const WorkList& w
 #if GRT_SEQ
   if (!ct.cams || ct.cam_rows == 0 || ct.n_cams == 0) return hipErrorInvalidValue;
 #endif
+#if GRT_LAPSE
+  if (vol) return hipErrorInvalidValue;
+  return with_chart<TRACE_CHARTS>(geometry, [&](auto g) {
+    return launch_g<decltype(g)::value, false>(d_scene, wl, ws, out, d_counter, d_stats, blocks, threads, tl,
+                                               tail_blocks, stream);
+  });
+#else
   return with_chart<TRACE_CHARTS>(geometry, [&](auto g) {
     constexpr int G = decltype(g)::value;
     return vol ? launch_g<G, true>(d_scene, wl, ws, out, d_counter, d_stats, blocks, threads, tl, tail_blocks,
@@ -2419,9 +2480,10 @@ hipError_t launch_trace(int geometry, const DevScene* d_scene, const WorkList& w
                : launch_g<G, false>(d_scene, wl, ws, out, d_counter, d_stats, blocks, threads, tl, tail_blocks,
                                     stream CAMS_ARG);
   });
+#endif
 }
 
-#if GRT_FUSED || GRT_KERR_BL_TU || GRT_SEQ
-}  // namespace fused / kerr_bl / seq
+#if GRT_FUSED || GRT_KERR_BL_TU || GRT_SEQ || GRT_LAPSE
+}  // namespace fused / kerr_bl / seq / lapse / lapse_kerr_bl
 #endif
 }  // namespace grt

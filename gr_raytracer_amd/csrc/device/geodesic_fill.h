@@ -1,5 +1,5 @@
 // geodesic_fill.h — a layer of geodesic.hip: the geometry buffer's fill.  Included by the
-// exact units (the exact build, the KerrBL unit, the sequence unit; not the fused one),
+// exact units (the exact build, the KerrBL unit, the sequence unit, the lapse unit; not the fused one),
 // after the shade kernel.
 
 // ============================================================ geometry buffer =====
@@ -11,10 +11,12 @@
 // ray.  A ray whose status is not 0 has no layers (layer_start is the scan of the trace's
 // own hit counts, zeroed for those rays).  The sequence unit's (grt_gbuffer_trace_sequence)
 // fills the buffer of a whole stack: slot idx is a ray of frame idx / (rows * cols), and its
-// camera is that frame's (observer_energy).
+// camera is that frame's (observer_energy).  The lapse unit's (grt_gbuffer_trace_lapse) also
+// writes each layer's lapse: the coordinate time the trace kept beside the layer's record
+// (window_pass) minus the camera's, the y[0] the ray started from.
 template <int G>
 __global__ void __launch_bounds__(256) gbuffer_fill_kernel(const DevScene* __restrict__ Sp, WorkList wl, Workspace ws,
-                                                           GBufferArrays gb CAMS_PARAM) {
+                                                           GBufferArrays gb CAMS_PARAM LAPSE_PARAM) {
   const DevScene& S = *Sp;
   glibc::tables_to_lds();  // whole block, before the early return
   const uint64_t idx = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
@@ -44,6 +46,9 @@ __global__ void __launch_bounds__(256) gbuffer_fill_kernel(const DevScene* __res
         gb.v[at] = geo[1];
         gb.redshift[at] = geo[2];
         gb.radius[at] = geo[3];
+#if GRT_LAPSE
+        lapse[at] = (r.pool ? ws.pool->pool_time[r.s] : ws.pool->slot_time[r.s]) - S.cam.pos[0];
+#endif
         ++at;
       }
     }

@@ -164,6 +164,28 @@ namespace seq {
 hipError_t launch_gbuffer_fill(int geometry, const DevScene* d_scene, const WorkList& wl, const Workspace& ws,
                                const GBufferArrays& gb, hipStream_t stream, CamTable ct);
 }
+// The exact trace and fill of a buffer that holds its lapse (geodesic_lapse.hip,
+// grt_gbuffer_trace_lapse), every chart but KerrBL, scenes without VolumetricDiscs (hipErrorInvalidValue
+// for `vol`).  The trace is launch_trace's and leaves the same workspace, pool and outputs;
+// it also writes the coordinate time of every candidate to ws.pool->slot_time / pool_time,
+// which must be there.  The fill is launch_gbuffer_fill's and also writes d_lapse[layer] = the
+// layer's candidate's time - the camera's, over the buffer's layers.
+namespace lapse {
+hipError_t launch_trace(int geometry, const DevScene* d_scene, const WorkList& wl, const Workspace& ws,
+                        const Outputs& out, unsigned long long* d_counter, unsigned long long* d_stats,
+                        int blocks, int threads, bool vol, const TailList& tl, int tail_blocks,
+                        hipStream_t stream);
+hipError_t launch_gbuffer_fill(int geometry, const DevScene* d_scene, const WorkList& wl, const Workspace& ws,
+                               const GBufferArrays& gb, hipStream_t stream, double* d_lapse);
+}  // namespace lapse
+namespace lapse_kerr_bl {  // KerrBL's (geodesic_lapse_kerr_bl.hip), as kerr_bl is to the exact build
+hipError_t launch_trace(int geometry, const DevScene* d_scene, const WorkList& wl, const Workspace& ws,
+                        const Outputs& out, unsigned long long* d_counter, unsigned long long* d_stats,
+                        int blocks, int threads, bool vol, const TailList& tl, int tail_blocks,
+                        hipStream_t stream);
+hipError_t launch_gbuffer_fill(int geometry, const DevScene* d_scene, const WorkList& wl, const Workspace& ws,
+                               const GBufferArrays& gb, hipStream_t stream, double* d_lapse);
+}  // namespace lapse_kerr_bl
 // A stacked buffer cut into its frames (gbuffer.hip): frame_start[i] = stack_start[i] -
 // stack_start[0] for i <= n, where stack_start points at the frame's first pixel.
 hipError_t gbuffer_rebase(const uint64_t* d_stack_start, uint64_t n, uint64_t* d_frame_start, hipStream_t stream);
@@ -210,9 +232,11 @@ hipError_t launch_gbuffer_shade_sub_stack(const DevScene* d_scene, const GBuffer
 // call; the single-time kernels compute it where a layer is coloured.
 hipError_t launch_gbuffer_orbit_rate(const DevScene* d_scene, const GBufferArrays& gb, uint64_t n_layers,
                                      double* d_omega, hipStream_t stream);
+// retarded (gbuffer_shade_times_retarded_kernel): layer k of a frame at its time + d_lapse[k]
+// (n_layers doubles; unread otherwise).
 hipError_t launch_gbuffer_shade_times(const DevScene* d_scene, const GBufferArrays& gb, const uint32_t* d_steps,
-                                      const double* d_times, uint32_t n_times, const double* d_omega, const Outputs& out,
-                                      hipStream_t stream);
+                                      const double* d_times, uint32_t n_times, const double* d_omega,
+                                      const double* d_lapse, bool retarded, const Outputs& out, hipStream_t stream);
 hipError_t launch_gbuffer_shade_at(const DevScene* d_scene, const GBufferArrays& gb, double t, const Outputs& out,
                                    hipStream_t stream);
 hipError_t launch_gbuffer_shade_sub_at(const DevScene* d_scene, const GBufferArrays& sub, const uint32_t* d_sub_steps,

@@ -1,5 +1,5 @@
 // orbit.cpp — host restatement of the disc's orbital motion (grt_api.h: grt_orbit_rate,
-// grt_gbuffer_orbit_uv).  The rule is the device's (device/gbuffer_shade.hip: orbit_rate, orbit_uv)
+// grt_gbuffer_orbit_uv, grt_gbuffer_orbit_uv_retarded).  The rule is the device's (device/gbuffer_shade.hip: orbit_rate, orbit_uv)
 // with the same operations in the same order, compiled without contraction, over the host
 // build of device/glibc_math.h: pow_fast / sincos_fast, and the host libm outside their fast
 // paths.  Device and host agree bit for bit for |omega t| < 105414350, the range of the exact
@@ -70,8 +70,11 @@ int grt_orbit_rate(int32_t geometry, double radius, double a, double r, double* 
   return 0;
 }
 
-int grt_gbuffer_orbit_uv(const grt_gbuffer_shape* shape, uint64_t n_layers, const uint8_t* object, const double* u,
-                         const double* v, const double* radius, double time, double* u_out, double* v_out) {
+// grt_gbuffer_orbit_uv (lapse NULL: every layer at `time`) and grt_gbuffer_orbit_uv_retarded
+// (a disc layer at time + lapse[k]).
+static int orbit_uv_layers(const grt_gbuffer_shape* shape, uint64_t n_layers, const uint8_t* object, const double* u,
+                           const double* v, const double* radius, const double* lapse, double time, double* u_out,
+                           double* v_out) {
   if (!shape || !object || !u || !v || !radius || !u_out || !v_out)
     return fail(-EINVAL, "grt_gbuffer_orbit_uv: null argument");
   if (!std::isfinite(time)) return fail(-EINVAL, "grt_gbuffer_orbit_uv: the time is not finite");
@@ -82,17 +85,32 @@ int grt_gbuffer_orbit_uv(const grt_gbuffer_shape* shape, uint64_t n_layers, cons
   // nothing is written before every index is known to be in range
   for (uint64_t k = 0; k < n_layers; ++k)
     if (object[k] >= shape->n_objects) return fail(-EINVAL, "grt_gbuffer_orbit_uv: an object index is out of range");
+  for (uint64_t k = 0; lapse && k < n_layers; ++k)
+    if (!std::isfinite(lapse[k])) return fail(-EINVAL, "grt_gbuffer_orbit_uv_retarded: a lapse is not finite");
   for (uint64_t k = 0; k < n_layers; ++k) {
     double uk = u[k], vk = v[k];
     if (shape->objects[object[k]].kind == GRT_OBJ_DISC) {
       double omega;
       orbit_rate(shape->geometry, shape->radius, shape->a, radius[k], &omega);
-      orbit_uv(omega, time, &uk, &vk);
+      const double te = lapse ? time + lapse[k] : time;  // the emission time
+      orbit_uv(omega, te, &uk, &vk);
     }
     u_out[k] = uk;
     v_out[k] = vk;
   }
   return 0;
+}
+
+int grt_gbuffer_orbit_uv(const grt_gbuffer_shape* shape, uint64_t n_layers, const uint8_t* object, const double* u,
+                         const double* v, const double* radius, double time, double* u_out, double* v_out) {
+  return orbit_uv_layers(shape, n_layers, object, u, v, radius, nullptr, time, u_out, v_out);
+}
+
+int grt_gbuffer_orbit_uv_retarded(const grt_gbuffer_shape* shape, uint64_t n_layers, const uint8_t* object,
+                                  const double* u, const double* v, const double* radius, const double* lapse,
+                                  double time, double* u_out, double* v_out) {
+  if (!lapse) return fail(-EINVAL, "grt_gbuffer_orbit_uv_retarded: null lapse");
+  return orbit_uv_layers(shape, n_layers, object, u, v, radius, lapse, time, u_out, v_out);
 }
 
 }  // extern "C"

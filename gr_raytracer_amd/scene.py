@@ -14,6 +14,7 @@ from __future__ import annotations
 import ctypes as C
 import errno
 import math
+import os
 from dataclasses import dataclass, field
 from pathlib import Path
 from typing import Optional, Sequence
@@ -225,17 +226,19 @@ class Scene:
         return res
 
     def trace_gbuffer(self, row0: int = 0, col0: int = 0, rows: Optional[int] = None, cols: Optional[int] = None,
-                      device: int = 0, adaptive: Optional[L.AdaptiveConfig] = None) -> "GBuffer":
+                      device: int = 0, adaptive: Optional[L.AdaptiveConfig] = None, lapse: bool = False) -> "GBuffer":
         """1-spp exact trace of a rectangle that keeps its geometry buffer (grt_gbuffer_trace):
         shade it again under any scene with the same shape key without integrating.  With
         `adaptive`, one `shade_section` with the scene as its own tracer follows, so the
-        buffer also holds the sub-rays of the pixels this scene's adaptive frame selects."""
+        buffer also holds the sub-rays of the pixels this scene's adaptive frame selects.
+        With `lapse`, the trace also records each layer's light-travel time
+        (grt_gbuffer_trace_lapse): the same arrays byte for byte, and `GBuffer.lapse()`."""
         rows = self.rows - row0 if rows is None else rows
         cols = self.cols - col0 if cols is None else cols
         h = C.c_void_p()
         st = L.Stats()
-        L.check(L.lib().grt_gbuffer_trace(self._s, device, row0, col0, rows, cols, C.byref(h), C.byref(st)),
-                "grt_gbuffer_trace")
+        name = "grt_gbuffer_trace_lapse" if lapse else "grt_gbuffer_trace"
+        L.check(getattr(L.lib(), name)(self._s, device, row0, col0, rows, cols, C.byref(h), C.byref(st)), name)
         gb = GBuffer(h, _stats_dict(st))
         if adaptive is not None:
             gb.shade_section(self, adaptive=adaptive, tracer=self)
@@ -686,22 +689,39 @@ class GBuffer:
         res.stats = {"kernel_ms": float(ms.value)}
         return res
 
+    def lapse(self):
+        """Each layer's light-travel time, downloaded (grt_gbuffer_lapse_download): n_layers
+        doubles <= 0, the chart's coordinate time of the hit minus the camera's; None for a
+        buffer that holds none."""
+        out = np.zeros(int(self.info.n_layers), np.float64)
+        rc = L.lib().grt_gbuffer_lapse_download(self._h, L.dptr(out))
+        if rc == -errno.ENODATA:
+            return None
+        L.check(rc, "grt_gbuffer_lapse_download")
+        return out
+
+    def set_lapse(self, lapse) -> None:
+        """Give the buffer a lapse, one finite double per layer (grt_gbuffer_lapse_upload)."""
+        a = np.ascontiguousarray(lapse, np.float64).reshape(-1)
+        L.check(L.lib().grt_gbuffer_lapse_upload(self._h, L.dptr(a), len(a)), "grt_gbuffer_lapse_upload")
+
     def shade_orbit(self, scene: "Scene", times, fields=("xyza", "xyza64", "class", "status", "stop", "steps"),
-                    device: Optional[int] = None) -> dict:
+                    device: Optional[int] = None, retarded: bool = False) -> dict:
         """The buffer under `scene`'s appearance at each of `times`, the disc's texture
         orbiting at the emitter's own rate (grt_gbuffer_shade_times; "fast light": one
         coordinate time per frame, no light-travel delay).  Frame k is `shade` of the buffer
         whose (u, v) went through gbuffer_orbit_uv at times[k], bit for bit.  Returns what
-        shade_sequence returns: the `fields` with a leading frame axis, plus "stats"."""
+        shade_sequence returns: the `fields` with a leading frame axis, plus "stats".
+        `retarded` (grt_gbuffer_shade_times_retarded; the buffer must hold a lapse): every
+        disc layer at its emission time times[k] + lapse, gbuffer_orbit_uv_retarded's rule."""
+        name = "grt_gbuffer_shade_times_retarded" if retarded else "grt_gbuffer_shade_times"
         info = self.info
         if device is not None and device != info.device:
-            raise L.GrtError(f"grt_gbuffer_shade_times failed (-22): the g-buffer is on device {info.device}, "
-                             f"not {device}")
+            raise L.GrtError(f"{name} failed (-22): the g-buffer is on device {info.device}, not {device}")
         t = np.ascontiguousarray(times, np.float64).reshape(-1)
         arrays, out = _frame_out_arrays(len(t), int(info.n_pixels), fields)
         ms = C.c_float()
-        L.check(L.lib().grt_gbuffer_shade_times(scene._s, self._h, len(t), L.dptr(t), C.byref(out), C.byref(ms)),
-                "grt_gbuffer_shade_times")
+        L.check(getattr(L.lib(), name)(scene._s, self._h, len(t), L.dptr(t), C.byref(out), C.byref(ms)), name)
         arrays["stats"] = {"kernel_ms": float(ms.value)}
         return arrays
 
@@ -815,10 +835,28 @@ class GBuffer:
         self.set_sub_arrays(sub, arrays)
 
     def save(self, path) -> None:
+        """Write the buffer's file, and beside it `<path>.lapse` when the buffer holds a lapse."""
         info = self.info
         out, c = _gbuffer_host_arrays(info)
         L.check(L.lib().grt_gbuffer_download(self._h, C.byref(c)), "grt_gbuffer_download")
         L.check(L.lib().grt_gbuffer_write_file(str(path).encode(), C.byref(info), C.byref(c)), "grt_gbuffer_write_file")
+        lapse = self.lapse()
+        if lapse is not None:
+            self.write_lapse_file(str(path) + ".lapse", info, lapse)
+
+    @staticmethod
+    def write_lapse_file(path, info: L.GBufferInfo, lapse) -> None:
+        a = np.ascontiguousarray(lapse, np.float64).reshape(-1)
+        L.check(L.lib().grt_gbuffer_lapse_write_file(str(path).encode(), C.byref(info), L.dptr(a), len(a)),
+                "grt_gbuffer_lapse_write_file")
+
+    @staticmethod
+    def read_lapse_file(path, info: L.GBufferInfo) -> np.ndarray:
+        """The lapse of a sidecar bound to the buffer `info`, on the host (no GPU needed)."""
+        out = np.zeros(int(info.n_layers), np.float64)
+        L.check(L.lib().grt_gbuffer_lapse_read_file(str(path).encode(), C.byref(info), L.dptr(out)),
+                "grt_gbuffer_lapse_read_file")
+        return out
 
     @staticmethod
     def read_file(path):
@@ -843,8 +881,12 @@ class GBuffer:
 
     @classmethod
     def load(cls, path, device: int = 0) -> "GBuffer":
+        """The buffer of a file, with the lapse of `<path>.lapse` when that file is there."""
         info, arrays = cls.read_file(path)
-        return cls.from_arrays(info, arrays, device)
+        gb = cls.from_arrays(info, arrays, device)
+        if os.path.exists(str(path) + ".lapse"):
+            gb.set_lapse(cls.read_lapse_file(str(path) + ".lapse", info))
+        return gb
 
     def close(self) -> None:
         if self._h:
@@ -1016,6 +1058,22 @@ def set_sequence_group(rays: int = 0) -> None:
     """Rays per launch group of Scene.render_sequence (grt_set_sequence_group; 0 = the
     default 2^22).  A group holds whole frames, at least one.  Scheduling only."""
     L.check(L.lib().grt_set_sequence_group(int(rays)), "grt_set_sequence_group")
+
+
+def gbuffer_orbit_uv_retarded(shape: L.GBufferShape, object, u, v, radius, lapse, time: float):
+    """gbuffer_orbit_uv with every disc layer at its emission time `time + lapse[k]`: the host
+    restatement of the rule GBuffer.shade_orbit(retarded=True) applies on the device
+    (grt_gbuffer_orbit_uv_retarded).  Returns new (u, v)."""
+    obj = np.ascontiguousarray(object, np.uint8).reshape(-1)
+    arr = [np.ascontiguousarray(x, np.float64).reshape(-1) for x in (u, v, radius, lapse)]
+    n = len(obj)
+    if any(len(x) != n for x in arr):
+        raise L.GrtError("grt_gbuffer_orbit_uv_retarded failed (-22): object, u, v, radius and lapse differ in length")
+    uo, vo = np.empty(n, np.float64), np.empty(n, np.float64)
+    L.check(L.lib().grt_gbuffer_orbit_uv_retarded(C.byref(shape), n, L.ptr(obj, C.c_uint8), L.dptr(arr[0]),
+                                                  L.dptr(arr[1]), L.dptr(arr[2]), L.dptr(arr[3]), float(time),
+                                                  L.dptr(uo), L.dptr(vo)), "grt_gbuffer_orbit_uv_retarded")
+    return uo, vo
 
 
 def load_camera_path(path) -> np.ndarray:

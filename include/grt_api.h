@@ -957,13 +957,13 @@ int grt_gbuffer_shade_section_sequence(grt_scene* appearance, uint32_t n, grt_gb
  * applies to the layers of GRT_OBJ_DISC objects with r = the layer's recorded radius; sphere
  * layers and the celestial sphere are static.  r_s and a are the appearance scene's (the
  * shape key makes them the traced ones).
- * "Fast light": all layers of a frame are shaded at the same coordinate time t.  The buffer
- * does not record t along the ray, and light-travel delay is ignored.
+ * "Fast light": all layers of a frame are shaded at the same coordinate time t, and light-travel
+ * delay is ignored ("Retarded time" below adds it for buffers traced with their lapse).
  * Host and device state the rule with the same operations in the same order, without
  * contraction, over the same glibc-exact pow and sincos: they agree bit for bit for
  * |Omega t| < 105414350 (the range of the exact sincos); beyond it the device uses the
  * fallback the render uses, within 1 ulp.
- * Not covered: light-travel delay, VolumetricDisc scenes (refused as everywhere), the fused
+ * Not covered: VolumetricDisc scenes (refused as everywhere), the fused
  * arithmetic, stacked adaptive frames over many times (loop grt_gbuffer_shade_section_at),
  * times combined with camera sequences, the multi-GPU frame, user-given rotation laws. */
 /* d(phi)/dt of the shade pass's disc emitter at radius r; +0.0 for the flat charts.
@@ -996,6 +996,56 @@ int grt_gbuffer_shade_section_at(grt_scene* appearance, grt_gbuffer* gb, const g
                                  uint8_t* class_out, uint8_t* status_out, uint64_t* n_supersampled,
                                  grt_subsample_failures* failures, grt_gbuffer_section_report* report,
                                  double time);
+
+/* Retarded time: each layer's light-travel time, and the orbital motion shaded with it.
+ *
+ * The integrator carries the chart's coordinate time as y[0].  A lapse trace keeps, per
+ * layer, lapse = (y[0] lerped over the hit's window by the chord parameter) - (the camera's
+ * y[0]): the coordinate time the light of that layer took to the camera, negated, since
+ * the traced momenta are past-directed -- every lapse is <= 0.  With it the orbital motion
+ * is shaded at the emission time: a disc layer is looked up at time + lapse instead of time
+ * (orbit_uv(omega, time + lapse[k], u, v): one add, then the rule above), so the far side
+ * of the disc and the higher-order images show the matter where it was when the light left.
+ * The lapse is an optional part of a buffer, beside its twelve arrays: grt_gbuffer_arrays,
+ * the .grtg format and the ABI version are as they were.  The time is the chart's own:
+ * Kerr-Schild's t and Boyer-Lindquist's t differ by a function of r, so each chart's movie
+ * is consistent in its own slicing and the two differ by a radius-dependent phase at time 0,
+ * as their phi already do.
+ * Not covered: lapses for the sub-sample set (grt_gbuffer_shade_section_at stays fast-light),
+ * camera sequences, the multi-GPU buffer, the fused arithmetic, VolumetricDisc scenes, and a
+ * time along the ray for the celestial sphere, which is static. */
+/* grt_gbuffer_trace through the kernels that record hit times: the same info and twelve
+ * arrays, byte for byte, the same pool-growth retries, always the exact kernels, -ENOTSUP
+ * for VolumetricDisc scenes; the buffer holds its lapse (n_layers doubles). */
+int grt_gbuffer_trace_lapse(grt_scene* scene, int device, uint32_t row0, uint32_t col0, uint32_t rows,
+                            uint32_t cols, grt_gbuffer** out, grt_stats* stats);
+/* The buffer's lapse to out[n_layers].  -ENODATA: the buffer holds none. */
+int grt_gbuffer_lapse_download(const grt_gbuffer* gb, double* out);
+/* Give the buffer a lapse (it replaces a held one).  -EINVAL: n_layers is not the buffer's,
+ * or an entry is not finite; the buffer is unchanged then. */
+int grt_gbuffer_lapse_upload(grt_gbuffer* gb, const double* lapse, uint64_t n_layers);
+/* The lapse's sidecar file, by convention <buffer file>.lapse: an 8-byte magic, the u32
+ * version and the u32 size of the info block, the buffer's grt_gbuffer_info (device zeroed;
+ * a reader refuses a sidecar whose copy differs from `info`), a u64 n_layers, the doubles.
+ * read: lapse NULL checks the file only; else lapse[info->n_layers].  -EINVAL: null
+ * argument, a count other than info->n_layers, a non-finite entry, a truncated file or one
+ * whose length disagrees with its sizes; -EIO: the file cannot be opened, read or written. */
+#define GRT_GBUFFER_LAPSE_FILE_VERSION 1
+int grt_gbuffer_lapse_write_file(const char* path, const grt_gbuffer_info* info, const double* lapse,
+                                 uint64_t n_layers);
+int grt_gbuffer_lapse_read_file(const char* path, const grt_gbuffer_info* info, double* lapse);
+/* grt_gbuffer_orbit_uv with each disc layer at time + lapse[k].  -EINVAL as
+ * grt_gbuffer_orbit_uv, and for a null or non-finite lapse (nothing is written then).
+ * u_out / v_out may alias u / v. */
+int grt_gbuffer_orbit_uv_retarded(const grt_gbuffer_shape* shape, uint64_t n_layers, const uint8_t* object,
+                                  const double* u, const double* v, const double* radius, const double* lapse,
+                                  double time, double* u_out, double* v_out);
+/* grt_gbuffer_shade_times with the retarded rule: arguments, launch groups and refusals are
+ * its own, plus -ENODATA for a buffer without a lapse.  Frame k equals grt_gbuffer_shade of
+ * the buffer whose disc layers' (u, v) went through grt_gbuffer_orbit_uv_retarded at
+ * times[k], bit for bit, in the range grt_gbuffer_shade_times promises it. */
+int grt_gbuffer_shade_times_retarded(grt_scene* appearance, const grt_gbuffer* gb, uint32_t n_times,
+                                     const double* times, const grt_frame_out* out, float* kernel_ms);
 
 /* The device hit pool that keeps the window candidates past a ray's GRT_MAX_HITS slots
  * (no reference counterpart: the reference's per-ray Vec grows, scene.rs:139-152).
