@@ -770,8 +770,10 @@ int enqueue_trace(grt_scene* s, DeviceCopy& dc, const grt::WorkList& wl_in, cons
   if (rc) return rc;
   if (tl.cap) HIP_TRY(hipMemsetAsync(dc.d_tail_ctl, 0, 16 * sizeof(unsigned long long), stream));
   // grt_set_arithmetic(1): the light charts' kernels built with FMA contraction
-  // (geodesic_fused.hip); Kerr-Schild always runs the exact ones
-  const bool fused = k.arith == 1 && !exact && s->desc.geometry != GRT_GEOM_KERR;
+  // (geodesic_fused.hip); Kerr-Schild always runs the exact ones, and so does a scene with a
+  // VolumetricDisc (contraction alone moves robust pixels of the stock KerrBL gas past 1e-4:
+  // tests/test_fused.py)
+  const bool fused = k.arith == 1 && !exact && s->desc.geometry != GRT_GEOM_KERR && !dc.vol;
   const auto launch = fused ? grt::fused::launch_trace
                             : (s->desc.geometry == GRT_GEOM_KERR_BL ? grt::kerr_bl::launch_trace : grt::launch_trace);
   // the exact KerrBL kernels are a unit of their own (geodesic_kerr_bl.hip)
@@ -1140,6 +1142,140 @@ int grt_debug_rkf_check(grt_scene* s, int device, uint64_t n, const double* stat
   HIP_TRY(hipMemcpy(out_short, b_s.p, n * 72, hipMemcpyDeviceToHost));
   HIP_TRY(hipMemcpy(out_full, b_f.p, n * 72, hipMemcpyDeviceToHost));
   HIP_TRY(hipMemcpy(guard, b_g.p, n, hipMemcpyDeviceToHost));
+  return 0;
+}
+
+// object `obj` of the scene is a VolumetricDisc (the vdisc checks' argument test; no device needed)
+static bool is_vdisc(const grt_scene* s, int64_t obj) {
+  return obj >= 0 && obj < (int64_t)s->desc.n_objects && s->desc.objects[obj].kind == GRT_OBJ_VOLUMETRIC_DISC;
+}
+
+// Test hook (not in grt_api.h): the VolumetricDisc device functions of volumetric.h for object
+// `obj` on n host inputs of 6 doubles each (vdisc_points_kernel; fn and the layout of in[6 n],
+// out[8 n] and flag[n]: kernels.h VdiscCheckFn and the kernel's comment).  n == 0 does nothing.
+int grt_debug_vdisc_points(grt_scene* s, int device, int obj, int fn, uint64_t n, const double* in, double* out,
+                           uint8_t* flag) {
+  if (!s) return fail(-EINVAL, "vdisc points: null scene");
+  if (fn < 0 || fn >= grt::VDISC_FN_COUNT) return fail(-EINVAL, "vdisc points: fn 0..4");
+  if (!is_vdisc(s, obj)) return fail(-EINVAL, "vdisc points: the object is not a VolumetricDisc of the scene");
+  if (n == 0) return 0;
+  if (!in || !out || !flag || n > (1ull << 24)) return fail(-EINVAL, "vdisc points: null buffer or n > 2^24");
+  DeviceCopy* dc;
+  int rc = ensure_device(s, device, &dc);
+  if (rc) return rc;
+  std::lock_guard<std::mutex> lk(dc->mu);
+  HIP_TRY(hipSetDevice(device));
+  DevBuf b_in, b_out, b_f;
+  if ((rc = b_in.alloc(n * 48)) || (rc = b_out.alloc(n * 64)) || (rc = b_f.alloc(n))) return rc;
+  HIP_TRY(hipMemcpy(b_in.p, in, n * 48, hipMemcpyHostToDevice));
+  HIP_TRY(grt::launch_vdisc_points(dc->d_scene, (uint32_t)obj, fn, n, (const double*)b_in.p, (double*)b_out.p,
+                                   (uint8_t*)b_f.p, nullptr));
+  HIP_TRY(hipDeviceSynchronize());
+  HIP_TRY(hipMemcpy(out, b_out.p, n * 64, hipMemcpyDeviceToHost));
+  HIP_TRY(hipMemcpy(flag, b_f.p, n, hipMemcpyDeviceToHost));
+  return 0;
+}
+
+// Test hook (not in grt_api.h): the production march_kernel over n host jobs.  Job i is a
+// candidate of object obj[i] at ro[3 i ..] with the chord direction dir[3 i ..] of a ray whose
+// frequency data is freq[3 i ..] = (observer energy, p_t, p_phi).  The workspace describes
+// exactly these jobs: ray i holds job i as its slot-0 candidate (rec, rec_dir, rc, jobs), or,
+// with as_pool, as record i of a HitPool (a JOB_POOL job); march[0] = n.  `blocks` blocks;
+// arith 0 runs the exact kernel (grt::march_kernel, KerrBL: grt::kerr_bl's), 1 the fused one
+// (grt::fused::march_kernel; refused for Kerr-Schild, as enqueue_trace never runs it there).
+// col[4 n]: the colour per job; counters[4]: march jobs, samples, noise samples, emitting
+// samples (grt_stats' march_* fields).  n == 0 launches nothing and zeroes the counters.
+int grt_debug_vdisc_march(grt_scene* s, int device, uint64_t n, const uint32_t* obj, const double* ro,
+                          const double* dir, const double* freq, int blocks, int arith, int as_pool, double* col,
+                          uint64_t* counters) {
+  if (!s) return fail(-EINVAL, "vdisc march: null scene");
+  if (arith != 0 && arith != 1) return fail(-EINVAL, "vdisc march: arith 0 (exact) or 1 (fused)");
+  if (arith == 1 && s->desc.geometry == GRT_GEOM_KERR)
+    return fail(-EINVAL, "vdisc march: Kerr-Schild has no fused kernels");
+  if (blocks < 1 || blocks > 4096) return fail(-EINVAL, "vdisc march: 1 <= blocks <= 4096");
+  if (n == 0) {
+    if (counters) std::fill(counters, counters + 4, 0ull);
+    return 0;
+  }
+  if (!obj || !ro || !dir || !freq || !col || !counters || n > (1ull << 16))
+    return fail(-EINVAL, "vdisc march: null buffer or n > 2^16");
+  for (uint64_t i = 0; i < n; ++i)
+    if (!is_vdisc(s, obj[i])) return fail(-EINVAL, "vdisc march: a job's object is not a VolumetricDisc of the scene");
+  DeviceCopy* dc;
+  int rc = ensure_device(s, device, &dc);
+  if (rc) return rc;
+  std::lock_guard<std::mutex> lk(dc->mu);
+  HIP_TRY(hipSetDevice(device));
+  const uint64_t MN = (uint64_t)GRT_WS_SLOTS * n;
+  constexpr size_t MARCH_WORDS = 8 + GRT_MAX_OBJECTS;
+  std::vector<grt::CandRec> rec(n);
+  std::vector<double> rec_dir(3 * MN, 0.0), rcv(6 * n, 0.0), p_pt(3 * n), p_dir(3 * n);
+  std::vector<uint64_t> jobs(n);
+  std::vector<uint8_t> p_obj(n);
+  for (uint64_t i = 0; i < n; ++i) {
+    std::memset(&rec[i], 0, sizeof(grt::CandRec));
+    rec[i].obj = obj[i];
+    p_obj[i] = (uint8_t)obj[i];
+    for (int k = 0; k < 3; ++k) {
+      rec[i].pt[k] = p_pt[k * n + i] = ro[3 * i + k];
+      rec_dir[k * MN + i] = p_dir[k * n + i] = dir[3 * i + k];
+    }
+    rcv[i] = freq[3 * i];
+    rcv[4 * n + i] = freq[3 * i + 1];
+    rcv[5 * n + i] = freq[3 * i + 2];
+    jobs[i] = as_pool ? (grt::JOB_POOL | (i << 31) | i) : (i << 8);
+  }
+  DevBuf b_rec, b_dir, b_vcol, b_rc, b_jobs, b_march, b_pool, b_pobj, b_ppt, b_pdir, b_pvcol;
+  if ((rc = b_rec.alloc(n * sizeof(grt::CandRec))) || (rc = b_dir.alloc(3 * MN * 8)) || (rc = b_vcol.alloc(4 * MN * 8)) ||
+      (rc = b_rc.alloc(6 * n * 8)) || (rc = b_jobs.alloc(n * 8)) || (rc = b_march.alloc(MARCH_WORDS * 8)) ||
+      (rc = b_pool.alloc(sizeof(grt::HitPool))) || (rc = b_pobj.alloc(n)) || (rc = b_ppt.alloc(3 * n * 8)) ||
+      (rc = b_pdir.alloc(3 * n * 8)) || (rc = b_pvcol.alloc(4 * n * 8)))
+    return rc;
+  unsigned long long march[MARCH_WORDS] = {};
+  march[0] = n;
+  grt::HitPool hp;
+  std::memset(&hp, 0, sizeof(hp));
+  hp.cap = n;
+  hp.obj = (uint8_t*)b_pobj.p;
+  hp.pt = (double*)b_ppt.p;
+  hp.dir = (double*)b_pdir.p;
+  hp.vcol = (double*)b_pvcol.p;
+  HIP_TRY(hipMemcpy(b_rec.p, rec.data(), n * sizeof(grt::CandRec), hipMemcpyHostToDevice));
+  HIP_TRY(hipMemcpy(b_dir.p, rec_dir.data(), 3 * MN * 8, hipMemcpyHostToDevice));
+  HIP_TRY(hipMemset(b_vcol.p, 0xff, 4 * MN * 8));  // NaN: a job the kernel did not colour shows
+  HIP_TRY(hipMemset(b_pvcol.p, 0xff, 4 * n * 8));
+  HIP_TRY(hipMemcpy(b_rc.p, rcv.data(), 6 * n * 8, hipMemcpyHostToDevice));
+  HIP_TRY(hipMemcpy(b_jobs.p, jobs.data(), n * 8, hipMemcpyHostToDevice));
+  HIP_TRY(hipMemcpy(b_march.p, march, sizeof(march), hipMemcpyHostToDevice));
+  HIP_TRY(hipMemcpy(b_pobj.p, p_obj.data(), n, hipMemcpyHostToDevice));
+  HIP_TRY(hipMemcpy(b_ppt.p, p_pt.data(), 3 * n * 8, hipMemcpyHostToDevice));
+  HIP_TRY(hipMemcpy(b_pdir.p, p_dir.data(), 3 * n * 8, hipMemcpyHostToDevice));
+  HIP_TRY(hipMemcpy(b_pool.p, &hp, sizeof(hp), hipMemcpyHostToDevice));
+  grt::Workspace ws;
+  std::memset(&ws, 0, sizeof(ws));
+  ws.n = n;
+  ws.rc = (double*)b_rc.p;
+  ws.rec = (grt::CandRec*)b_rec.p;
+  ws.rec_dir = (double*)b_dir.p;
+  ws.vcol = (double*)b_vcol.p;
+  ws.jobs = (uint64_t*)b_jobs.p;
+  ws.march = (unsigned long long*)b_march.p;
+  ws.pool = (const grt::HitPool*)b_pool.p;
+  const int g = s->desc.geometry;
+  const auto launch = arith == 1 ? grt::fused::launch_march
+                                 : (g == GRT_GEOM_KERR_BL ? grt::kerr_bl::launch_march : grt::launch_march);
+  HIP_TRY(launch(g, dc->d_scene, ws, blocks, nullptr));
+  HIP_TRY(hipDeviceSynchronize());
+  const uint64_t stride = as_pool ? n : MN;
+  std::vector<double> vcol(4 * stride);
+  HIP_TRY(hipMemcpy(vcol.data(), as_pool ? b_pvcol.p : b_vcol.p, 4 * stride * 8, hipMemcpyDeviceToHost));
+  HIP_TRY(hipMemcpy(march, b_march.p, sizeof(march), hipMemcpyDeviceToHost));
+  for (uint64_t i = 0; i < n; ++i)
+    for (int q = 0; q < 4; ++q) col[4 * i + q] = vcol[q * stride + i];
+  counters[0] = march[3];
+  counters[1] = march[2];
+  counters[2] = march[4];
+  counters[3] = march[5];
   return 0;
 }
 

@@ -1868,6 +1868,64 @@ hipError_t launch_rkf_check(const DevScene* d_scene, const double* d_states, con
   return hipGetLastError();
 }
 
+// Device check of the VolumetricDisc arithmetic (tests/test_gpu_volumetric_checks.py): one
+// lane per input, object `obj` of the scene, the production functions of volumetric.h
+// unchanged, the permutation tables and gradient rows staged as march_kernel stages them.
+// Input i is in[6 i ..], its results out[8 i ..] and flag[i]; per request (VdiscCheckFn):
+//   PERLIN   (x, y, z)      out[0] = perlin3
+//   DENSITY  p              out[0] = density, out[1..4] = PlaneAngle x, y, sp, cp, out[5] = phi
+//                           (atan2 of the returned y, x: vdisc_density's own line), flag = noise
+//   CHORD    from, to       flag = hit, out[0] = t, out[1..3] = the point
+//   EXIT     ro, rd         flag = found, out[0] = the distance
+//   NO_MORE  p, rd          flag = vdisc_no_more_density
+__global__ void __launch_bounds__(256) vdisc_points_kernel(const DevScene* __restrict__ Sp, uint32_t obj, int fn,
+                                                           uint64_t n, const double* __restrict__ in,
+                                                           double* __restrict__ out, uint8_t* __restrict__ flag) {
+  const DevScene& S = *Sp;
+  __shared__ uint8_t lds_perm[GRT_MAX_OBJECTS * 256];
+  __shared__ double lds_grad[16 * 4];
+  if (threadIdx.x < 64) lds_grad[threadIdx.x] = (threadIdx.x & 3u) == 3u ? 0.0 : grad_coef(threadIdx.x >> 2, threadIdx.x & 3u);
+  for (unsigned i = threadIdx.x; i < GRT_MAX_OBJECTS * 256u; i += blockDim.x) lds_perm[i] = S.perm[i >> 8][i & 255u];
+  glibc::tables_to_lds();  // whole block, before the early return; includes the block barrier
+  const uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  const DevObject& o = S.obj[obj];
+  const uint8_t* P = lds_perm + o.perm_slot * 256u;
+  const double* q = in + 6 * i;
+  const V3 a{q[0], q[1], q[2]}, b{q[3], q[4], q[5]};
+  double r[8] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
+  bool f = false;
+  switch (fn) {
+    case VDISC_FN_PERLIN: r[0] = perlin3(P, lds_grad, a.x, a.y, a.z); break;
+    case VDISC_FN_DENSITY: {
+      PlaneAngle pa{0.0, 0.0, 0.0, 0.0};
+      r[0] = vdisc_density(o, P, lds_grad, a, &pa, &f);
+      if (f) {
+        r[1] = pa.x;
+        r[2] = pa.y;
+        r[3] = pa.sp;
+        r[4] = pa.cp;
+        r[5] = atan2(pa.y, pa.x);
+      }
+      break;
+    }
+    case VDISC_FN_CHORD: f = vdisc_chord(o, q, q + 3, &r[0], &r[1]); break;
+    case VDISC_FN_EXIT: f = vdisc_exit_distance(o, a, b, &r[0]); break;
+    case VDISC_FN_NO_MORE: f = vdisc_no_more_density(o, a, b); break;
+    default: break;
+  }
+#pragma unroll
+  for (int k = 0; k < 8; ++k) out[8 * i + k] = r[k];
+  flag[i] = f ? 1 : 0;
+}
+
+hipError_t launch_vdisc_points(const DevScene* d_scene, uint32_t obj, int fn, uint64_t n, const double* d_in,
+                               double* d_out, uint8_t* d_flag, hipStream_t stream) {
+  hipLaunchKernelGGL(vdisc_points_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, stream, d_scene, obj, fn, n,
+                     d_in, d_out, d_flag);
+  return hipGetLastError();
+}
+
 #if GRT_PATH_COUNT
 // this unit's counters plus the KerrBL unit's
 hipError_t path_read(unsigned long long* out, bool reset) {
@@ -2482,6 +2540,18 @@ hipError_t launch_trace(int geometry, const DevScene* d_scene, const WorkList& w
   });
 #endif
 }
+
+#if GRT_MAIN_TU || GRT_FUSED || GRT_KERR_BL_TU
+// Test hook (grt_debug_vdisc_march): this unit's march_kernel alone, as launch_g launches it.
+hipError_t launch_march(int geometry, const DevScene* d_scene, const Workspace& ws, int blocks, hipStream_t stream) {
+  if (blocks <= 0 || !ws.rec || !ws.rec_dir || !ws.vcol || !ws.jobs || !ws.march || !ws.rc || !ws.pool)
+    return hipErrorInvalidValue;
+  return with_chart<TRACE_CHARTS>(geometry, [&](auto g) {
+    hipLaunchKernelGGL((march_kernel<decltype(g)::value>), dim3(blocks), dim3(256), 0, stream, d_scene, ws);
+    return hipGetLastError();
+  });
+}
+#endif
 
 #if GRT_FUSED || GRT_KERR_BL_TU || GRT_SEQ || GRT_LAPSE
 }  // namespace fused / kerr_bl / seq / lapse / lapse_kerr_bl

@@ -79,6 +79,29 @@ hipError_t launch_rhs_check(int geometry, const DevScene* d_scene, const double*
                             uint64_t n, double* d_out, uint8_t* d_pred, hipStream_t stream);
 hipError_t launch_rkf_check(const DevScene* d_scene, const double* d_states, const double* d_h, uint64_t n,
                             double* d_short, double* d_full, uint8_t* d_guard, hipStream_t stream);
+// test hook: the VolumetricDisc device functions (volumetric.h) of object `obj` on n inputs
+// of 6 doubles each, 8 doubles and a flag byte out per input (vdisc_points_kernel says which)
+enum VdiscCheckFn {
+  VDISC_FN_PERLIN = 0,   // perlin3 with the object's permutation table
+  VDISC_FN_DENSITY = 1,  // vdisc_density
+  VDISC_FN_CHORD = 2,    // vdisc_chord
+  VDISC_FN_EXIT = 3,     // vdisc_exit_distance
+  VDISC_FN_NO_MORE = 4,  // vdisc_no_more_density
+  VDISC_FN_COUNT = 5,
+};
+hipError_t launch_vdisc_points(const DevScene* d_scene, uint32_t obj, int fn, uint64_t n, const double* d_in,
+                               double* d_out, uint8_t* d_flag, hipStream_t stream);
+// test hook: march_kernel<geometry> alone, `blocks` blocks of 256 threads, over the jobs the
+// caller filed in `ws` (jobs, march[0] = their count, the march cursors zeroed): the exact
+// unit's (every chart but KerrBL), the exact KerrBL unit's and the fused unit's (every chart
+// but Kerr-Schild); hipErrorInvalidValue for a chart the unit does not build
+hipError_t launch_march(int geometry, const DevScene* d_scene, const Workspace& ws, int blocks, hipStream_t stream);
+namespace kerr_bl {
+hipError_t launch_march(int geometry, const DevScene* d_scene, const Workspace& ws, int blocks, hipStream_t stream);
+}
+namespace fused {
+hipError_t launch_march(int geometry, const DevScene* d_scene, const Workspace& ws, int blocks, hipStream_t stream);
+}
 #if GRT_PATH_COUNT
 hipError_t path_read(unsigned long long* out, bool reset);  // 2 * 14 words
 #endif

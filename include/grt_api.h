@@ -1203,7 +1203,10 @@ int grt_xyz_to_srgb8_device(int device, const double* xyza, size_t n, int32_t to
  * algorithm and operation order, one rounding per fused pair -- which is faster (C2 -17%,
  * C3 -13%) and keeps every robust pixel within the north-star 1e-4 relative per channel
  * (tests/test_fused.py), but no longer bit-identical; Kerr-Schild always runs exact (its
- * finite-difference metric turns the changed roundings into other step sequences).
+ * finite-difference metric turns the changed roundings into other step sequences), and so
+ * does every scene with a GRT_OBJ_VOLUMETRIC_DISC: the gas's noise turns the last bits of a
+ * window's chord into colour differences above 1e-4 on pixels that no libm probe moves
+ * (DESIGN.md section 19), so such a frame is the exact frame, bit for bit, in either mode.
  * It applies to frame traces (grt_render_*, grt_supersample_shard*, grt_render_frame_multi);
  * trajectories (grt_trace_*), monitors, the work-order probe and camera sequences
  * (grt_render_sequence) always run exact.

@@ -144,7 +144,8 @@ static inline double quad_form(const double* v, const Mat4& M, const double* w) 
 // ------------------------------------------------------ chart conversions ----
 // Sensitivity probes (tests only).  Bit mask: 1 = controller pow() one ulp up,
 // 2 = one ulp down, 4 = the RHS's sin() one ulp up and cos() one ulp down, 8 / 16 =
-// shading angles one ulp up / down (see shade_angle).  Used to
+// shading angles one ulp up / down (see shade_angle), 32 / 64 = the VolumetricDisc's two
+// in-plane angles (compute_density and get_uv) one ulp up / down (see vdisc_angle).  Used to
 // measure how strongly a last-ulp libm difference propagates on a scene; a pixel that
 // moves under any probe is "libm-sensitive" (tests/test_gpu_parity.py).
 static int g_libm_probe = 0;
@@ -176,6 +177,14 @@ static inline void rhs_sincos(double x, double* s, double* c) {
 static inline double shade_angle(double v) {
   if (g_libm_probe & 8) return std::nextafter(v, INFINITY);
   if (g_libm_probe & 16) return std::nextafter(v, -INFINITY);
+  return v;
+}
+
+// probe bits 32 / 64: the VolumetricDisc's in-plane angle (atan2 in compute_density and in
+// get_uv, which feeds the noise coordinates and the texture coordinates) one ulp up / down
+static inline double vdisc_angle(double v) {
+  if (g_libm_probe & 32) return std::nextafter(v, INFINITY);
+  if (g_libm_probe & 64) return std::nextafter(v, -INFINITY);
   return v;
 }
 
@@ -1296,7 +1305,12 @@ struct VDisc {  // volumetric_disc.rs:21-95
     }
     return t;
   }
-  double compute_density(const Vec3& p) const {  // :97-138
+  // phi_in: the in-plane angle given by the caller in place of atan2 (oracle_vdisc_density_phi:
+  // the one operation of the density whose bits depend on the platform's libm)
+  // plane_out (x_local, y_local) and *noise_out = whether the noise was evaluated (the point passed both
+  // early returns): oracle_vdisc_plane_n, for the device check of the same three values
+  double compute_density(const Vec3& p, const double* phi_in = nullptr, double* plane_out = nullptr,
+                         bool* noise_out = nullptr) const {  // :97-138
     double h = std::fabs(dot3(p, axis));
     double r = norm3(cross3(p, axis));
     double rin = o->inner_radius, rout = o->outer_radius;
@@ -1311,7 +1325,9 @@ struct VDisc {  // volumetric_disc.rs:21-95
     boundary_falloff *= std::exp(-1.0 / rust_max(d2 * d2, 0.0001));
     double x_local = dot3(p, e1);
     double y_local = dot3(p, e2);
-    double phi = std::atan2(y_local, x_local);
+    if (plane_out) { plane_out[0] = x_local; plane_out[1] = y_local; }
+    if (noise_out) *noise_out = true;
+    double phi = phi_in ? *phi_in : vdisc_angle(std::atan2(y_local, x_local));
     double sp, cp;
     g_sincos(phi, &sp, &cp);  // phi.cos() and phi.sin() in one block: one sincos
     double noise_phi_x = cp * o->noise_scale[1];
@@ -1324,7 +1340,7 @@ struct VDisc {  // volumetric_disc.rs:21-95
   void get_uv(const Vec3& p, double* u, double* v) const {  // :140-152
     double x = dot3(p, e1), y = dot3(p, e2);
     double rr = std::sqrt(x * x + y * y);
-    double phi = std::atan2(y, x);
+    double phi = vdisc_angle(std::atan2(y, x));
     double r = (rr - o->inner_radius) / (o->outer_radius - o->inner_radius);
     double sp, cp;
     g_sincos(phi, &sp, &cp);
@@ -2143,6 +2159,103 @@ int oracle_vdisc_raymarch(const grt_scene_desc* d, int object, const double* ro,
   out4[3] = c.alpha;
   if (samples) *samples = n;
   return e;
+}
+
+// compute_density with the in-plane angle phi given by the caller in place of std::atan2.
+double oracle_vdisc_density_phi(const grt_scene_desc* d, int object, const double* p, double phi) {
+  VDisc V;
+  V.init(&d->objects[object]);
+  return V.compute_density(Vec3{p[0], p[1], p[2]}, &phi);
+}
+// precompute_exit_distance alone: 1 and *out when a crossing lies within max_steps * step_size.
+int oracle_vdisc_exit_distance(const grt_scene_desc* d, int object, const double* ro, const double* rd, double* out) {
+  VDisc V;
+  V.init(&d->objects[object]);
+  double e = 0.0;
+  bool f = V.precompute_exit_distance(Vec3{ro[0], ro[1], ro[2]}, Vec3{rd[0], rd[1], rd[2]}, &e);
+  *out = f ? e : 0.0;
+  return f ? 1 : 0;
+}
+// Array forms: n inputs per call (xyz / p / ro / rd are n x 3, row-major).
+void oracle_perlin_n(uint32_t seed, uint64_t n, const double* xyz, double* out) {
+  uint8_t P[256];
+  noise09::permutation_table(seed, P);
+  for (uint64_t i = 0; i < n; ++i) out[i] = noise09::perlin_3d(P, xyz[3 * i], xyz[3 * i + 1], xyz[3 * i + 2]);
+}
+// phi == NULL: oracle_vdisc_density; else oracle_vdisc_density_phi with phi[i]
+void oracle_vdisc_density_n(const grt_scene_desc* d, int object, uint64_t n, const double* p, const double* phi,
+                            double* out) {
+  VDisc V;
+  V.init(&d->objects[object]);
+  for (uint64_t i = 0; i < n; ++i)
+    out[i] = V.compute_density(Vec3{p[3 * i], p[3 * i + 1], p[3 * i + 2]}, phi ? phi + i : nullptr);
+}
+// compute_density's in-plane coordinates xy[2 i ..] = (x_local, y_local) and noise[i] = whether the point
+// reached the noise (inside rin .. rout with a vertical falloff >= 0.001); xy is (0, 0) where it did not
+void oracle_vdisc_plane_n(const grt_scene_desc* d, int object, uint64_t n, const double* p, double* xy, uint8_t* noise) {
+  VDisc V;
+  V.init(&d->objects[object]);
+  for (uint64_t i = 0; i < n; ++i) {
+    bool f = false;
+    xy[2 * i] = xy[2 * i + 1] = 0.0;
+    V.compute_density(Vec3{p[3 * i], p[3 * i + 1], p[3 * i + 2]}, nullptr, xy + 2 * i, &f);
+    noise[i] = f ? 1 : 0;
+  }
+}
+// the density at p + k * step * rd for k = 0 .. steps (steps + 1 samples): nonzero[i] = any of them > 0
+void oracle_vdisc_density_along_n(const grt_scene_desc* d, int object, uint64_t n, const double* p, const double* rd,
+                                  double step, uint64_t steps, uint8_t* nonzero) {
+  VDisc V;
+  V.init(&d->objects[object]);
+  for (uint64_t i = 0; i < n; ++i) {
+    uint8_t any = 0;
+    for (uint64_t k = 0; k <= steps && !any; ++k) {
+      double t = (double)k * step;
+      Vec3 q{p[3 * i] + rd[3 * i] * t, p[3 * i + 1] + rd[3 * i + 1] * t, p[3 * i + 2] + rd[3 * i + 2] * t};
+      any = V.compute_density(q) > 0.0;
+    }
+    nonzero[i] = any;
+  }
+}
+void oracle_vdisc_exit_distance_n(const grt_scene_desc* d, int object, uint64_t n, const double* ro, const double* rd,
+                                  uint8_t* found, double* out) {
+  for (uint64_t i = 0; i < n; ++i) found[i] = (uint8_t)oracle_vdisc_exit_distance(d, object, ro + 3 * i, rd + 3 * i, out + i);
+}
+// a and b are n x 3 Cartesian points; hit[n], t[n], point[n x 3]
+void oracle_vdisc_intersects_n(const grt_scene_desc* d, int object, uint64_t n, const double* a, const double* b,
+                               uint8_t* hit, double* t, double* point) {
+  VDisc V;
+  V.init(&d->objects[object]);
+  for (uint64_t i = 0; i < n; ++i) {
+    Vec3 vp{0.0, 0.0, 0.0}, dir;
+    double ti = 0.0;
+    bool h = V.intersects(Vec3{a[3 * i], a[3 * i + 1], a[3 * i + 2]}, Vec3{b[3 * i], b[3 * i + 1], b[3 * i + 2]}, &ti, &vp, &dir);
+    hit[i] = h ? 1 : 0;
+    t[i] = h ? ti : 0.0;
+    point[3 * i] = h ? vp.x : 0.0;
+    point[3 * i + 1] = h ? vp.y : 0.0;
+    point[3 * i + 2] = h ? vp.z : 0.0;
+  }
+}
+// oracle_vdisc_raymarch over n jobs (one scene context): object[n], ro / rd / freq n x 3, err[n], out n x 4, samples[n]
+void oracle_vdisc_raymarch_n(const grt_scene_desc* d, uint64_t n, const uint32_t* object, const double* ro,
+                             const double* rd, const double* freq, int use_cached_exit, int32_t* err, double* out,
+                             uint64_t* samples) {
+  SceneCtx S;
+  init_ctx(S, d);
+  for (uint64_t i = 0; i < n; ++i) {
+    FrequencyData f{freq[3 * i], freq[3 * i + 1], freq[3 * i + 2]};
+    XYZA c{0.0, 0.0, 0.0, 0.0};
+    uint64_t ns = 0;
+    const uint32_t k = object[i];
+    err[i] = vdisc_raymarch(S.vd[k], S.obj_tex[k], *S.g, d->geometry, Vec3{ro[3 * i], ro[3 * i + 1], ro[3 * i + 2]},
+                            Vec3{rd[3 * i], rd[3 * i + 1], rd[3 * i + 2]}, f, use_cached_exit != 0, &c, &ns);
+    out[4 * i] = c.x;
+    out[4 * i + 1] = c.y;
+    out[4 * i + 2] = c.z;
+    out[4 * i + 3] = c.alpha;
+    samples[i] = ns;
+  }
 }
 
 // ---- output stage (color.rs:193-298), as Raytracer::render_section calls it for

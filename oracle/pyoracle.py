@@ -83,6 +83,17 @@ def lib():
         L.oracle_vdisc_density.restype = _d
         L.oracle_vdisc_density.argtypes = [vp, C.c_int, _pd]
         L.oracle_vdisc_raymarch.argtypes = [vp, C.c_int, _pd, _pd, _pd, C.c_int, _pd, _u64p]
+        L.oracle_vdisc_density_phi.restype = _d
+        L.oracle_vdisc_density_phi.argtypes = [vp, C.c_int, _pd, _d]
+        L.oracle_vdisc_exit_distance.argtypes = [vp, C.c_int, _pd, _pd, _pd]
+        L.oracle_perlin_n.argtypes = [C.c_uint32, C.c_uint64, _pd, _pd]
+        L.oracle_vdisc_density_n.argtypes = [vp, C.c_int, C.c_uint64, _pd, _pd, _pd]
+        L.oracle_vdisc_plane_n.argtypes = [vp, C.c_int, C.c_uint64, _pd, _pd, _u8p]
+        L.oracle_vdisc_density_along_n.argtypes = [vp, C.c_int, C.c_uint64, _pd, _pd, _d, C.c_uint64, _u8p]
+        L.oracle_vdisc_exit_distance_n.argtypes = [vp, C.c_int, C.c_uint64, _pd, _pd, _u8p, _pd]
+        L.oracle_vdisc_intersects_n.argtypes = [vp, C.c_int, C.c_uint64, _pd, _pd, _u8p, _pd, _pd]
+        L.oracle_vdisc_raymarch_n.argtypes = [vp, C.c_uint64, _u32p, _pd, _pd, _pd, C.c_int, C.POINTER(C.c_int32), _pd,
+                                              _u64p]
         _lib = L
     return _lib
 
@@ -296,6 +307,92 @@ def vdisc_raymarch(desc, obj: int, ro, rd, freq=(1.0, 1.0, 0.0), cached=True):
                                       _dp(np.asarray(rd, np.float64)), _dp(np.asarray(freq, np.float64)),
                                       1 if cached else 0, _dp(out), C.byref(n))
     return err, out, n.value
+
+
+def vdisc_density_phi(desc, obj: int, p, phi: float) -> float:
+    """compute_density with the in-plane angle given by the caller in place of atan2."""
+    return lib().oracle_vdisc_density_phi(_addr(desc), obj, _dp(np.asarray(p, np.float64)), phi)
+
+
+def vdisc_exit_distance(desc, obj: int, ro, rd):
+    """precompute_exit_distance alone: (found, distance)."""
+    out = C.c_double()
+    f = lib().oracle_vdisc_exit_distance(_addr(desc), obj, _dp(np.asarray(ro, np.float64)),
+                                         _dp(np.asarray(rd, np.float64)), C.byref(out))
+    return bool(f), out.value
+
+
+def _n3(a):
+    a = np.ascontiguousarray(a, np.float64).reshape(-1, 3)
+    return a, len(a)
+
+
+# array forms: n inputs per call
+def perlin_n(seed: int, xyz) -> np.ndarray:
+    x, n = _n3(xyz)
+    out = np.zeros(n)
+    lib().oracle_perlin_n(seed, n, _dp(x), _dp(out))
+    return out
+
+
+def vdisc_density_n(desc, obj: int, p, phi=None) -> np.ndarray:
+    """vdisc_density per row of p, or vdisc_density_phi with phi[i] when phi is given."""
+    x, n = _n3(p)
+    out = np.zeros(n)
+    ph = None if phi is None else np.ascontiguousarray(phi, np.float64)
+    assert ph is None or ph.shape == (n,)
+    lib().oracle_vdisc_density_n(_addr(desc), obj, n, _dp(x), _dp(ph) if ph is not None else None, _dp(out))
+    return out
+
+
+def vdisc_plane_n(desc, obj: int, p):
+    """compute_density's in-plane x_local, y_local per row and whether the row reached the noise."""
+    x, n = _n3(p)
+    xy, noise = np.zeros((n, 2)), np.zeros(n, np.uint8)
+    lib().oracle_vdisc_plane_n(_addr(desc), obj, n, _dp(x), _dp(xy), noise.ctypes.data_as(_u8p))
+    return xy[:, 0], xy[:, 1], noise.astype(bool)
+
+
+def vdisc_density_along_n(desc, obj: int, p, rd, step: float, steps: int) -> np.ndarray:
+    """Per row: whether the density is > 0 at any of p + k * step * rd, k = 0 .. steps."""
+    x, n = _n3(p)
+    d, m = _n3(rd)
+    assert n == m
+    out = np.zeros(n, np.uint8)
+    lib().oracle_vdisc_density_along_n(_addr(desc), obj, n, _dp(x), _dp(d), step, steps, out.ctypes.data_as(_u8p))
+    return out.astype(bool)
+
+
+def vdisc_exit_distance_n(desc, obj: int, ro, rd):
+    x, n = _n3(ro)
+    d, m = _n3(rd)
+    assert n == m
+    found, out = np.zeros(n, np.uint8), np.zeros(n)
+    lib().oracle_vdisc_exit_distance_n(_addr(desc), obj, n, _dp(x), _dp(d), found.ctypes.data_as(_u8p), _dp(out))
+    return found.astype(bool), out
+
+
+def vdisc_intersects_n(desc, obj: int, a, b):
+    """object_intersects of a VolumetricDisc per row (Cartesian points): hit, t, point (n, 3)."""
+    x, n = _n3(a)
+    y, m = _n3(b)
+    assert n == m
+    hit, t, pt = np.zeros(n, np.uint8), np.zeros(n), np.zeros((n, 3))
+    lib().oracle_vdisc_intersects_n(_addr(desc), obj, n, _dp(x), _dp(y), hit.ctypes.data_as(_u8p), _dp(t), _dp(pt))
+    return hit.astype(bool), t, pt
+
+
+def vdisc_raymarch_n(desc, obj, ro, rd, freq, cached=True):
+    """vdisc_raymarch per job: err (n,), colour (n, 4), samples (n,)."""
+    x, n = _n3(ro)
+    d, _ = _n3(rd)
+    f, _ = _n3(freq)
+    k = np.ascontiguousarray(obj, np.uint32)
+    assert len(d) == len(f) == len(k) == n
+    err, out, ns = np.zeros(n, np.int32), np.zeros((n, 4)), np.zeros(n, np.uint64)
+    lib().oracle_vdisc_raymarch_n(_addr(desc), n, k.ctypes.data_as(_u32p), _dp(x), _dp(d), _dp(f), 1 if cached else 0,
+                                  err.ctypes.data_as(C.POINTER(C.c_int32)), _dp(out), ns.ctypes.data_as(_u64p))
+    return err, out, ns
 
 
 # ---- geometry probes (the reference's unit tests, tests/test_reference_kats.py) ----
