@@ -1176,6 +1176,49 @@ int grt_debug_vdisc_points(grt_scene* s, int device, int obj, int fn, uint64_t n
   return 0;
 }
 
+// Test hook (not in grt_api.h): the surface path's device functions on n host rows of 8 doubles
+// each (surface_points_kernel; fn and the layout of in[8 n], out[8 n] and flag[n]: kernels.h
+// SurfaceCheckFn and the kernel's comment).  obj: the Disc of DISC_CHORD, the Sphere of
+// SPHERE_CHORD, the object whose table LUT_INDEX (a Kerr temperature table) and TEMPERATURE
+// read and whose texture TEXTURE samples; -1 for LUT_INDEX over the blackbody table, the
+// celestial TEXTURE, and every other request.  n == 0 does nothing.
+int grt_debug_surface_points(grt_scene* s, int device, int obj, int fn, uint64_t n, const double* in, double* out,
+                             uint8_t* flag) {
+  if (!s) return fail(-EINVAL, "surface points: null scene");
+  if (fn < 0 || fn >= grt::SURFACE_FN_COUNT) return fail(-EINVAL, "surface points: fn 0..7");
+  const grt_scene_desc& d = s->desc;
+  if (obj < -1 || obj >= (int64_t)d.n_objects) return fail(-EINVAL, "surface points: obj is -1 or an object of the scene");
+  const grt_object_desc* o = obj < 0 ? nullptr : &d.objects[obj];
+  const bool has_lut = o && o->temp_kind == GRT_TEMP_KERR_LUT && o->lut_n >= 2 && s->lut_r[obj].size() == o->lut_n;
+  bool ok = true;
+  switch (fn) {
+    case grt::SURFACE_FN_DISC_CHORD: ok = o && o->kind == GRT_OBJ_DISC; break;
+    case grt::SURFACE_FN_SPHERE_CHORD: ok = o && o->kind == GRT_OBJ_SPHERE; break;
+    case grt::SURFACE_FN_LUT_INDEX: ok = o ? has_lut : d.bb_n >= 2; break;
+    case grt::SURFACE_FN_TEMPERATURE: ok = o && o->kind != GRT_OBJ_SPHERE && (o->temp_kind == GRT_TEMP_CONSTANT || has_lut); break;
+    case grt::SURFACE_FN_BLACKBODY: ok = !o && d.bb_n >= 2; break;
+    case grt::SURFACE_FN_TEXTURE: break;  // every texture of a created scene is complete (validate_desc)
+    default: ok = !o; break;              // WINDOW_FAR, BLEND: no object
+  }
+  if (!ok) return fail(-EINVAL, "surface points: obj does not fit the request");
+  if (n == 0) return 0;
+  if (!in || !out || !flag || n > (1ull << 24)) return fail(-EINVAL, "surface points: null buffer or n > 2^24");
+  DeviceCopy* dc;
+  int rc = ensure_device(s, device, &dc);
+  if (rc) return rc;
+  std::lock_guard<std::mutex> lk(dc->mu);
+  HIP_TRY(hipSetDevice(device));
+  DevBuf b_in, b_out, b_f;
+  if ((rc = b_in.alloc(n * 64)) || (rc = b_out.alloc(n * 64)) || (rc = b_f.alloc(n))) return rc;
+  HIP_TRY(hipMemcpy(b_in.p, in, n * 64, hipMemcpyHostToDevice));
+  HIP_TRY(grt::launch_surface_points(d.geometry, dc->d_scene, obj, fn, n, (const double*)b_in.p, (double*)b_out.p,
+                                     (uint8_t*)b_f.p, nullptr));
+  HIP_TRY(hipDeviceSynchronize());
+  HIP_TRY(hipMemcpy(out, b_out.p, n * 64, hipMemcpyDeviceToHost));
+  HIP_TRY(hipMemcpy(flag, b_f.p, n, hipMemcpyDeviceToHost));
+  return 0;
+}
+
 // Test hook (not in grt_api.h): the production march_kernel over n host jobs.  Job i is a
 // candidate of object obj[i] at ro[3 i ..] with the chord direction dir[3 i ..] of a ray whose
 // frequency data is freq[3 i ..] = (observer energy, p_t, p_phi).  The workspace describes

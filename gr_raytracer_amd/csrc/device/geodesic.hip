@@ -1926,6 +1926,84 @@ hipError_t launch_vdisc_points(const DevScene* d_scene, uint32_t obj, int fn, ui
   return hipGetLastError();
 }
 
+// Device check of the surface path's pieces (tests/test_gpu_surface_checks.py): one lane per
+// input row, the production functions of this file and of appearance.h unchanged.  Row i is
+// in[8 i ..], its results out[8 i ..] and flag[i]; `obj` is an object of the scene, or -1 for
+// the celestial texture / the blackbody table.  Per request (SurfaceCheckFn):
+//   DISC_CHORD    from xyz, to xyz           flag = hit, out[0] = t, out[1..3] = the point
+//   SPHERE_CHORD  from xyz, to xyz (world)   flag = hit, out[0] = t, out[1..3] = the local point
+//   WINDOW_FAR    ya[1..3], yb[1..3]         flag = window_far<G, VOL>, VOL = the scene has a gas
+//   LUT_INDEX     x                          out[0] = lut_index over obj's lut_r (-1: bb_log_t)
+//   TEMPERATURE   radius                     out[0] = status, out[1] = the temperature
+//   BLACKBODY     temperature                out[0..3] = sample_blackbody, out[4] = its own
+//                                            log10(fmax(T, 10)) (texture.rs:150, OCML's log10)
+//   TEXTURE       u, v, redshift, T          out[0..3] = texture_color, out[4] = 1 where the
+//                                            beaming factor is glibc's (pow_fast took it, or the
+//                                            exponent is 0), 0 where rpow fell back to OCML
+//   BLEND         self xyza, other xyza      out[0..3] = blend(self, other)
+// Only WINDOW_FAR reads the chart G.
+template <int G>
+__global__ void __launch_bounds__(256) surface_points_kernel(const DevScene* __restrict__ Sp, int obj, int fn,
+                                                             uint64_t n, const double* __restrict__ in,
+                                                             double* __restrict__ out, uint8_t* __restrict__ flag) {
+  const DevScene& S = *Sp;
+  glibc::tables_to_lds();  // whole block, before the early return; includes the block barrier
+  const uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  const double* q = in + 8 * i;
+  const DevObject& o = S.obj[obj < 0 ? 0 : obj];
+  const DevTexture& tex = obj < 0 ? S.celestial : o.tex;
+  double r[8] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
+  bool f = false;
+  switch (fn) {
+    case SURFACE_FN_DISC_CHORD: f = disc_chord(o, q, q + 3, &r[0], &r[1]); break;
+    case SURFACE_FN_SPHERE_CHORD: f = sphere_chord(o, q, q + 3, &r[0], &r[1]); break;
+    case SURFACE_FN_WINDOW_FAR: {
+      const double ya[4] = {0.0, q[0], q[1], q[2]}, yb[4] = {0.0, q[3], q[4], q[5]};
+      f = S.has_vol ? window_far<G, true>(S, ya, yb) : window_far<G, false>(S, ya, yb);
+      break;
+    }
+    case SURFACE_FN_LUT_INDEX: {
+      const double* a = obj < 0 ? S.bb_log_t : o.lut_r;
+      const uint32_t m = obj < 0 ? S.bb_n : o.lut_n;
+      r[0] = (double)lut_index(a, m, a[0], a[m - 1], q[0]);
+      break;
+    }
+    case SURFACE_FN_TEMPERATURE: r[0] = (double)compute_temperature(o, q[0], &r[1]); break;
+    case SURFACE_FN_BLACKBODY: {
+      const XYZA c = sample_blackbody(S, q[0]);
+      r[0] = c.x, r[1] = c.y, r[2] = c.z, r[3] = c.a;
+      r[4] = log10(fmax(q[0], 10.0));
+      break;
+    }
+    case SURFACE_FN_TEXTURE: {
+      const XYZA c = texture_color(S, tex, q[0], q[1], q[2], q[3]);
+      r[0] = c.x, r[1] = c.y, r[2] = c.z, r[3] = c.a;
+      double p;
+      r[4] = (tex.beaming == 0.0 || glibc::pow_fast(q[2], tex.beaming, &p)) ? 1.0 : 0.0;
+      break;
+    }
+    case SURFACE_FN_BLEND: {
+      const XYZA c = blend(XYZA{q[0], q[1], q[2], q[3]}, XYZA{q[4], q[5], q[6], q[7]});
+      r[0] = c.x, r[1] = c.y, r[2] = c.z, r[3] = c.a;
+      break;
+    }
+    default: break;
+  }
+#pragma unroll
+  for (int k = 0; k < 8; ++k) out[8 * i + k] = r[k];
+  flag[i] = f ? 1 : 0;
+}
+
+hipError_t launch_surface_points(int geometry, const DevScene* d_scene, int obj, int fn, uint64_t n, const double* d_in,
+                                 double* d_out, uint8_t* d_flag, hipStream_t stream) {
+  return with_chart<DIAG_CHARTS>(geometry, [&](auto g) {
+    hipLaunchKernelGGL(surface_points_kernel<decltype(g)::value>, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, stream,
+                       d_scene, obj, fn, n, d_in, d_out, d_flag);
+    return hipGetLastError();
+  });
+}
+
 #if GRT_PATH_COUNT
 // this unit's counters plus the KerrBL unit's
 hipError_t path_read(unsigned long long* out, bool reset) {

@@ -91,6 +91,23 @@ enum VdiscCheckFn {
 };
 hipError_t launch_vdisc_points(const DevScene* d_scene, uint32_t obj, int fn, uint64_t n, const double* d_in,
                                double* d_out, uint8_t* d_flag, hipStream_t stream);
+// test hook: the surface path's pieces (geodesic.hip chord tests and window filter,
+// appearance.h lookups) on n rows of 8 doubles each, 8 doubles and a flag byte out per row
+// (surface_points_kernel says which); obj: an object of the scene, -1 where a request takes
+// the celestial texture or the blackbody table
+enum SurfaceCheckFn {
+  SURFACE_FN_DISC_CHORD = 0,    // disc_chord
+  SURFACE_FN_SPHERE_CHORD = 1,  // sphere_chord
+  SURFACE_FN_WINDOW_FAR = 2,    // window_far<G, VOL> of the scene's chart
+  SURFACE_FN_LUT_INDEX = 3,     // lut_index over the object's lut_r, or bb_log_t
+  SURFACE_FN_TEMPERATURE = 4,   // compute_temperature
+  SURFACE_FN_BLACKBODY = 5,     // sample_blackbody
+  SURFACE_FN_TEXTURE = 6,       // texture_color of the object's texture, or the celestial one
+  SURFACE_FN_BLEND = 7,         // blend
+  SURFACE_FN_COUNT = 8,
+};
+hipError_t launch_surface_points(int geometry, const DevScene* d_scene, int obj, int fn, uint64_t n, const double* d_in,
+                                 double* d_out, uint8_t* d_flag, hipStream_t stream);
 // test hook: march_kernel<geometry> alone, `blocks` blocks of 256 threads, over the jobs the
 // caller filed in `ws` (jobs, march[0] = their count, the march cursors zeroed): the exact
 // unit's (every chart but KerrBL), the exact KerrBL unit's and the fused unit's (every chart

@@ -1026,12 +1026,15 @@ struct TextureMap {
     };
     return add(add(add(mul(w00, c00), mul(w10, c10)), mul(w01, c01)), mul(w11, c11));
   }
-  XYZA sample_blackbody(double temperature) const {  // texture.rs:149-195
+  // log_t_in: log10(max(temperature, 10)) given by the caller in place of std::log10
+  // (oracle_blackbody_n, oracle_texture_color_n: the one operation of the lookup whose bits
+  // depend on the platform's libm)
+  XYZA sample_blackbody(double temperature, const double* log_t_in = nullptr) const {  // texture.rs:149-195
     uint32_t n = scene->bb_n;
     const double* lt = scene->bb_log_t;
     const double* c = scene->bb_xyz;
     XYZA first{c[0], c[1], c[2], 1.0}, last{c[3 * (n - 1)], c[3 * (n - 1) + 1], c[3 * (n - 1) + 2], 1.0};
-    double log_t = std::log10(std::fmax(temperature, 10.0));
+    double log_t = log_t_in ? *log_t_in : std::log10(std::fmax(temperature, 10.0));
     if (!std::isfinite(log_t)) return first;
     if (log_t <= lt[0]) return first;
     if (log_t >= lt[n - 1]) return last;
@@ -1048,7 +1051,7 @@ struct TextureMap {
     double t = (log_t - lt0) / (lt1 - lt0);
     return XYZA{c0[0] + t * (c1[0] - c0[0]), c0[1] + t * (c1[1] - c0[1]), c0[2] + t * (c1[2] - c0[2]), 1.0};
   }
-  XYZA color_at_uv(double u, double v, double redshift, double temperature) const {
+  XYZA color_at_uv(double u, double v, double redshift, double temperature, const double* log_t_in = nullptr) const {
     switch (d->kind) {
       case GRT_TEX_BITMAP:  // texture.rs:93-102
         return apply_beaming(bilinear(u, v), redshift, d->beaming_exponent);
@@ -1059,7 +1062,7 @@ struct TextureMap {
         return apply_beaming(XYZA{c[0], c[1], c[2], c[3]}, redshift, d->beaming_exponent);
       }
       default:  // GRT_TEX_BLACKBODY, texture.rs:198-210
-        return apply_beaming(sample_blackbody(temperature * redshift), redshift, d->beaming_exponent);
+        return apply_beaming(sample_blackbody(temperature * redshift, log_t_in), redshift, d->beaming_exponent);
     }
   }
 };
@@ -2128,6 +2131,67 @@ int oracle_object_intersects(const grt_scene_desc* d, int object, const double* 
     *t_out = in.t;
   }
   return hit ? 1 : 0;
+}
+
+// Array forms of the surface path's pieces (tests/surface_cases.py): n rows per call.
+// a and b are n x 3 Cartesian points; object is a Disc or a Sphere; hit[n], t[n], point[n x 3]
+// (the world point, as disc_intersects and sphere_intersects return it); 0 where no hit
+void oracle_object_intersects_n(const grt_scene_desc* d, int object, uint64_t n, const double* a, const double* b,
+                                uint8_t* hit, double* t, double* point) {
+  const grt_object_desc& o = d->objects[object];
+  for (uint64_t i = 0; i < n; ++i) {
+    Point pa{CS::Cartesian, 0.0, {0.0, a[3 * i], a[3 * i + 1], a[3 * i + 2]}};
+    Point pb{CS::Cartesian, 0.0, {0.0, b[3 * i], b[3 * i + 1], b[3 * i + 2]}};
+    Intersection in;
+    bool h = o.kind == GRT_OBJ_DISC ? disc_intersects(o, pa, pb, &in) : sphere_intersects(o, pa, pb, &in);
+    hit[i] = h ? 1 : 0;
+    t[i] = h ? in.t : 0.0;
+    for (int k = 0; k < 3; ++k) point[3 * i + k] = h ? in.point.v[k + 1] : 0.0;
+  }
+}
+// to_cartesian (point.rs:125-154) of n native-chart positions (r, theta, phi) -- (x, y, z) on the
+// Cartesian charts: xyz[n x 3]
+void oracle_to_cartesian_n(const grt_scene_desc* d, uint64_t n, const double* pos, double* xyz) {
+  SceneCtx S;
+  init_ctx(S, d);
+  for (uint64_t i = 0; i < n; ++i) {
+    const double p[4] = {0.0, pos[3 * i], pos[3 * i + 1], pos[3 * i + 2]};
+    Point c = to_cartesian(S.g->make_point(p));
+    for (int k = 0; k < 3; ++k) xyz[3 * i + k] = c.v[k + 1];
+  }
+}
+// compute_temperature of the object per radius: status[n] (grt_status), value[n] (0 where not OK)
+void oracle_compute_temperature_n(const grt_scene_desc* d, int object, uint64_t n, const double* radius,
+                                  int32_t* status, double* value) {
+  for (uint64_t i = 0; i < n; ++i) {
+    double v = 0.0;
+    Err e = compute_temperature(d->objects[object], radius[i], &v);
+    status[i] = e;
+    value[i] = e == OK ? v : 0.0;
+  }
+}
+// sample_blackbody per temperature, out[n x 4]; log_t == NULL: std::log10, else log_t[i] in its place
+void oracle_blackbody_n(const grt_scene_desc* d, uint64_t n, const double* temperature, const double* log_t,
+                        double* out) {
+  TextureMap tm{&d->celestial, d};
+  for (uint64_t i = 0; i < n; ++i) {
+    XYZA c = tm.sample_blackbody(temperature[i], log_t ? log_t + i : nullptr);
+    out[4 * i] = c.x; out[4 * i + 1] = c.y; out[4 * i + 2] = c.z; out[4 * i + 3] = c.alpha;
+  }
+}
+// color_at_uv per row uvzt[4 i ..] = (u, v, redshift, temperature), object -1 = celestial; log_t as
+// in oracle_blackbody_n (of temperature * redshift; read by a blackbody texture only)
+void oracle_texture_color_n(const grt_scene_desc* d, int object, uint64_t n, const double* uvzt, const double* log_t,
+                            double* out) {
+  TextureMap tm{object < 0 ? &d->celestial : &d->objects[object].texture, d};
+  for (uint64_t i = 0; i < n; ++i) {
+    const double* q = uvzt + 4 * i;
+    XYZA c = tm.color_at_uv(q[0], q[1], q[2], q[3], log_t ? log_t + i : nullptr);
+    out[4 * i] = c.x; out[4 * i + 1] = c.y; out[4 * i + 2] = c.z; out[4 * i + 3] = c.alpha;
+  }
+}
+void oracle_blend_n(uint64_t n, const double* self_c, const double* other, double* out) {
+  for (uint64_t i = 0; i < n; ++i) oracle_blend(self_c + 4 * i, other + 4 * i, out + 4 * i);
 }
 
 // ---- VolumetricDisc pieces (volumetric_disc.rs tests, :693-786) ----

@@ -94,6 +94,12 @@ def lib():
         L.oracle_vdisc_intersects_n.argtypes = [vp, C.c_int, C.c_uint64, _pd, _pd, _u8p, _pd, _pd]
         L.oracle_vdisc_raymarch_n.argtypes = [vp, C.c_uint64, _u32p, _pd, _pd, _pd, C.c_int, C.POINTER(C.c_int32), _pd,
                                               _u64p]
+        L.oracle_object_intersects_n.argtypes = [vp, C.c_int, C.c_uint64, _pd, _pd, _u8p, _pd, _pd]
+        L.oracle_to_cartesian_n.argtypes = [vp, C.c_uint64, _pd, _pd]
+        L.oracle_compute_temperature_n.argtypes = [vp, C.c_int, C.c_uint64, _pd, C.POINTER(C.c_int32), _pd]
+        L.oracle_blackbody_n.argtypes = [vp, C.c_uint64, _pd, _pd, _pd]
+        L.oracle_texture_color_n.argtypes = [vp, C.c_int, C.c_uint64, _pd, _pd, _pd]
+        L.oracle_blend_n.argtypes = [C.c_uint64, _pd, _pd, _pd]
         _lib = L
     return _lib
 
@@ -393,6 +399,70 @@ def vdisc_raymarch_n(desc, obj, ro, rd, freq, cached=True):
     lib().oracle_vdisc_raymarch_n(_addr(desc), n, k.ctypes.data_as(_u32p), _dp(x), _dp(d), _dp(f), 1 if cached else 0,
                                   err.ctypes.data_as(C.POINTER(C.c_int32)), _dp(out), ns.ctypes.data_as(_u64p))
     return err, out, ns
+
+
+# array forms of the surface path's pieces (tests/surface_cases.py)
+def _opt(a, n):
+    if a is None:
+        return None, None
+    a = np.ascontiguousarray(a, np.float64)
+    assert a.shape == (n,)
+    return a, _dp(a)
+
+
+def object_intersects_n(desc, obj: int, a, b):
+    """disc_intersects / sphere_intersects per row (Cartesian points): hit, t, world point (n, 3)."""
+    x, n = _n3(a)
+    y, m = _n3(b)
+    assert n == m
+    hit, t, pt = np.zeros(n, np.uint8), np.zeros(n), np.zeros((n, 3))
+    lib().oracle_object_intersects_n(_addr(desc), obj, n, _dp(x), _dp(y), hit.ctypes.data_as(_u8p), _dp(t), _dp(pt))
+    return hit.astype(bool), t, pt
+
+
+def to_cartesian_n(desc, pos) -> np.ndarray:
+    """to_cartesian per native-chart position (r, theta, phi): (n, 3)."""
+    x, n = _n3(pos)
+    out = np.zeros((n, 3))
+    lib().oracle_to_cartesian_n(_addr(desc), n, _dp(x), _dp(out))
+    return out
+
+
+def compute_temperature_n(desc, obj: int, radius):
+    """compute_temperature of object obj per radius: status (n,), value (n,) (0 where not OK)."""
+    r = np.ascontiguousarray(radius, np.float64).reshape(-1)
+    status, val = np.zeros(len(r), np.int32), np.zeros(len(r))
+    lib().oracle_compute_temperature_n(_addr(desc), obj, len(r), _dp(r), status.ctypes.data_as(C.POINTER(C.c_int32)),
+                                       _dp(val))
+    return status, val
+
+
+def blackbody_n(desc, temperature, log_t=None) -> np.ndarray:
+    """sample_blackbody per temperature (n, 4); with log_t, log_t[i] stands in for log10(max(T, 10))."""
+    t = np.ascontiguousarray(temperature, np.float64).reshape(-1)
+    lt, ltp = _opt(log_t, len(t))
+    out = np.zeros((len(t), 4))
+    lib().oracle_blackbody_n(_addr(desc), len(t), _dp(t), ltp, _dp(out))
+    return out
+
+
+def texture_color_n(desc, obj: int, uvzt, log_t=None) -> np.ndarray:
+    """color_at_uv per row (u, v, redshift, temperature), obj -1 = celestial: (n, 4); log_t as in
+    blackbody_n, of temperature * redshift."""
+    q = np.ascontiguousarray(uvzt, np.float64).reshape(-1, 4)
+    lt, ltp = _opt(log_t, len(q))
+    out = np.zeros((len(q), 4))
+    lib().oracle_texture_color_n(_addr(desc), obj, len(q), _dp(q), ltp, _dp(out))
+    return out
+
+
+def blend_n(self_c, other) -> np.ndarray:
+    a = np.ascontiguousarray(self_c, np.float64).reshape(-1, 4)
+    b = np.ascontiguousarray(other, np.float64).reshape(-1, 4)
+    assert len(a) == len(b)
+    out = np.zeros((len(a), 4))
+    lib().oracle_blend_n(len(a), _dp(a), _dp(b), _dp(out))
+    return out
 
 
 # ---- geometry probes (the reference's unit tests, tests/test_reference_kats.py) ----
