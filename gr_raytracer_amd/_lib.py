@@ -170,6 +170,7 @@ class GBufferArrays(C.Structure):
 
 GBUFFER_FILE_VERSION = 1
 GBUFFER_SUB_FILE_VERSION = 1
+GBUFFER_SUB_LAPSE_FILE_VERSION = 1
 
 
 class GBufferSubInfo(C.Structure):
@@ -378,6 +379,19 @@ def lib() -> C.CDLL:
         "grt_gbuffer_orbit_uv_retarded": (C.c_int, [C.POINTER(GBufferShape), u64, C.POINTER(C.c_uint8), _pd, _pd, _pd,
                                                     _pd, _d, _pd, _pd]),
         "grt_gbuffer_shade_times_retarded": (C.c_int, [vp, vp, u32, _pd, C.POINTER(FrameOut), C.POINTER(C.c_float)]),
+        "grt_gbuffer_supersample_lapse": (C.c_int, [vp, vp, u32, u64, C.POINTER(C.c_uint32), C.POINTER(Stats)]),
+        "grt_gbuffer_sub_has_lapse": (C.c_int, [vp]),
+        "grt_gbuffer_sub_clear": (C.c_int, [vp]),
+        "grt_gbuffer_sub_lapse_download": (C.c_int, [vp, _pd]),
+        "grt_gbuffer_sub_lapse_upload": (C.c_int, [vp, _pd, u64]),
+        "grt_gbuffer_shade_section_at_retarded": (C.c_int, [vp, vp, C.POINTER(AdaptiveConfig), _pd, vp, _pd,
+                                                            C.POINTER(C.c_uint8), C.POINTER(C.c_uint8),
+                                                            C.POINTER(C.c_uint64), C.POINTER(SubsampleFailures),
+                                                            C.POINTER(GBufferSectionReport), _d]),
+        "grt_gbuffer_sub_lapse_write_file": (C.c_int, [C.c_char_p, C.POINTER(GBufferInfo), C.POINTER(GBufferSubInfo),
+                                                       _pd, u64]),
+        "grt_gbuffer_sub_lapse_read_file": (C.c_int, [C.c_char_p, C.POINTER(GBufferInfo), C.POINTER(GBufferSubInfo),
+                                                      _pd]),
         "grt_gbuffer_sub_info_get": (C.c_int, [vp, C.POINTER(GBufferSubInfo)]),
         "grt_gbuffer_sub_download": (C.c_int, [vp, C.POINTER(C.c_uint32), C.POINTER(GBufferArrays)]),
         "grt_gbuffer_sub_upload": (C.c_int, [vp, C.POINTER(GBufferSubInfo), C.POINTER(C.c_uint32),
@@ -445,6 +459,9 @@ EXPORTED_SYMBOLS = [
     "grt_orbit_rate", "grt_gbuffer_orbit_uv", "grt_gbuffer_shade_times", "grt_gbuffer_shade_section_at",
     "grt_gbuffer_trace_lapse", "grt_gbuffer_lapse_download", "grt_gbuffer_lapse_upload", "grt_gbuffer_lapse_write_file",
     "grt_gbuffer_lapse_read_file", "grt_gbuffer_orbit_uv_retarded", "grt_gbuffer_shade_times_retarded",
+    "grt_gbuffer_supersample_lapse", "grt_gbuffer_sub_has_lapse", "grt_gbuffer_sub_clear",
+    "grt_gbuffer_sub_lapse_download", "grt_gbuffer_sub_lapse_upload", "grt_gbuffer_shade_section_at_retarded",
+    "grt_gbuffer_sub_lapse_write_file", "grt_gbuffer_sub_lapse_read_file",
 ]
 
 

@@ -18,6 +18,7 @@
 //                        [--filename-pattern frame-%04d.png] [--adaptive-stacked]
 //     | reshade-orbit --gbuffer a.grtg --times T0,DT,K --filename-pattern f-%04d.png [--retarded]
 //                     [--raw-out-pattern f-%04d.raw] [--first-index 0] [--adaptive]
+//                     [--adaptive-retarded]
 //     | blackbody -t T [-r Z]
 //     | blackbody-spectrum [--min-temperature T] [--max-temperature T] [--min-redshift Z]
 //                          [--max-redshift Z] [--width N] [--height N] [-f FILE]
@@ -82,6 +83,14 @@
 // writes it to F.grtg.lapse; F.grtg has the bytes it has without the flag.  `reshade-orbit
 // --retarded` reads that sidecar and shades every disc layer at its emission time
 // (grt_gbuffer_shade_times_retarded); a missing sidecar is a usage error.
+// `gbuffer --adaptive --lapse` fills a timed sub-sample set: the sub-rays of the same selection
+// with their light-travel times, written to F.grtg.sub.lapse beside F.grtg.sub (each of the
+// other three files has the bytes its flag writes alone).  `reshade-orbit --adaptive-retarded`
+// is --adaptive under the retarded rule (grt_gbuffer_shade_section_at_retarded): it needs
+// F.grtg.lapse, and F.grtg.sub.lapse wherever F.grtg.sub is there; a set it tops up stays
+// timed, and both sidecars are rewritten once at the end when it grew.  `reshade --adaptive`
+// and `reshade-orbit --adaptive` load F.grtg.sub.lapse when it is there and write it back
+// with F.grtg.sub, so a timed set stays one.
 #include <algorithm>
 #include <charconv>
 #include <chrono>
@@ -124,6 +133,7 @@ static int usage(const char* msg) {
                "           (--adaptive-stacked: the adaptive frames of the sequence, the sub-rays in F-%%04d.grtg.sub)\n"
                "       grt [global options] --config-file FILE reshade-orbit --gbuffer F.grtg --times T0,DT,K\n"
                "           --filename-pattern F-%%04d.png [--raw-out-pattern F-%%04d.raw] [--first-index N] [--adaptive | --retarded]\n"
+               "           [--adaptive-retarded]  (the adaptive frames under the retarded rule: F.grtg.lapse, F.grtg.sub.lapse)\n"
                "           (frame k: the disc's texture after orbiting for T0 + k DT; one trace, K frames)\n"
                "       grt [global options] blackbody -t T [-r Z]\n"
                "       grt [global options] blackbody-spectrum [--min-temperature T] [--max-temperature T]\n"
@@ -408,13 +418,37 @@ struct GBufferSubHost {
       : sub(s), sub_pixel(s.n_sub_pixels), rays(s.n_sub_rays, s.n_sub_layers) {}
 };
 
+// A timed set's lapse goes beside it, to `<path>.lapse` (grt_gbuffer_sub_lapse_write_file).
 static int save_sub_sidecar(const grt_gbuffer* gb, const grt_gbuffer_info& info, const std::string& path) {
   grt_gbuffer_sub_info sub;
   if (grt_gbuffer_sub_info_get(gb, &sub)) return 1;
   GBufferSubHost h(sub);
   const grt_gbuffer_arrays arr = h.rays.arrays();
-  return grt_gbuffer_sub_download(gb, h.sub_pixel.data(), &arr) ||
-         grt_gbuffer_sub_write_file(path.c_str(), &info, &sub, h.sub_pixel.data(), &arr);
+  if (grt_gbuffer_sub_download(gb, h.sub_pixel.data(), &arr) ||
+      grt_gbuffer_sub_write_file(path.c_str(), &info, &sub, h.sub_pixel.data(), &arr))
+    return 1;
+  if (grt_gbuffer_sub_has_lapse(gb) != 1) return 0;
+  std::vector<double> lapse(sub.n_sub_layers);
+  return grt_gbuffer_sub_lapse_download(gb, lapse.data()) ||
+         grt_gbuffer_sub_lapse_write_file((path + ".lapse").c_str(), &info, &sub, lapse.data(), sub.n_sub_layers);
+}
+
+static bool file_exists(const std::string& path) {
+  FILE* f = std::fopen(path.c_str(), "rb");
+  if (f) std::fclose(f);
+  return f != nullptr;
+}
+
+// The lapse of the set just loaded from `<sidecar>` (its info `sub`), when `<sidecar>.lapse` is
+// there: the set is then a timed one.  A sidecar of another or of a since-grown set fails.
+static int load_sub_lapse_sidecar(grt_gbuffer* gb, const grt_gbuffer_info& info, const grt_gbuffer_sub_info& sub,
+                                  const std::string& sidecar) {
+  const std::string path = sidecar + ".lapse";
+  if (!file_exists(path)) return 0;
+  std::vector<double> lapse(sub.n_sub_layers);
+  if (grt_gbuffer_sub_lapse_read_file(path.c_str(), &info, &sub, lapse.data())) return 1;
+  if (sub.samples_per_axis == 0) return 0;  // no set to time
+  return grt_gbuffer_sub_lapse_upload(gb, lapse.data(), sub.n_sub_layers);
 }
 
 // render-sequence: a camera-path file, one camera per line `x,y,z,phi,theta,psi` (the
@@ -498,6 +532,7 @@ int main(int argc, char** argv) {
   std::string orbit_times, raw_out_pattern;  // reshade-orbit --times T0,DT,K, --raw-out-pattern
   bool gbuffer_lapse = false;   // gbuffer --lapse: record each layer's light-travel time (F.grtg.lapse)
   bool orbit_retarded = false;  // reshade-orbit --retarded: every disc layer at its emission time
+  bool orbit_adaptive_retarded = false;  // reshade-orbit --adaptive-retarded: --adaptive under that rule
   double orbit_t0 = 0.0, orbit_dt = 0.0;
   long long first_index = 0;
   std::vector<std::string> args(argv + 1, argv + argc);
@@ -533,6 +568,10 @@ int main(int argc, char** argv) {
     }
     if (action == "gbuffer" && a == "--lapse") {
       gbuffer_lapse = true;
+      continue;
+    }
+    if (action == "reshade-orbit" && a == "--adaptive-retarded") {
+      orbit_adaptive_retarded = true;
       continue;
     }
     if (action == "reshade-orbit" && a == "--retarded") {
@@ -765,15 +804,18 @@ int main(int argc, char** argv) {
       return usage("--raw-out-pattern needs one %d or %0Nd conversion for the frame index");
     if (!raw_out.empty()) return usage("reshade-orbit writes many frames: give --raw-out-pattern, not --raw-out");
     if (orbit_retarded && gbuffer_adaptive)
-      return usage("reshade-orbit --retarded does not combine with --adaptive: the sub-sample set records no lapse, "
-                   "the adaptive frame stays fast-light");
-    if (orbit_retarded) {  // the lapse's sidecar must be there
-      FILE* f = std::fopen((gbuffer_file + ".lapse").c_str(), "rb");
-      if (!f)
-        return usage(("reshade-orbit --retarded needs the lapse sidecar " + gbuffer_file +
-                      ".lapse (trace with `gbuffer --lapse`)").c_str());
-      std::fclose(f);
-    }
+      return usage("reshade-orbit --retarded does not combine with --adaptive: --retarded shades the 1-spp frames; "
+                   "the adaptive frames under the retarded rule are --adaptive-retarded");
+    if (orbit_adaptive_retarded && (gbuffer_adaptive || orbit_retarded))
+      return usage("reshade-orbit --adaptive-retarded does not combine with --adaptive or --retarded: it is the "
+                   "adaptive frame under the retarded rule by itself");
+    if ((orbit_retarded || orbit_adaptive_retarded) && !file_exists(gbuffer_file + ".lapse"))  // the lapse's sidecar
+      return usage(("reshade-orbit " + std::string(orbit_retarded ? "--retarded" : "--adaptive-retarded") +
+                    " needs the lapse sidecar " + gbuffer_file + ".lapse (trace with `gbuffer --lapse`)").c_str());
+    if (orbit_adaptive_retarded && file_exists(gbuffer_file + ".sub") && !file_exists(gbuffer_file + ".sub.lapse"))
+      return usage(("reshade-orbit --adaptive-retarded: the sub-sample set " + gbuffer_file + ".sub has no lapse sidecar " +
+                    gbuffer_file + ".sub.lapse: remove it (its sub-rays are then traced again, timed) or re-run "
+                    "`gbuffer --adaptive --lapse`").c_str());
   }
   if (filename.empty())
     filename = (action == "render" || action == "reshade") ? "render.png" : (action == "render-ray" ? "rendered-ray.csv" : "rendered-ray-at.csv");
@@ -837,9 +879,19 @@ int main(int argc, char** argv) {
       return usage(("--width / --height must be the g-buffer's frame, " + std::to_string(gb_info.cols) + " x " +
                     std::to_string(gb_info.rows)).c_str());
     // the lapse's sidecar: its header, its binding to this buffer and its entries
-    if (orbit_retarded && grt_gbuffer_lapse_read_file((gbuffer_file + ".lapse").c_str(), &gb_info, nullptr)) {
+    if ((orbit_retarded || orbit_adaptive_retarded) &&
+        grt_gbuffer_lapse_read_file((gbuffer_file + ".lapse").c_str(), &gb_info, nullptr)) {
       std::fprintf(stderr, "Error: %s\n", grt_last_error());
       return 1;
+    }
+    // and the set's two sidecars: their headers, lengths and bindings, the lapse's entries
+    if (orbit_adaptive_retarded && file_exists(gbuffer_file + ".sub")) {
+      grt_gbuffer_sub_info held;
+      if (grt_gbuffer_sub_read_file((gbuffer_file + ".sub").c_str(), &gb_info, &held, nullptr, nullptr) ||
+          grt_gbuffer_sub_lapse_read_file((gbuffer_file + ".sub.lapse").c_str(), &gb_info, &held, nullptr)) {
+        std::fprintf(stderr, "Error: %s\n", grt_last_error());
+        return 1;
+      }
     }
   }
 
@@ -926,7 +978,30 @@ int main(int argc, char** argv) {
                    transport_name(grep.transport), grep.gather_ms);
     }
     grt_gbuffer_section_report srep;
-    if (gbuffer_adaptive) {  // this scene's own adaptive frame: the buffer then holds its selection's sub-rays
+    if (gbuffer_adaptive && gbuffer_lapse) {
+      // the same selection's sub-rays with their lapses, a timed set: the mask pass paints the
+      // selected pixels and traces nothing (no shaded pixel has the paint's alpha of -1), then
+      // grt_gbuffer_supersample_lapse appends them in the order the top-up below would
+      std::memset(&srep, 0, sizeof(srep));
+      if (ac.enabled) {
+        const double paint[4] = {-1.0, -1.0, -1.0, -1.0};
+        std::vector<double> frame(4 * (size_t)gb_info.n_pixels);
+        std::vector<uint32_t> px;
+        if (grt_gbuffer_shade_section(scene, gb, &ac, paint, nullptr, frame.data(), nullptr, nullptr, nullptr, nullptr,
+                                      nullptr)) {
+          std::fprintf(stderr, "Error: %s\n", grt_last_error());
+          return 1;
+        }
+        for (size_t p = 0; p < (size_t)gb_info.n_pixels; ++p)
+          if (frame[4 * p + 3] == -1.0) px.push_back((uint32_t)p);
+        if (grt_gbuffer_supersample_lapse(scene, gb, ac.samples_per_axis, px.size(), px.data(), &srep.top_up)) {
+          std::fprintf(stderr, "Error: %s\n", grt_last_error());
+          return 1;
+        }
+        srep.n_selected = srep.n_traced = px.size();
+        srep.trace_ms = srep.top_up.kernel_ms;
+      }
+    } else if (gbuffer_adaptive) {  // this scene's own adaptive frame: the buffer then holds its selection's sub-rays
       std::vector<double> frame(4 * (size_t)gb_info.n_pixels);
       if (grt_gbuffer_shade_section(scene, gb, &ac, nullptr, scene, frame.data(), nullptr, nullptr, nullptr, nullptr,
                                     &srep)) {
@@ -954,6 +1029,17 @@ int main(int argc, char** argv) {
         return 1;
       }
       std::fprintf(stderr, "[grt] INFO saved lapse to %s.lapse\n", filename.c_str());
+      if (gbuffer_adaptive) {
+        if (grt_gbuffer_sub_has_lapse(gb) != 1) {  // no set (adaptive sampling is off): an empty sidecar beside the empty .sub
+          grt_gbuffer_sub_info none;
+          if (grt_gbuffer_sub_info_get(gb, &none) ||
+              grt_gbuffer_sub_lapse_write_file((filename + ".sub.lapse").c_str(), &gb_info, &none, nullptr, 0)) {
+            std::fprintf(stderr, "Error: %s\n", grt_last_error());
+            return 1;
+          }
+        }
+        std::fprintf(stderr, "[grt] INFO saved sub-sample lapse to %s.sub.lapse\n", filename.c_str());
+      }
     }
     if (gbuffer_adaptive)
       std::fprintf(stderr, "[grt] sub-sample set: %llu selected pixels traced (%llu sub-rays, %.1f ms), saved to %s.sub\n",
@@ -1023,7 +1109,8 @@ int main(int argc, char** argv) {
         GBufferSubHost h(before);
         const grt_gbuffer_arrays sarr = h.rays.arrays();
         if (grt_gbuffer_sub_read_file(sidecar.c_str(), &gb_info, &before, h.sub_pixel.data(), &sarr) ||
-            grt_gbuffer_sub_upload(gb, &before, h.sub_pixel.data(), &sarr)) {
+            grt_gbuffer_sub_upload(gb, &before, h.sub_pixel.data(), &sarr) ||
+            load_sub_lapse_sidecar(gb, gb_info, before, sidecar)) {  // with its lapse the set stays timed
           std::fprintf(stderr, "Error: %s\n", grt_last_error());
           return 1;
         }
@@ -1082,6 +1169,7 @@ int main(int argc, char** argv) {
   }
   if (action == "reshade-orbit") {  // one traced frame at K times under this config's appearance
     const uint32_t K = (uint32_t)n_frames;
+    const bool adaptive = gbuffer_adaptive || orbit_adaptive_retarded;  // the adaptive frames, under either rule
     const size_t n = gb_info.n_pixels, nl = gb_info.n_layers;
     GBufferHost host(n, nl);
     const grt_gbuffer_arrays arr = host.arrays();
@@ -1096,15 +1184,23 @@ int main(int argc, char** argv) {
     std::vector<double> xyza(n * 4 * K);
     float shade_ms = 0;
     grt_scene* tracer = nullptr;
-    std::vector<uint8_t> status(gbuffer_adaptive ? n * K : 0);
+    std::vector<uint8_t> status(adaptive ? n * K : 0);
     std::vector<uint64_t> nsel(K, 0);
-    const uint64_t fail_cap = gbuffer_adaptive ? 1u << 16 : 0;  // failed sub-rays logged per frame
+    const uint64_t fail_cap = adaptive ? 1u << 16 : 0;  // failed sub-rays logged per frame
     std::vector<uint32_t> fail_pix(fail_cap * K), fail_sample(fail_cap * K), fail_steps(fail_cap * K);
     std::vector<uint8_t> fail_status(fail_cap * K), fail_stop(fail_cap * K);
     std::vector<grt_subsample_failures> fails(K);
     double mask[4];
     const double* maskp = nullptr;
-    if (gbuffer_adaptive) {
+    if (orbit_retarded || orbit_adaptive_retarded) {  // the buffer's lapse from its sidecar (checked before the GPU was touched)
+      std::vector<double> lapse(nl);
+      if (grt_gbuffer_lapse_read_file((gbuffer_file + ".lapse").c_str(), &gb_info, lapse.data()) ||
+          grt_gbuffer_lapse_upload(gb, lapse.data(), nl)) {
+        std::fprintf(stderr, "Error: %s\n", grt_last_error());
+        return 1;
+      }
+    }
+    if (adaptive) {
       // as `reshade --adaptive`: this config's scene with the file's recorded camera and
       // integration parameters is the appearance and the tracer of the missing sub-rays
       grt_scene_desc td = *d;
@@ -1130,7 +1226,8 @@ int main(int argc, char** argv) {
         GBufferSubHost h(before);
         const grt_gbuffer_arrays sarr = h.rays.arrays();
         if (grt_gbuffer_sub_read_file(sidecar.c_str(), &gb_info, &before, h.sub_pixel.data(), &sarr) ||
-            grt_gbuffer_sub_upload(gb, &before, h.sub_pixel.data(), &sarr)) {
+            grt_gbuffer_sub_upload(gb, &before, h.sub_pixel.data(), &sarr) ||
+            load_sub_lapse_sidecar(gb, gb_info, before, sidecar)) {  // with its lapse the set stays timed
           std::fprintf(stderr, "Error: %s\n", grt_last_error());
           return 1;
         }
@@ -1144,8 +1241,9 @@ int main(int argc, char** argv) {
                                           fail_status.data() + fail_cap * k, 0, fail_stop.data() + fail_cap * k,
                                           fail_steps.data() + fail_cap * k};
         grt_gbuffer_section_report srep;
-        if (grt_gbuffer_shade_section_at(tracer, gb, &ac, maskp, tracer, xyza.data() + n * 4 * k, nullptr,
-                                         status.data() + n * k, &nsel[k], &fails[k], &srep, times[k])) {
+        if ((orbit_adaptive_retarded ? grt_gbuffer_shade_section_at_retarded : grt_gbuffer_shade_section_at)(
+                tracer, gb, &ac, maskp, tracer, xyza.data() + n * 4 * k, nullptr, status.data() + n * k, &nsel[k],
+                &fails[k], &srep, times[k])) {
           std::fprintf(stderr, "Error: %s\n", grt_last_error());
           return 1;
         }
@@ -1166,14 +1264,6 @@ int main(int argc, char** argv) {
       }
     } else {
       grt_frame_out fo{nullptr, xyza.data(), nullptr, nullptr, nullptr, nullptr};
-      if (orbit_retarded) {  // the buffer's lapse from its sidecar (checked before the GPU was touched)
-        std::vector<double> lapse(nl);
-        if (grt_gbuffer_lapse_read_file((gbuffer_file + ".lapse").c_str(), &gb_info, lapse.data()) ||
-            grt_gbuffer_lapse_upload(gb, lapse.data(), nl)) {
-          std::fprintf(stderr, "Error: %s\n", grt_last_error());
-          return 1;
-        }
-      }
       if ((orbit_retarded ? grt_gbuffer_shade_times_retarded : grt_gbuffer_shade_times)(scene, gb, K, times.data(), &fo,
                                                                                         &shade_ms)) {
         std::fprintf(stderr, "Error: %s\n", grt_last_error());
@@ -1195,7 +1285,7 @@ int main(int argc, char** argv) {
         std::fprintf(stderr, "[grt] INFO Tone mapping method: %s\n",
                      opts.tone_mapping == GRT_TONE_GLOBAL_LINEAR ? "GlobalLinear" : "Reinhard");
       }
-      if (gbuffer_adaptive) {  // the frame's ray log, as `reshade --adaptive` writes it
+      if (adaptive) {  // the frame's ray log, as `reshade --adaptive` writes it
         const std::vector<uint8_t> f_status(status.begin() + n * k, status.begin() + n * (k + 1));
         log_frame_rays(0, 0, gb_info.cols, f_status, host.stop, host.steps, ac.enabled && !maskp, nsel[k], fails[k]);
       }

@@ -122,6 +122,11 @@ struct GBufferSub {
   DevBuf sub_block;  // u32[n_pixels], GBUFFER_NIL where a pixel has no block (derived, never stored)
   std::vector<uint32_t> h_block;  // host copy of sub_block
   GBufferDev arr;
+  // A set is timed or untimed, decided when its first block is appended (sub_fill) or by
+  // grt_gbuffer_sub_lapse_upload.  A timed set holds one lapse per sub-layer beside the twelve
+  // arrays: f64[cap_layers], indexed as they are, grown with them.
+  bool timed = false;
+  DevBuf lapse;
   uint64_t per() const { return (uint64_t)spa * spa; }
   uint64_t n_rays() const { return n_pix * per(); }
   // the pixel -> block map, all NIL, before any block exists
@@ -141,9 +146,11 @@ struct GBufferSub {
     return 0;
   }
   int reserve_layers(uint64_t want) {
-    if (want <= cap_layers && arr.a[GB_object].p) return 0;
+    if (want <= cap_layers && arr.a[GB_object].p && (!timed || lapse.p)) return 0;
     const uint64_t cap = std::max<uint64_t>({want, 2 * cap_layers, 4096});
     if (int rc = arr.grow(true, n_layers, cap)) return rc;
+    if (timed)
+      if (int rc = grow_buf(lapse, 8 * n_layers, 8 * cap)) return rc;
     cap_layers = cap;
     return 0;
   }
@@ -741,8 +748,11 @@ static int check_spa(const grt_gbuffer* gb, uint32_t spa) {
 // The fill is gbuffer_fill_kernel over the chunk's own work list, its arrays pointing at
 // the chunk's place in the set; a chunk launches exactly its rays, so no live count.
 // acc / ms[2]: counters and event times (trace; scan + fill), added to.
+// `lapse` decides the kind of an empty set: timed (the lapse units trace and fill, the set's
+// lapse array written at the set-wide layer offsets beside the twelve) or untimed (the exact
+// units, as ever).  A set that holds blocks keeps its kind, whoever asks.
 static int sub_fill(grt_scene* tracer, grt_gbuffer* gb, uint32_t spa, const std::vector<uint32_t>& px,
-                    unsigned long long acc[8], double ms[2]) {
+                    unsigned long long acc[8], double ms[2], bool lapse = false) {
   const uint64_t m = px.size();
   if (m == 0) return 0;
   const grt_gbuffer_info& info = gb->info;
@@ -754,6 +764,8 @@ static int sub_fill(grt_scene* tracer, grt_gbuffer* gb, uint32_t spa, const std:
   HIP_TRY(hipSetDevice(info.device));
   if ((rc = S.ensure_map(info.n_pixels))) return rc;
   S.spa = spa;
+  if (S.n_pix == 0) S.timed = lapse;
+  const bool timed = S.timed;
   const uint64_t per = S.per();
   if ((S.n_pix + m) * per + 1 > (uint64_t)INT_MAX) return fail(-EOVERFLOW, "more than INT_MAX - 1 sub-rays");
   SuperBufs C;  // the chunking of enqueue_supersample; the buffers are this call's own
@@ -780,7 +792,7 @@ static int sub_fill(grt_scene* tracer, grt_gbuffer* gb, uint32_t spa, const std:
     const grt::Outputs o{(float*)xyza.p,         (uint8_t*)cls.p,       S.arr.status() + off, nullptr,
                          S.arr.steps() + off,    S.arr.stop() + off,    (uint32_t*)hits.p};
     float t_ms = 0;
-    if ((rc = trace_exact(tracer, *dc, wo, o, acc, &t_ms))) return rc;
+    if ((rc = trace_exact(tracer, *dc, wo, o, acc, &t_ms, nullptr, nullptr, timed))) return rc;
     ms[0] += t_ms;
     if ((rc = stream_order(*dc, st))) return rc;
     HIP_TRY(hipEventRecord(dc->ev0, st));
@@ -790,7 +802,9 @@ static int sub_fill(grt_scene* tracer, grt_gbuffer* gb, uint32_t spa, const std:
     if ((rc = S.reserve_layers(S.n_layers + n_new))) return rc;
     HIP_TRY(grt::gbuffer_sub_append((const uint64_t*)local.p, nr, S.n_layers, S.arr.layer_start() + off, d_chunk, mc,
                                     (uint32_t)S.n_pix, (uint32_t*)S.sub_block.p, (uint32_t*)S.sub_pixel.p, st));
-    if ((rc = enqueue_fill(tracer, *dc, wo, nr, S.arr.view(off, nr), st))) return rc;
+    if ((rc = enqueue_fill(tracer, *dc, wo, nr, S.arr.view(off, nr), st, nullptr,
+                           timed ? (double*)S.lapse.p : nullptr)))
+      return rc;
     HIP_TRY(hipEventRecord(dc->ev1, st));
     HIP_TRY(hipEventSynchronize(dc->ev1));
     float f_ms = 0;
@@ -827,6 +841,9 @@ static int check_sequence_buffers(uint32_t n, grt_gbuffer* const* buffers, bool 
                                ") of a frame of " + std::to_string(i.camera.rows) + " x " +
                                std::to_string(i.camera.cols) + " pixels, not the whole frame");
     if (sub_pass && check_spa(buffers[f], spa)) return fail(-EINVAL, frame + grt_last_error());
+    if (sub_pass && buffers[f]->sub.timed)  // the stacked traces take camera tables, which lapse traces refuse
+      return fail(-EINVAL, frame + "the g-buffer's sub-sample set is timed (it holds lapses): the stacked calls "
+                               "fill and shade untimed sets only");
     if (tracer)
       if (int rc = check_tracer(buffers[f], tracer, false)) return fail(rc, frame + grt_last_error());
   }
@@ -988,34 +1005,56 @@ static int sub_fill_sequence(grt_scene* tracer, uint32_t K, grt_gbuffer* const* 
   return 0;
 }
 
-extern "C" {
-
-int grt_gbuffer_supersample(grt_scene* tracer, grt_gbuffer* gb, uint32_t spa, uint64_t n, const uint32_t* pixels,
-                            grt_stats* stats) {
+// grt_gbuffer_supersample, and with `lapse` grt_gbuffer_supersample_lapse.
+static int supersample_impl(grt_scene* tracer, grt_gbuffer* gb, uint32_t spa, uint64_t n, const uint32_t* pixels,
+                            grt_stats* stats, bool lapse) {
   if (!tracer || !gb || (n && !pixels)) return fail(-EINVAL, "null argument");
   int rc;
   if ((rc = check_spa(gb, spa)) || (rc = check_tracer(gb, tracer))) return rc;
+  if (lapse && gb->sub.n_pix && !gb->sub.timed)
+    return fail(-EINVAL, "g-buffer: the sub-sample set of " + std::to_string(gb->sub.n_pix) +
+                             " pixels is untimed (it holds no lapse): grt_gbuffer_sub_clear it, or give it one "
+                             "(grt_gbuffer_sub_lapse_upload)");
   if (stats) std::memset(stats, 0, sizeof(*stats));
   std::vector<uint32_t> px;
   if ((rc = missing_of("", gb, n, pixels, &px))) return rc;
   unsigned long long acc[8] = {0, 0, 0, 0, 0, 0, 0, 0};
   double ms[2] = {0.0, 0.0};
-  if ((rc = sub_fill(tracer, gb, spa, px, acc, ms))) return rc;
+  if ((rc = sub_fill(tracer, gb, spa, px, acc, ms, lapse))) return rc;
   if (stats) stats_from(acc, (float)ms[0], stats);
   return 0;
 }
 
+extern "C" {
+
+int grt_gbuffer_supersample(grt_scene* tracer, grt_gbuffer* gb, uint32_t spa, uint64_t n, const uint32_t* pixels,
+                            grt_stats* stats) {
+  return supersample_impl(tracer, gb, spa, n, pixels, stats, false);
+}
+
+int grt_gbuffer_supersample_lapse(grt_scene* tracer, grt_gbuffer* gb, uint32_t spa, uint64_t n, const uint32_t* pixels,
+                                  grt_stats* stats) {
+  return supersample_impl(tracer, gb, spa, n, pixels, stats, true);
+}
+
 }  // extern "C"
 
-// grt_gbuffer_shade_section (time == nullptr: the static kernels, exactly its launches) and
-// grt_gbuffer_shade_section_at (the kernels at *time): one pipeline.  The set is geometry:
-// a top-up appends what grt_gbuffer_supersample leaves, whatever the time.
+// grt_gbuffer_shade_section (SECTION_STATIC: the static kernels, exactly its launches),
+// grt_gbuffer_shade_section_at (SECTION_AT: the kernels at `time`) and
+// grt_gbuffer_shade_section_at_retarded (SECTION_AT_RETARDED: the kernels at `time` + each
+// layer's lapse): one pipeline.  The mode picks the 1-spp launch and the sub-ray launch and
+// nothing else.  The set is geometry: a top-up appends what grt_gbuffer_supersample leaves,
+// whatever the time; the retarded mode needs a timed set, and fills an empty one timed.
+enum SectionMode { SECTION_STATIC, SECTION_AT, SECTION_AT_RETARDED };
 static int shade_section_impl(grt_scene* s, grt_gbuffer* gb, const grt_adaptive_config* cfg, const double* mask_xyza,
                               grt_scene* tracer, double* xyza_out, uint8_t* class_out, uint8_t* status_out,
                               uint64_t* n_supersampled, grt_subsample_failures* failures,
-                              grt_gbuffer_section_report* report, const double* time) {
+                              grt_gbuffer_section_report* report, SectionMode mode, double time) {
   if (!s || !gb || !cfg || !xyza_out) return fail(-EINVAL, "null argument");
-  if (time && !std::isfinite(*time)) return fail(-EINVAL, "g-buffer: the time is not finite");
+  if (mode != SECTION_STATIC && !std::isfinite(time)) return fail(-EINVAL, "g-buffer: the time is not finite");
+  const bool retarded = mode == SECTION_AT_RETARDED;
+  if (retarded && !gb->has_lapse)
+    return fail(-ENODATA, "the g-buffer holds no lapse (grt_gbuffer_trace_lapse, grt_gbuffer_lapse_upload)");
   if (cfg->samples_per_axis == 0) return fail(-EINVAL, "adaptive_sampling.samples_per_axis must be greater than zero");
   int rc = grt_gbuffer_shape_compatible(&gb->info.shape, &s->desc);
   if (rc) return rc;
@@ -1025,6 +1064,10 @@ static int shade_section_impl(grt_scene* s, grt_gbuffer* gb, const grt_adaptive_
   if (sub_pass && (rc = check_spa(gb, spa))) return rc;
   if (sub_pass && tracer && (rc = check_tracer(gb, tracer))) return rc;
   if (report) std::memset(report, 0, sizeof(*report));
+  if (retarded && sub_pass && gb->sub.n_pix && !gb->sub.timed)
+    return fail(-ENODATA, "g-buffer: the sub-sample set of " + std::to_string(gb->sub.n_pix) + " pixels and " +
+                              std::to_string(gb->sub.n_layers) + " layers is untimed (it holds no lapse): "
+                              "grt_gbuffer_sub_clear it, or give it one (grt_gbuffer_sub_lapse_upload)");
   if (n_supersampled) *n_supersampled = 0;
   if (failures) failures->count = 0;
   const int device = gb->info.device;
@@ -1069,9 +1112,13 @@ static int shade_section_impl(grt_scene* s, grt_gbuffer* gb, const grt_adaptive_
     const grt::GBufferArrays sv = S.view();
     for (uint32_t c = 0; c < B.n_chunks; ++c) {
       const uint64_t base = (uint64_t)c * B.chunk_pix;
-      if (time)
+      if (retarded)
+        HIP_TRY(grt::launch_gbuffer_shade_sub_at_retarded(dc->d_scene, sv, S.arr.steps(), (const uint32_t*)S.sub_block.p,
+                                                          P.held_px + base, B.chunk_pix, d_cnt + 2, base, spa, time,
+                                                          (const double*)S.lapse.p, so, st));
+      else if (mode == SECTION_AT)
         HIP_TRY(grt::launch_gbuffer_shade_sub_at(dc->d_scene, sv, S.arr.steps(), (const uint32_t*)S.sub_block.p,
-                                                 P.held_px + base, B.chunk_pix, d_cnt + 2, base, spa, *time, so, st));
+                                                 P.held_px + base, B.chunk_pix, d_cnt + 2, base, spa, time, so, st));
       else
         HIP_TRY(grt::launch_gbuffer_shade_sub(dc->d_scene, sv, S.arr.steps(), (const uint32_t*)S.sub_block.p,
                                               P.held_px + base, B.chunk_pix, d_cnt + 2, base, spa, so, st));
@@ -1092,7 +1139,10 @@ static int shade_section_impl(grt_scene* s, grt_gbuffer* gb, const grt_adaptive_
   if ((rc = stream_order(*dc, st))) return rc;
   if (supersampled) HIP_TRY(hipMemsetAsync(d_cnt, 0, 32, st));
   HIP_TRY(hipEventRecord(dc->ev0, st));
-  if (time) HIP_TRY(grt::launch_gbuffer_shade_at(dc->d_scene, gb->view(), *time, b.outputs(), st));
+  if (retarded)
+    HIP_TRY(grt::launch_gbuffer_shade_at_retarded(dc->d_scene, gb->view(), time, (const double*)gb->lapse.p,
+                                                  b.outputs(), st));
+  else if (mode == SECTION_AT) HIP_TRY(grt::launch_gbuffer_shade_at(dc->d_scene, gb->view(), time, b.outputs(), st));
   else HIP_TRY(grt::launch_gbuffer_shade(dc->d_scene, gb->view(), b.outputs(), st));
   if (supersampled) {
     if ((rc = P.enqueue_select(st, b.x64, b.cls, adaptive_params(cfg, w, h, cfg->minimum_luminance), d_cnt))) return rc;
@@ -1119,7 +1169,7 @@ static int shade_section_impl(grt_scene* s, grt_gbuffer* gb, const grt_adaptive_
     std::vector<uint32_t> px(n_missing);
     HIP_TRY(hipMemcpy(px.data(), P.missing_px, 4 * n_missing, hipMemcpyDeviceToHost));
     lk.unlock();  // the tracer may be this scene: sub_fill takes its device's lock
-    rc = sub_fill(tracer, gb, spa, px, acc, trace_ms);
+    rc = sub_fill(tracer, gb, spa, px, acc, trace_ms, retarded);
     lk.lock();
     if (rc) return rc;
     HIP_TRY(hipSetDevice(device));
@@ -1151,7 +1201,7 @@ int grt_gbuffer_shade_section(grt_scene* s, grt_gbuffer* gb, const grt_adaptive_
                               uint64_t* n_supersampled, grt_subsample_failures* failures,
                               grt_gbuffer_section_report* report) {
   return shade_section_impl(s, gb, cfg, mask_xyza, tracer, xyza_out, class_out, status_out, n_supersampled, failures,
-                            report, nullptr);
+                            report, SECTION_STATIC, 0.0);
 }
 
 int grt_gbuffer_shade_section_at(grt_scene* s, grt_gbuffer* gb, const grt_adaptive_config* cfg, const double* mask_xyza,
@@ -1159,7 +1209,16 @@ int grt_gbuffer_shade_section_at(grt_scene* s, grt_gbuffer* gb, const grt_adapti
                                  uint64_t* n_supersampled, grt_subsample_failures* failures,
                                  grt_gbuffer_section_report* report, double time) {
   return shade_section_impl(s, gb, cfg, mask_xyza, tracer, xyza_out, class_out, status_out, n_supersampled, failures,
-                            report, &time);
+                            report, SECTION_AT, time);
+}
+
+int grt_gbuffer_shade_section_at_retarded(grt_scene* s, grt_gbuffer* gb, const grt_adaptive_config* cfg,
+                                          const double* mask_xyza, grt_scene* tracer, double* xyza_out,
+                                          uint8_t* class_out, uint8_t* status_out, uint64_t* n_supersampled,
+                                          grt_subsample_failures* failures, grt_gbuffer_section_report* report,
+                                          double time) {
+  return shade_section_impl(s, gb, cfg, mask_xyza, tracer, xyza_out, class_out, status_out, n_supersampled, failures,
+                            report, SECTION_AT_RETARDED, time);
 }
 
 // grt_gbuffer_shade_times, and with `retarded` grt_gbuffer_shade_times_retarded.
@@ -1532,6 +1591,50 @@ int grt_gbuffer_sub_upload(grt_gbuffer* gb, const grt_gbuffer_sub_info* sub, con
     for (uint64_t j = 0; j < m; ++j) N->h_block[sub_pixel[j]] = (uint32_t)j;
   }
   std::swap(gb->sub, *N);  // the old set's arrays are freed with N
+  return 0;
+}
+
+int grt_gbuffer_sub_has_lapse(const grt_gbuffer* gb) {
+  if (!gb) return fail(-EINVAL, "null argument");
+  return gb->sub.spa && gb->sub.timed ? 1 : 0;
+}
+
+int grt_gbuffer_sub_clear(grt_gbuffer* gb) {
+  if (!gb) return fail(-EINVAL, "null argument");
+  HIP_TRY(hipSetDevice(gb->info.device));
+  GBufferSub none;
+  std::swap(gb->sub, none);  // the set's arrays, map and lapse are freed with `none`
+  return 0;
+}
+
+int grt_gbuffer_sub_lapse_download(const grt_gbuffer* gb, double* out) {
+  if (!gb) return fail(-EINVAL, "null argument");
+  const GBufferSub& S = gb->sub;
+  if (S.spa == 0 || !S.timed)
+    return fail(-ENODATA, "the g-buffer's sub-sample set holds no lapse (grt_gbuffer_supersample_lapse, "
+                          "grt_gbuffer_sub_lapse_upload)");
+  if (S.n_layers == 0) return 0;
+  if (!out) return fail(-EINVAL, "null argument");
+  HIP_TRY(hipSetDevice(gb->info.device));
+  HIP_TRY(hipMemcpy(out, S.lapse.p, 8 * S.n_layers, hipMemcpyDeviceToHost));
+  return 0;
+}
+
+int grt_gbuffer_sub_lapse_upload(grt_gbuffer* gb, const double* lapse, uint64_t n) {
+  if (!gb || (!lapse && n)) return fail(-EINVAL, "null argument");
+  GBufferSub& S = gb->sub;
+  if (S.spa == 0) return fail(-EINVAL, "g-buffer: a lapse for a sub-sample set, but the buffer holds no set");
+  if (n != S.n_layers)
+    return fail(-EINVAL, "a lapse of " + std::to_string(n) + " entries for a sub-sample set of " +
+                             std::to_string(S.n_layers) + " layers");
+  for (uint64_t k = 0; k < n; ++k)
+    if (!std::isfinite(lapse[k])) return fail(-EINVAL, "lapse[" + std::to_string(k) + "] is not finite");
+  HIP_TRY(hipSetDevice(gb->info.device));
+  DevBuf fresh;  // as large as the layer arrays: a later fill grows it with them
+  if (int rc = fresh.alloc(8 * std::max(S.cap_layers, n))) return rc;
+  if (n) HIP_TRY(hipMemcpy(fresh.p, lapse, 8 * n, hipMemcpyHostToDevice));
+  S.lapse = std::move(fresh);  // what the set held is freed
+  S.timed = true;
   return 0;
 }
 

@@ -64,11 +64,13 @@ GDEV void orbit_uv(double omega, double t, double* u, double* v) {
 // time t, the rate read from omega[k] (gbuffer_orbit_rate_kernel wrote it): the same
 // expression either way, so the same bits.  SHADE_RETARDED: SHADE_AT_CACHED with layer k at
 // its emission time t + lapse[k] (grt_gbuffer_shade_times_retarded): one add, then orbit_uv.
-enum ShadeMode { SHADE_STATIC, SHADE_AT, SHADE_AT_CACHED, SHADE_RETARDED };
+// SHADE_RETARDED_AT: SHADE_RETARDED with the rate computed where it is used, as SHADE_AT does
+// (grt_gbuffer_shade_section_at_retarded): the same expression, so the cached form's bits.
+enum ShadeMode { SHADE_STATIC, SHADE_AT, SHADE_AT_CACHED, SHADE_RETARDED, SHADE_RETARDED_AT };
 
 // The colour of layer k.  In the two time modes a disc layer's (u, v) goes through orbit_uv
 // before the texture lookup; t and omega are unused in SHADE_STATIC, lapse in every mode but
-// SHADE_RETARDED.
+// the two retarded ones.
 template <ShadeMode MODE>
 GDEV int gbuffer_layer_color(const DevScene& S, const GBufferArrays& gb, uint64_t k, double t,
                              const double* __restrict__ omega, const double* __restrict__ lapse, XYZA* col) {
@@ -83,6 +85,8 @@ GDEV int gbuffer_layer_color(const DevScene& S, const GBufferArrays& gb, uint64_
   double u = gb.u[k], v = gb.v[k];
   if constexpr (MODE == SHADE_RETARDED) {
     if (o.kind == GRT_OBJ_DISC) orbit_uv(omega[k], t + lapse[k], &u, &v);
+  } else if constexpr (MODE == SHADE_RETARDED_AT) {
+    if (o.kind == GRT_OBJ_DISC) orbit_uv(orbit_rate(S, gb.radius[k]), t + lapse[k], &u, &v);
   } else if constexpr (MODE != SHADE_STATIC) {
     if (o.kind == GRT_OBJ_DISC) orbit_uv(MODE == SHADE_AT_CACHED ? omega[k] : orbit_rate(S, gb.radius[k]), t, &u, &v);
   }
@@ -290,6 +294,40 @@ __global__ void __launch_bounds__(256) gbuffer_orbit_rate_kernel(const DevScene*
   omega[k] = S.obj[gb.object[k]].kind == GRT_OBJ_DISC ? orbit_rate(S, gb.radius[k]) : 0.0;
 }
 
+// gbuffer_shade_at_kernel under the retarded rule (the 1-spp pass of
+// grt_gbuffer_shade_section_at_retarded): each disc layer at t + lapse[layer], the buffer's lapse.
+__global__ void __launch_bounds__(256) gbuffer_shade_at_retarded_kernel(const DevScene* __restrict__ Sp,
+                                                                        GBufferArrays gb, double t,
+                                                                        const double* __restrict__ lapse,
+                                                                        Outputs out) {
+  const DevScene& S = *Sp;
+  glibc::tables_to_lds();  // whole block, before the early return
+  const uint64_t idx = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (idx >= gb.n) return;
+  gbuffer_shade_ray<SHADE_RETARDED_AT>(S, gb, idx, out, idx, t, nullptr, lapse);
+}
+
+// gbuffer_shade_sub_at_kernel under the retarded rule (the supersample pass of
+// grt_gbuffer_shade_section_at_retarded): sub_lapse is the set's lapse, one entry per
+// sub-layer, indexed as the set's layer arrays are.
+__global__ void __launch_bounds__(256) gbuffer_shade_sub_at_retarded_kernel(
+    const DevScene* __restrict__ Sp, GBufferArrays sub, const uint32_t* __restrict__ sub_steps,
+    const uint32_t* __restrict__ sub_block, const uint32_t* __restrict__ sel, uint64_t n_sel,
+    const unsigned long long* __restrict__ d_count, uint64_t base, uint32_t per, double t,
+    const double* __restrict__ sub_lapse, Outputs out) {
+  const DevScene& S = *Sp;
+  // a block past the held pixels (the empty chunks of a pass) has nothing to do
+  if (base + (uint64_t)blockIdx.x * blockDim.x / per >= *d_count) return;
+  glibc::tables_to_lds();  // whole block, before the per-lane early return
+  const uint64_t k = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  const uint64_t j = k / per;
+  if (j >= n_sel || base + j >= *d_count) return;
+  const uint64_t src = (uint64_t)sub_block[sel[j]] * per + k % per;
+  if (src >= sub.n) return;  // a pixel the set does not hold: the split never lists one
+  if (out.steps) out.steps[k] = sub_steps[src];
+  gbuffer_shade_ray<SHADE_RETARDED_AT>(S, sub, src, out, k, t, nullptr, sub_lapse);
+}
+
 hipError_t launch_gbuffer_orbit_rate(const DevScene* d_scene, const GBufferArrays& gb, uint64_t n_layers,
                                      double* d_omega, hipStream_t stream) {
   if (n_layers == 0) return hipSuccess;
@@ -371,6 +409,29 @@ hipError_t launch_gbuffer_shade_sub_stack(const DevScene* d_scene, const GBuffer
   if (npix == 0 || n_frames == 0 || n > 0xffffffffull * 256) return hipErrorInvalidValue;
   hipLaunchKernelGGL(gbuffer_shade_sub_stack_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, stream, d_scene,
                      d_frames, n_frames, npix, d_sel, n_sel, d_count, base, spa * spa, out);
+  return hipGetLastError();
+}
+
+hipError_t launch_gbuffer_shade_at_retarded(const DevScene* d_scene, const GBufferArrays& gb, double t,
+                                            const double* d_lapse, const Outputs& out, hipStream_t stream) {
+  if (gb.n == 0) return hipSuccess;
+  if (!d_lapse) return hipErrorInvalidValue;
+  hipLaunchKernelGGL(gbuffer_shade_at_retarded_kernel, dim3((unsigned)((gb.n + 255) / 256)), dim3(256), 0, stream,
+                     d_scene, gb, t, d_lapse, out);
+  return hipGetLastError();
+}
+
+hipError_t launch_gbuffer_shade_sub_at_retarded(const DevScene* d_scene, const GBufferArrays& sub,
+                                                const uint32_t* d_sub_steps, const uint32_t* d_sub_block,
+                                                const uint32_t* d_sel, uint64_t n_sel,
+                                                const unsigned long long* d_count, uint64_t base, uint32_t spa,
+                                                double t, const double* d_sub_lapse, const Outputs& out,
+                                                hipStream_t stream) {
+  const uint64_t n = n_sel * spa * spa;
+  if (n == 0) return hipSuccess;
+  if (!d_sub_lapse) return hipErrorInvalidValue;
+  hipLaunchKernelGGL(gbuffer_shade_sub_at_retarded_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, stream,
+                     d_scene, sub, d_sub_steps, d_sub_block, d_sel, n_sel, d_count, base, spa * spa, t, d_sub_lapse, out);
   return hipGetLastError();
 }
 

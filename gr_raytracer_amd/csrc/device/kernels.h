@@ -283,6 +283,17 @@ hipError_t launch_gbuffer_shade_sub_at(const DevScene* d_scene, const GBufferArr
                                        const uint32_t* d_sub_block, const uint32_t* d_sel, uint64_t n_sel,
                                        const unsigned long long* d_count, uint64_t base, uint32_t spa, double t,
                                        const Outputs& out, hipStream_t stream);
+// The two single-time launches under the retarded rule (gbuffer_shade_at_retarded_kernel,
+// gbuffer_shade_sub_at_retarded_kernel): layer k at t + d_lapse[k], the buffer's lapse over its
+// layers, the set's over the set's.  hipErrorInvalidValue for a null lapse.
+hipError_t launch_gbuffer_shade_at_retarded(const DevScene* d_scene, const GBufferArrays& gb, double t,
+                                            const double* d_lapse, const Outputs& out, hipStream_t stream);
+hipError_t launch_gbuffer_shade_sub_at_retarded(const DevScene* d_scene, const GBufferArrays& sub,
+                                                const uint32_t* d_sub_steps, const uint32_t* d_sub_block,
+                                                const uint32_t* d_sel, uint64_t n_sel,
+                                                const unsigned long long* d_count, uint64_t base, uint32_t spa,
+                                                double t, const double* d_sub_lapse, const Outputs& out,
+                                                hipStream_t stream);
 // The selected pixels d_sel (*d_count of them, ascending) split by sub_block into the ones
 // the set holds and the ones it misses, each in ascending order, with their counts
 // (gbuffer.hip; n_max <= INT_MAX entries of room).  d_flags: 2 * n_max bytes of scratch.

@@ -23,6 +23,7 @@ const char SUB_MAGIC[8] = {'G', 'R', 'T', 'G', 'S', 'U', 'B', '\0'};
 constexpr uint64_t SUB_HEADER_BYTES = HEADER_BYTES + sizeof(grt_gbuffer_sub_info);
 const char LAPSE_MAGIC[8] = {'G', 'R', 'T', 'G', 'L', 'P', 'S', '\0'};
 constexpr uint64_t LAPSE_HEADER_BYTES = HEADER_BYTES + 8;
+const char SUB_LAPSE_MAGIC[8] = {'G', 'R', 'T', 'G', 'S', 'L', 'P', '\0'};  // its header is SUB_HEADER_BYTES long
 // no frame comes near these; they keep the size arithmetic below far from overflow
 constexpr uint64_t MAX_PIXELS = (1ull << 31) - 2;
 constexpr uint64_t MAX_LAYERS = 1ull << 40;
@@ -416,6 +417,92 @@ int grt_gbuffer_lapse_read_file(const char* path, const grt_gbuffer_info* info, 
   if (length != LAPSE_HEADER_BYTES + 8 * l)  // l <= MAX_LAYERS (gbuffer_check_info): no overflow
     return fail(-EINVAL, name + "file length " + std::to_string(length) + " disagrees with its sizes (" +
                              std::to_string(LAPSE_HEADER_BYTES + 8 * l) + " expected)");
+  // the entries go through a buffer of the file's: the caller's array is written only once all are finite
+  std::vector<double> v(l);
+  if (l && std::fread(v.data(), 8, l, file.f) != l) return fail(-EIO, name + "cannot read the lapse");
+  for (uint64_t k = 0; k < l; ++k)
+    if (!std::isfinite(v[k])) return fail(-EINVAL, name + "lapse[" + std::to_string(k) + "] is not finite");
+  if (lapse && l) std::memcpy(lapse, v.data(), 8 * l);
+  return 0;
+}
+
+// ---- the sub-sample set's lapse sidecar ----
+// magic, version and info-block size, the bound info, the set's sub-info, the doubles.  The
+// sub-info binds the sidecar to the set it was written for: a `.sub` that grew since has
+// other counts, and its stale `.sub.lapse` is refused.
+int grt_gbuffer_sub_lapse_write_file(const char* path, const grt_gbuffer_info* info, const grt_gbuffer_sub_info* sub,
+                                     const double* lapse, uint64_t n_sub_layers) {
+  if (!path) return fail(-EINVAL, "null path");
+  if (int rc = grt_host::gbuffer_sub_check(info, sub, nullptr, nullptr)) return rc;
+  if (n_sub_layers != sub->n_sub_layers)
+    return fail(-EINVAL, "g-buffer: a lapse of " + std::to_string(n_sub_layers) + " entries for " +
+                             std::to_string(sub->n_sub_layers) + " sub-ray layers");
+  if (n_sub_layers && !lapse) return fail(-EINVAL, "g-buffer: null lapse");
+  for (uint64_t k = 0; k < n_sub_layers; ++k)
+    if (!std::isfinite(lapse[k])) return fail(-EINVAL, "g-buffer: lapse[" + std::to_string(k) + "] is not finite");
+  File file;
+  file.f = std::fopen(path, "wb");
+  if (!file.f) return fail(-EIO, std::string("cannot create ") + path);
+  const uint32_t head[2] = {GRT_GBUFFER_SUB_LAPSE_FILE_VERSION, (uint32_t)sizeof(grt_gbuffer_info)};
+  const grt_gbuffer_info bound = bound_info(info);
+  grt_gbuffer_sub_info si = *sub;
+  si._pad = 0;
+  bool ok = true;
+  auto put = [&](const void* p, uint64_t bytes) {
+    if (ok && bytes) ok = std::fwrite(p, 1, bytes, file.f) == bytes;
+  };
+  put(SUB_LAPSE_MAGIC, 8);
+  put(head, 8);
+  put(&bound, sizeof(bound));
+  put(&si, sizeof(si));
+  put(lapse, 8 * n_sub_layers);
+  FILE* f = file.f;
+  file.f = nullptr;
+  if (std::fclose(f) != 0) ok = false;
+  if (!ok) return fail(-EIO, std::string("cannot write ") + path);
+  return 0;
+}
+
+int grt_gbuffer_sub_lapse_read_file(const char* path, const grt_gbuffer_info* info, const grt_gbuffer_sub_info* sub,
+                                    double* lapse) {
+  if (!path || !info || !sub) return fail(-EINVAL, "null argument");
+  if (int rc = grt_host::gbuffer_sub_check(info, sub, nullptr, nullptr)) return rc;
+  File file;
+  file.f = std::fopen(path, "rb");
+  if (!file.f) return fail(-EIO, std::string("cannot open ") + path);
+  const std::string name = std::string(path) + ": ";
+  if (std::fseek(file.f, 0, SEEK_END) != 0) return fail(-EIO, name + "cannot seek");
+  const long end = std::ftell(file.f);
+  if (end < 0 || std::fseek(file.f, 0, SEEK_SET) != 0) return fail(-EIO, name + "cannot seek");
+  const uint64_t length = (uint64_t)end;
+  if (length < SUB_HEADER_BYTES) return fail(-EINVAL, name + "too short for a sub-sample lapse header");
+  char magic[8];
+  uint32_t head[2];
+  grt_gbuffer_info in;
+  grt_gbuffer_sub_info si;
+  if (std::fread(magic, 1, 8, file.f) != 8 || std::fread(head, 1, 8, file.f) != 8)
+    return fail(-EIO, name + "cannot read the header");
+  if (std::memcmp(magic, SUB_LAPSE_MAGIC, 8) != 0)
+    return fail(-EINVAL, name + "not a g-buffer sub-sample lapse file (magic)");
+  if (head[0] != GRT_GBUFFER_SUB_LAPSE_FILE_VERSION)
+    return fail(-EINVAL, name + "sub-sample lapse file version " + std::to_string(head[0]) + ", this library reads " +
+                             std::to_string(GRT_GBUFFER_SUB_LAPSE_FILE_VERSION));
+  if (head[1] != sizeof(grt_gbuffer_info)) return fail(-EINVAL, name + "info block of another size");
+  if (std::fread(&in, 1, sizeof(in), file.f) != sizeof(in) || std::fread(&si, 1, sizeof(si), file.f) != sizeof(si))
+    return fail(-EIO, name + "cannot read the info blocks");
+  const grt_gbuffer_info bound = bound_info(info);
+  if (std::memcmp(&in, &bound, sizeof(in)) != 0)
+    return fail(-EINVAL, name + "the lapse belongs to another g-buffer (its info block differs)");
+  grt_gbuffer_sub_info want = *sub;
+  want._pad = 0;
+  if (std::memcmp(&si, &want, sizeof(si)) != 0)
+    return fail(-EINVAL, name + "the lapse belongs to another sub-sample set (" + std::to_string(si.n_sub_pixels) +
+                             " pixels and " + std::to_string(si.n_sub_layers) + " layers, the set has " +
+                             std::to_string(want.n_sub_pixels) + " and " + std::to_string(want.n_sub_layers) + ")");
+  const uint64_t l = want.n_sub_layers;  // <= MAX_LAYERS (gbuffer_sub_check): no overflow
+  if (length != SUB_HEADER_BYTES + 8 * l)
+    return fail(-EINVAL, name + "file length " + std::to_string(length) + " disagrees with its sizes (" +
+                             std::to_string(SUB_HEADER_BYTES + 8 * l) + " expected)");
   // the entries go through a buffer of the file's: the caller's array is written only once all are finite
   std::vector<double> v(l);
   if (l && std::fread(v.data(), 8, l, file.f) != l) return fail(-EIO, name + "cannot read the lapse");

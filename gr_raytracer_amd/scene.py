@@ -232,7 +232,8 @@ class Scene:
         `adaptive`, one `shade_section` with the scene as its own tracer follows, so the
         buffer also holds the sub-rays of the pixels this scene's adaptive frame selects.
         With `lapse`, the trace also records each layer's light-travel time
-        (grt_gbuffer_trace_lapse): the same arrays byte for byte, and `GBuffer.lapse()`."""
+        (grt_gbuffer_trace_lapse): the same arrays byte for byte, and `GBuffer.lapse()`; with
+        both, the sub-rays are filled with theirs (a timed set, `GBuffer.sub_lapse()`)."""
         rows = self.rows - row0 if rows is None else rows
         cols = self.cols - col0 if cols is None else cols
         h = C.c_void_p()
@@ -240,7 +241,14 @@ class Scene:
         name = "grt_gbuffer_trace_lapse" if lapse else "grt_gbuffer_trace"
         L.check(getattr(L.lib(), name)(self._s, device, row0, col0, rows, cols, C.byref(h), C.byref(st)), name)
         gb = GBuffer(h, _stats_dict(st))
-        if adaptive is not None:
+        if adaptive is not None and lapse:
+            # the static frame's own selection (what `adaptive` alone fills), traced timed: the
+            # mask pass paints the selected pixels and traces nothing, and no shaded pixel has
+            # the mask's alpha of -1
+            if adaptive.enabled:
+                res, _ = gb.shade_section(self, adaptive=adaptive, sampling_mask_xyza=(-1.0, -1.0, -1.0, -1.0))
+                gb.supersample(self, np.flatnonzero(res.xyza64[:, 3] == -1.0), adaptive.samples_per_axis, lapse=True)
+        elif adaptive is not None:
             gb.shade_section(self, adaptive=adaptive, tracer=self)
         return gb
 
@@ -744,26 +752,61 @@ class GBuffer:
         held, c, px = _gbuffer_sub_host_arrays(sub, arrays)
         L.check(L.lib().grt_gbuffer_sub_upload(self._h, C.byref(sub), px, C.byref(c)), "grt_gbuffer_sub_upload")
 
-    def supersample(self, tracer: "Scene", pixels, samples_per_axis: int) -> dict:
+    def supersample(self, tracer: "Scene", pixels, samples_per_axis: int, lapse: bool = False) -> dict:
         """Trace the sub-rays of `pixels` (indices into the rectangle) under `tracer` and
-        append them to the set; pixels already held are skipped.  Returns the traces' stats."""
+        append them to the set; pixels already held are skipped.  Returns the traces' stats.
+        With `lapse` the set is a timed one (grt_gbuffer_supersample_lapse): each sub-layer's
+        light-travel time beside the same arrays."""
         px = np.ascontiguousarray(pixels, np.uint32).reshape(-1)
         st = L.Stats()
-        L.check(L.lib().grt_gbuffer_supersample(tracer._s, self._h, samples_per_axis, len(px), L.ptr(px, C.c_uint32),
-                                                C.byref(st)), "grt_gbuffer_supersample")
+        name = "grt_gbuffer_supersample_lapse" if lapse else "grt_gbuffer_supersample"
+        L.check(getattr(L.lib(), name)(tracer._s, self._h, samples_per_axis, len(px), L.ptr(px, C.c_uint32),
+                                       C.byref(st)), name)
         return _stats_dict(st)
+
+    @property
+    def sub_has_lapse(self) -> bool:
+        """Whether the sub-sample set is a timed one (grt_gbuffer_sub_has_lapse)."""
+        rc = L.lib().grt_gbuffer_sub_has_lapse(self._h)
+        if rc < 0:
+            L.check(rc, "grt_gbuffer_sub_has_lapse")
+        return rc == 1
+
+    def sub_lapse(self):
+        """The set's lapse, downloaded (grt_gbuffer_sub_lapse_download): n_sub_layers doubles,
+        indexed as the set's layer arrays; None for an untimed or absent set."""
+        out = np.zeros(int(self.sub_info.n_sub_layers), np.float64)
+        rc = L.lib().grt_gbuffer_sub_lapse_download(self._h, L.dptr(out))
+        if rc == -errno.ENODATA:
+            return None
+        L.check(rc, "grt_gbuffer_sub_lapse_download")
+        return out
+
+    def set_sub_lapse(self, lapse) -> None:
+        """Give the set a lapse, one finite double per sub-layer, and so make it timed
+        (grt_gbuffer_sub_lapse_upload)."""
+        a = np.ascontiguousarray(lapse, np.float64).reshape(-1)
+        L.check(L.lib().grt_gbuffer_sub_lapse_upload(self._h, L.dptr(a), len(a)), "grt_gbuffer_sub_lapse_upload")
+
+    def clear_sub(self) -> None:
+        """Drop the sub-sample set, whatever its kind (grt_gbuffer_sub_clear)."""
+        L.check(L.lib().grt_gbuffer_sub_clear(self._h), "grt_gbuffer_sub_clear")
 
     def shade_section(self, scene: "Scene", adaptive: Optional[L.AdaptiveConfig] = None,
                       tracer: Optional["Scene"] = None, sampling_mask_xyza=None, failure_capacity: int = 0,
-                      log_events: bool = False, time: Optional[float] = None):
+                      log_events: bool = False, time: Optional[float] = None, retarded: bool = False):
         """The adaptive frame of the buffer under `scene`'s appearance
         (grt_gbuffer_shade_section): bit-identical to `render_section_ex` of a scene with
         this appearance and the traced geometry, camera and integration parameters.
         Selected pixels whose sub-rays the buffer does not hold are traced under `tracer`
         and appended; without a tracer they raise GBufferMissing.  With `time` the disc's
         texture has orbited for that coordinate time (grt_gbuffer_shade_section_at; the set
-        keeps unrotated numbers).  Returns (SectionResult, report dict); the result's stats
-        are the top-up's."""
+        keeps unrotated numbers).  With `retarded` as well every disc layer is shaded at its
+        emission time `time` + lapse (grt_gbuffer_shade_section_at_retarded): the buffer must
+        hold a lapse and the set be timed or empty; a top-up fills an empty set timed.
+        Returns (SectionResult, report dict); the result's stats are the top-up's."""
+        if retarded and time is None:
+            raise ValueError("shade_section: retarded=True needs a time")
         n = int(self.info.n_pixels)
         out = np.zeros((n, 4), np.float64)
         cls = np.zeros(n, np.uint8)
@@ -780,13 +823,15 @@ class GBuffer:
                                     L.ptr(fn, C.c_uint32) if log_events else None)
         rep = L.GBufferSectionReport()
         what = "grt_gbuffer_shade_section" if time is None else "grt_gbuffer_shade_section_at"
+        if retarded:
+            what = "grt_gbuffer_shade_section_at_retarded"
         args = (scene._s, self._h, C.byref(adaptive or scene.adaptive), L.dptr(mask) if mask is not None else None,
                 tracer._s if tracer is not None else None, L.dptr(out), L.ptr(cls, C.c_uint8),
                 L.ptr(status, C.c_uint8), C.byref(nsel), C.byref(fails), C.byref(rep))
         if time is None:
             rc = L.lib().grt_gbuffer_shade_section(*args)
         else:
-            rc = L.lib().grt_gbuffer_shade_section_at(*args, float(time))
+            rc = getattr(L.lib(), what)(*args, float(time))
         report = {"n_selected": int(rep.n_selected), "n_held": int(rep.n_held), "n_traced": int(rep.n_traced),
                   "n_missing": int(rep.n_missing), "shade_ms": float(rep.shade_ms), "trace_ms": float(rep.trace_ms),
                   "top_up": _stats_dict(rep.top_up)}
@@ -805,12 +850,30 @@ class GBuffer:
                              rows[failed], a["stop"], a["steps"], events), report
 
     def save_sub(self, path) -> None:
-        """Write the sub-sample set's sidecar (grt_gbuffer_sub_write_file)."""
+        """Write the sub-sample set's sidecar (grt_gbuffer_sub_write_file), and beside it
+        `<path>.lapse` when the set is timed."""
         info, sub = self.info, self.sub_info
         out, c, px = _gbuffer_sub_host_arrays(sub)
         L.check(L.lib().grt_gbuffer_sub_download(self._h, px, C.byref(c)), "grt_gbuffer_sub_download")
         L.check(L.lib().grt_gbuffer_sub_write_file(str(path).encode(), C.byref(info), C.byref(sub), px, C.byref(c)),
                 "grt_gbuffer_sub_write_file")
+        lapse = self.sub_lapse()
+        if lapse is not None:
+            self.write_sub_lapse_file(str(path) + ".lapse", info, sub, lapse)
+
+    @staticmethod
+    def write_sub_lapse_file(path, info: L.GBufferInfo, sub: L.GBufferSubInfo, lapse) -> None:
+        a = np.ascontiguousarray(lapse, np.float64).reshape(-1)
+        L.check(L.lib().grt_gbuffer_sub_lapse_write_file(str(path).encode(), C.byref(info), C.byref(sub), L.dptr(a),
+                                                         len(a)), "grt_gbuffer_sub_lapse_write_file")
+
+    @staticmethod
+    def read_sub_lapse_file(path, info: L.GBufferInfo, sub: L.GBufferSubInfo) -> np.ndarray:
+        """The lapse of a sidecar bound to the buffer `info` and its set `sub`, on the host."""
+        out = np.zeros(int(sub.n_sub_layers), np.float64)
+        L.check(L.lib().grt_gbuffer_sub_lapse_read_file(str(path).encode(), C.byref(info), C.byref(sub), L.dptr(out)),
+                "grt_gbuffer_sub_lapse_read_file")
+        return out
 
     @staticmethod
     def read_sub_file(path, info: L.GBufferInfo):
@@ -830,9 +893,16 @@ class GBuffer:
                 "grt_gbuffer_sub_write_file")
 
     def load_sub(self, path) -> None:
-        """Read a sidecar written for this buffer and make it the buffer's set."""
-        sub, arrays = self.read_sub_file(path, self.info)
+        """Read a sidecar written for this buffer and make it the buffer's set: a timed one
+        when `<path>.lapse` is there (a sidecar of another or of a since-grown set is refused)."""
+        info = self.info
+        sub, arrays = self.read_sub_file(path, info)
+        lapse = None
+        if os.path.exists(str(path) + ".lapse"):
+            lapse = self.read_sub_lapse_file(str(path) + ".lapse", info, sub)
         self.set_sub_arrays(sub, arrays)
+        if lapse is not None:
+            self.set_sub_lapse(lapse)
 
     def save(self, path) -> None:
         """Write the buffer's file, and beside it `<path>.lapse` when the buffer holds a lapse."""

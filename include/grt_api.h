@@ -1011,9 +1011,9 @@ int grt_gbuffer_shade_section_at(grt_scene* appearance, grt_gbuffer* gb, const g
  * Kerr-Schild's t and Boyer-Lindquist's t differ by a function of r, so each chart's movie
  * is consistent in its own slicing and the two differ by a radius-dependent phase at time 0,
  * as their phi already do.
- * Not covered: lapses for the sub-sample set (grt_gbuffer_shade_section_at stays fast-light),
- * camera sequences, the multi-GPU buffer, the fused arithmetic, VolumetricDisc scenes, and a
- * time along the ray for the celestial sphere, which is static. */
+ * The sub-sample set takes lapses too ("Retarded time, adaptive" below).
+ * Not covered: camera sequences, the multi-GPU buffer, the fused arithmetic, VolumetricDisc
+ * scenes, and a time along the ray for the celestial sphere, which is static. */
 /* grt_gbuffer_trace through the kernels that record hit times: the same info and twelve
  * arrays, byte for byte, the same pool-growth retries, always the exact kernels, -ENOTSUP
  * for VolumetricDisc scenes; the buffer holds its lapse (n_layers doubles). */
@@ -1046,6 +1046,67 @@ int grt_gbuffer_orbit_uv_retarded(const grt_gbuffer_shape* shape, uint64_t n_lay
  * times[k], bit for bit, in the range grt_gbuffer_shade_times promises it. */
 int grt_gbuffer_shade_times_retarded(grt_scene* appearance, const grt_gbuffer* gb, uint32_t n_times,
                                      const double* times, const grt_frame_out* out, float* kernel_ms);
+
+/* Retarded time, adaptive: lapses for the sub-sample set, and the adaptive frame shaded with them.
+ *
+ * A set is timed or untimed.  A timed set holds one lapse per sub-layer (n_sub_layers doubles,
+ * indexed as the set's layer arrays are), beside its twelve arrays: grt_gbuffer_sub_info, the
+ * .sub format and the ABI version are as they were.  The kind is fixed when the first block is
+ * appended: grt_gbuffer_supersample_lapse and a top-up of grt_gbuffer_shade_section_at_retarded
+ * make an empty set timed, the other entries make it untimed, and every later fill of a set
+ * keeps its kind whichever entry asked for it (a timed set is always filled through the kernels
+ * that record hit times; the twelve arrays are byte for byte the same either way).
+ * grt_gbuffer_sub_upload leaves an untimed set, grt_gbuffer_sub_lapse_upload makes it timed,
+ * grt_gbuffer_sub_clear drops a set of either kind.  The stacked calls
+ * (grt_gbuffer_supersample_sequence, grt_gbuffer_shade_section_sequence) trace with camera
+ * tables, which the lapse kernels do not take: they return -EINVAL, naming the frame, for a
+ * buffer whose set is timed.
+ * Not covered: several times in one stacked adaptive call (loop
+ * grt_gbuffer_shade_section_at_retarded), one top-up for a whole movie, camera sequences, the
+ * multi-GPU buffer, the fused arithmetic, VolumetricDisc scenes. */
+/* grt_gbuffer_supersample into a timed set: its arguments, rules and refusals, the sub-rays
+ * traced through the kernels that record hit times.  -EINVAL when the set holds blocks and is
+ * untimed (grt_last_error gives its pixel count). */
+int grt_gbuffer_supersample_lapse(grt_scene* tracer, grt_gbuffer* gb, uint32_t samples_per_axis, uint64_t n,
+                                  const uint32_t* pixels, grt_stats* stats);
+/* 1: the buffer's set is timed; 0: untimed, or no set; -EINVAL: null buffer. */
+int grt_gbuffer_sub_has_lapse(const grt_gbuffer* gb);
+/* Drop the buffer's set: its arrays, its pixel map and its kind.  The buffer then holds no set. */
+int grt_gbuffer_sub_clear(grt_gbuffer* gb);
+/* The set's lapse to out[n_sub_layers].  -ENODATA: the set is untimed, or there is none. */
+int grt_gbuffer_sub_lapse_download(const grt_gbuffer* gb, double* out);
+/* Give the set a lapse (it replaces a held one) and so make it timed.  -EINVAL: the buffer
+ * holds no set, n is not the set's n_sub_layers, or an entry is not finite; nothing changes then. */
+int grt_gbuffer_sub_lapse_upload(grt_gbuffer* gb, const double* lapse, uint64_t n);
+/* grt_gbuffer_shade_section_at under the retarded rule: the same arguments and pipeline, the
+ * 1-spp pass with the buffer's lapse and the sub-ray pass with the set's, each disc layer at
+ * time + its lapse.  The frame equals grt_gbuffer_shade_section of the buffer whose arrays and
+ * set arrays went through grt_gbuffer_orbit_uv_retarded at `time`, bit for bit.  -ENODATA: the
+ * buffer holds no lapse; the sub-ray pass would run on a set that holds blocks and is untimed
+ * (grt_last_error gives its pixel and layer counts); or, as ever, pixels are missing and there
+ * is no tracer.  A top-up fills an empty set timed.  With a mask or cfg->enabled == 0 the set
+ * is not touched and only the buffer's lapse is needed. */
+int grt_gbuffer_shade_section_at_retarded(grt_scene* appearance, grt_gbuffer* gb, const grt_adaptive_config* cfg,
+                                          const double* sampling_mask_xyza, grt_scene* tracer, double* xyza_out,
+                                          uint8_t* class_out, uint8_t* status_out, uint64_t* n_supersampled,
+                                          grt_subsample_failures* failures, grt_gbuffer_section_report* report,
+                                          double time);
+/* The set's lapse sidecar, by convention <buffer file>.sub.lapse.  Little-endian, no padding:
+ *   8 B   magic "GRTGSLP\0"
+ *   u32   version (GRT_GBUFFER_SUB_LAPSE_FILE_VERSION), u32 sizeof(grt_gbuffer_info)
+ *   grt_gbuffer_info          the buffer's, device zeroed
+ *   grt_gbuffer_sub_info      the set's: a .sub that grew since leaves this sidecar stale
+ *   f64[n_sub_layers]
+ * read: lapse NULL checks the file only; else lapse[sub->n_sub_layers], written only after
+ * every check.  `info` and `sub` are the buffer's and the set's.  -EINVAL: null argument, an
+ * info or sub-info that differs from the file's, a count other than sub->n_sub_layers, a
+ * non-finite entry, a wrong magic or version, a truncated file or one whose length disagrees
+ * with its sizes; -EIO: the file cannot be opened, read or written. */
+#define GRT_GBUFFER_SUB_LAPSE_FILE_VERSION 1
+int grt_gbuffer_sub_lapse_write_file(const char* path, const grt_gbuffer_info* info, const grt_gbuffer_sub_info* sub,
+                                     const double* lapse, uint64_t n_sub_layers);
+int grt_gbuffer_sub_lapse_read_file(const char* path, const grt_gbuffer_info* info, const grt_gbuffer_sub_info* sub,
+                                    double* lapse);
 
 /* The device hit pool that keeps the window candidates past a ray's GRT_MAX_HITS slots
  * (no reference counterpart: the reference's per-ray Vec grows, scene.rs:139-152).
