@@ -169,6 +169,12 @@ namespace lapse {
 #ifndef GRT_QUICK_STEP
 #define GRT_QUICK_STEP 1  // Schwarzschild: the far-field accepted step as one straight-line block
 #endif
+#ifndef GRT_STEADY_LOOP
+#define GRT_STEADY_LOOP 1  // Schwarzschild: quick steps of a wave with h == 1 everywhere in a loop of their own (steady_step_mask)
+#endif
+#ifndef GRT_SCALAR_VOTES
+#define GRT_SCALAR_VOTES 1  // Schwarzschild: wave votes compared as lane masks on the scalar side (wave_all)
+#endif
 #ifndef GRT_KL_STAGES
 #define GRT_KL_STAGES 4  // how many leading stages (k1, k2, ...) those kernels park in LDS
 #endif
@@ -789,6 +795,70 @@ GDEV bool quick_step_ok(const DevScene& S, double err_sq, const double* y, const
   return ok & fin & (rb > S.horizon_r) & (hi * hi < S.cel_lo2) & (i_next != S.max_steps - 1);
 }
 
+// The scene constants of quick_step_ok that integrate_kernel's steady loop reads, taken
+// once at the loop's entry (a scene of at most STEADY_OBJECTS objects: every Schwarzschild
+// scene of the reference has at most two).  Wave-uniform flags are lane masks, all or none.
+constexpr uint32_t STEADY_OBJECTS = 2;
+struct SteadyScene {
+  double tiny_err_sq, horizon_r, cel_lo2;
+  uint64_t last;  // max_steps - 1
+  double shell_lo[STEADY_OBJECTS], shell_hi[STEADY_OBJECTS];
+  uint64_t off[STEADY_OBJECTS], disc[STEADY_OBJECTS];  // no object k; object k is a disc
+};
+GDEV SteadyScene steady_scene(const DevScene& S) {
+  SteadyScene q;
+  q.tiny_err_sq = S.tiny_err_sq;
+  q.horizon_r = S.horizon_r;
+  q.cel_lo2 = S.cel_lo2;
+  q.last = S.max_steps - 1;
+#pragma unroll
+  for (uint32_t k = 0; k < STEADY_OBJECTS; ++k) {
+    const DevObject& o = S.obj[k];  // obj[] has 8 slots
+    q.off[k] = k < S.n_objects ? 0ull : ~0ull;
+    q.disc[k] = o.kind == GRT_OBJ_DISC ? ~0ull : 0ull;
+    q.shell_lo[k] = o.shell_lo;
+    q.shell_hi[k] = o.shell_hi;
+  }
+  return q;
+}
+// Whether the steady loop may run for this scene: the objects fit SteadyScene;
+// horizon_r >= 0, so that rb > horizon_r of one step proves ra > 0 on the next; and
+// far_a == 0 (every Schwarzschild scene: api.hip), so that |rb| + far_a is |rb| (|rb| is
+// never -0, and x + 0.0 is x for every other x).
+GDEV bool steady_scene_ok(const DevScene& S) {
+  return S.n_objects <= STEADY_OBJECTS && S.horizon_r >= 0.0 && S.far_a == 0.0;
+}
+
+// The lanes that pass quick_step_ok<G, true> in integrate_kernel's steady loop, where y is
+// the yn of a step that passed quick_step_ok (or this) on the same lanes with the same
+// scene.  The tests on (ra, ta) that the b-side tests of that step imply are dropped
+// (DESIGN section 4): far_ok; ta inside one of the two theta bands, so one compare against a
+// bound between them says which; ra > 0.0 (ra > horizon_r >= 0, steady_scene_ok); out_a of
+// every object (out_b of that step, the same expression on the same values).  Every compare
+// is voted on by itself and the votes are combined as masks (wave_all's reason): the result
+// equals the executing lanes' mask iff quick_step_ok holds on all of them.
+template <int G>
+GDEV uint64_t steady_step_mask(const SteadyScene& q, double err_sq, const double* y, const double* yn, uint64_t i_next) {
+  static_assert(G == GRT_GEOM_SCHWARZSCHILD, "quick step: Schwarzschild only");
+  constexpr double N_LO = -1.5707963257948966, N_HI = 1.5707963257948966;
+  constexpr double S_LO = 1.5707963277948966, S_HI = 4.7123889793846899;
+  const double ra = y[1], rb = yn[1], ta = y[2], tb = yn[2];
+  const uint64_t a_north = __ballot(ta < N_HI);  // ta < N_HI (north band) or ta > S_LO > N_HI (south band)
+  const uint64_t north = a_north & __ballot(tb > N_LO) & __ballot(tb < N_HI);
+  const uint64_t south = ~a_north & __ballot(tb > S_LO) & __ballot(tb < S_HI);
+  const uint64_t disc_ok = (north | south) & __ballot(ra >= 1e-3 * rb) & __ballot(rb >= 1e-3 * ra);
+  const double hi = fabs(rb);
+  uint64_t ok = __ballot(err_sq < q.tiny_err_sq);
+#pragma unroll
+  for (uint32_t k = 0; k < STEADY_OBJECTS; ++k) {
+    const uint64_t out_b = __ballot(rb > q.shell_hi[k]) | __ballot(hi < q.shell_lo[k]);
+    ok &= q.off[k] | (q.disc[k] & disc_ok) | (~q.disc[k] & out_b);
+  }
+  // one vote for the eight class tests: a v_cmp_class result is not taken as a lane mask
+  ok &= __ballot(finite_not_neg_zero8(yn));
+  return ok & __ballot(rb > q.horizon_r) & __ballot(hi * hi < q.cel_lo2) & __ballot(i_next != q.last);
+}
+
 // The step-size controller of rkf45 (runge_kutta.rs:148-178) after one attempt with
 // error norm `err` at step h_cur.  Accepted: h_next is the next step's h.  Rejected:
 // h_cur is the retry's step (STEP_RETRY), or the 100th retry failed (STEP_FAILED,
@@ -1358,10 +1428,20 @@ __global__ void __launch_bounds__(256, integrate_waves(G, VOL)) integrate_kernel
       full = S.rkf_short == 0;
       again = S.rkf_short == 2;
     }
+    // The steady loop: the general iteration takes the attempt without
+    // UNIT_H (h * o with h == 1 is o), and a wave whose quick step leaves every lane at
+    // h_cur == 1.0 stays in a loop of unit attempts and reduced tests (steady_step_mask) until a
+    // lane misses the test; then it goes on below with yn and err_sq of that attempt, as it
+    // does from the quick step.  Two copies of the attempt, as before.
+    constexpr bool STEADY = GRT_STEADY_LOOP && QUICK && UNIT_H_COPY && SHORT;
     while (!full) {
-      err_sq = (UNIT_H_COPY && __ballot(active && h_cur != 1.0) == 0)
-                   ? rkf_attempt<G, UNIT_H_COPY, false, NKL, SHORT>(S, rc, y, h_cur, yn)
-                   : rkf_attempt<G, false, false, NKL, SHORT>(S, rc, y, h_cur, yn);
+      if constexpr (STEADY) {
+        err_sq = rkf_attempt<G, false, false, NKL, SHORT>(S, rc, y, h_cur, yn);
+      } else {
+        err_sq = (UNIT_H_COPY && __ballot(active && h_cur != 1.0) == 0)
+                     ? rkf_attempt<G, UNIT_H_COPY, false, NKL, SHORT>(S, rc, y, h_cur, yn)
+                     : rkf_attempt<G, false, false, NKL, SHORT>(S, rc, y, h_cur, yn);
+      }
       n_att++;
       PATH_COUNT(6);
 #if GRT_RAY_TIMES
@@ -1371,7 +1451,8 @@ __global__ void __launch_bounds__(256, integrate_waves(G, VOL)) integrate_kernel
         // every lane of the wave on the commonest accepted step (quick_step_ok): the
         // general path's updates in one straight-line block, then straight on to the next
         // attempt (no ray ended, so no lane needs a refill)
-        if (__ballot(!quick_step_ok<G, SHORT>(S, err_sq, y, yn, i + 1)) == 0) {
+        const bool q_ok = quick_step_ok<G, SHORT>(S, err_sq, y, yn, i + 1);
+        if (GRT_SCALAR_VOTES ? wave_all(q_ok) : __ballot(!q_ok) == 0) {
           h = rclamp(h_cur * H_GROWTH, H_MIN, H_MAX);
           i++;
           n_acc++;
@@ -1380,6 +1461,27 @@ __global__ void __launch_bounds__(256, integrate_waves(G, VOL)) integrate_kernel
           for (int k = 0; k < 8; ++k) y[k] = yn[k];
           retries = 0;
           h_cur = rclamp(h, H_MIN, H_MAX);
+          if constexpr (STEADY) {
+            // h_cur == 1.0 on every lane: each step of the loop would set h = clamp(4 * 1.0) =
+            // 1.0 and h_cur = 1.0 again, so both stay as they are, with retries and c_valid
+            if (steady_scene_ok(S) && wave_all(h_cur == 1.0)) {
+              const SteadyScene q = steady_scene(S);
+              while (true) {
+                err_sq = rkf_attempt<G, true, false, NKL, SHORT>(S, rc, y, 1.0, yn);
+                n_att++;
+                PATH_COUNT(6);
+#if GRT_RAY_TIMES
+                ray_att++;
+#endif
+                if (steady_step_mask<G>(q, err_sq, y, yn, i + 1) != __ballot(true)) break;
+                i++;
+                n_acc++;
+#pragma unroll
+                for (int k = 0; k < 8; ++k) y[k] = yn[k];
+              }
+              break;
+            }
+          }
           continue;
         }
       }
@@ -1392,7 +1494,7 @@ __global__ void __launch_bounds__(256, integrate_waves(G, VOL)) integrate_kernel
       // meridional plane) or one going non-finite; lanes that met the premise get their bits
       // again.  One copy, without UNIT_H (h * o with h == 1 is o), inlined: out of line it
       // cost the kernel 464 B of scratch per lane for the call's saves, against 112 B.
-      if (full || again || __ballot(!rkf_short_ok(err_sq, yn)) != 0) {
+      if (full || again || (GRT_SCALAR_VOTES ? !wave_all(rkf_short_ok(err_sq, yn)) : __ballot(!rkf_short_ok(err_sq, yn)) != 0)) {
         PATH_COUNT(7);
         err_sq = rkf_attempt<G, false, false, NKL>(S, rc, y, h_cur, yn);
         if (full) {

@@ -286,6 +286,11 @@ GDEV void path_count(int k) {
 #define PATH_COUNT(k) ((void)0)
 #endif
 
+// Whether every lane executing this holds p: the votes of p and of the executing lanes are
+// taken as 64-bit masks and compared on the scalar side (`__ballot(!p) == 0` is lowered
+// through a 0/1 vector register and a compare of it: 2 VALU per vote).
+GDEV bool wave_all(bool p) { return __ballot(p) == __ballot(true); }
+
 // sincos(theta), then body(sin, cos, fast).  When every lane of the wave is in one of
 // sincos's region-B cases (x near pi/2; glibc_math.h sincos_b_*), the sincos is the
 // straight-line form of that case and body runs in the same basic block, so its own
@@ -301,14 +306,31 @@ GDEV void path_count(int k) {
 // sincos through the body (a ballot between the two cost 1 %: DESIGN.md 3).
 template <int K>
 using div_form = std::integral_constant<int, K>;  // 0 IEEE, 1 range-free, 2 range-free with radius == 1.0
-template <bool FDIV = false, bool UNIT = false, class F>
-GDEV void with_sincos(double theta, bool fast_ok, F&& body, bool div_ok = false, bool unit = false) {
+// VOTES (Schwarzschild, GRT_SCALAR_VOTES): div_ok is the wave's vote on it, a 64-bit lane mask
+// (schw_div_ok_render_mask), and the region-B case predicates are voted on compare by compare
+// (a vote on one compare is that compare's own lane mask; a vote on a product of compares
+// goes through a 0/1 vector register); the four cases are then decided by mask arithmetic
+// against the executing lanes.  The same decisions.
+template <bool FDIV = false, bool UNIT = false, bool VOTES = false, class F, class D = bool>
+GDEV void with_sincos(double theta, bool fast_ok, F&& body, D div_ok = false, bool unit = false) {
 #if GRT_SINCOS_B
   if (fast_ok) {
     double st, ct;
-    const bool tab = glibc::sincos_b_table_ok(theta), tay = glibc::sincos_b_taylor_ok(theta);
+    [[maybe_unused]] bool tab = false, tay = false;
+    [[maybe_unused]] uint64_t ex = 0, mt = 0, my = 0, md = 0;
+    if constexpr (VOTES) {
+      static_assert(std::is_same<D, uint64_t>::value, "with_sincos<VOTES>: div_ok as a lane mask");
+      const uint64_t mb = __ballot(glibc::sincos_b_region(theta)), ms = __ballot(glibc::sincos_b_small(theta));
+      ex = __ballot(true);
+      mt = mb & ~ms;
+      my = mb & ms;
+      md = div_ok;
+    } else {
+      tab = glibc::sincos_b_table_ok(theta);
+      tay = glibc::sincos_b_taylor_ok(theta);
+    }
     if constexpr (FDIV) {
-      if (__ballot(!(tab & div_ok)) == 0) {
+      if (VOTES ? (mt & md) == ex : __ballot(!(tab & div_ok)) == 0) {
         PATH_COUNT(0);
         if constexpr (UNIT) {
           if (unit) {
@@ -321,7 +343,7 @@ GDEV void with_sincos(double theta, bool fast_ok, F&& body, bool div_ok = false,
         body(st, ct, true, std::true_type{});
         return;
       }
-      if (__ballot(!(tay & div_ok)) == 0) {
+      if (VOTES ? (my & md) == ex : __ballot(!(tay & div_ok)) == 0) {
         PATH_COUNT(1);
         if constexpr (UNIT) {
           if (unit) {
@@ -335,13 +357,13 @@ GDEV void with_sincos(double theta, bool fast_ok, F&& body, bool div_ok = false,
         return;
       }
     }
-    if (__ballot(!tab) == 0) {
+    if (VOTES ? mt == ex : __ballot(!tab) == 0) {
       PATH_COUNT(2);
       glibc::sincos_b_table(theta, &st, &ct);
       body(st, ct, true, std::false_type{});
       return;
     }
-    if (__ballot(!tay) == 0) {
+    if (VOTES ? my == ex : __ballot(!tay) == 0) {
       PATH_COUNT(2);
       glibc::sincos_b_taylor(theta, &st, &ct);
       body(st, ct, true, std::false_type{});
@@ -357,7 +379,10 @@ GDEV void with_sincos(double theta, bool fast_ok, F&& body, bool div_ok = false,
     double ca, cda;
     const bool rc2 = k >= 0x400368fdu && k < 0x419921fbu && glibc::reduce_sincos_nf(theta, &ca, &cda) == 2;
     const bool rb = k >= 0x3feb6000u && k < 0x400368fdu;
-    if (fast_ok && __ballot(!(rb & div_ok)) == 0) PATH_COUNT(12);
+    bool dk;
+    if constexpr (VOTES) dk = ((div_ok >> (threadIdx.x & 63)) & 1) != 0;
+    else dk = div_ok;
+    if (fast_ok && __ballot(!(rb & dk)) == 0) PATH_COUNT(12);
     else if (fast_ok && __ballot(!rb) == 0) PATH_COUNT(13);
     if (__ballot(!ra_tab) == 0) PATH_COUNT(8);
     else if (__ballot(!ra) == 0) PATH_COUNT(9);
@@ -416,6 +441,14 @@ GDEV bool schw_div_ok_render(const DevScene& S, double r) {
   return schw_div_ok(S, r);
 #endif
 }
+#if GRT_SCALAR_VOTES
+// schw_div_ok_render as the vote of the executing lanes, one vote per compare (with_sincos<VOTES>)
+GDEV uint64_t schw_div_ok_render_mask(const DevScene& S, double r) {
+  static_assert(GRT_DIV_OK_CHEAP, "schw_div_ok_render_mask: the two-compare predicate");
+  const uint64_t lo = __ballot(r > S.div_r_lo), hi = __ballot(r < 0x1p100);
+  return S.div_fast ? lo & hi : 0ull;
+}
+#endif
 GDEV bool bl_div_ok(const DevScene& S, double r, double del, double l_z) {
   return S.div_fast && (fabs(r) < 0x1p100) & in_div_range(del) & (fabs(l_z) > 0x1p-200) & (fabs(l_z) < 0x1p100);
 }
@@ -507,8 +540,13 @@ GDEV void rhs(const DevScene& S, const RayConst& rc, const double* y, double* o)
       } else body(st, ct, true, std::false_type{});
       return;
     }
+#if GRT_SCALAR_VOTES
+    with_sincos<GRT_FAST_DIV, GRT_UNIT_RADIUS, true>(theta, S.div_share, body, schw_div_ok_render_mask(S, r),
+                                                     S.unit_radius != 0);
+#else
     with_sincos<GRT_FAST_DIV, GRT_UNIT_RADIUS>(theta, S.div_share, body, schw_div_ok_render(S, r),
                                                S.unit_radius != 0);
+#endif
   } else if constexpr (G == GRT_GEOM_EUCLIDEAN_SPHERICAL) {  // euclidean_spherical.rs:48-70
     double r = y[1], theta = y[2];
     double v_t = y[4], v_r = y[5], v_theta = y[6], v_phi = y[7];

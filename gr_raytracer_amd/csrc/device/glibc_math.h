@@ -416,6 +416,17 @@ GRT_GLIBC_FN bool sincos_fast(double x, double* sinx, double* cosx) {
 // code: region B (0.855469 <= |x| < 2.426265, where sin x = +-do_cos(pi/2 - |x|) and
 // cos x = do_sin(a, da)) with do_sin's table path (|a| >= TAYLOR_MAX).  sincos_b_table_ok
 // says whether x is in that case; sincos_b_table then returns sincos_fast's bits.
+// The two compares of sincos_b_table_ok / sincos_b_taylor_ok, for callers that vote on each
+// (geodesic_rhs.h with_sincos): table_ok = region & !small, taylor_ok = region & small.
+GRT_GLIBC_FN bool sincos_b_region(double x) {
+  const uint32_t k = (uint32_t)(as_u64(x) >> 32) & 0x7fffffffu;
+  return k - 0x3feb6000u < 0x400368fdu - 0x3feb6000u;
+}
+GRT_GLIBC_FN bool sincos_b_small(double x) {
+  const double y = HP0 - fabs_(x);
+  const double a = y + HP1;
+  return fabs_(a) < TAYLOR_MAX;
+}
 GRT_GLIBC_FN bool sincos_b_table_ok(double x) {
   const uint32_t k = (uint32_t)(as_u64(x) >> 32) & 0x7fffffffu;
   const double y = HP0 - fabs_(x);
